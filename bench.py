@@ -9,9 +9,14 @@ clip, T=0, timestamps on, max_tokens 448) with pcm already resident in HBM.
     python bench.py --gpus 1 --steps 3 --warmup 1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (dominant kernel class, measured
-live with HIP events on the library's stream) and `cpu_baseline` (the fp32 CPU restatement, oracle/, timed on the
-host cores of this box on a bounded sample).
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run only sets up, warms up, times the --steps
+passes and prints the headline fields (`metric`, `value`, `unit`, `ms_per_step`, ...).  With --full the line also carries
+`roofline` / `stages` (dominant kernel class and per-stage device time, measured live with HIP events on the library's
+stream, plus strictly serial passes when R > 1 replicas run), `codec`, `lm`, `config0` and `cpu_baseline` (the fp32 CPU
+restatement, oracle/, timed on the host cores on a bounded sample).
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR    # + the last timed pass's outputs as DIR/<name>.npy
 """
 from __future__ import annotations
 
@@ -38,6 +43,56 @@ HBM_PEAK_GBS = 8000.0
 def log(*a):
     if int(os.environ.get("RANK", "0")) == 0:
         print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, arrays: dict) -> list[str]:
+    """--dump-outputs: every array as dirname/<name>.npy, float64 kept, everything else as float32 (token ids < 2^24 are exact);
+    refuses non-finite entries (split_nonfinite encodes them) and more than DUMP_LIMIT_BYTES in all.  Returns the paths written."""
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+        if not np.isfinite(conv[name]).all():
+            raise ValueError(f"--dump-outputs: {name} has non-finite entries")
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    paths = []
+    for name, a in conv.items():
+        paths.append(os.path.join(dirname, name + ".npy"))
+        np.save(paths[-1], a)
+    return paths
+
+
+NONFINITE_CODES = {"nan": 1, "-inf": 2, "+inf": 3}
+
+
+def split_nonfinite(name: str, a: np.ndarray) -> dict:
+    """A float output as two finite arrays, losslessly: <name> holds the value where it is finite and 0 elsewhere, <name>_nonfinite
+    the kind of every entry (0 finite, 1 NaN, 2 -inf, 3 +inf).  avg_logprob is NaN by the decoding rules themselves whenever a step
+    had every token masked (WhisperDecoding.swift evaluates the timestamp heuristic on the raw logits, so after two timestamps in a
+    row it can mask the text tokens while the pair rule masks every timestamp; log(softmax) of that step is NaN): the headline
+    workload's synthetic weights reach such a step in every clip."""
+    a = np.asarray(a)
+    kind = np.zeros(a.shape, np.int32)
+    kind[np.isnan(a)] = NONFINITE_CODES["nan"]
+    kind[np.isneginf(a)] = NONFINITE_CODES["-inf"]
+    kind[np.isposinf(a)] = NONFINITE_CODES["+inf"]
+    return {name: np.where(kind == 0, a, 0).astype(a.dtype), name + "_nonfinite": kind}
+
+
+def pass_outputs(tokens: np.ndarray, n_tok: np.ndarray, avg: np.ndarray, nsp: np.ndarray) -> dict:
+    """What a caller of the transcribe path receives for one pass (WhisperModel.transcribe_windows: tokens[b, :n[b]], avg logprob,
+    no-speech probability): the token rows as one [B, max_tokens] array with -1 past each clip's count; the two float outputs through
+    split_nonfinite."""
+    tokens = np.asarray(tokens)
+    n_tok = np.asarray(n_tok)
+    keep = np.arange(tokens.shape[1])[None, :] < n_tok[:, None]
+    return {"tokens": np.where(keep, tokens, -1), "n_tokens": n_tok, **split_nonfinite("avg_logprob", avg), **split_nonfinite("no_speech_prob", nsp)}
 
 
 def cpu_baseline(dims_name: str, seed: int, n_threads: int, max_new_tokens: int, repeats: int = 3):
@@ -602,6 +657,12 @@ def main():
                     help="R > 1 replicas: single = each replica's whole pass on one stream; prio = decode chains on HIGH-priority streams, every replica's "
                          "encoder half on its own normal-priority stream (mia_whisper_set_encode_stream)")
     ap.add_argument("--dp", default="abi", choices=["abi", "torch"], help="token all-gather at N > 1: mia_dp_* (RCCL behind the C ABI, ONE communicator on the rank's exchange stream) or torch.distributed")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: roofline / stages (instrumented passes; serial passes when R > 1), and the codec, "
+                         "LM, config0 and CPU-baseline legs (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed pass's outputs (tokens, n_tokens, avg_logprob, no_speech_prob; the float ones "
+                         "with a <name>_nonfinite companion marking NaN / inf entries) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -814,10 +875,11 @@ def main():
     # ---- serial execution (replica 0 alone, instrumented): `roofline` and `stages` describe THIS execution -- HIP events on the
     # library's stream over whole passes with nothing else on the GPU, next to its own wall-clock throughput -- so that one set of
     # numbers describes one execution.  (Under R concurrent streams a launch's wall duration includes waiting for the other streams'
-    # kernels and says nothing about the kernel; the pipelined timed region below therefore runs un-instrumented.)
+    # kernels and says nothing about the kernel; the pipelined timed region below therefore runs un-instrumented.)  --full only: a
+    # plain run goes from the warm-up straight to the timed region, un-instrumented at every R.
     n_serial = 1 if R == 1 else 2
     serial_exec = None
-    if R > 1:
+    if args.full and R > 1:
         # a lone decode loop streams its weights non-temporal, concurrent loops on one weight copy load them cacheable
         # (mia_whisper_set_weight_sharing): the serial execution runs in the lone-loop form -- one untimed pass re-captures the step graph
         if args.weight_sharing == "auto":
@@ -849,7 +911,7 @@ def main():
         if args.weight_sharing == "auto":
             reps[0].model.set_weight_sharing(R)
         run_passes(R)                                  # untimed: replica 0 re-captures its step graph in the shared-weights form
-    else:
+    elif args.full:
         ctx.profile(True)
         ctx.profile_reset()
     fence()
@@ -864,7 +926,10 @@ def main():
         elapsed = float(t.item())
 
     n_gen = reps[0].n_tok.cpu().numpy()
-    prof = {k: ctx.profile_read(k) for k in prof_keys} if R == 1 else prof_serial
+    if rank == 0 and args.dump_outputs:
+        last = reps[(args.steps - 1) % R]             # pass i of run_passes runs on replica i % R (both schedules)
+        dump_outputs(args.dump_outputs, pass_outputs(last.tokens.cpu().numpy(), last.n_tok.cpu().numpy(), last.avg.cpu().numpy(),
+                                                     last.nsp.cpu().numpy()))
     ms_per_step = elapsed / args.steps * 1e3
     audio_s = 30.0 * B * world
     value = audio_s * args.steps / elapsed
@@ -914,14 +979,18 @@ def main():
         stg["decode"]["steps_per_pass"] = steps_d / max(n_d, 1)
         return rl, stg
 
-    roofline, stage = summarize(prof, args.steps if R == 1 else n_serial)
-    roofline["measured_over"] = ("the timed region (serial passes)" if R == 1 else
-                                 f"{n_serial} serial passes on one replica in this process, nothing else on the GPU (`execution`); the pipelined timed region of `value` runs {R} concurrent streams un-instrumented")
-    if serial_exec:
-        roofline["execution"] = serial_exec
-    steps_d, n_d = prof["decode"][2], prof["decode"][0]
-    if R > 1:      # device-level view of the timed region: algorithmic decode bytes of every pass over the wall time (encoders run in the same time)
-        roofline["timed_region_decode_bytes_over_wall_GBs"] = round(dec_bytes_per_step * (steps_d / max(n_d, 1)) * args.steps / elapsed / 1e9, 1)
+    dec_steps = {}
+    if args.full:
+        prof = {k: ctx.profile_read(k) for k in prof_keys} if R == 1 else prof_serial
+        roofline, stage = summarize(prof, args.steps if R == 1 else n_serial)
+        roofline["measured_over"] = ("the timed region (serial passes)" if R == 1 else
+                                     f"{n_serial} serial passes on one replica in this process, nothing else on the GPU (`execution`); the pipelined timed region of `value` runs {R} concurrent streams un-instrumented")
+        if serial_exec:
+            roofline["execution"] = serial_exec
+        steps_d, n_d = prof["decode"][2], prof["decode"][0]
+        if R > 1:      # device-level view of the timed region: algorithmic decode bytes of every pass over the wall time (encoders run in the same time)
+            roofline["timed_region_decode_bytes_over_wall_GBs"] = round(dec_bytes_per_step * (steps_d / max(n_d, 1)) * args.steps / elapsed / 1e9, 1)
+        dec_steps = {"decoder_steps_per_pass": steps_d / max(n_d, 1)}
 
     out = {
         "metric": "audio-sec/s (Whisper large-v3-turbo b=32) at 1/2/4/8 GPU; codec samples/s",
@@ -931,7 +1000,7 @@ def main():
         "config": {"workload": f"Whisper {args.model} {args.dtype}, batch={B}x30 s synthetic clips per MI355X, log-mel+encode+greedy decode "
                                f"(T=0, timestamps, max_tokens 448, one window per clip), random-init N(0,0.02^2) weights",
                    "clips_per_gpu": B, "global_batch": B * world, "parallelism": f"dp{world}",
-                   "generated_tokens_per_clip_mean": float(n_gen.mean()), "decoder_steps_per_pass": steps_d / max(n_d, 1),
+                   "generated_tokens_per_clip_mean": float(n_gen.mean()), **dec_steps,
                    "realtime_factor": round(value, 1), "replicas": R, "exchange": dp_mode,
                    "schedule": args.schedule if R > 1 else "serial",
                    "pipeline": ("strictly serial passes" if R == 1 else
@@ -939,24 +1008,26 @@ def main():
                                 ("rounds of up to R passes: all encoders, then all decoders concurrently (decoders of different batches overlap each other; an encoder beside a decoder does not)"
                                  if args.schedule == "phased" else
                                  "passes dealt round-robin: the encoder of one batch overlaps the decoder of another") +
-                                "; the decode steps load the shared weights cacheable (mia_whisper_set_weight_sharing; the serial `execution` runs the lone-loop, non-temporal form)" +
+                                "; the decode steps load the shared weights cacheable (mia_whisper_set_weight_sharing" +
+                                ("; the serial `execution` runs the lone-loop, non-temporal form)" if args.full else ")") +
                                 "; every pass is a complete log-mel + encode + decode of its 32 clips")},
-        "roofline": roofline, "stages": stage,
     }
-    if rank == 0 and not args.no_codec:
+    if args.full:
+        out["roofline"], out["stages"] = roofline, stage
+    if rank == 0 and args.full and not args.no_codec:
         torch.cuda.set_stream(reps[0].stream)     # the codec leg times library work with torch events: same stream as the context
         out["codec"] = codec_bench(ctx, torch)
-    if rank == 0 and args.lm and not args.no_lm:
+    if rank == 0 and args.full and args.lm and not args.no_lm:
         try:
             out["lm"] = lm_bench(ctx, torch, args.lm, args.lm_batch)
         except Exception as e:   # the side legs must never take the headline number down with them
             out["lm"] = {"error": repr(e)}
-    if rank == 0 and not args.no_config0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_config0 and not args.no_cpu_baseline:
         try:
             out["config0"] = config0_leg(ctx, torch)
         except Exception as e:
             out["config0"] = {"error": repr(e)}
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         try:
             ncpu = min(16, len(os.sched_getaffinity(0)))   # the GPU box's CPU share for one GPU is 16 cores
             out["cpu_baseline"] = cpu_baseline(args.model, args.seed, ncpu, args.cpu_tokens)

@@ -9,10 +9,12 @@ guard for both the oracle and the HIP path), they are NOT outputs of the referen
 Inputs are stored next to the expected outputs so that the tests do not depend on RNG reproducibility; weights are NOT stored:
 they are regenerated from mlx-swift-audio_amd/synthetic.py (PCG64 streams keyed by tensor name) and a checksum of a few tensors is stored.
 """
+import contextlib
 import os
 import sys
 
 import numpy as np
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -24,6 +26,21 @@ from oracle import campplus as OCP, codec as OC, flow as OF, hift as OH, lm as O
 
 def wsum(w, keys):
     return np.asarray([float(np.asarray(w[k], np.float64).sum()) for k in keys], np.float64)
+
+
+@contextlib.contextmanager
+def oracle_f64(mod):
+    """The oracle module `mod` evaluates in float64 inside the block (its _t() casts to float64, torch's default dtype is float64): the
+    same arithmetic with rounding far below the drift guards' tolerances, so its frozen outputs reproduce on every CPU (fp32 results
+    move by a few 1e-5 with the CPU's kernel choice)."""
+    t, dt = mod._t, torch.get_default_dtype()
+    mod._t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64))
+    torch.set_default_dtype(torch.float64)
+    try:
+        yield
+    finally:
+        mod._t = t
+        torch.set_default_dtype(dt)
 
 
 def logmel():
@@ -74,6 +91,9 @@ def codecs():
     dw = S.dac_weights(dcfg, seed=4)
     dcodes = rng.integers(0, dcfg.codebook_size, (dcfg.n_codebooks, 9)).astype(np.int32)
     d.update(dac_codes=dcodes, dac_pcm=OC.DACOracle(dcfg, dw).decode_from_codes(dcodes))
+    with oracle_f64(OC):
+        d.update(snac_pcm_f64=OC.SNACOracle(cfg, w).decode([c.tolist() for c in codes], noise),
+                 dac_pcm_f64=OC.DACOracle(dcfg, dw).decode_from_codes(dcodes))
     np.savez_compressed(os.path.join(OUT, "codecs_micro.npz"), **d)
 
 

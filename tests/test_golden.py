@@ -54,15 +54,33 @@ def test_oracle_whisper_golden():
     np.testing.assert_allclose(lg, g["logits_clip0"], atol=2e-4)
 
 
-def test_oracle_codecs_golden():
+def test_oracle_codecs_golden(monkeypatch):
+    """The 1e-5 drift guard evaluates the oracle's arithmetic in float64 against float64 frozen outputs: in fp32 the SNAC / DAC stacks
+    move by 2-4e-5 with the CPU's kernel choice (AVX-512 vs AVX2 convolutions), more than the guard's tolerance, while the float64
+    evaluation agrees across CPUs to ~1e-13.  The fp32 oracle (what the GPU tests compare against) must stay within 1e-4 of it."""
+    import torch
     from oracle import codec as OC
     g = _load("codecs_micro.npz")
-    cfg = S.SNAC_CONFIGS["snac_micro"]
-    ora = OC.SNACOracle(cfg, S.snac_weights(cfg, seed=3))
+    cfg, dcfg = S.SNAC_CONFIGS["snac_micro"], S.DAC_CONFIGS["dac_micro"]
+    sw, dw = S.snac_weights(cfg, seed=3), S.dac_weights(dcfg, seed=4)
     codes = [g[f"snac_codes{i}"].tolist() for i in range(len(cfg.vq_strides))]
-    np.testing.assert_allclose(ora.decode(codes, g["snac_noise"]), g["snac_pcm"], atol=1e-5)
-    dcfg = S.DAC_CONFIGS["dac_micro"]
-    np.testing.assert_allclose(OC.DACOracle(dcfg, S.dac_weights(dcfg, seed=4)).decode_from_codes(g["dac_codes"]), g["dac_pcm"], atol=1e-5)
+    snac32 = OC.SNACOracle(cfg, sw).decode(codes, g["snac_noise"])
+    dac32 = OC.DACOracle(dcfg, dw).decode_from_codes(g["dac_codes"])
+    monkeypatch.setattr(OC, "_t", lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)))
+    dt = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    try:
+        snac64 = OC.SNACOracle(cfg, sw).decode(codes, g["snac_noise"])
+        dac64 = OC.DACOracle(dcfg, dw).decode_from_codes(g["dac_codes"])
+    finally:
+        torch.set_default_dtype(dt)
+    assert snac64.dtype == dac64.dtype == np.float64
+    np.testing.assert_allclose(snac64, g["snac_pcm_f64"], atol=1e-5)
+    np.testing.assert_allclose(dac64, g["dac_pcm_f64"], atol=1e-5)
+    np.testing.assert_allclose(snac32, g["snac_pcm_f64"], atol=1e-4)
+    np.testing.assert_allclose(dac32, g["dac_pcm_f64"], atol=1e-4)
+    np.testing.assert_allclose(g["snac_pcm"], g["snac_pcm_f64"], atol=1e-4)      # the fp32 vectors the GPU half compares against
+    np.testing.assert_allclose(g["dac_pcm"], g["dac_pcm_f64"], atol=1e-4)
 
 
 def test_oracle_cosyvoice2_golden():

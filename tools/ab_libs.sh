@@ -2,7 +2,7 @@
 # comparable inside ONE gpurun call).
 #
 #   here (CPU container):   bash tools/ab_libs.sh prepare <git-ref>     # builds <git-ref> -> ab_libs/libmia_base.so, the working tree -> ab_libs/libmia_new.so
-#   on the GPU box:         gpurun -- 'bash tools/ab_libs.sh run "python bench.py --no-lm --no-codec --no-config0 --no-cpu-baseline" 2'
+#   on the MI355X machine:  bash tools/ab_libs.sh run "python bench.py --full --no-lm --no-codec --no-config0 --no-cpu-baseline" 2
 #
 # `run` alternates base / new N times, prints value, serial-step ms and serial value of each bench line, and leaves the NEW library in place.
 # ab_libs/ is git-ignored but travels with the gpurun snapshot.
