@@ -6,7 +6,7 @@
 // (TTS/Orpheus/TTSEngine/OrpheusTTS.swift:375-470): repetition penalty -> temperature -> top-p -> categorical.
 //
 // Decode at batch 1 is HBM-bound on the weights (Orpheus-3B: 6.6 GB bf16 per token).  Every projection is the skinny
-// MFMA GEMM of decode_kernels.hip (weights HBM -> VGPR once, split-K partials summed in a fixed order by the consumer
+// MFMA GEMM of skinny_rowmajor.hip (weights HBM -> VGPR once, split-K partials summed in a fixed order by the consumer
 // kernel); RMSNorm / RoPE / KV-cache write / GQA attention / SwiGLU / sampling are fused around it; one hipGraph per token.
 // The prompt is consumed one position per step through the same graph (identical maths to a causal prefill).
 // Stochastic stage: the categorical draw takes an explicit uniform per step (inverse CDF over the kept tokens in index
@@ -17,14 +17,17 @@
 #include <string>
 #include <vector>
 
-#include "decode.h"
 #include "gemm.h"
+#include "mia_device.h"
+#include "mia_internal.h"
+#include "ops.h"
+#include "skinny.h"
 
 struct LmState { int pos; int n_hist; int finished; int n_gen; int n_embeds; int n_out; int u_cursor; int n_prompt; int min_len; int max_len; };   // min/max_len: RAS loop, per sequence
 
 struct RasParams { float top_p; int top_k; int win; float tau; int eos; int min_len; int max_len; int n_uniforms; };
 
-// MLX-affine 4- / 8-bit copy of one fused matrix in MFMA fragment order (decode_kernels.hip: skinny_gemm_qi); null = use the 16-bit weights
+// MLX-affine 4- / 8-bit copy of one fused matrix in MFMA fragment order (skinny_quant.hip: skinny_gemm_qi); null = use the 16-bit weights
 struct Q4W { uint32_t* wfrag = nullptr; float* stfrag = nullptr; };
 
 struct LmLayer {
@@ -34,7 +37,7 @@ struct LmLayer {
   void* wo = nullptr;                            // [hidden][Hq*dh]
   void* wgu = nullptr;                           // [2*inter][hidden], rows interleaved gate/up
   void* wdown = nullptr;                         // [hidden][inter]
-  // the same four in MFMA-fragment order (decode.h) for the decode step's skinny GEMMs: one contiguous 1 KB per wave load instead of
+  // the same four in MFMA-fragment order (skinny.h) for the decode step's skinny GEMMs: one contiguous 1 KB per wave load instead of
   // 16 rows x 64 B (tools/micro/skinny_probe.hip, Orpheus-3B shapes, one sequence: 48.3 -> 43.7 us per layer); the batched prompt
   // pass (gemm.hip) keeps reading the row-major copies
   void* wqkv_f = nullptr; void* wo_f = nullptr; void* wgu_f = nullptr; void* wdown_f = nullptr;
@@ -1139,7 +1142,7 @@ int lm_enqueue_step(mia_lm* m, bool sampling, const mia_lm_sampler& sp, int n_pr
   const int D = c.hidden, dh = c.head_dim, Nq = c.n_heads * dh, Nk = c.n_kv_heads * dh, Nqkv = Nq + 2 * Nk;
   const bool f16 = m->dtype == MIA_F16;
   // nb sequences = nb rows of every skinny GEMM: the weights are still read once per step
-  // RMSNorm rides on the GEMMs (decode.h, SkinnyArgs): the two residual-writing projections (o, down) add into x, emit the next block's
+  // RMSNorm rides on the GEMMs (skinny.h, SkinnyArgs): the two residual-writing projections (o, down) add into x, emit the next block's
   // activation x * norm weight (16 bit) and per-tile sums of squares; the GEMM that consumes it scales its accumulators by rstd.  Two
   // launches less per layer than "GEMM -> split-K partials -> reduce + norm kernel" (5.1 us each on Orpheus-3B, 56 per token).
   // Up to 4 sequences (the latency-critical case).  Wider batches keep the split-K + reduce / norm chain: without a cross-workgroup split the

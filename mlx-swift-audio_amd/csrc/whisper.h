@@ -20,10 +20,10 @@
 
 struct LinearW {
   void* w = nullptr;       // 16-bit [N][K]
-  void* wf = nullptr;      // decoder only: the same matrix in MFMA-fragment order (decode.h), read by the step's skinny GEMMs
+  void* wf = nullptr;      // decoder only: the same matrix in MFMA-fragment order (skinny.h), read by the step's skinny GEMMs
   float* b = nullptr;      // fp32 [N] or null
   // decoder Linears fed by a LayerNorm: c1[n] = sum_k W[n][k] gamma[k], c2[n] = sum_k W[n][k] beta[k] (fp32, of the 16-bit weights), so
-  // that LN(x) W^T = rstd (W (x * gamma) - mean c1) + c2 and the step can feed x * gamma (decode.h, "LayerNorm carried across the chain")
+  // that LN(x) W^T = rstd (W (x * gamma) - mean c1) + c2 and the step can feed x * gamma (skinny.h, "LayerNorm carried across the chain")
   float* c1 = nullptr;
   float* c2 = nullptr;
   int N = 0, K = 0;

@@ -61,7 +61,7 @@ int enqueue_step(mia_whisper* w, const DecodeParams& p, const AlignHook* hook = 
   hipStream_t s = w->ctx->stream;
   const int B = w->cur_B, D = p.D, H = p.H, C = p.n_ctx, T = w->dims.n_audio_ctx;
   const uint16_t* dh = (const uint16_t*)w->dh;
-  // A operands (dh, da, dg) and weights (LinearW::wf) are in MFMA-fragment order (decode.h); out_frag: the output is the next GEMM's A
+  // A operands (dh, da, dg) and weights (LinearW::wf) are in MFMA-fragment order (skinny.h); out_frag: the output is the next GEMM's A
   auto skinny = [&](const uint16_t* A, int64_t lda, const LinearW& lw, bool use_bias, void* out, int64_t ldo, int S, int act, int mode,
                     uint16_t* ck = nullptr, uint16_t* cv = nullptr, int out_frag = 0, const float* stat_in = nullptr, const LNW* next_ln = nullptr,
                     float* stat_out = nullptr, const float* c1 = nullptr, const float* c2 = nullptr) {
@@ -73,11 +73,11 @@ int enqueue_step(mia_whisper* w, const DecodeParams& p, const AlignHook* hook = 
     return dec_launch_skinny(w, a, mode, s);
   };
   const int S_d = pick_split(D, 2), S_4d = pick_split(4 * D, 4);   // x 4 waves of intra-workgroup split-K each
-  // LayerNorm carried across the chain (decode.h): the three residual-writing projections of a layer (self-attention out, cross-attention
+  // LayerNorm carried across the chain (skinny.h): the three residual-writing projections of a layer (self-attention out, cross-attention
   // out, fc2) add into x, store x * gamma of the NEXT LayerNorm as the next GEMM's operand plus per-tile (sum x, sum x^2); the GEMM that
   // consumes it applies mean / rstd / beta through its folded constants.  Used for the two attention output projections (8 of the 12
   // reduce + LayerNorm launches of a step go); fc2 keeps the split form (below).
-  const bool fused_ln = D % 32 == 0 && w->dec[0].qkv.c1 != nullptr;
+  const bool fused_ln = D % 32 == 0 && D <= 2048 && w->dec[0].qkv.c1 != nullptr;    // D <= 2048: the consumer sums at most 128 tiles (LnStat)
   float* st_a = w->dstat;                                          // two alternating buffers: a producer never overwrites what its
   float* st_b = w->dstat + (size_t)(D / 16) * w->cap_B * 2;        // own consumer is still reading (the chain is strictly serial anyway)
   // (the split greedy head embeds the next position itself: only the very first step needs this launch, done by the caller)

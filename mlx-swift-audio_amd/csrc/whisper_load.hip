@@ -224,7 +224,7 @@ extern "C" mia_whisper* mia_whisper_load(mia_ctx* ctx, const mia_whisper_dims* d
   }
   w->dec_ln = L.ln("decoder.ln", D);
   if (!L.err.empty()) { mia_whisper_free(w); return fail(L.err); }
-  {  // the decode step reads its weights in MFMA-fragment order (decode.h): one repack per matrix, on the device
+  {  // the decode step reads its weights in MFMA-fragment order (skinny.h): one repack per matrix, on the device
     bool ok = true;
     auto frag = [&](const void* src, int N, int K) -> void* {
       if (!ok || !src) return nullptr;
@@ -239,7 +239,7 @@ extern "C" mia_whisper* mia_whisper_load(mia_ctx* ctx, const mia_whisper_dims* d
       for (LinearW* lw : {&b.qkv, &b.out, &b.cq, &b.cout, &b.mlp1, &b.mlp2}) lw->wf = frag(lw->w, lw->N, lw->K);
     w->tok_emb_f = frag(w->tok_emb, d.n_vocab, D);
     if (!ok) { mia_whisper_free(w); return fail("fragment-order repack of the decoder weights failed"); }
-    // LayerNorm fold constants of every decoder Linear that consumes a LayerNorm (whisper.h LinearW::c1 / c2; decode.h)
+    // LayerNorm fold constants of every decoder Linear that consumes a LayerNorm (whisper.h LinearW::c1 / c2; skinny.h)
     auto fold = [&](const void* w16, int N, const LNW& ln, float** c1, float** c2, const float* bias = nullptr) {
       if (!ok || !w16) return;
       void* p1 = nullptr; void* p2 = nullptr;

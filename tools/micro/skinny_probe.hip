@@ -2,7 +2,8 @@
 // replayed from a hipGraph over a pool of distinct weight matrices larger than the 256 MB MALL (every launch streams HBM-cold weights,
 // as in the real step), in several tile / wave / pipeline forms per shape.  Prints us per launch (graph replay, boundary included).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I../../mlx-swift-audio_amd/csrc -o skinny_probe skinny_probe.hip
-#include "../../mlx-swift-audio_amd/csrc/decode_kernels.hip"
+#include "../../mlx-swift-audio_amd/csrc/skinny_rowmajor.hip"
+#include "../../mlx-swift-audio_amd/csrc/skinny_frag.hip"
 
 #include <chrono>
 #include <cstdio>
@@ -27,6 +28,53 @@ __global__ __launch_bounds__(256) void k_stream(const uint16_t* __restrict__ w, 
     for (int u = 0; u < NL; ++u) acc += v[u][0] + v[u][7];
   }
   if (acc == 0x7fffffff) out[blockIdx.x] = 1.f;
+}
+
+// the scalar-store epilogue the library's kernels started with (one 2- or 4-byte store per element): kept here as the probe's baseline
+// lane holds C[m = m0 + mt*16 + r][n = n0 + 16t + 4c + j]
+template <typename T, int MODE, int NT>
+__device__ __forceinline__ void skinny_epilogue(const SkinnyArgs& a, const f32x4 (&acc)[NT][2], int n0, int m0, int split, int lane) {
+  const int r = lane & 15, c = lane >> 4;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int n = n0 + 16 * t + 4 * c;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+      const int m = m0 + mt * 16 + r;
+      if (m >= a.M) continue;
+      const f32x4 av = acc[t][mt];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (n + j >= a.N) continue;
+        float v = av[j];
+        if (MODE == SK_PARTIAL) {
+          reinterpret_cast<float*>(a.out)[((int64_t)split * a.M + m) * a.N + n + j] = v;
+          continue;
+        }
+        if (a.bias) v += a.bias[n + j];
+        if (MODE == SK_SWIGLU) {   // interleaved rows: even column = gate, odd column = up
+          if (j & 1) continue;
+          float u = av[j + 1];
+          if (a.bias) u += a.bias[n + j + 1];
+          const float sg = v / (1.0f + __expf(-v));
+          reinterpret_cast<uint16_t*>(a.out)[(int64_t)m * a.ldo + ((n + j) >> 1)] = T::from_f32(sg * u);
+          continue;
+        }
+        if (a.act == MIA_ACT_GELU) v = gelu_erf(v);
+        if (MODE == SK_OUTF32) reinterpret_cast<float*>(a.out)[(int64_t)m * a.ldo + n + j] = v;
+        else if (MODE == SK_OUT16) reinterpret_cast<uint16_t*>(a.out)[(int64_t)m * a.ldo + n + j] = T::from_f32(v);
+        else {  // SK_QKV: [0,D) -> q, [D,2D) -> self K cache, [2D,3D) -> self V cache at position pos
+          const int nn = n + j;
+          if (nn < a.D) reinterpret_cast<uint16_t*>(a.out)[(int64_t)m * a.ldo + nn] = T::from_f32(v);
+          else {
+            const int hd = (nn - a.D) % a.D, h = hd >> 6, d = hd & 63;
+            uint16_t* cache = nn < 2 * a.D ? a.cache_k : a.cache_v;
+            cache[(((int64_t)m * a.H + h) * a.n_ctx + a.pos[m]) * 64 + d] = T::from_f32(v);
+          }
+        }
+      }
+    }
+  }
 }
 
 // dec_skinny_flat with the weights addressed in MFMA-fragment order (tile, k-step, lane): one contiguous 1 KB per wave instruction.
