@@ -62,7 +62,8 @@ int mia_synchronize(mia_ctx* ctx);
 /* ---- profiling ------------------------------------------------------------------------------ */
 /* Optional HIP-event timing of kernel classes on the ctx stream (events bracket each launch of the class).
  * Classes: "logmel" (work = algorithmic bytes), "enc_gemm", "crosskv_gemm", "enc_attention" (work = FLOPs),
- * "enc_norm" (bytes), "decode" (work = decoder steps).  Reading synchronises the stream. */
+ * "enc_norm" (bytes), "decode" (work = decoder steps), "mel_gather" (bytes; mia_whisper_encode_audio_windows).  Reading synchronises
+ * the stream. */
 int mia_profile_enable(mia_ctx* ctx, int on);
 int mia_profile_reset(mia_ctx* ctx);
 int mia_profile_read(mia_ctx* ctx, const char* kernel_class, int64_t* launches, double* total_ms, double* total_work);
@@ -285,6 +286,36 @@ int mia_whisper_set_weight_sharing(mia_whisper* w, int concurrent_readers);
 int mia_whisper_transcribe_windows(mia_whisper* w, const float* pcm, const int64_t* offs, int B, int64_t pad_right,
                                    const mia_decode_opts* opts, int32_t* tokens, int32_t* n_tokens, float* avg_logprob,
                                    float* no_speech_prob, int mem);
+
+/* ---- device-resident log-mel for the seek loop ---------------------------------------------------
+ * WhisperSTT.transcribe computes the log-mel of the WHOLE clip once (+ 30 s of zeros), keeps it on the device and slices every 30 s
+ * window out of it there (STT/Whisper/WhisperSTT.swift:140-145 whisperLogMelSpectrogram(audio:nMels:padding: nSamples); :171-182
+ * mel[seek ..< seek + segmentSize], padOrTrimMel, .asType(.float16)).  mia_whisper_audio is that tensor for a batch of clips, owned by
+ * the library.
+ *   mia_whisper_audio_create: log-mel of n_clips whole clips (pcm / offs as in mia_logmel_whisper, pcm in `mem`; pad_right zeros appended
+ *     to each, the reference passes 480000) in ONE batched launch, kept in HBM as fp32 [n_clips][F][n_mels] with
+ *     F = max_b (len_b + pad_right) / 160; frames past a clip's own count are 0.0 (as mia_logmel_whisper).  A clip's values do not
+ *     depend on the batch it is computed in.  n_mels is the model's (a multiple of 8).  NULL on failure (mia_last_error of w's context).
+ *     Free it before the context of `w`.
+ *   mia_whisper_audio_frames: F.
+ *   mia_whisper_audio_read (test hook): frames [first_frame, first_frame + n_frames) of `clip` -> out, host float32 [n_frames][n_mels]. */
+typedef struct mia_whisper_audio mia_whisper_audio;
+mia_whisper_audio* mia_whisper_audio_create(mia_whisper* w, const float* pcm, const int64_t* offs, int n_clips, int64_t pad_right,
+                                            int mem);
+void mia_whisper_audio_free(mia_whisper_audio* a);
+int64_t mia_whisper_audio_frames(const mia_whisper_audio* a);
+int mia_whisper_audio_read(mia_whisper_audio* a, int clip, int64_t first_frame, int64_t n_frames, float* out);
+/* model.encode of B windows addressed inside a resident mel (the loop body's encode, WhisperSTT.swift:171-182 -> WhisperDecoding.swift:98;
+ * findAlignment's own encoder pass, WhisperTiming.swift:590-598; detectLanguage's, WhisperSTT.swift:155-161): window b = frames
+ * [seek[b], seek[b] + n_valid[b]) of clip clip[b], zero-padded to 2*n_audio_ctx rows (padOrTrimMel), rounded to the compute dtype
+ * (round to nearest even) and written straight into the encoder's input layout by one gather kernel; then the encoder and the cross
+ * K/V exactly as mia_whisper_encode.  Bit-identical to mia_whisper_encode of the same windows sliced, padded and rounded on the host.
+ * clip / seek / n_valid are host arrays of B entries; clip[] may repeat an index.  MIA_ERR_INVALID_ARGUMENT (before anything is
+ * launched) for B <= 0, clip[b] outside [0, n_clips), seek[b] < 0, n_valid[b] outside [0, 2*n_audio_ctx], seek[b] + n_valid[b] > F,
+ * or an audio made for another n_mels or device.  Honours mia_whisper_set_encode_stream like mia_whisper_encode_windows; profiling
+ * class of the gather: "mel_gather" (work = bytes). */
+int mia_whisper_encode_audio_windows(mia_whisper* w, mia_whisper_audio* a, const int32_t* clip, const int64_t* seek,
+                                     const int32_t* n_valid, int B);
 
 /* Word-timestamp alignment: the tensor half of findAlignment (STT/Whisper/WhisperTiming.swift:558-748; model.forwardWithCrossQK,
  * STT/Whisper/WhisperModel.swift:95-99).  For every clip of the last encode: a teacher-forced decoder pass over

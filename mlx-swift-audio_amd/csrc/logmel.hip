@@ -323,6 +323,14 @@ size_t mia_logmel_scratch_bytes(int B, int64_t n_out, int n_mels) {
          align_up((size_t)B * n_out * n_mels * sizeof(float), 256);
 }
 
+// The single-pass (time-major, unit column stride) form parks only one minimum per 32-frame block where the general form keeps an fp32
+// copy of the whole output: callers that know they take it AND emit every frame of every clip (n_out >= (len_b + pad_right) / 160 for all
+// b, so that no block lies past n_out) size their scratch with this -- the resident mel of many long clips (whisper_audio.hip).
+size_t mia_logmel_direct_scratch_bytes(int B, int64_t n_out) {
+  return align_up((size_t)B * sizeof(ClipInfo), 256) + align_up((size_t)B * sizeof(int), 256) +
+         align_up((size_t)B * (size_t)((n_out + FB - 1) / FB) * sizeof(float), 256);
+}
+
 int mia_logmel_device(mia_ctx* ctx, const float* pcm_dev, const int64_t* offs_host, int B, int n_mels, int window_kind,
                       int64_t pad_right, int64_t n_out, void* out_dev, int out_dtype, bool channel_major,
                       int64_t clip_stride, int64_t row_stride, int64_t col_stride, int64_t row_off, void* scratch) {

@@ -141,12 +141,39 @@ struct mia_whisper {
   hipStream_t enc_stream = nullptr;
   hipEvent_t ev_enc_begin = nullptr, ev_enc_end = nullptr;
 
+  // ---- window table of mia_whisper_encode_audio_windows (whisper_audio.hip): one 16-byte record per batch row, staged in pinned host
+  // memory and copied on the encode's stream; ev_win marks the copy's end, so the next call waits for it before refilling the staging
+  void* win_dev = nullptr;
+  void* win_host = nullptr;
+  int win_cap = 0;
+  hipEvent_t ev_win = nullptr;
+
   // ---- test hooks (never set by the product path)
   int debug_flags = 0;                // mia_whisper_set_debug: bit 0 = launch every step directly (no hipGraph), bit 1 = one-workgroup head
   float* trace = nullptr;             // mia_whisper_trace_logits: fp32 [trace_n][n_text_ctx][V], row p = the logits computed at position p
   int32_t* trace_clips = nullptr;     // device int32 [trace_n]: batch rows traced
   int trace_n = 0;
   std::vector<int32_t> trace_clip_ids;
+};
+
+// The encoder half on its own stream (mia_whisper_set_encode_stream): everything between begin and end is enqueued on w->enc_stream, which
+// first waits for what the context's stream holds (the previous decode still reads the cross K/V this encode rewrites); the context's
+// stream then waits for the encoder's tail.  Within one handle the order of work is unchanged; across handles the encoder and decode
+// queues can now carry different priorities.
+struct EncStreamScope {
+  mia_whisper* w; hipStream_t saved; bool on;
+  explicit EncStreamScope(mia_whisper* w_) : w(w_), saved(w_->ctx->stream), on(w_->enc_stream != nullptr) {
+    if (!on) return;
+    (void)hipEventRecord(w->ev_enc_begin, saved);
+    (void)hipStreamWaitEvent(w->enc_stream, w->ev_enc_begin, 0);
+    w->ctx->stream = w->enc_stream;
+  }
+  ~EncStreamScope() {
+    if (!on) return;
+    (void)hipEventRecord(w->ev_enc_end, w->enc_stream);
+    w->ctx->stream = saved;
+    (void)hipStreamWaitEvent(saved, w->ev_enc_end, 0);
+  }
 };
 
 // whisper_encode.hip
@@ -157,6 +184,7 @@ int whisper_decode(mia_whisper* w, const mia_decode_opts* o, int32_t* tokens, in
                    float* no_speech_prob, int mem);
 // logmel.hip
 size_t mia_logmel_scratch_bytes(int B, int64_t n_out, int n_mels);
+size_t mia_logmel_direct_scratch_bytes(int B, int64_t n_out);   // enough for a time-major, unit-column-stride output (no fp32 intermediate)
 int mia_logmel_device(mia_ctx* ctx, const float* pcm_dev, const int64_t* offs_host, int B, int n_mels, int window_kind,
                       int64_t pad_right, int64_t n_out, void* out_dev, int out_dtype, bool channel_major,
                       int64_t clip_stride, int64_t row_stride, int64_t col_stride, int64_t row_off, void* scratch);

@@ -276,6 +276,9 @@ extern "C" void mia_whisper_free(mia_whisper* w) {
   for (void* p : w->allocs) (void)hipFree(p);
   if (w->ev_enc_begin) (void)hipEventDestroy(w->ev_enc_begin);
   if (w->ev_enc_end) (void)hipEventDestroy(w->ev_enc_end);
+  if (w->win_dev) (void)hipFree(w->win_dev);
+  if (w->win_host) (void)hipHostFree(w->win_host);
+  if (w->ev_win) (void)hipEventDestroy(w->ev_win);
   if (w->trace) (void)hipFree(w->trace);
   if (w->trace_clips) (void)hipFree(w->trace_clips);
   if (w->parent) w->parent->n_clones -= 1;

@@ -14,11 +14,17 @@ gives the words; add_word_timestamps deals them to the segments; seek then follo
 `hallucination_silence_threshold` the anomaly / surrounding-silence rules skip or drop hallucinated segments.
 language = None (:155-161, :662-695): `detect_fn` runs the [sot] probe on every clip's first window and each clip decodes with its
 own language token.
+
+Window references (`window_refs=True`): the reference keeps the clip's mel on the device and slices it there (:140-145, :171-182).  The
+loop then never touches a mel array: in the place of `mels`, decode_fn / align_fn / detect_fn receive the list of
+WindowRef(clip, seek, n_valid) of the rows they are asked to process, and the callbacks address a device-resident mel with them
+(WhisperSTT.transcribe(resident=True) -> whisper.WhisperAudio / WhisperModel.encode_audio_windows).
 """
 from __future__ import annotations
 
 import zlib
 from dataclasses import dataclass, field
+from typing import NamedTuple
 
 import numpy as np
 
@@ -26,6 +32,27 @@ N_FRAMES = 3000
 HOP_LENGTH = 160
 SAMPLE_RATE = 16000
 N_SAMPLES = 480000
+
+
+class WindowRef(NamedTuple):
+    """One window of the seek loop by address: frames [seek, seek + n_valid) of clip `clip`'s padded mel, zero-padded to a full window."""
+    clip: int
+    seek: int
+    n_valid: int
+
+
+TASKS = ("transcribe", "translate")
+
+
+def _check_task(task: str) -> str:
+    if task not in TASKS:
+        raise ValueError(f"task must be one of {TASKS}, got {task!r}")
+    return task
+
+
+def _rows(mels, idx):
+    """The sub-batch `idx` of a window batch in either form (numpy mels or a WindowRef list)."""
+    return mels[idx] if isinstance(mels, np.ndarray) else [mels[j] for j in idx]
 
 
 @dataclass
@@ -110,19 +137,22 @@ def transcribe_batch(full_mels: list[np.ndarray], n_samples: list[int], decode_f
                      logprob_threshold: float | None = -1.0, compression_ratio_threshold: float | None = 2.4,
                      max_tokens: int = 448, rng: np.random.Generator | None = None, n_audio_ctx: int = 1500,
                      word_timestamps: bool = False, align_fn=None, hallucination_silence_threshold: float | None = None,
-                     detect_fn=None) -> list[TranscriptionResult]:
+                     detect_fn=None, window_refs: bool = False) -> list[TranscriptionResult]:
     """full_mels[b]: log-mel of clip b + 30 s of zeros (WhisperSTT.swift:140-145), fp32 [frames, n_mels]; n_samples[b]: audio samples.
     rng supplies the explicit uniforms of the T>0 fallback draws (the reference uses an unseeded system RNG).
     language: an index for every clip, a list of per-clip indices, or None = detect (detect_fn(mels [n, 3000, n_mels]) -> [(index, prob)]);
       with per-clip languages decode_fn / align_fn receive the list as a last argument.
     word_timestamps: timestamps == .word; align_fn(mels [n, 3000, n_mels], text_tokens, num_frames[, languages]) -> list of
-      timing.WordTiming lists (findAlignment of every listed clip's window)."""
+      timing.WordTiming lists (findAlignment of every listed clip's window).
+    window_refs: full_mels is not used (pass None); wherever a callback takes `mels` it receives the list of WindowRef of the same rows
+      in the same order instead (module docstring).  Every clip's mel is taken to hold n_samples[b] // 160 + 3000 frames."""
     from . import timing as T
     n_frames = 2 * n_audio_ctx
     input_stride = n_frames // n_audio_ctx
     time_precision = float(input_stride * HOP_LENGTH) / SAMPLE_RATE
     tsb, eot = special.timestamp_begin, special.eot
-    clips = [_ClipState(m, n // HOP_LENGTH) for m, n in zip(full_mels, n_samples)]
+    clips = [_ClipState(None, n // HOP_LENGTH) for n in n_samples] if window_refs else \
+        [_ClipState(m, n // HOP_LENGTH) for m, n in zip(full_mels, n_samples)]
     rng = rng or np.random.default_rng(0)
     hst = hallucination_silence_threshold
     if word_timestamps and align_fn is None:
@@ -132,7 +162,10 @@ def transcribe_batch(full_mels: list[np.ndarray], n_samples: list[int], decode_f
     if language is None:
         if detect_fn is None:
             raise ValueError("language=None needs detect_fn")
-        first = np.stack([pad_or_trim_mel(c.mel[:n_frames], n_frames) for c in clips])
+        if window_refs:
+            first = [WindowRef(i, 0, min(n_frames, c.content_frames + N_FRAMES)) for i, c in enumerate(clips)]
+        else:
+            first = np.stack([pad_or_trim_mel(c.mel[:n_frames], n_frames) for c in clips])
         for c, (li, lp) in zip(clips, detect_fn(first)):
             c.language, c.language_prob = int(li), float(lp)
     elif per_clip_lang:
@@ -149,7 +182,10 @@ def transcribe_batch(full_mels: list[np.ndarray], n_samples: list[int], decode_f
         # ---- window of every active clip (WhisperSTT.swift:171-186)
         seg_size = {i: min(n_frames, clips[i].content_frames - clips[i].seek) for i in act}
         seg_dur = {i: seg_size[i] * HOP_LENGTH / SAMPLE_RATE for i in act}
-        mels = np.stack([pad_or_trim_mel(clips[i].mel[clips[i].seek:clips[i].seek + seg_size[i]], n_frames) for i in act])
+        if window_refs:
+            mels = [WindowRef(i, clips[i].seek, seg_size[i]) for i in act]
+        else:
+            mels = np.stack([pad_or_trim_mel(clips[i].mel[clips[i].seek:clips[i].seek + seg_size[i]], n_frames) for i in act])
         prompts = [clips[i].all_tokens[clips[i].prompt_reset_since:] if condition_on_previous_text else [] for i in act]
         # the Swift does not truncate the prompt (appendix A3); keep the tail that still leaves room to generate
         prompts = [p[-(max_tokens // 2 - 1):] for p in prompts]
@@ -163,7 +199,7 @@ def transcribe_batch(full_mels: list[np.ndarray], n_samples: list[int], decode_f
             temps = [seqs[i][min(level, len(seqs[i]) - 1)] for i in pending]
             idx = [act.index(i) for i in pending]
             uni = rng.random((len(pending), max_tokens)).astype(np.float32) if any(t > 0 for t in temps) else None
-            res = _call_decode(decode_fn, mels[idx], [prompts[j] for j in idx], temps, uni, [clips[i].language for i in pending], per_clip_lang)
+            res = _call_decode(decode_fn, _rows(mels, idx), [prompts[j] for j in idx], temps, uni, [clips[i].language for i in pending], per_clip_lang)
             nxt = []
             for i, t, r in zip(pending, temps, res):
                 clips[i].passes += 1
@@ -249,7 +285,7 @@ def transcribe_batch(full_mels: list[np.ndarray], n_samples: list[int], decode_f
             if want:
                 idx = [act.index(i) for i in want]
                 text_tokens = [[t for s in staged[i]["current"] for t in s.tokens if t < eot] for i in want]
-                args = (mels[idx], text_tokens, [seg_size[i] for i in want])
+                args = (_rows(mels, idx), text_tokens, [seg_size[i] for i in want])
                 got = align_fn(*args, [clips[i].language for i in want]) if per_clip_lang else align_fn(*args)
                 alignments = dict(zip(want, got))
 
@@ -344,62 +380,91 @@ class WhisperSTT:
         self.alignment_heads = alignment_heads            # [(layer, head)]: the checkpoint's alignment_heads (WhisperModel.swift:95-99)
         self.split_to_word_tokens = split_to_word_tokens  # tokens + [eot] -> (words, token groups) (WhisperTokenizer.swift:546-670)
 
-    def _decode_fn(self, language_index, timestamps, max_tokens):
+    def _encode(self, mels, audio):
+        """model.encode of a window batch: numpy mels go through the host (round + upload), WindowRef lists address the resident
+        `audio`.  The handle remembers the window list of its last resident encode: a request for exactly that list again (the
+        .word alignment right after a level-0 decode of the same rows, detection followed by the first decode) keeps the audio
+        features and cross K/V it already holds -- the encoder is deterministic, so this changes no result."""
+        if isinstance(mels, np.ndarray):
+            self.model.encode(mels)
+            return
+        wins = tuple((int(c), int(s), int(n)) for c, s, n in mels)
+        if self.model.last_audio_windows == (audio, wins):
+            return
+        self.model.encode_audio_windows(audio, [w[0] for w in wins], [w[1] for w in wins], [w[2] for w in wins])
+
+    def _decode_fn(self, language_index, timestamps, max_tokens, task="transcribe", audio=None):
         from . import whisper as HW
         st = self.model.special
+        _check_task(task)
 
         def fn(mels, prompts, temps, uniforms, langs=None):
-            self.model.encode(mels)
+            self._encode(mels, audio)
             inits, sot_idx = [], []
             for b, p in enumerate(prompts):
-                sot_seq = st.sot_sequence(language_index if langs is None else langs[b], "transcribe")
+                sot_seq = st.sot_sequence(language_index if langs is None else langs[b], task)
                 pre = ([st.sot_prev] + list(p)) if p else []
                 sot_idx.append(len(pre))
                 toks = pre + sot_seq + ([] if timestamps else [st.no_timestamps])
                 inits.append(toks)
-            o = HW.DecodingOptions(language_index=language_index, timestamps=timestamps, suppress_ids=self.suppress_ids, blank_ids=self.blank_ids,
-                                   max_tokens=max_tokens)
+            o = HW.DecodingOptions(task=task, language_index=language_index, timestamps=timestamps, suppress_ids=self.suppress_ids,
+                                   blank_ids=self.blank_ids, max_tokens=max_tokens)
             return self.model.decode_ragged(o, inits, sot_idx, temps, uniforms)
         return fn
 
-    def _align_fn(self, language_index):
+    def _align_fn(self, language_index, task="transcribe", audio=None):
         from . import timing as T
         st = self.model.special
+        _check_task(task)
 
         def fn(mels, text_tokens, num_frames, langs=None):
             # findAlignment runs its own encoder pass on the window (model.forwardWithCrossQK, WhisperTiming.swift:590-598)
-            self.model.encode(mels)
+            self._encode(mels, audio)
             if langs is None or len(set(langs)) <= 1:
                 li = language_index if langs is None else langs[0]
-                return T.find_alignment(self.model, text_tokens, num_frames, st.sot_sequence(li, "transcribe"), st, self.alignment_heads,
+                return T.find_alignment(self.model, text_tokens, num_frames, st.sot_sequence(li, task), st, self.alignment_heads,
                                         self.split_to_word_tokens)
             # clips with different language tokens: the sot sequence is part of the teacher-forced prefix, one call per language
             out = [None] * len(text_tokens)
             for li in sorted(set(langs)):
                 sel = [b for b, l in enumerate(langs) if l == li]
-                self.model.encode(mels[sel])
+                self._encode(_rows(mels, sel), audio)
                 for b, wt in zip(sel, T.find_alignment(self.model, [text_tokens[b] for b in sel], [num_frames[b] for b in sel],
-                                                       st.sot_sequence(li, "transcribe"), st, self.alignment_heads, self.split_to_word_tokens)):
+                                                       st.sot_sequence(li, task), st, self.alignment_heads, self.split_to_word_tokens)):
                     out[b] = wt
             return out
         return fn
 
-    def _detect_fn(self):
+    def _detect_fn(self, audio=None):
         def fn(mels):
-            self.model.encode(mels)
+            self._encode(mels, audio)
             return self.model.detect_language()
         return fn
 
-    def transcribe(self, clips, language_index=0, timestamps=True, max_tokens=448, rng=None, word_timestamps=False, **kw):
+    def transcribe(self, clips, language_index=0, timestamps=True, max_tokens=448, rng=None, word_timestamps=False, resident=True,
+                   task="transcribe", **kw):
         """language_index None = detect per clip (WhisperSTT.swift:155-161); word_timestamps = timestamps == .word (needs the
-        checkpoint's alignment_heads and a word splitter, given to the constructor)."""
+        checkpoint's alignment_heads and a word splitter, given to the constructor); task = DecodingOptions.task, "transcribe" or
+        "translate" (the task token of the sot sequence, :120,203,449).
+        resident (default): the log-mel of every whole clip is computed in one batched launch and stays on the device; the loop names
+        its windows by (clip, seek, n_valid) and they are sliced, padded and rounded there (:140-145,171-182).  resident=False computes
+        the mel clip by clip into host memory, slices and rounds it in numpy and uploads every window -- the same results bit for bit."""
         from . import audio as A
+        from . import whisper as HW
+        _check_task(task)
         d = self.model.dims
         clips = [np.ascontiguousarray(c, np.float32) for c in clips]
-        mels = [A.whisper_log_mel_spectrogram(self.ctx, c, d.n_mels, padding=N_SAMPLES) for c in clips]
         if word_timestamps and (self.alignment_heads is None or self.split_to_word_tokens is None):
             raise ValueError("word_timestamps needs alignment_heads and split_to_word_tokens")
-        return transcribe_batch(mels, [c.shape[0] for c in clips], self._decode_fn(language_index, timestamps, max_tokens), self.tokenizer,
-                                self.model.special, language=language_index, max_tokens=max_tokens, rng=rng, n_audio_ctx=d.n_audio_ctx,
-                                word_timestamps=word_timestamps, align_fn=self._align_fn(language_index) if word_timestamps else None,
-                                detect_fn=self._detect_fn() if language_index is None else None, **kw)
+        audio = HW.WhisperAudio(self.model, clips, pad_right=N_SAMPLES) if resident else None
+        mels = None if resident else [A.whisper_log_mel_spectrogram(self.ctx, c, d.n_mels, padding=N_SAMPLES) for c in clips]
+        try:
+            return transcribe_batch(mels, [c.shape[0] for c in clips], self._decode_fn(language_index, timestamps, max_tokens, task, audio),
+                                    self.tokenizer, self.model.special, language=language_index, max_tokens=max_tokens, rng=rng,
+                                    n_audio_ctx=d.n_audio_ctx, word_timestamps=word_timestamps,
+                                    align_fn=self._align_fn(language_index, task, audio) if word_timestamps else None,
+                                    detect_fn=self._detect_fn(audio) if language_index is None else None, window_refs=resident, **kw)
+        finally:
+            if audio is not None:
+                self.model.last_audio_windows = None      # the handle must not match (or keep alive) an audio that is gone
+                audio.close()

@@ -60,6 +60,16 @@ def _declare(lib):
     lib.mia_whisper_encode_windows.argtypes = [vp, vp, vp, i32, C.c_int64, i32]
     lib.mia_whisper_transcribe_windows.restype = i32
     lib.mia_whisper_transcribe_windows.argtypes = [vp, vp, vp, i32, C.c_int64, C.POINTER(_DecodeOpts), vp, vp, vp, vp, i32]
+    lib.mia_whisper_audio_create.restype = vp
+    lib.mia_whisper_audio_create.argtypes = [vp, vp, vp, i32, C.c_int64, i32]
+    lib.mia_whisper_audio_free.restype = None
+    lib.mia_whisper_audio_free.argtypes = [vp]
+    lib.mia_whisper_audio_frames.restype = C.c_int64
+    lib.mia_whisper_audio_frames.argtypes = [vp]
+    lib.mia_whisper_audio_read.restype = i32
+    lib.mia_whisper_audio_read.argtypes = [vp, i32, C.c_int64, C.c_int64, vp]
+    lib.mia_whisper_encode_audio_windows.restype = i32
+    lib.mia_whisper_encode_audio_windows.argtypes = [vp, vp, vp, vp, vp, i32]
     lib._whisper_declared = True
 
 
@@ -134,6 +144,7 @@ class WhisperModel:
         ctx.adopt(self)
         self.special = SpecialTokens.for_vocab(dims.n_vocab)
         self._keep = []
+        self.last_audio_windows = None   # (WhisperAudio, window tuple) while the handle holds the encode of exactly these windows
 
     @staticmethod
     def load(ctx: _lib.Context, dims, weights: dict[str, np.ndarray], dtype: int = _lib.BF16) -> "WhisperModel":
@@ -241,7 +252,25 @@ class WhisperModel:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, f"mel must be [B,{2 * d.n_audio_ctx},{d.n_mels}], got {mel.shape}")
         m = self.to_compute_dtype(mel) if mel.dtype == np.float32 else np.ascontiguousarray(mel)
         self.B = m.shape[0]
+        self.last_audio_windows = None
         self.ctx.check(self.ctx.lib.mia_whisper_encode(self.h, m.ctypes.data, self.B, _lib.MEM_HOST))
+
+    def encode_audio_windows(self, audio: "WhisperAudio", clip, seek, n_valid) -> None:
+        """model.encode of the windows mel[clip[b]][seek[b] : seek[b] + n_valid[b]] of a device-resident mel, zero-padded to
+        2*n_audio_ctx frames and rounded to the compute dtype on the device (mia_whisper_encode_audio_windows; the loop body's
+        padOrTrimMel(...).asType(.float16) + encode, WhisperSTT.swift:171-182).  Bit-identical to encode() of the same windows
+        sliced on the host."""
+        c = np.ascontiguousarray(clip, np.int32).reshape(-1)
+        s = np.ascontiguousarray(seek, np.int64).reshape(-1)
+        n = np.ascontiguousarray(n_valid, np.int32).reshape(-1)
+        if not (c.size == s.size == n.size):
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, "clip, seek and n_valid must have one entry per window")
+        if audio.h is None:
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, "the audio object is closed")
+        self.last_audio_windows = None
+        self.ctx.check(self.ctx.lib.mia_whisper_encode_audio_windows(self.h, audio.h, c.ctypes.data, s.ctypes.data, n.ctypes.data, int(c.size)))
+        self.B = int(c.size)
+        self.last_audio_windows = (audio, tuple(zip(c.tolist(), s.tolist(), n.tolist())))
 
     def audio_features(self) -> np.ndarray:
         d = self.dims
@@ -346,6 +375,7 @@ class WhisperModel:
         self.ctx.check(self.ctx.lib.mia_whisper_transcribe_windows(self.h, pcm.ctypes.data, offs.ctypes.data, B, pad_right, C.byref(co),
                                                                    tokens.ctypes.data, n.ctypes.data, avg.ctypes.data, nsp.ctypes.data,
                                                                    _lib.MEM_HOST))
+        self.last_audio_windows = None
         self.B = B
         return [DecodingResult(tokens[b, :n[b]].tolist(), float(avg[b]), float(nsp[b])) for b in range(B)]
 
@@ -357,6 +387,7 @@ class WhisperModel:
         host syncs of the decode loop's early-exit poll)."""
         offs = np.ascontiguousarray(offs, np.int64)
         co, keep = self._opts(o)     # three small arrays: rebuilt per call, so mutating `o` between calls takes effect
+        self.last_audio_windows = None
         self.B = len(offs) - 1
         self.ctx.check(self.ctx.lib.mia_whisper_transcribe_windows(self.h, pcm_ptr, offs.ctypes.data, self.B, pad_right, C.byref(co),
                                                                    tokens_ptr, n_ptr, avg_ptr, nsp_ptr, _lib.MEM_DEVICE))
@@ -365,6 +396,7 @@ class WhisperModel:
     def encode_windows_device(self, pcm_ptr: int, offs: np.ndarray, pad_right: int = _audio.N_SAMPLES) -> None:
         """The first half of transcribe_windows_device (log-mel + encoder, mia_whisper_encode_windows): only enqueues."""
         offs = np.ascontiguousarray(offs, np.int64)
+        self.last_audio_windows = None
         self.B = len(offs) - 1
         self.ctx.check(self.ctx.lib.mia_whisper_encode_windows(self.h, pcm_ptr, offs.ctypes.data, self.B, pad_right, _lib.MEM_DEVICE))
 
@@ -372,6 +404,49 @@ class WhisperModel:
         """The second half: greedy decode of the batch encoded last, outputs to device pointers."""
         co, keep = self._opts(o)
         self.ctx.check(self.ctx.lib.mia_whisper_decode_greedy(self.h, C.byref(co), tokens_ptr, n_ptr, avg_ptr, nsp_ptr, _lib.MEM_DEVICE))
+
+
+class WhisperAudio:
+    """Device-resident log-mel of a batch of whole clips (mia_whisper_audio): what WhisperSTT.transcribe keeps in `mel` for the
+    length of its seek loop (WhisperSTT.swift:140-145), fp32 [n_clips][frames][n_mels] in HBM, computed in one batched launch."""
+
+    def __init__(self, model: WhisperModel, clips, pad_right: int = _audio.N_SAMPLES):
+        self.ctx, self.h = model.ctx, None
+        clips = [np.ascontiguousarray(c, np.float32).reshape(-1) for c in clips]
+        if not clips:
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, "empty batch")
+        offs = np.zeros(len(clips) + 1, np.int64)
+        np.cumsum([c.shape[0] for c in clips], out=offs[1:])
+        pcm = np.concatenate(clips) if len(clips) > 1 else clips[0]
+        self.n_clips, self.n_mels = len(clips), int(model.dims.n_mels)
+        self.clip_frames = [(int(c.shape[0]) + pad_right) // _audio.HOP_LENGTH for c in clips]   # frames of each clip's own padded mel
+        h = self.ctx.lib.mia_whisper_audio_create(model.h, pcm.ctypes.data, offs.ctypes.data, len(clips), pad_right, _lib.MEM_HOST)
+        if not h:
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, self.ctx.lib.mia_last_error(self.ctx.h).decode())
+        self.h = h
+        self.ctx.adopt(self)
+
+    @property
+    def frames(self) -> int:
+        """Frames held per clip (the longest clip's count; shorter clips are followed by 0.0 rows)."""
+        return int(self.ctx.lib.mia_whisper_audio_frames(self.h))
+
+    def read(self, clip: int, first_frame: int, n_frames: int) -> np.ndarray:
+        """Test hook: frames [first_frame, first_frame + n_frames) of one clip as float32 [n_frames, n_mels]."""
+        out = np.empty((max(int(n_frames), 0), self.n_mels), np.float32)
+        self.ctx.check(self.ctx.lib.mia_whisper_audio_read(self.h, int(clip), int(first_frame), int(n_frames), out.ctypes.data))
+        return out
+
+    def close(self):
+        if self.h and getattr(self.ctx, 'h', None):
+            self.ctx.lib.mia_whisper_audio_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class GreedyDecoder:
