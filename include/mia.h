@@ -232,7 +232,10 @@ int mia_whisper_set_gemm_variant(mia_whisper* w, int variant);
 
 /* Test hooks of the decode step (never used by the product path).
  *   mia_whisper_set_debug: bit 0 = launch every step's kernels directly instead of replaying the captured hipGraph, bit 1 = the
- *     one-workgroup decode head at temperature 0 too (normally the split argmax head).  Results must not change.
+ *     one-workgroup decode head at temperature 0 too (normally the split argmax head).  Results must not change.  Bit 2 = the step
+ *     keeps every LayerNorm in its own reduce + LayerNorm kernel instead of carrying x * gamma across the attention output
+ *     projections: the control chain of tests/test_norm_carry_gpu.py (same function, other 16-bit rounding points).  Other bits are
+ *     MIA_ERR_INVALID_ARGUMENT.
  *   mia_whisper_trace_logits: from now on every decode step ALSO copies the raw fp32 logits (before the logit rules) of the listed
  *     batch rows into a trace [n_clips][n_text_ctx][n_vocab], filed under the position of the token the step consumed -- the copy is a
  *     node of the same captured step graph, so the trace is what the graph computed.  n_clips = 0 switches it off (<= 8 rows).

@@ -40,7 +40,8 @@ struct GemmArgs {
 // true when mia_gemm_launch will run these arguments on the kernel and epilogue form that implement the ln_* fields
 bool mia_gemm_ln_ok(const GemmArgs& g);
 // (mean, rstd) per row from a producer's ln_part: stat [M][2]
-int mia_ln_finalize_launch(const float* part, int n_slices, int D, float eps, float* stat, int M, hipStream_t s);
+// rs_scale: the inverse of the producer's pre-scale of x * ln_gamma (skinny.h, mia_carry_prescale); ln_c1 is folded with the scaled gamma
+int mia_ln_finalize_launch(const float* part, int n_slices, int D, float eps, float* stat, int M, hipStream_t s, float rs_scale = 1.f);
 
 // returns nullptr when the arguments satisfy the kernel's shape/alignment assumptions, else a message
 const char* mia_gemm_check(const GemmArgs& g);

@@ -33,6 +33,8 @@ struct Q4W { uint32_t* wfrag = nullptr; float* stfrag = nullptr; };
 struct LmLayer {
   Q4W q_qkv, q_o, q_gu, q_down;
   float* in_norm = nullptr; float* post_norm = nullptr;
+  // the same gains times mia_carry_prescale (skinny.h) for the fused chain's SK_RESID producers, and 1 / that scale for the consumers
+  float* in_norm_c = nullptr; float* post_norm_c = nullptr; float in_rs = 1.f, post_rs = 1.f;
   void* wqkv = nullptr; float* bqkv = nullptr;   // [(Hq+2Hkv)*dh][hidden]
   void* wo = nullptr;                            // [hidden][Hq*dh]
   void* wgu = nullptr;                           // [2*inter][hidden], rows interleaved gate/up
@@ -60,7 +62,7 @@ struct mia_lm {
   int gen_rows = 0;
   float* embeds = nullptr;      // fp32 [max_ctx][hidden]: caller-provided prompt embeddings (Qwen2LM.inference builds its prompt from three tables)
   int32_t* out_tokens = nullptr;  // [max_ctx] emitted tokens of the RAS loop
-  float* final_norm = nullptr;
+  float* final_norm = nullptr; float* final_norm_c = nullptr; float final_rs = 1.f;
   float* inv_freq = nullptr;    // [dh/2]
   std::vector<LmLayer> layers;
   // state
@@ -1106,6 +1108,15 @@ struct LmLoader {
     return p;
   }
   float* up32(const std::vector<float>& v) { float* d = (float*)dev(v.size() * 4); if (d) (void)hipMemcpy(d, v.data(), v.size() * 4, hipMemcpyHostToDevice); return d; }
+  // the gain of a carried RMSNorm times its pre-scale (skinny.h, mia_carry_prescale); *rs = 1 / scale.  `plain` when the scale is 1.
+  float* carried(const std::vector<float>& g, float* rs, float* plain) {
+    const float p = mia_carry_prescale(g.data(), (int)g.size(), m->dtype);
+    *rs = 1.f / p;
+    if (p == 1.f) return plain;
+    std::vector<float> v(g);
+    for (float& x : v) x *= p;
+    return up32(v);
+  }
   void* up16(const std::vector<float>& v) {
     std::vector<uint16_t> q(v.size());
     if (m->dtype == MIA_F16) for (size_t i = 0; i < v.size(); ++i) { _Float16 hh = (_Float16)v[i]; memcpy(&q[i], &hh, 2); }
@@ -1155,9 +1166,9 @@ int lm_enqueue_step(mia_lm* m, bool sampling, const mia_lm_sampler& sp, int n_pr
   float* ss_d = m->ss + (size_t)ss_tiles * m->B_cap;     // written by down-proj, read by the next q|k|v (or the head)
   struct Norm { const float* ss = nullptr; };            // consumer side: which partial sums (null = activation already normalised)
   auto skinny = [&](const void* A, int64_t lda, const void* W, const void* Wf, const float* bias, void* out, int64_t ldo, int N, int K, int S, int mode,
-                    const Q4W* qw = nullptr, const float* ss_in = nullptr, const float* nw = nullptr, float* ss_out = nullptr) {
+                    const Q4W* qw = nullptr, const float* ss_in = nullptr, const float* nw = nullptr, float* ss_out = nullptr, float rs_scale = 1.f) {
     SkinnyArgs a{(const uint16_t*)A, lda, (const uint16_t*)W, bias, out, ldo, nullptr, nullptr, nullptr, nb, N, K, S, MIA_ACT_NONE, 0, 0, 0};
-    if (ss_in) { a.ss_in = ss_in; a.ss_tiles = ss_tiles; a.ss_dim = D; a.eps = c.rms_eps; }
+    if (ss_in) { a.ss_in = ss_in; a.ss_tiles = ss_tiles; a.ss_dim = D; a.eps = c.rms_eps; a.rs_scale = rs_scale; }
     if (mode == SK_RESID) { a.xres = m->x; a.nw = nw; a.ss_out = ss_out; }
     if (m->q4 && qw && qw->wfrag) return skinny_gemm_q_launch(a, qw->wfrag, qw->stfrag, m->q_bits, mode, m->dtype, s);
     if (Wf) { a.W = (const uint16_t*)Wf; a.w_frag = 1; }      // same K order and partition as the row-major form: identical results
@@ -1171,13 +1182,14 @@ int lm_enqueue_step(mia_lm* m, bool sampling, const mia_lm_sampler& sp, int n_pr
     uint16_t* kc = (uint16_t*)m->k_cache + (size_t)l * layer_stride;
     uint16_t* vc = (uint16_t*)m->v_cache + (size_t)l * layer_stride;
     const float* next_norm = l + 1 < c.n_layers ? m->layers[l + 1].in_norm : m->final_norm;
+    const float* next_norm_c = l + 1 < c.n_layers ? m->layers[l + 1].in_norm_c : m->final_norm_c;
     if (fused_norm) {
       // layer 0 reads the embedding kernel's (normalised) h; later layers the previous down-proj's x * norm weight + its sums of squares
-      if (skinny(m->h, D, L.wqkv, L.wqkv_f, nullptr, m->qkv_part, 0, Nqkv, D, m->S_qkv, SK_PARTIAL, &L.q_qkv, l > 0 ? ss_d : nullptr)) return -1;
+      if (skinny(m->h, D, L.wqkv, L.wqkv_f, nullptr, m->qkv_part, 0, Nqkv, D, m->S_qkv, SK_PARTIAL, &L.q_qkv, l > 0 ? ss_d : nullptr, nullptr, nullptr, L.in_rs)) return -1;
       lm_launch_attention(m, true, nb, nullptr, kc, vc, m->att, nullptr, m->qkv_part, m->S_qkv, L.bqkv);      // RoPE + cache row + attention
-      if (skinny(m->att, Nq, L.wo, L.wo_f, nullptr, m->h, D, D, Nq, 1, SK_RESID, &L.q_o, nullptr, L.post_norm, ss_o)) return -1;
-      if (skinny(m->h, D, L.wgu, L.wgu_f, nullptr, m->act, c.inter, 2 * c.inter, D, 1, SK_SWIGLU, &L.q_gu, ss_o)) return -1;
-      if (skinny(m->act, c.inter, L.wdown, L.wdown_f, nullptr, m->h, D, D, c.inter, 1, SK_RESID, &L.q_down, nullptr, next_norm, ss_d)) return -1;
+      if (skinny(m->att, Nq, L.wo, L.wo_f, nullptr, m->h, D, D, Nq, 1, SK_RESID, &L.q_o, nullptr, L.post_norm_c, ss_o)) return -1;
+      if (skinny(m->h, D, L.wgu, L.wgu_f, nullptr, m->act, c.inter, 2 * c.inter, D, 1, SK_SWIGLU, &L.q_gu, ss_o, nullptr, nullptr, L.post_rs)) return -1;
+      if (skinny(m->act, c.inter, L.wdown, L.wdown_f, nullptr, m->h, D, D, c.inter, 1, SK_RESID, &L.q_down, nullptr, next_norm_c, ss_d)) return -1;
       continue;
     }
     if (skinny(m->h, D, L.wqkv, L.wqkv_f, nullptr, m->qkv_part, 0, Nqkv, D, m->S_qkv, SK_PARTIAL, &L.q_qkv)) return -1;
@@ -1190,7 +1202,7 @@ int lm_enqueue_step(mia_lm* m, bool sampling, const mia_lm_sampler& sp, int n_pr
   }
 #undef LAUNCH_T
   const int HV = m->head_vocab > 0 ? m->head_vocab : c.vocab;
-  if (skinny(m->h, D, m->lm_head, m->lm_head_f, m->head_bias, m->logits, HV, HV, D, 1, SK_OUTF32, &m->q_head, fused_norm && c.n_layers > 0 ? ss_d : nullptr)) return -1;
+  if (skinny(m->h, D, m->lm_head, m->lm_head_f, m->head_bias, m->logits, HV, HV, D, 1, SK_OUTF32, &m->q_head, fused_norm && c.n_layers > 0 ? ss_d : nullptr, nullptr, nullptr, m->final_rs)) return -1;
   if (ras) hipLaunchKernelGGL(lm_sample_ras, dim3(nb), dim3(1024), 0, s, m->logits, HV, m->tokens, m->out_tokens, m->uniforms, m->state, *ras, c.max_ctx);
   else if (sampling) lm_sample_launch(s, m->logits, HV, m->tokens, m->hist, m->uniforms, m->state, (SmxWs*)m->smx, sp, n_prompt, c.max_ctx, nb);
   else hipLaunchKernelGGL(lm_advance, dim3(nb), dim3(1), 0, s, m->state);
@@ -1372,7 +1384,7 @@ extern "C" mia_lm* mia_lm_load(mia_ctx* ctx, const mia_lm_config* cfg, const mia
   if (L.to_f32("model.embed_tokens.weight", t, c.vocab, D)) m->embed = L.up16(t);
   if (c.tie_embeddings) m->lm_head = m->embed;
   else if (L.find("lm_head.weight", false) && L.to_f32("lm_head.weight", t, c.vocab, D)) m->lm_head = L.up16(t);
-  if (L.to_f32("model.norm.weight", t, D, 0)) m->final_norm = L.up32(t);
+  if (L.to_f32("model.norm.weight", t, D, 0)) { m->final_norm = L.up32(t); m->final_norm_c = L.carried(t, &m->final_rs, m->final_norm); }
   if (const mia_tensor_view* hv = L.find("llm_decoder.weight", false)) {      // Qwen2LM: separate output head + speech embedding
     if (hv->ndim == 2 && hv->shape[1] == D) {
       m->head_vocab = (int)hv->shape[0];
@@ -1406,8 +1418,8 @@ extern "C" mia_lm* mia_lm_load(mia_ctx* ctx, const mia_lm_config* cfg, const mia
   for (int l = 0; l < c.n_layers && L.err.empty(); ++l) {
     const std::string p = "model.layers." + std::to_string(l);
     LmLayer& ly = m->layers[l];
-    if (L.to_f32(p + ".input_layernorm.weight", t, D, 0)) ly.in_norm = L.up32(t);
-    if (L.to_f32(p + ".post_attention_layernorm.weight", t, D, 0)) ly.post_norm = L.up32(t);
+    if (L.to_f32(p + ".input_layernorm.weight", t, D, 0)) { ly.in_norm = L.up32(t); ly.in_norm_c = L.carried(t, &ly.in_rs, ly.in_norm); }
+    if (L.to_f32(p + ".post_attention_layernorm.weight", t, D, 0)) { ly.post_norm = L.up32(t); ly.post_norm_c = L.carried(t, &ly.post_rs, ly.post_norm); }
     std::vector<float> qkv((size_t)(Nq + 2 * Nk) * D);
     if (L.to_f32(p + ".self_attn.q_proj.weight", t, Nq, D) && L.to_f32(p + ".self_attn.k_proj.weight", t2, Nk, D) && L.to_f32(p + ".self_attn.v_proj.weight", t3, Nk, D)) {
       memcpy(qkv.data(), t.data(), t.size() * 4); memcpy(qkv.data() + t.size(), t2.data(), t2.size() * 4); memcpy(qkv.data() + t.size() + t2.size(), t3.data(), t3.size() * 4);

@@ -1,6 +1,7 @@
 // skinny.h -- the skinny (M <= 32 rows per block-z) MFMA GEMMs of the per-token decode steps: modes, operand layouts, arguments and the
 // model-independent launchers.  Used by the LM step (lm.hip) and the Whisper step (decode.h); includes no model header.
 #pragma once
+#include <cmath>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -42,11 +43,29 @@ struct SkinnyArgs {
   //   rstd[m] = rsqrt(sum_t ss_in[t][m] / ss_dim + eps) before bias and activation -- linear, so it commutes with the contraction.
   float* xres = nullptr; const float* nw = nullptr; float* ss_out = nullptr;
   const float* ss_in = nullptr; int ss_tiles = 0; int ss_dim = 0; float eps = 0.f;
+  // range of the carried operand (mia_carry_prescale below): the producer's nw is the norm gain times a power of two p, the consumer
+  // multiplies rstd by rs_scale = 1 / p (exact, so inside the normal range of the 16-bit type nothing changes)
+  float rs_scale = 1.f;
   // LayerNorm form (the Whisper step, fragment-order kernels): ss_* hold PAIRS (sum x, sum x^2) per (tile, row); a consumer passes the
   // Linear's folded constants c1[n] = sum_k W[n][k] gamma[k], c2[n] = sum_k W[n][k] beta[k] and its epilogue computes
   //   LN(x) W^T = rstd (acc - mean c1) + c2      with acc = W (x * gamma), the activation the SK_RESID producer stored
   const float* c1 = nullptr; const float* c2 = nullptr;
 };
+
+// Pre-scale p = 2^-k of a carried operand x * gain (RMSNorm and LayerNorm chains, the encoder's hand-over).  The operand is rounded to
+// 16 bit BEFORE the division by rms / std, so on F16 handles its range is the residual's, not the normalised row's: a residual of 3e4
+// under a gain of 4 is inf (max 65504).  F16: k = 3 + ilogb(max |gain|), i.e. the stored |x * gain * p| < |x| / 4 whatever the gains
+// are -- finite for residuals up to 2.6e5, and a residual as small as 1e-3 (where eps starts to matter) still lands above the f16
+// subnormals' resolution: 2^-24 against 1e-4 is the 16-bit rounding of a normal value.  BF16 has fp32's range: p = 1.
+inline float mia_carry_prescale(const float* gain, int n, int dtype) {
+  if (dtype != MIA_F16) return 1.f;
+  float mx = 0.f;
+  for (int i = 0; i < n; ++i) { const float a = fabsf(gain[i]); if (a > mx) mx = a; }
+  if (!(mx > 0.f) || !std::isfinite(mx)) return 1.f;
+  int k = 3 + ilogbf(mx);
+  k = k < -24 ? -24 : (k > 40 ? 40 : k);
+  return ldexpf(1.f, -k);
+}
 
 // row-major [N][K] 16-bit -> weight fragment order (dst holds ceil(N/16)*16*K elements; rows past N are zero)
 int dec_launch_repack_wfrag(const void* src, void* dst, int N, int K, hipStream_t s);

@@ -48,7 +48,7 @@ __device__ __forceinline__ void skinny_rstd_prepare(const SkinnyArgs& a, float* 
     for (int u = 0; u < 8; ++u) { const int t = lane + 64 * u; p[u] = t < a.ss_tiles ? a.ss_in[(int64_t)t * a.M + m0 + j] : 0.f; }   // tiles <= 512
     float v = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
     v = wave_sum(v);
-    if (lane == 0) rs[j] = rsqrtf(v / (float)a.ss_dim + a.eps);
+    if (lane == 0) rs[j] = rsqrtf(v / (float)a.ss_dim + a.eps) * a.rs_scale;
   }
 }
 

@@ -119,7 +119,7 @@ struct LnStat {
       if (l16 == 0 && j < rows) {
         const float mean = v1 / (float)a.ss_dim;
         const float var = fmaxf(v2 / (float)a.ss_dim - mean * mean, 0.f);
-        st[2 * j] = mean; st[2 * j + 1] = rsqrtf(var + a.eps);
+        st[2 * j] = mean; st[2 * j + 1] = rsqrtf(var + a.eps) * a.rs_scale;      // (c1 carries the producer's pre-scale: skinny.h)
       }
     }
   }

@@ -26,12 +26,14 @@ struct LinearW {
   // that LN(x) W^T = rstd (W (x * gamma) - mean c1) + c2 and the step can feed x * gamma (skinny.h, "LayerNorm carried across the chain")
   float* c1 = nullptr;
   float* c2 = nullptr;
+  float ln_rs = 1.f;       // consumers of a CARRIED operand: 1 / the pre-scale folded into c1 and into the producer's gain (LNW::gc)
   int N = 0, K = 0;
 };
 
 struct LNW {
   float* g = nullptr;
   float* b = nullptr;
+  float* gc = nullptr;     // g x mia_carry_prescale (skinny.h): the gain a residual-writing GEMM stores x with; == g where nothing is carried
 };
 
 struct EncBlockW {
@@ -62,6 +64,7 @@ struct DecodeParams {  // immutable per graph (kernel argument, by value)
   int greedy;                   // every clip decodes at temperature 0: the argmax head may be split over several workgroups
   int trace;                    // test hook (mia_whisper_trace_logits): the step also copies the traced clips' logits out
   int head_single;              // test hook (mia_whisper_set_debug bit 1): one-workgroup head even at temperature 0
+  int split_ln;                 // test hook (mia_whisper_set_debug bit 2): no LayerNorm carried across the GEMMs (reduce + LayerNorm chain)
 };
 
 struct mia_whisper {
@@ -149,7 +152,7 @@ struct mia_whisper {
   hipEvent_t ev_win = nullptr;
 
   // ---- test hooks (never set by the product path)
-  int debug_flags = 0;                // mia_whisper_set_debug: bit 0 = launch every step directly (no hipGraph), bit 1 = one-workgroup head
+  int debug_flags = 0;                // mia_whisper_set_debug: bit 0 = launch every step directly (no hipGraph), bit 1 = one-workgroup head, bit 2 = split LayerNorm chain
   float* trace = nullptr;             // mia_whisper_trace_logits: fp32 [trace_n][n_text_ctx][V], row p = the logits computed at position p
   int32_t* trace_clips = nullptr;     // device int32 [trace_n]: batch rows traced
   int trace_n = 0;

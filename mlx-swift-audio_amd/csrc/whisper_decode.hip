@@ -68,8 +68,8 @@ int enqueue_step(mia_whisper* w, const DecodeParams& p, const AlignHook* hook = 
     SkinnyArgs a{A, lda, (const uint16_t*)lw.wf, use_bias ? lw.b : nullptr, out, ldo, ck, cv, w->clip.pos, B, lw.N, lw.K, S, act, D, H, C};
     a.out_frag = out_frag;
     a.w_keep = w->weight_sharing;
-    if (stat_in) { a.ss_in = stat_in; a.ss_tiles = D / 16; a.ss_dim = D; a.eps = 1e-5f; a.c1 = c1 ? c1 : lw.c1; a.c2 = c2 ? c2 : lw.c2; }
-    if (mode == SK_RESID) { a.xres = w->dx; a.nw = next_ln->g; a.ss_out = stat_out; }
+    if (stat_in) { a.ss_in = stat_in; a.ss_tiles = D / 16; a.ss_dim = D; a.eps = 1e-5f; a.c1 = c1 ? c1 : lw.c1; a.c2 = c2 ? c2 : lw.c2; a.rs_scale = lw.ln_rs; }
+    if (mode == SK_RESID) { a.xres = w->dx; a.nw = next_ln->gc; a.ss_out = stat_out; }
     return dec_launch_skinny(w, a, mode, s);
   };
   const int S_d = pick_split(D, 2), S_4d = pick_split(4 * D, 4);   // x 4 waves of intra-workgroup split-K each
@@ -77,7 +77,7 @@ int enqueue_step(mia_whisper* w, const DecodeParams& p, const AlignHook* hook = 
   // out, fc2) add into x, store x * gamma of the NEXT LayerNorm as the next GEMM's operand plus per-tile (sum x, sum x^2); the GEMM that
   // consumes it applies mean / rstd / beta through its folded constants.  Used for the two attention output projections (8 of the 12
   // reduce + LayerNorm launches of a step go); fc2 keeps the split form (below).
-  const bool fused_ln = D % 32 == 0 && D <= 2048 && w->dec[0].qkv.c1 != nullptr;    // D <= 2048: the consumer sums at most 128 tiles (LnStat)
+  const bool fused_ln = D % 32 == 0 && D <= 2048 && w->dec[0].qkv.c1 != nullptr && !p.split_ln;    // D <= 2048: the consumer sums at most 128 tiles (LnStat)
   float* st_a = w->dstat;                                          // two alternating buffers: a producer never overwrites what its
   float* st_b = w->dstat + (size_t)(D / 16) * w->cap_B * 2;        // own consumer is still reading (the chain is strictly serial anyway)
   // (the split greedy head embeds the next position itself: only the very first step needs this launch, done by the caller)
@@ -161,7 +161,7 @@ int whisper_decode(mia_whisper* w, const mia_decode_opts* o, int32_t* tokens, in
   p.eot = o->eot; p.no_speech = o->no_speech; p.no_timestamps = o->no_timestamps; p.timestamp_begin = o->timestamp_begin;
   p.timestamps = o->timestamps ? 1 : 0; p.max_tokens = o->max_tokens;
   p.max_initial_ts = o->max_initial_timestamp_index; p.max_new_tokens = o->max_new_tokens;
-  p.trace = w->trace ? 1 : 0; p.head_single = (w->debug_flags & 2) ? 1 : 0;
+  p.trace = w->trace ? 1 : 0; p.head_single = (w->debug_flags & 2) ? 1 : 0; p.split_ln = (w->debug_flags & 4) ? 1 : 0;
   if (w->trace)
     for (int i = 0; i < w->trace_n; ++i) MIA_CHECK_ARG(ctx, w->trace_clip_ids[i] < w->cur_B, "decode: traced clip %d is not in this batch of %d", w->trace_clip_ids[i], w->cur_B);
 
@@ -465,7 +465,7 @@ extern "C" int mia_whisper_align(mia_whisper* w, const int32_t* tokens, int stri
 // ---- test hooks ---------------------------------------------------------------------------------------------------------------------
 extern "C" int mia_whisper_set_debug(mia_whisper* w, int flags) {
   if (!w) return MIA_ERR_MODEL_NOT_LOADED;
-  MIA_CHECK_ARG(w->ctx, flags >= 0 && flags <= 3, "set_debug: flags must be 0..3 (got %d)", flags);
+  MIA_CHECK_ARG(w->ctx, flags >= 0 && flags <= 7, "set_debug: flags must be 0..7 (got %d)", flags);
   w->debug_flags = flags;
   return MIA_OK;
 }

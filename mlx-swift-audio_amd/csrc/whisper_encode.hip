@@ -171,13 +171,13 @@ int whisper_encode_from_padded_mel(mia_whisper* w, int B) {
       g1.A = w->h; g1.lda = D; g1.W = b.mlp1.w; g1.bias = b.mlp1.b; g1.act = MIA_ACT_GELU;
       g1.C = w->g; g1.ldc = 4 * D; g1.M = M; g1.N = 4 * D; g1.K = D; g1.variant = w->gemm_variant;
       GemmArgs fo = go, f1 = g1;
-      fo.ln_gamma = b.mlp_ln.g; fo.ln_out = w->h; fo.ln_ld = D; fo.ln_part = w->enc_part;
+      fo.ln_gamma = b.mlp_ln.gc; fo.ln_out = w->h; fo.ln_ld = D; fo.ln_part = w->enc_part;
       f1.ln_stat = w->enc_stat; f1.ln_c1 = b.mlp1.c1; f1.bias = b.mlp1.c2;
       const bool carry = b.mlp1.c1 && b.mlp1.c2 && mia_gemm_ln_ok(fo) && mia_gemm_ln_ok(f1);
       if ((rc = gemm(w, carry ? fo : go)) != MIA_OK) return rc;
       if (carry) {
         const int rec = mia_prof_begin(w->ctx, MIA_PROF_ENC_NORM, (double)M * (D / 64) * 8.0);
-        const int frc = mia_ln_finalize_launch(w->enc_part, D / 64, D, 1e-5f, w->enc_stat, M, s);
+        const int frc = mia_ln_finalize_launch(w->enc_part, D / 64, D, 1e-5f, w->enc_stat, M, s, b.mlp1.ln_rs);
         mia_prof_end(w->ctx, rec);
         if (frc) return mia_fail(w->ctx, MIA_ERR_DEVICE, "ln finalize launch failed");
       } else if ((rc = norm(w, b.mlp_ln, w->h, M, D)) != MIA_OK) return rc;

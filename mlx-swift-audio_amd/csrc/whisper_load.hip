@@ -106,7 +106,7 @@ struct Loader {
     LNW o;
     const mia_tensor_view* g = find(p + ".weight"); const mia_tensor_view* b = find(p + ".bias");
     if (!expect(g, {D}, p + ".weight") || !expect(b, {D}, p + ".bias")) return o;
-    std::vector<float> v; to_f32(g, v); o.g = upload_f32(v); to_f32(b, v); o.b = upload_f32(v);
+    std::vector<float> v; to_f32(g, v); o.g = upload_f32(v); o.gc = o.g; to_f32(b, v); o.b = upload_f32(v);
     return o;
   }
   // one or several [N_i][K] matrices stacked along N; bias_flags[i] says whether part i has a bias
@@ -240,6 +240,17 @@ extern "C" mia_whisper* mia_whisper_load(mia_ctx* ctx, const mia_whisper_dims* d
     w->tok_emb_f = frag(w->tok_emb, d.n_vocab, D);
     if (!ok) { mia_whisper_free(w); return fail("fragment-order repack of the decoder weights failed"); }
     // LayerNorm fold constants of every decoder Linear that consumes a LayerNorm (whisper.h LinearW::c1 / c2; skinny.h)
+    // carried LayerNorms (decoder: cross_attn_ln, mlp_ln; encoder: mlp_ln) get the pre-scaled gain of skinny.h (mia_carry_prescale)
+    auto carried = [&](LNW& ln, LinearW& consumer) {
+      if (!ok || !ln.g) return;
+      std::vector<float> g((size_t)D);
+      if (hipMemcpy(g.data(), ln.g, (size_t)D * 4, hipMemcpyDeviceToHost) != hipSuccess) { ok = false; return; }
+      const float p = mia_carry_prescale(g.data(), D, w->dtype);
+      if (p == 1.f) return;
+      for (float& v : g) v *= p;
+      ln.gc = L.upload_f32(g);
+      consumer.ln_rs = 1.f / p;
+    };
     auto fold = [&](const void* w16, int N, const LNW& ln, float** c1, float** c2, const float* bias = nullptr) {
       if (!ok || !w16) return;
       void* p1 = nullptr; void* p2 = nullptr;
@@ -248,9 +259,11 @@ extern "C" mia_whisper* mia_whisper_load(mia_ctx* ctx, const mia_whisper_dims* d
       if (hipMalloc(&p2, (size_t)N * 4) != hipSuccess) { ok = false; return; }
       w->allocs.push_back(p2);
       *c1 = (float*)p1; *c2 = (float*)p2;
-      if (dec_launch_lnfold(w16, N, D, ln.g, ln.b, *c1, *c2, w->dtype, ctx->stream, bias) != 0) ok = false;
+      if (dec_launch_lnfold(w16, N, D, ln.gc, ln.b, *c1, *c2, w->dtype, ctx->stream, bias) != 0) ok = false;
     };
     for (DecBlockW& b : w->dec) {
+      carried(b.cross_ln, b.cq);
+      carried(b.mlp_ln, b.mlp1);
       fold(b.qkv.w, b.qkv.N, b.attn_ln, &b.qkv.c1, &b.qkv.c2);
       fold(b.cq.w, b.cq.N, b.cross_ln, &b.cq.c1, &b.cq.c2);
       fold(b.mlp1.w, b.mlp1.N, b.mlp_ln, &b.mlp1.c1, &b.mlp1.c2);
@@ -258,7 +271,7 @@ extern "C" mia_whisper* mia_whisper_load(mia_ctx* ctx, const mia_whisper_dims* d
     fold(w->tok_emb, d.n_vocab, w->dec_ln, &w->emb_c1, &w->emb_c2);
     // encoder: the Linear behind mlp_ln takes its LayerNorm through the GEMM (gemm.h "LayerNorm carried across two GEMMs"); c2 includes the bias
     if (d.n_audio_state == D)
-      for (EncBlockW& b : w->enc) fold(b.mlp1.w, b.mlp1.N, b.mlp_ln, &b.mlp1.c1, &b.mlp1.c2, b.mlp1.b);
+      for (EncBlockW& b : w->enc) { carried(b.mlp_ln, b.mlp1); fold(b.mlp1.w, b.mlp1.N, b.mlp_ln, &b.mlp1.c1, &b.mlp1.c2, b.mlp1.b); }
     if (!ok) { mia_whisper_free(w); return fail("LayerNorm fold of the decoder weights failed"); }
   }
   if (hipDeviceSynchronize() != hipSuccess) { mia_whisper_free(w); return fail("device error during upload"); }

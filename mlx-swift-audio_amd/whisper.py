@@ -179,7 +179,7 @@ class WhisperModel:
         self.ctx.check(lib.mia_whisper_set_gemm_variant(self.h, int(variant)))
 
     def set_debug(self, flags: int) -> None:
-        """Test hook (mia_whisper_set_debug): bit 0 = no hipGraph, bit 1 = one-workgroup head."""
+        """Test hook (mia_whisper_set_debug): bit 0 = no hipGraph, bit 1 = one-workgroup head, bit 2 = split reduce + LayerNorm chain (no carried LayerNorm)."""
         lib = self.ctx.lib
         lib.mia_whisper_set_debug.restype = C.c_int
         lib.mia_whisper_set_debug.argtypes = [C.c_void_p, C.c_int]

@@ -49,6 +49,7 @@ class LMOracle:
         self.w = {k: torch.from_numpy(np.ascontiguousarray(v, np.float32)) for k, v in weights.items()}
         self.freqs = torch.from_numpy(llama3_freqs(cfg.head_dim, cfg.rope_theta, cfg.rope_llama3, cfg.rope_factor, cfg.rope_low,
                                                    cfg.rope_high, cfg.rope_old_ctx))
+        self.taps = None            # test hook: a list here receives (norm name, residual [L, hidden]) at every o-proj / down-proj hand-over
         self.reset()
 
     def reset(self):
@@ -102,10 +103,14 @@ class LMOracle:
                 s = s.masked_fill(~mask, -float("inf"))
             o = (torch.softmax(s, dim=-1) @ vv).transpose(0, 1).reshape(L, -1)
             h = h + o @ W[p + ".self_attn.o_proj.weight"].t()
+            if self.taps is not None:
+                self.taps.append((p + ".post_attention_layernorm", h.clone()))
             xn = _rms(h, W[p + ".post_attention_layernorm.weight"], c.rms_eps)
             g = xn @ W[p + ".mlp.gate_proj.weight"].t()
             u = xn @ W[p + ".mlp.up_proj.weight"].t()
             h = h + (torch.nn.functional.silu(g) * u) @ W[p + ".mlp.down_proj.weight"].t()
+            if self.taps is not None:
+                self.taps.append((f"model.layers.{l + 1}.input_layernorm" if l + 1 < c.n_layers else "model.norm", h.clone()))
         self.offset += L
         return _rms(h, W["model.norm.weight"], c.rms_eps)
 

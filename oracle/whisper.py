@@ -114,6 +114,7 @@ class WhisperOracle:
             self.w["encoder.positional_embedding"] = _t(sinusoids(dims.n_audio_ctx, dims.n_audio_state))
         if threads:
             torch.set_num_threads(threads)
+        self.taps = None            # test hook: a list here receives (LayerNorm name, residual [B, n, D]) in front of every cross_attn_ln / mlp_ln
         n = dims.n_text_ctx
         idx = torch.arange(n)
         self.mask = torch.where(idx[:, None] < idx[None, :], torch.tensor(-float("inf")), torch.tensor(0.0))  # TextDecoder.swift:38-42
@@ -161,11 +162,15 @@ class WhisperOracle:
         x = x + y
         new_cross = cross_kv
         if xa is not None:
+            if self.taps is not None:
+                self.taps.append((p + ".cross_attn_ln", x.clone()))
             y, new_cross, cqk = self._attn(p + ".cross_attn", _layer_norm(x, W[p + ".cross_attn_ln.weight"], W[p + ".cross_attn_ln.bias"]),
                                            n_head, xa=xa, kv_cache=cross_kv)
             if cross_qk_out is not None:
                 cross_qk_out.append(cqk)
             x = x + y
+        if self.taps is not None:
+            self.taps.append((p + ".mlp_ln", x.clone()))
         h = _layer_norm(x, W[p + ".mlp_ln.weight"], W[p + ".mlp_ln.bias"])
         x = x + _linear(_gelu(_linear(h, W[p + ".mlp1.weight"], W[p + ".mlp1.bias"])), W[p + ".mlp2.weight"], W[p + ".mlp2.bias"])
         return x, (new_self, new_cross)

@@ -132,7 +132,9 @@ def test_trace_hook_errors(ctx):
     with pytest.raises(m.MiaError):
         model.read_logit_trace(0, 0, 1)                     # no trace requested
     with pytest.raises(m.MiaError):
-        model.set_debug(4)
+        model.set_debug(8)                                  # bits 0..2 are hooks; anything above is rejected
+    with pytest.raises(m.MiaError):
+        model.set_debug(-1)
     model.trace_logits([3])
     model.encode(_mel(dims, 2, 0, "f16"))
     from mlx_swift_audio_amd import whisper as HW
