@@ -1,0 +1,90 @@
+// lm.h -- host-side interface between the LM decode sources: lm.hip (step kernels, prompt pass, step graph, entry points),
+// lm_sample.hip (the top-p and RAS samplers) and lm_load.hip (checkpoint loader, state buffers, packed-weight attach).
+#pragma once
+#include <vector>
+
+#include "mia_internal.h"
+
+struct LmState { int pos; int n_hist; int finished; int n_gen; int n_embeds; int n_out; int u_cursor; int n_prompt; int min_len; int max_len; };   // min/max_len: RAS loop, per sequence
+
+struct RasParams { float top_p; int top_k; int win; float tau; int eos; int min_len; int max_len; int n_uniforms; };
+
+// MLX-affine 4- / 8-bit copy of one fused matrix in MFMA fragment order (skinny_quant.hip: skinny_gemm_qi); null = use the 16-bit weights
+struct Q4W { uint32_t* wfrag = nullptr; float* stfrag = nullptr; };
+
+struct LmLayer {
+  Q4W q_qkv, q_o, q_gu, q_down;
+  float* in_norm = nullptr; float* post_norm = nullptr;
+  // the same gains times mia_carry_prescale (skinny.h) for the fused chain's SK_RESID producers, and 1 / that scale for the consumers
+  float* in_norm_c = nullptr; float* post_norm_c = nullptr; float in_rs = 1.f, post_rs = 1.f;
+  void* wqkv = nullptr; float* bqkv = nullptr;   // [(Hq+2Hkv)*dh][hidden]
+  void* wo = nullptr;                            // [hidden][Hq*dh]
+  void* wgu = nullptr;                           // [2*inter][hidden], rows interleaved gate/up
+  void* wdown = nullptr;                         // [hidden][inter]
+  // the same four in MFMA-fragment order (skinny.h) for the decode step's skinny GEMMs: one contiguous 1 KB per wave load instead of
+  // 16 rows x 64 B (tools/micro/skinny_probe.hip, Orpheus-3B shapes, one sequence: 48.3 -> 43.7 us per layer); the batched prompt
+  // pass (gemm.hip) keeps reading the row-major copies
+  void* wqkv_f = nullptr; void* wo_f = nullptr; void* wgu_f = nullptr; void* wdown_f = nullptr;
+};
+
+struct mia_lm {
+  mia_ctx* ctx = nullptr;
+  mia_lm_config cfg{};
+  int dtype = MIA_BF16;
+  std::vector<void*> allocs;
+  void* embed = nullptr;        // 16-bit [V][hidden]
+  void* lm_head = nullptr;      // 16-bit [V][hidden] (== embed when tied)
+  void* lm_head_f = nullptr;    // lm_head in MFMA-fragment order (decode step)
+  Q4W q_head;                   // 4-bit copy of lm_head (mia_lm_attach_q4)
+  int q_bits = 0;               // 4 | 8 once packed weights are attached (mia_lm_attach_quantized), 0 = none
+  bool q4 = false;              // the step GEMVs stream the packed weights
+  float* head_bias = nullptr;   // optional (CosyVoice2 llm_decoder)
+  int head_vocab = 0;           // rows of lm_head (CosyVoice2: speech vocabulary + 3)
+  void* gen_embed = nullptr;    // 16-bit [rows][hidden]: embedding of GENERATED ids when it differs from embed (speech_embedding)
+  int gen_rows = 0;
+  float* embeds = nullptr;      // fp32 [max_ctx][hidden]: caller-provided prompt embeddings (Qwen2LM.inference builds its prompt from three tables)
+  int32_t* out_tokens = nullptr;  // [max_ctx] emitted tokens of the RAS loop
+  float* final_norm = nullptr; float* final_norm_c = nullptr; float final_rs = 1.f;
+  float* inv_freq = nullptr;    // [dh/2]
+  std::vector<LmLayer> layers;
+  // state
+  void* k_cache = nullptr; void* v_cache = nullptr;   // [L][Hkv][max_ctx][dh]
+  float* x = nullptr; void* h = nullptr; float* qkv_part = nullptr; void* q = nullptr; void* att = nullptr; void* act = nullptr;
+  float* partial = nullptr; float* logits = nullptr;
+  float* ss = nullptr;          // [2][hidden / 16][B]: per-tile partial sums of squares of the residual stream (SK_RESID producers)
+  int32_t* tokens = nullptr;    // [max_ctx] full sequence
+  int32_t* hist = nullptr;      // [64] repetition window (ring, oldest first)
+  float* uniforms = nullptr;    // [max_ctx]
+  void* smx = nullptr;            // top-p sampler scratch, lm_sample_ws_bytes() per sequence (slice records + radix slabs)
+  LmState* state = nullptr;
+  hipGraphExec_t graph = nullptr;       // one decode step (forward / top-p sampler / RAS sampler), re-captured when its sampler arguments change
+  int graph_mode = -1;                  // 0 forward, 1 top-p, 2 RAS
+  int debug_flags = 0;                  // test hook (mia_lm_set_debug): bit 0 = no hipGraph, bit 1 = no batched prompt pass
+  mia_lm_sampler graph_sampler{};
+  RasParams graph_ras{};
+  int S_qkv = 1, S_o = 1, S_down = 1;
+  // batched prompt pass (lm_prefill_rows): row buffers for one chunk of PF_ROWS positions, allocated on first use
+  char* pf_buf = nullptr;
+  // sequences decoded side by side (mia_lm_set_batch): every state buffer above holds B_cap rows / caches; the single-sequence entry
+  // points use row 0
+  int B_cap = 1;
+  int graph_nb = 0;
+  std::vector<void*> state_allocs;
+};
+
+// launch a kernel template's F16 or BF16 instance; expects `const bool f16` and `hipStream_t s` in scope
+#define LAUNCH_T(kern, grid, block, lds, ...) do { if (f16) hipLaunchKernelGGL((kern<F16>), grid, block, lds, s, __VA_ARGS__); else hipLaunchKernelGGL((kern<BF16>), grid, block, lds, s, __VA_ARGS__); } while (0)
+
+// ---- lm_sample.hip: row b of every array belongs to sequence b (logits [B][V]; tokens / uniforms / out_tokens [B][max_ctx]; hist [B][64]) ----
+// top-p sampler, six launches.  ws: lm_sample_ws_bytes() per sequence.  n_prompt < 0: every sequence's state holds its own prompt length
+void lm_sample_launch(hipStream_t s, float* logits, int V, int32_t* tokens, int32_t* hist, const float* uniforms, LmState* st, void* ws, const mia_lm_sampler& sp,
+                      int n_prompt, int max_ctx, int B);
+size_t lm_sample_ws_bytes();
+// RAS sampler, one launch; V <= LM_RAS_MAX_VOCAB (the kernel keeps the whole row in registers)
+constexpr int LM_RAS_MAX_VOCAB = 8192;
+void lm_sample_ras_launch(hipStream_t s, const float* logits, int V, int32_t* tokens, int32_t* out_tokens, const float* uniforms, LmState* st, const RasParams& rp,
+                          int max_ctx, int B);
+
+// ---- lm_load.hip ----
+// every per-sequence buffer, for B sequences side by side (rows of the skinny GEMMs; caches [L][B][Hkv][max_ctx][dh]); drops the step graph
+int lm_alloc_state(mia_lm* m, int B);

@@ -1,5 +1,5 @@
 // skinny.h -- the skinny (M <= 32 rows per block-z) MFMA GEMMs of the per-token decode steps: modes, operand layouts, arguments and the
-// model-independent launchers.  Used by the LM step (lm.hip) and the Whisper step (decode.h); includes no model header.
+// model-independent launchers.  Used by the LM step (lm.hip; fragment repack at load in lm_load.hip) and the Whisper step (decode.h); includes no model header.
 #pragma once
 #include <cmath>
 #include <hip/hip_runtime.h>

@@ -39,7 +39,7 @@ __device__ __forceinline__ bool skinny_wave_reduce(f32x4 (&acc)[NT][2], int wave
 // reduction barrier when the workgroup has one) reads rs[row].  Lanes take tiles t = lane, lane + 64, ...; fixed-order sums.
 __device__ __forceinline__ void skinny_rstd_prepare(const SkinnyArgs& a, float* rs, int m0, int wave, int lane) {
   if (!a.ss_in || wave != 0) return;
-  // (the LM step uses this form with at most 4 rows -- lm.hip keeps the unfused chain for wider batches -- so a row at a time is fine:
+  // (the LM step uses this form with at most 4 rows -- lm.hip:lm_enqueue_step keeps the unfused chain for wider batches -- so a row at a time is fine:
   // all of a row's loads are issued together, one wave reduction per row)
   const int rows = a.M - m0 < 32 ? a.M - m0 : 32;
   for (int j = 0; j < rows; ++j) {

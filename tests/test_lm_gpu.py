@@ -254,6 +254,48 @@ def test_ras_batch_equals_single_utterance_runs(ctx):
     model.close()
 
 
+@pytest.mark.parametrize("kind", ["top_p", "ras"])
+def test_direct_launch_equals_graph(ctx, kind):
+    """The four generate entry points with every step launched directly (set_debug(1)) against the replayed step graph (set_debug(0)),
+    same handle, prompts and uniforms: both modes issue the same kernels with the same arguments, so the ids are identical, and batch
+    equals solo inside each mode.  Top-p: prompts of 8 and 9 ids straddle the single-sequence prompt-pass threshold (7 positions walk
+    the step, 8 take the batched pass), 40 new tokens cross two polls of `finished`, and the drawn stop id ends some sequences early."""
+    import mlx_swift_audio_amd as m
+    from mlx_swift_audio_amd import lm as HL
+    if kind == "top_p":
+        cfg = S.LM_CONFIGS["llama-micro128"]
+        model = HL.CausalLM.load(ctx, cfg, S.lm_weights(cfg, seed=8, round_to="bf16"), m.BF16)
+        rng = np.random.default_rng(5)
+        prompts = [rng.integers(0, cfg.vocab - 1, n).tolist() for n in (1, 8, 9, 17)]
+        n_new = 40
+        u = rng.random((len(prompts), n_new)).astype(np.float32)
+        stop = int(rng.integers(0, cfg.vocab))
+        kw = dict(temperature=0.8, top_p=0.9, rep_penalty=1.2, rep_window=16, max_new_tokens=n_new, stop_ids=(stop,))
+        solo = lambda: [model.generate(p, u[b], **kw) for b, p in enumerate(prompts)]
+        batch = lambda: model.generate_batch(prompts, u, **kw)
+    else:
+        cfg = S.LM_CONFIGS["qwen-micro"]
+        S_TOK = 200
+        w = S.lm_weights(cfg, seed=5, round_to="f16")
+        w.update(S.qwen2lm_extra_weights(cfg, S_TOK, seed=5, round_to="f16"))
+        model = HL.CausalLM.load(ctx, cfg, w, m.F16)
+        rng = np.random.default_rng(11)
+        xs = [rng.standard_normal((n, cfg.hidden)).astype(np.float32) for n in (15, 4, 33, 9)]
+        mins, maxs = [12, 3, 20, 8], [60, 25, 90, 40]
+        u = rng.random((len(xs), 600)).astype(np.float32)
+        solo = lambda: [model.generate_ras(xs[b], u[b], mins[b], maxs[b], S_TOK) for b in range(len(xs))]
+        batch = lambda: model.generate_ras_batch(xs, u, mins, maxs, S_TOK)
+    model.set_batch(4)
+    got = {}
+    for flags in (0, 1):
+        model.set_debug(flags)
+        got[flags] = (solo(), batch())
+        assert got[flags][1] == got[flags][0], flags       # batch == solo inside the mode
+        assert all(len(ids) > 0 for ids in got[flags][0])
+    assert got[1] == got[0]                                # direct launch == graph replay, every call
+    model.close()
+
+
 def test_orpheus_sentence_loop_batched_equals_sequential(ctx):
     """OrpheusTTS mirror: generate_chunks (sentences side by side) returns, per sentence, what generate_chunk returns.  (With a
     3 000-id micro vocabulary no id falls in Orpheus' audio-code range, so the SNAC leg yields empty audio on both sides; the SNAC
