@@ -366,6 +366,25 @@ int mia_snac_decode(mia_codec* c, const int32_t* const* codes, const int32_t* n_
 /* Replaces DACCodec.decodeFromCodes (Codec/DAC/DACModel.swift:303-306) for one sequence: codes int32 [n_codebooks][T]. */
 int mia_dac_decode(mia_codec* c, const int32_t* codes, int n_codebooks, int64_t T, float* pcm, int64_t pcm_capacity,
                    int64_t* n_samples, int mem);
+/* n_utt utterances in one pass; utterance u = mia_snac_decode of its own codes / noise, bit for bit (every convolution runs once over
+ * the stacked sequences; a sequence's rows past its own end read as zero, exactly the padding a single call sees).
+ * codes: utterance after utterance, level after level, concatenated; n_codes[u*n_levels + i] ids of level i of utterance u (a level
+ *        whose expansion differs from that utterance's latent length is skipped for that utterance only).
+ * noise: each utterance's slab exactly as mia_snac_decode takes it, concatenated (slab u holds mia_codec_noise_len(T0_u) values), or NULL.
+ * pcm:   utterance u at pcm + pcm_off[u]; pcm_off has n_utt + 1 entries, pcm_off[u+1] - pcm_off[u] >= mia_codec_output_len(T0_u);
+ *        n_samples[u] receives the count.  1 <= n_utt <= 64.
+ * n_codes, pcm_off and n_samples are HOST arrays whatever `mem` is; `mem` describes codes, noise and pcm.  Scratch: three buffers of
+ * n_utt x (largest stage of the longest utterance), grow-only. */
+int mia_snac_decode_batch(mia_codec* c, int n_utt, const int32_t* codes, const int32_t* n_codes, int n_levels, const float* noise,
+                          int64_t n_noise, float* pcm, const int64_t* pcm_off, int64_t* n_samples, int mem);
+/* The same for DAC: codes of utterance u are [n_codebooks][T[u]], utterances concatenated; T (host) has n_utt entries. */
+int mia_dac_decode_batch(mia_codec* c, int n_utt, const int32_t* codes, int n_codebooks, const int64_t* T, float* pcm,
+                         const int64_t* pcm_off, int64_t* n_samples, int mem);
+/* Bytes of activations (all utterances, three buffers) up to which a stage of the batch entries runs stacked; from the first stage
+ * above it every utterance runs the rest of the program on its own, with the single call's launches.  Stage 0 always runs stacked.
+ * Default: 256 MiB (the Infinity Cache) for SNAC, whose late stages are memory-bound; no limit for DAC.  bytes < 0 restores the
+ * handle's default.  The waveforms do not depend on it, only the time. */
+int mia_codec_set_stack_budget(mia_codec* c, int64_t bytes);
 /* Encoder side of the DAC codec: replaces DACCodec.encode (Codec/DAC/DACModel.swift:284-296): preprocess (right-pad to the hop
  * length :308-317) -> DACEncoder (:43-86; blocks :15-38) -> residual vector quantisation (DACQuantize.swift:147-190, nearest entry
  * on L2-normalised vectors :87-115, first index on ties).  mia_dac_load_encoder attaches the `encoder.*` and

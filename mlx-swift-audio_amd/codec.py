@@ -50,7 +50,16 @@ def _declare(lib):
     lib.mia_snac_decode.argtypes = [vp, C.POINTER(vp), vp, i32, vp, i64, vp, i64, C.POINTER(i64), i32]
     lib.mia_dac_decode.restype = i32
     lib.mia_dac_decode.argtypes = [vp, vp, i32, i64, vp, i64, C.POINTER(i64), i32]
+    lib.mia_snac_decode_batch.restype = i32
+    lib.mia_snac_decode_batch.argtypes = [vp, i32, vp, vp, i32, vp, i64, vp, vp, vp, i32]
+    lib.mia_dac_decode_batch.restype = i32
+    lib.mia_dac_decode_batch.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32]
+    lib.mia_codec_set_stack_budget.restype = i32
+    lib.mia_codec_set_stack_budget.argtypes = [vp, i64]
     lib._codec_declared = True
+
+
+MAX_BATCH = 64          # utterances per mia_*_decode_batch call
 
 
 def _views(weights):
@@ -74,6 +83,10 @@ class _Codec:
 
     def noise_len(self, latent_len: int) -> int:
         return int(self.ctx.lib.mia_codec_noise_len(self.h, latent_len))
+
+    def set_stack_budget(self, n_bytes: int) -> None:
+        """mia_codec_set_stack_budget: up to which activation size a stage of decode_batch runs stacked (negative = default)."""
+        self.ctx.check(self.ctx.lib.mia_codec_set_stack_budget(self.h, n_bytes))
 
     def close(self):
         if self.h and getattr(self.ctx, 'h', None):
@@ -112,6 +125,27 @@ class SNACDecoder(_Codec):
                                                     0 if nz is None else nz.size, pcm.ctypes.data, pcm.size, C.byref(ns), _lib.MEM_HOST))
         return pcm[:ns.value]
 
+    def decode_batch(self, codes_list: list[list[list[int]]], noises: list | None = None) -> list[np.ndarray]:
+        """mia_snac_decode_batch: several utterances in one pass (at most MAX_BATCH); codes_list[u] is what decode() takes, noises a
+        matching list of arrays or None.  Every waveform equals its own decode(...) bit for bit."""
+        U, nl = len(codes_list), max(len(c) for c in codes_list)
+        n = np.zeros((U, nl), np.int32)
+        flat, T0 = [], []
+        for u, codes in enumerate(codes_list):
+            arrs = [np.ascontiguousarray(c, np.int32).reshape(-1) for c in codes]
+            n[u, :len(arrs)] = [a.size for a in arrs]
+            flat += arrs
+            T0.append(max([int(a.size) * s for a, s in zip(arrs, self.cfg.vq_strides)], default=0))
+        codes = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(0, np.int32))
+        nz = None if noises is None else np.ascontiguousarray(np.concatenate([np.asarray(z, np.float32).reshape(-1) for z in noises]))
+        off = np.zeros(U + 1, np.int64)
+        off[1:] = np.cumsum([self.output_len(t) for t in T0])
+        pcm = np.empty(max(int(off[-1]), 1), np.float32)
+        ns = np.zeros(U, np.int64)
+        self.ctx.check(self.ctx.lib.mia_snac_decode_batch(self.h, U, codes.ctypes.data, n.ctypes.data, nl, None if nz is None else nz.ctypes.data,
+                                                          0 if nz is None else nz.size, pcm.ctypes.data, off.ctypes.data, ns.ctypes.data, _lib.MEM_HOST))
+        return [pcm[off[u]:off[u] + ns[u]].copy() for u in range(U)]
+
 
 class DACCodec(_Codec):
     @staticmethod
@@ -140,14 +174,39 @@ class DACCodec(_Codec):
         return codes[:, :ns.value]
 
     def decode_from_codes(self, codes: np.ndarray) -> np.ndarray:
-        """decodeFromCodes: codes int [B, n_codebooks, T] (or [n_codebooks, T]) -> float32 [B, samples] (or [samples])."""
+        """decodeFromCodes: codes int [B, n_codebooks, T] (or [n_codebooks, T]) -> float32 [B, samples] (or [samples]).  B > 1 goes
+        through mia_dac_decode_batch, MAX_BATCH sequences per call."""
         codes = np.ascontiguousarray(codes, np.int32)
         single = codes.ndim == 2
         if single:
             codes = codes[None]
         B, ncb, T = codes.shape
         out = np.empty((B, self.output_len(T)), np.float32)
-        for b in range(B):
+        if B == 1:
             ns = C.c_int64(0)
-            self.ctx.check(self.ctx.lib.mia_dac_decode(self.h, codes[b].ctypes.data, ncb, T, out[b].ctypes.data, out.shape[1], C.byref(ns), _lib.MEM_HOST))
+            self.ctx.check(self.ctx.lib.mia_dac_decode(self.h, codes[0].ctypes.data, ncb, T, out[0].ctypes.data, out.shape[1], C.byref(ns), _lib.MEM_HOST))
+        for b in range(0, B if B > 1 else 0, MAX_BATCH):
+            n = min(MAX_BATCH, B - b)
+            Ts = np.full(n, T, np.int64)
+            off = np.arange(n + 1, dtype=np.int64) * out.shape[1]
+            ns = np.zeros(n, np.int64)
+            self.ctx.check(self.ctx.lib.mia_dac_decode_batch(self.h, n, codes[b].ctypes.data, ncb, Ts.ctypes.data, out[b].ctypes.data, off.ctypes.data,
+                                                             ns.ctypes.data, _lib.MEM_HOST))
         return out[0] if single else out
+
+    def decode_batch(self, codes_list: list[np.ndarray]) -> list[np.ndarray]:
+        """mia_dac_decode_batch on ragged input: codes_list[u] int [n_codebooks, T_u] (at most MAX_BATCH) -> one float32 [samples_u] each,
+        bit-identical to decode_from_codes of each alone."""
+        arrs = [np.ascontiguousarray(c, np.int32) for c in codes_list]
+        U, ncb = len(arrs), arrs[0].shape[0]
+        if any(a.ndim != 2 or a.shape[0] != ncb for a in arrs):
+            raise ValueError("decode_batch: every utterance must be [n_codebooks, T]")
+        Ts = np.asarray([a.shape[1] for a in arrs], np.int64)
+        codes = np.ascontiguousarray(np.concatenate([a.reshape(-1) for a in arrs]))
+        off = np.zeros(U + 1, np.int64)
+        off[1:] = np.cumsum([self.output_len(int(t)) for t in Ts])
+        pcm = np.empty(max(int(off[-1]), 1), np.float32)
+        ns = np.zeros(U, np.int64)
+        self.ctx.check(self.ctx.lib.mia_dac_decode_batch(self.h, U, codes.ctypes.data, ncb, Ts.ctypes.data, pcm.ctypes.data, off.ctypes.data,
+                                                         ns.ctypes.data, _lib.MEM_HOST))
+        return [pcm[off[u]:off[u] + ns[u]].copy() for u in range(U)]

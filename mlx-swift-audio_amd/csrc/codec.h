@@ -36,6 +36,9 @@ struct ConvGemmArgs {
   int n_seq = 1;
   int64_t x_seq_step = 0, y_seq_step = 0;
   const int32_t* seq_len = nullptr;    // device [n_seq], optional
+  // noise term under stacked sequences (needs seq_len, T_out rows == T_in rows): sequence u's value for row r is
+  // noise[noise_seq_off[u] + r]; its rows at or past seq_len[u] have no noise value and are not written
+  const int32_t* noise_seq_off = nullptr;   // device [n_seq]
 };
 
 constexpr int MIA_MAX_LEVELS = 4;
@@ -46,6 +49,21 @@ struct EmbedArgs {
   const float* bias[MIA_MAX_LEVELS];      // [C]
   int stride[MIA_MAX_LEVELS];
   int n_levels, cb_dim;
+  // stacked sequences: level l of sequence u reads codes_base + seq_code_off[u * MIA_MAX_LEVELS + l] (negative = skipped for that
+  // sequence); codes[] is then unused
+  const int32_t* codes_base;
+  const int64_t* seq_code_off;            // device [n_seq][MIA_MAX_LEVELS], or null
+};
+
+// Stacked sequences for the element-wise kernels, in the tap GEMM's layout: n sequences side by side, sequence u at row u * step of the
+// buffer (step = 0: T, the launch's rows per sequence), len[u] <= T of them valid.  Rows at or past len[u] read as zero, like rows past T in a single call,
+// and are never written.  n = 1 with len = null: the single-sequence launch, unchanged.
+struct SeqArgs {
+  int n = 1;
+  const int32_t* len = nullptr;           // device [n]
+  int64_t step = 0;                       // rows between sequences (>= T), 0 = T
+  const int32_t* noise_off = nullptr;     // device [n]: sequence u's noise values start at noise + noise_off[u]   (noise_mod1)
+  const int64_t* out_off = nullptr;       // device [n]: sequence u's samples go to out + out_off[u]                (conv_out1)
 };
 
 const char* codec_conv_gemm_check(const ConvGemmArgs& g);
@@ -53,10 +71,11 @@ const char* codec_conv_gemm_check(const ConvGemmArgs& g);
 double codec_alg_bytes(bool reset);
 int codec_conv_gemm_launch(const ConvGemmArgs& g, int phases, hipStream_t s);
 int codec_dwconv_launch(const float* x, float* y, const float* w, const float* bias, const float* a_pre, const float* a_post, int T, int C,
-                        int K, int dil, hipStream_t s);
-int codec_conv_out1_launch(const float* x, float* out, const float* w, const float* bias, const float* alpha, int T, int C, int K, hipStream_t s);
-int codec_embed_launch(const EmbedArgs& a, float* z, int T, int C, hipStream_t s);
-int codec_noise1_launch(float* x, const float* w, const float* noise, int T, int C, hipStream_t s);
+                        int K, int dil, hipStream_t s, const SeqArgs& q = SeqArgs());
+int codec_conv_out1_launch(const float* x, float* out, const float* w, const float* bias, const float* alpha, int T, int C, int K, hipStream_t s,
+                           const SeqArgs& q = SeqArgs());
+int codec_embed_launch(const EmbedArgs& a, float* z, int T, int C, hipStream_t s, const SeqArgs& q = SeqArgs());
+int codec_noise1_launch(float* x, const float* w, const float* noise, int T, int C, hipStream_t s, const SeqArgs& q = SeqArgs());
 int codec_conv_in1_launch(const float* x, float* y, const float* w, const float* bias, int64_t T, int C, int K, int pad, hipStream_t s);
 int codec_vq_assign_launch(const float* zE, const float* cbn, const float* cbn_sq, const float* cb, const float* weff, const float* bias,
                            float* residual, int32_t* codes, int T, int C, int cs, int cd, hipStream_t s);

@@ -5,8 +5,11 @@
 // DACCodec.decodeFromCodes (Codec/DAC/DACModel.swift:303-306 -> DACQuantize.swift:192-220 -> DACModel.swift:120-164,
 // DACLayers.swift).  Weight normalisation g*v/(||v||+1e-12) is folded ONCE at load (the reference recomputes it on every
 // forward, WNConv1d.swift:73-74).  The Gaussian of SNAC's NoiseBlock is an explicit input (null = no noise).
+#include <climits>
 #include <cmath>
+#include <cstdint>
 #include <map>
+#include <numeric>
 #include <string>
 #include <vector>
 
@@ -45,6 +48,13 @@ struct mia_codec {
   int32_t* d_codes = nullptr; size_t codes_cap = 0;
   float* d_noise = nullptr; size_t noise_cap = 0;
   float* d_pcm = nullptr; size_t pcm_cap = 0;
+  // per-call tables of the stacked decode (Stack below): pinned staging owned by the handle, so that the memory behind the upload
+  // outlives it on every return path; tab_ev marks the last upload's end and is waited for before the staging is written again
+  void* h_tab = nullptr; void* d_tab = nullptr; size_t tab_cap = 0;
+  hipEvent_t tab_ev = nullptr;
+  // bytes of activations up to which a stage of the batch entries runs stacked (mia_codec_set_stack_budget).  SNAC: the Infinity Cache;
+  // DAC (mia_dac_load): no limit -- measured both ways, see decode_batch_enqueue
+  int64_t stack_budget_default = 256ll << 20, stack_budget = 256ll << 20;
   // ---- encoder side (mia_dac_load_encoder): conv_in1 -> [3 residual units, snake + strided conv] x n -> snake + conv3, then the RVQ stages
   bool has_encoder = false;
   int enc_dim = 0, hop = 1;
@@ -171,26 +181,69 @@ void plan(const mia_codec* c, int64_t T0, size_t& max_floats, int64_t& T_final, 
   if (noise_total) *noise_total = noff;
 }
 
-// run the program: buf[0] holds the latent [T0][latent]; pcm receives T_final samples
-int run(mia_codec* c, int64_t T0, const float* d_noise, float* d_pcm) {
+// Stacked utterances (mia_snac_decode_batch / mia_dac_decode_batch): U sequences side by side in every buffer, sequence u at row
+// u * (rows of the longest utterance at that stage) -- the layout of the HiFT batch.  Every table lives on the device:
+//   len        [stages][U]  valid rows of each utterance; the stage advances at every transposed convolution
+//   noise_off  [blocks][U]  where utterance u's values for that noise block start in the concatenated slabs
+//   pcm_off    [U]          where utterance u's samples go
+// Every sequence owns `slab` floats of each scratch buffer (a multiple of every channel count, so that it is a whole number of rows at
+// every stage, and at least the largest stage of the longest utterance).
+// U = 0 (the single-call entries): the launches are exactly the unstacked ones.
+struct Stack {
+  int U = 0;
+  int64_t slab = 0;
+  const int32_t* len = nullptr;
+  const int32_t* noise_off = nullptr;
+  const int64_t* pcm_off = nullptr;
+};
+
+// valid rows of a T0-row latent at every stage of the program
+std::vector<int64_t> stage_rows(const mia_codec* c, int64_t T0) {
+  std::vector<int64_t> r{T0};
+  for (const Op& op : c->ops) if (op.kind == OP_CONVT) r.push_back((r.back() - 1) * op.stride - 2 * op.pad + 2 * op.stride);
+  return r;
+}
+
+// where a run of the program stands: the stream x [T][C] with its two side buffers, the noise values consumed, the stage (transposed
+// convolutions passed) and the noise blocks passed
+struct Cursor {
+  float* x; float* h; float* y;
+  int64_t T; int C;
+  int64_t noff = 0;
+  int stage = 0, nblock = 0;
+};
+
+// run ops [begin, end) of the program from cursor k (op 0: k.x holds the latent [T0][latent]); the output conv writes T_final samples to
+// d_pcm.  Stacked: k.T = the longest utterance's rows.
+// (The DAC residual unit's first convolution is a "side" conv, stride == -1: h = conv(x) with x kept as the stream.)
+int run(mia_codec* c, Cursor& k, size_t begin, size_t end, const float* d_noise, float* d_pcm, const Stack& st = Stack()) {
   hipStream_t s = c->ctx->stream;
-  float* x = c->buf[0]; float* h = c->buf[1]; float* y = c->buf[2];
-  int64_t T = T0; int C = c->latent; int64_t noff = 0;
-  for (const Op& op : c->ops) {
+  float*& x = k.x; float*& h = k.h; float*& y = k.y;
+  int64_t& T = k.T; int& C = k.C; int64_t& noff = k.noff;
+  int& stage = k.stage; int& nblock = k.nblock;
+  auto seq = [&]() { SeqArgs q; if (st.U) { q.n = st.U; q.len = st.len + (size_t)stage * st.U; q.step = st.slab / C; } return q; };
+  auto seq_gemm = [&](ConvGemmArgs& g) {
+    if (!st.U) return;
+    g.n_seq = st.U; g.x_seq_step = st.slab / g.ldx; g.y_seq_step = st.slab / g.ldy; g.seq_len = st.len + (size_t)stage * st.U;
+  };
+  for (size_t oi = begin; oi < end; ++oi) {
+    const Op& op = c->ops[oi];
     switch (op.kind) {
       case OP_DW:
-        if (codec_dwconv_launch(x, h, op.w, op.b, op.a_pre, op.a_post, (int)T, C, op.taps, op.dil, s)) return mia_fail(c->ctx, MIA_ERR_DEVICE, "codec: dwconv launch failed");
+        if (codec_dwconv_launch(x, h, op.w, op.b, op.a_pre, op.a_post, (int)T, C, op.taps, op.dil, s, seq())) return mia_fail(c->ctx, MIA_ERR_DEVICE, "codec: dwconv launch failed");
         if (!op.residual) std::swap(x, h);     // plain depthwise layer: its output becomes the stream
         break;
       case OP_CONV: {
+        const bool side = op.stride == -1;
         ConvGemmArgs g;
         g.X = op.residual ? h : x; g.ldx = op.Cin; g.T_in = (int)T; g.W = op.w; g.bias = op.b; g.alpha = op.a_pre;
         g.M = (int)T; g.N = op.N; g.Cin = op.Cin; g.taps = op.taps; g.dil = op.dil; g.pad = op.pad; g.T_out = (int)T;
         if (op.residual) { g.R = x; g.ldr = op.N; g.Y = x; g.ldy = op.N; }
-        else { g.Y = y; g.ldy = op.N; }
+        else { g.Y = side ? h : y; g.ldy = op.N; }
+        seq_gemm(g);
         if (const char* e = codec_conv_gemm_check(g)) return mia_fail(c->ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
         if (codec_conv_gemm_launch(g, 1, s)) return mia_fail(c->ctx, MIA_ERR_DEVICE, "codec: conv launch failed");
-        if (!op.residual) { std::swap(x, y); C = op.N; }
+        if (!op.residual && !side) { std::swap(x, y); C = op.N; }
         break;
       }
       case OP_CONVT: {
@@ -199,29 +252,39 @@ int run(mia_codec* c, int64_t T0, const float* d_noise, float* d_pcm) {
         g.X = x; g.ldx = op.Cin; g.T_in = (int)T; g.W = op.w; g.w_phase_stride = (int64_t)op.N * 2 * op.Cin; g.bias = op.b; g.alpha = op.a_pre;
         g.M = (int)T + 1; g.N = op.N; g.Cin = op.Cin; g.taps = 2; g.dil = 1; g.pad = 1;
         g.Y = y; g.ldy = op.N; g.T_out = (int)T_out; g.y_row_mul = op.stride; g.y_row_off = -op.pad; g.y_phase_step = 1;
+        seq_gemm(g);
         if (const char* e = codec_conv_gemm_check(g)) return mia_fail(c->ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
         if (codec_conv_gemm_launch(g, op.stride, s)) return mia_fail(c->ctx, MIA_ERR_DEVICE, "codec: convT launch failed");
-        std::swap(x, y); C = op.N; T = T_out;
+        std::swap(x, y); C = op.N; T = T_out; ++stage;
         break;
       }
       case OP_NOISE1:
-        if (d_noise && codec_noise1_launch(x, op.w, d_noise + noff, (int)T, C, s)) return mia_fail(c->ctx, MIA_ERR_DEVICE, "codec: noise launch failed");
-        noff += T;
+        if (d_noise) {
+          SeqArgs q = seq();
+          if (st.U) q.noise_off = st.noise_off + (size_t)nblock * st.U;
+          if (codec_noise1_launch(x, op.w, st.U ? d_noise : d_noise + noff, (int)T, C, s, q)) return mia_fail(c->ctx, MIA_ERR_DEVICE, "codec: noise launch failed");
+        }
+        noff += T; ++nblock;
         break;
       case OP_NOISEC:
         if (d_noise) {
           ConvGemmArgs g;
           g.X = x; g.ldx = C; g.T_in = (int)T; g.W = op.w; g.M = (int)T; g.N = C; g.Cin = C; g.T_out = (int)T;
-          g.R = x; g.ldr = C; g.noise = d_noise + noff; g.Y = y; g.ldy = C;
+          g.R = x; g.ldr = C; g.noise = st.U ? d_noise : d_noise + noff; g.Y = y; g.ldy = C;
+          seq_gemm(g);
+          if (st.U) g.noise_seq_off = st.noise_off + (size_t)nblock * st.U;
           if (const char* e = codec_conv_gemm_check(g)) return mia_fail(c->ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
           if (codec_conv_gemm_launch(g, 1, s)) return mia_fail(c->ctx, MIA_ERR_DEVICE, "codec: noise gemm launch failed");
           std::swap(x, y);
         }
-        noff += T;
+        noff += T; ++nblock;
         break;
-      case OP_OUT1:
-        if (codec_conv_out1_launch(x, d_pcm, op.w, op.b, op.a_pre, (int)T, C, op.taps, s)) return mia_fail(c->ctx, MIA_ERR_DEVICE, "codec: output conv launch failed");
+      case OP_OUT1: {
+        SeqArgs q = seq();
+        q.out_off = st.pcm_off;
+        if (codec_conv_out1_launch(x, d_pcm, op.w, op.b, op.a_pre, (int)T, C, op.taps, s, q)) return mia_fail(c->ctx, MIA_ERR_DEVICE, "codec: output conv launch failed");
         break;
+      }
     }
   }
   return MIA_OK;
@@ -247,48 +310,13 @@ void add_residual_unit_dac(Loader& L, const std::string& p, int C, int dil, std:
   c2.a_pre = L.alpha(p + ".block.layers.2.alpha", C, false);
   L.dense_conv(p + ".block.layers.3", C, 1, C, true, c2);
   // encode "side" conv as: OP_CONV writing into h.  The executor treats a non-residual OP_CONV as a stream change, so mark it
-  // with N == Cin and a dedicated flag through `stride = -1`.
+  // with N == Cin and a dedicated flag through `stride = -1` (run() keeps x as the stream for it).
   c1.stride = -1;
   ops.push_back(c1);
   ops.push_back(c2);
 }
 
 }  // namespace
-
-// The DAC residual unit needs "h = conv(x)" with x kept: handled here by a tiny specialisation of the executor loop.
-static int run_codec(mia_codec* c, int64_t T0, const float* d_noise, float* d_pcm) {
-  bool has_side = false;
-  for (const Op& op : c->ops) if (op.kind == OP_CONV && op.stride == -1) has_side = true;
-  if (!has_side) return run(c, T0, d_noise, d_pcm);
-  hipStream_t s = c->ctx->stream;
-  float* x = c->buf[0]; float* h = c->buf[1]; float* y = c->buf[2];
-  int64_t T = T0; int C = c->latent;
-  for (const Op& op : c->ops) {
-    if (op.kind == OP_CONV) {
-      const bool side = op.stride == -1;
-      ConvGemmArgs g;
-      g.X = op.residual ? h : x; g.ldx = op.Cin; g.T_in = (int)T; g.W = op.w; g.bias = op.b; g.alpha = op.a_pre;
-      g.M = (int)T; g.N = op.N; g.Cin = op.Cin; g.taps = op.taps; g.dil = op.dil; g.pad = op.pad; g.T_out = (int)T;
-      if (op.residual) { g.R = x; g.ldr = op.N; g.Y = x; g.ldy = op.N; }
-      else { g.Y = side ? h : y; g.ldy = op.N; }
-      if (const char* e = codec_conv_gemm_check(g)) return mia_fail(c->ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
-      if (codec_conv_gemm_launch(g, 1, s)) return mia_fail(c->ctx, MIA_ERR_DEVICE, "codec: conv launch failed");
-      if (!op.residual && !side) { std::swap(x, y); C = op.N; }
-    } else if (op.kind == OP_CONVT) {
-      const int64_t T_out = (T - 1) * op.stride - 2 * op.pad + 2 * op.stride;
-      ConvGemmArgs g;
-      g.X = x; g.ldx = op.Cin; g.T_in = (int)T; g.W = op.w; g.w_phase_stride = (int64_t)op.N * 2 * op.Cin; g.bias = op.b; g.alpha = op.a_pre;
-      g.M = (int)T + 1; g.N = op.N; g.Cin = op.Cin; g.taps = 2; g.dil = 1; g.pad = 1;
-      g.Y = y; g.ldy = op.N; g.T_out = (int)T_out; g.y_row_mul = op.stride; g.y_row_off = -op.pad; g.y_phase_step = 1;
-      if (const char* e = codec_conv_gemm_check(g)) return mia_fail(c->ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
-      if (codec_conv_gemm_launch(g, op.stride, s)) return mia_fail(c->ctx, MIA_ERR_DEVICE, "codec: convT launch failed");
-      std::swap(x, y); C = op.N; T = T_out;
-    } else if (op.kind == OP_OUT1) {
-      if (codec_conv_out1_launch(x, d_pcm, op.w, op.b, op.a_pre, (int)T, C, op.taps, s)) return mia_fail(c->ctx, MIA_ERR_DEVICE, "codec: output conv launch failed");
-    }
-  }
-  return MIA_OK;
-}
 
 static mia_codec* codec_fail(mia_ctx* ctx, mia_codec* c, const std::string& m) {
   ctx->err = "codec_load: " + m;
@@ -305,6 +333,9 @@ extern "C" void mia_codec_free(mia_codec* c) {
   if (c->d_codes) (void)hipFree(c->d_codes);
   if (c->d_noise) (void)hipFree(c->d_noise);
   if (c->d_pcm) (void)hipFree(c->d_pcm);
+  if (c->d_tab) (void)hipFree(c->d_tab);
+  if (c->h_tab) (void)hipHostFree(c->h_tab);
+  if (c->tab_ev) (void)hipEventDestroy(c->tab_ev);
   if (c->d_audio) (void)hipFree(c->d_audio);
   if (c->d_ze) (void)hipFree(c->d_ze);
   delete c;
@@ -393,6 +424,7 @@ extern "C" mia_codec* mia_dac_load(mia_ctx* ctx, const mia_dac_config* cfg, cons
   if (cfg->latent_dim % 32 || cfg->decoder_dim % 32 || (cfg->decoder_dim >> cfg->n_rates) % 32) return codec_fail(ctx, nullptr, "DAC channel counts must be multiples of 32");
   if (hipSetDevice(ctx->device) != hipSuccess) return codec_fail(ctx, nullptr, "hipSetDevice failed");
   mia_codec* c = new mia_codec(); c->ctx = ctx; c->kind = 1;
+  c->stack_budget = c->stack_budget_default = INT64_MAX;
   Loader L; L.c = c;
   for (int i = 0; i < n_tensors; ++i) if (tensors[i].name && tensors[i].data) L.by_name[tensors[i].name] = &tensors[i];
   load_quantizers(L, c, cfg->n_codebooks, cfg->latent_dim, cfg->codebook_size, cfg->codebook_dim);
@@ -445,13 +477,20 @@ static int decode_common(mia_codec* c, const EmbedArgs& ea, int64_t T0, const fl
   }
   if (codec_embed_launch(ea, c->buf[0], (int)T0, c->latent, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "codec: embed launch failed");
   float* dst = mem == MIA_MEM_DEVICE ? pcm : c->d_pcm;
-  rc = run_codec(c, T0, d_noise, dst);
+  Cursor k{c->buf[0], c->buf[1], c->buf[2], T0, c->latent};
+  rc = run(c, k, 0, c->ops.size(), d_noise, dst);
   if (rc != MIA_OK) return rc;
   if (n_out) *n_out = T_final;
   if (mem == MIA_MEM_HOST) {
     MIA_HIP(ctx, hipMemcpyAsync(pcm, c->d_pcm, (size_t)T_final * 4, hipMemcpyDeviceToHost, ctx->stream));
     MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
+  return MIA_OK;
+}
+
+extern "C" int mia_codec_set_stack_budget(mia_codec* c, int64_t bytes) {
+  if (!c) return MIA_ERR_MODEL_NOT_LOADED;
+  c->stack_budget = bytes < 0 ? c->stack_budget_default : bytes;
   return MIA_OK;
 }
 
@@ -516,6 +555,204 @@ extern "C" int mia_dac_decode(mia_codec* c, const int32_t* codes, int n_codebook
   }
   MIA_CHECK_ARG(ctx, pcm_capacity >= mia_codec_output_len(c, T), "dac_decode: pcm buffer too small");
   return decode_common(c, ea, T, nullptr, 0, pcm, n_samples, mem);
+}
+
+// ---- stacked decode: n_utt utterances in one pass -----------------------------------------------------------------------------------------
+namespace {
+
+struct BatchUtt { int64_t T0 = 0, n_out = 0, noise_len = 0; int64_t code_off[MIA_MAX_LEVELS] = {-1, -1, -1, -1}; };
+
+// enqueue one stacked decode: every argument has been checked, nothing has touched the GPU yet
+int decode_batch_enqueue(mia_codec* c, std::vector<BatchUtt>& ut, const int strides[MIA_MAX_LEVELS], int n_levels, const int32_t* codes, size_t n_codes_total,
+                        const float* noise, float* pcm, const int64_t* pcm_off, int64_t* n_samples, int mem) {
+  mia_ctx* ctx = c->ctx;
+  hipStream_t s = ctx->stream;
+  const int U = (int)ut.size();
+  const bool dev = mem == MIA_MEM_DEVICE;
+  int64_t Tmax = 0, pcm_total = 0, noise_total = 0;
+  for (const BatchUtt& b : ut) { Tmax = std::max(Tmax, b.T0); pcm_total += b.n_out; noise_total += b.noise_len; }
+  if (noise_total == 0) noise = nullptr;
+  size_t max_floats; int64_t T_final;
+  plan(c, Tmax, max_floats, T_final);
+  const size_t n_stages = stage_rows(c, Tmax).size();
+  size_t n_blocks = 0;
+  for (const Op& op : c->ops) if (op.kind == OP_NOISE1 || op.kind == OP_NOISEC) ++n_blocks;
+  // floats per utterance per buffer: the largest stage of the longest utterance, rounded up to a whole number of rows at every stage
+  int64_t row_lcm = c->latent;
+  for (const Op& op : c->ops) if (op.kind == OP_CONVT || (op.kind == OP_CONV && !op.residual)) row_lcm = std::lcm<int64_t>(row_lcm, op.N);
+  const int64_t slab = ((int64_t)max_floats + row_lcm - 1) / row_lcm * row_lcm;
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = ensure(c, (size_t)slab * (size_t)U);            // three buffers of n_utt x (largest stage of the longest utterance)
+  if (rc != MIA_OK) return rc;
+  if (!dev) {
+    if ((rc = ensure_buf(c, c->d_pcm, c->pcm_cap, (size_t)pcm_total)) != MIA_OK) return rc;
+    if ((rc = ensure_buf(c, c->d_codes, c->codes_cap, n_codes_total)) != MIA_OK) return rc;
+    if (noise && (rc = ensure_buf(c, c->d_noise, c->noise_cap, (size_t)noise_total)) != MIA_OK) return rc;
+  }
+  // tables: [pcm_off U | code_off U x MIA_MAX_LEVELS] int64, then [len stages x U | noise_off blocks x U] int32 -- one upload per call
+  const size_t n64 = (size_t)U * (1 + MIA_MAX_LEVELS), n32 = (size_t)U * (n_stages + n_blocks), bytes = n64 * 8 + n32 * 4;
+  if (!c->tab_ev) MIA_HIP(ctx, hipEventCreateWithFlags(&c->tab_ev, hipEventDisableTiming));
+  else MIA_HIP(ctx, hipEventSynchronize(c->tab_ev));       // the previous call's upload has left the staging
+  if (bytes > c->tab_cap) {
+    MIA_HIP(ctx, hipStreamSynchronize(s));
+    if (c->d_tab) (void)hipFree(c->d_tab);
+    if (c->h_tab) (void)hipHostFree(c->h_tab);
+    c->d_tab = c->h_tab = nullptr; c->tab_cap = 0;
+    MIA_HIP(ctx, hipHostMalloc(&c->h_tab, bytes, hipHostMallocDefault));
+    MIA_HIP(ctx, hipMalloc(&c->d_tab, bytes));
+    c->tab_cap = bytes;
+  }
+  int64_t* h64 = (int64_t*)c->h_tab; int32_t* h32 = (int32_t*)(h64 + n64);
+  int64_t po = 0, zo = 0;
+  for (int u = 0; u < U; ++u) {
+    h64[u] = dev ? pcm_off[u] : po;                        // host: packed in d_pcm, copied out per utterance below
+    for (int l = 0; l < MIA_MAX_LEVELS; ++l) h64[U + (size_t)u * MIA_MAX_LEVELS + l] = ut[u].code_off[l];
+    const std::vector<int64_t> rows = stage_rows(c, ut[u].T0);
+    for (size_t k = 0; k < n_stages; ++k) h32[k * U + u] = (int32_t)rows[k];
+    std::vector<int64_t> noffs; size_t mf; int64_t tf;
+    plan(c, ut[u].T0, mf, tf, &noffs);
+    for (size_t k = 0; k < n_blocks; ++k) h32[(n_stages + k) * U + u] = (int32_t)(zo + noffs[k]);
+    po += ut[u].n_out; zo += ut[u].noise_len;
+  }
+  MIA_HIP(ctx, hipMemcpyAsync(c->d_tab, c->h_tab, bytes, hipMemcpyHostToDevice, s));
+  MIA_HIP(ctx, hipEventRecord(c->tab_ev, s));
+  Stack st; st.U = U; st.slab = slab;
+  st.pcm_off = (const int64_t*)c->d_tab;
+  st.len = (const int32_t*)((const int64_t*)c->d_tab + n64);
+  st.noise_off = st.len + n_stages * U;
+  const int32_t* d_codes = codes; const float* d_noise = noise;
+  if (!dev) {                                              // (decode_batch_common synchronises before the caller gets its arrays back)
+    MIA_HIP(ctx, hipMemcpyAsync(c->d_codes, codes, n_codes_total * 4, hipMemcpyHostToDevice, s));
+    d_codes = c->d_codes;
+    if (noise) { MIA_HIP(ctx, hipMemcpyAsync(c->d_noise, noise, (size_t)noise_total * 4, hipMemcpyHostToDevice, s)); d_noise = c->d_noise; }
+  }
+  EmbedArgs ea{}; ea.n_levels = n_levels; ea.cb_dim = c->cb_dim;
+  for (int i = 0; i < n_levels; ++i) { ea.codebook[i] = c->codebook[i]; ea.weff[i] = c->weff[i]; ea.bias[i] = c->ebias[i]; ea.stride[i] = strides[i]; }
+  ea.codes_base = d_codes; ea.seq_code_off = (const int64_t*)c->d_tab + U;
+  SeqArgs q0; q0.n = U; q0.len = st.len; q0.step = slab / c->latent;
+  if (codec_embed_launch(ea, c->buf[0], (int)Tmax, c->latent, s, q0)) return mia_fail(ctx, MIA_ERR_DEVICE, "codec: embed launch failed");
+  // Stages run stacked while all the utterances' activations there (three buffers) fit the budget.  SNAC: 256 MiB, the Infinity Cache.
+  // Its early stages have too few rows per utterance to fill the CUs, and stacking fills them; from the first stage that does not fit,
+  // every utterance runs the rest of the program on its own slab, one after the other, with the single call's launches.  A late
+  // stage of ONE utterance fills the chip, and its depthwise + 1x1 layers are memory-bound and hand their activations over through
+  // the cache, which a pass over all utterances per layer streams from HBM instead: every stage stacked measured 3-4 % SLOWER than
+  // the loop of single calls at 8 and 32 chunks of 171 frames, this split 2 % faster.  DAC's dense 7-tap convolutions are
+  // compute-bound and gain from the larger grids at every stage (8 x 750 steps: 10 % faster with every stage stacked, 1 % with the
+  // split), so its default is no limit.  LABNOTES, "stacked codec decode".  Stage 0 is always stacked.
+  size_t split = c->ops.size();
+  { int64_t T = Tmax;
+    for (size_t i = 0; i < c->ops.size(); ++i) {
+      const Op& op = c->ops[i];
+      if (op.kind != OP_CONVT) continue;
+      T = (T - 1) * op.stride - 2 * op.pad + 2 * op.stride;
+      if ((double)U * 3.0 * (double)T * op.N * 4.0 > (double)c->stack_budget) { split = i; break; }
+    } }
+  float* dst = dev ? pcm : c->d_pcm;
+  Cursor k{c->buf[0], c->buf[1], c->buf[2], Tmax, c->latent};
+  if ((rc = run(c, k, 0, split, d_noise, dst, st)) != MIA_OK) return rc;
+  if (split < c->ops.size()) {
+    int64_t zo_u = 0;
+    for (int u = 0; u < U; ++u) {
+      std::vector<int64_t> noffs; size_t mf; int64_t tf;
+      plan(c, ut[u].T0, mf, tf, &noffs);
+      Cursor ku{k.x + (int64_t)u * slab, k.h + (int64_t)u * slab, k.y + (int64_t)u * slab, stage_rows(c, ut[u].T0)[k.stage], k.C};
+      ku.noff = zo_u + ((size_t)k.nblock < noffs.size() ? noffs[k.nblock] : 0); ku.stage = k.stage; ku.nblock = k.nblock;
+      if ((rc = run(c, ku, split, c->ops.size(), d_noise, dst + h64[u])) != MIA_OK) return rc;
+      zo_u += ut[u].noise_len;
+    }
+  }
+  if (n_samples) for (int u = 0; u < U; ++u) n_samples[u] = ut[u].n_out;
+  if (!dev) {
+    po = 0;
+    for (int u = 0; u < U; ++u) {
+      MIA_HIP(ctx, hipMemcpyAsync(pcm + pcm_off[u], c->d_pcm + po, (size_t)ut[u].n_out * 4, hipMemcpyDeviceToHost, s));
+      po += ut[u].n_out;
+    }
+  }
+  return MIA_OK;
+}
+
+// shared tail of the two batch entries.  Host memory: the caller's codes / noise / pcm are behind asynchronous copies, so the stream is
+// synchronised on EVERY return path, the failing ones included (the tables' staging belongs to the handle and needs no such care).
+int decode_batch_common(mia_codec* c, std::vector<BatchUtt>& ut, const int strides[MIA_MAX_LEVELS], int n_levels, const int32_t* codes, size_t n_codes_total,
+                        const float* noise, float* pcm, const int64_t* pcm_off, int64_t* n_samples, int mem) {
+  int rc = decode_batch_enqueue(c, ut, strides, n_levels, codes, n_codes_total, noise, pcm, pcm_off, n_samples, mem);
+  if (mem == MIA_MEM_HOST && hipStreamSynchronize(c->ctx->stream) != hipSuccess && rc == MIA_OK)
+    rc = mia_fail(c->ctx, MIA_ERR_DEVICE, "codec: device error in the stacked decode");
+  return rc;
+}
+
+// lengths every utterance needs, and the checks both entries share; `what` prefixes the messages
+int batch_lengths(mia_codec* c, std::vector<BatchUtt>& ut, const float* noise, int64_t n_noise, const int64_t* pcm_off, const char* what) {
+  mia_ctx* ctx = c->ctx;
+  int64_t noise_total = 0;
+  MIA_CHECK_ARG(ctx, pcm_off[0] >= 0, "%s: pcm_off[0] is negative", what);
+  for (size_t u = 0; u < ut.size(); ++u) {
+    ut[u].n_out = mia_codec_output_len(c, ut[u].T0);
+    ut[u].noise_len = mia_codec_noise_len(c, ut[u].T0);
+    noise_total += ut[u].noise_len;
+    MIA_CHECK_ARG(ctx, pcm_off[u + 1] - pcm_off[u] >= ut[u].n_out, "%s: pcm room of utterance %d too small (%lld < %lld)", what, (int)u,
+                  (long long)(pcm_off[u + 1] - pcm_off[u]), (long long)ut[u].n_out);
+  }
+  MIA_CHECK_ARG(ctx, noise_total < (1ll << 31), "%s: too many noise values for one call", what);
+  if (noise && noise_total > 0)
+    MIA_CHECK_ARG(ctx, n_noise == noise_total, "%s: noise must hold %lld values, the sum over the utterances (got %lld)", what, (long long)noise_total, (long long)n_noise);
+  return MIA_OK;
+}
+
+}  // namespace
+
+extern "C" int mia_snac_decode_batch(mia_codec* c, int n_utt, const int32_t* codes, const int32_t* n_codes, int n_levels, const float* noise,
+                                     int64_t n_noise, float* pcm, const int64_t* pcm_off, int64_t* n_samples, int mem) {
+  if (!c) return MIA_ERR_MODEL_NOT_LOADED;
+  mia_ctx* ctx = c->ctx;
+  MIA_CHECK_ARG(ctx, c->kind == 0, "snac_decode_batch: handle is not a SNAC model");
+  MIA_CHECK_ARG(ctx, n_utt >= 1 && n_utt <= 64, "snac_decode_batch: n_utt must be 1..64 (got %d)", n_utt);
+  MIA_CHECK_ARG(ctx, codes && n_codes && pcm && pcm_off && n_levels > 0, "snac_decode_batch: null arguments");
+  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "snac_decode_batch: bad mem");
+  std::vector<BatchUtt> ut(n_utt);
+  size_t off = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    const int32_t* n = n_codes + (size_t)u * n_levels;
+    // expanded length = max_i n_i * stride_i; a level whose expansion differs is skipped for this utterance, as embedCodes does
+    for (int i = 0; i < c->n_levels && i < n_levels; ++i) if (n[i] > 0) ut[u].T0 = std::max<int64_t>(ut[u].T0, (int64_t)n[i] * c->vq_stride[i]);
+    MIA_CHECK_ARG(ctx, ut[u].T0 > 0, "snac_decode_batch: utterance %d has no codes", u);
+    for (int i = 0; i < n_levels; ++i) {
+      if (n[i] <= 0) continue;
+      if (i < c->n_levels && (int64_t)n[i] * c->vq_stride[i] == ut[u].T0) {
+        for (int k = 0; k < n[i] && mem == MIA_MEM_HOST; ++k)
+          MIA_CHECK_ARG(ctx, codes[off + k] >= 0 && codes[off + k] < c->cb_size, "snac_decode_batch: code %d out of range at level %d of utterance %d", codes[off + k], i, u);
+        ut[u].code_off[i] = (int64_t)off;
+      }
+      off += n[i];
+    }
+  }
+  if (int rc = batch_lengths(c, ut, noise, n_noise, pcm_off, "snac_decode_batch")) return rc;
+  return decode_batch_common(c, ut, c->vq_stride, c->n_levels, codes, off, noise, pcm, pcm_off, n_samples, mem);
+}
+
+extern "C" int mia_dac_decode_batch(mia_codec* c, int n_utt, const int32_t* codes, int n_codebooks, const int64_t* T, float* pcm,
+                                    const int64_t* pcm_off, int64_t* n_samples, int mem) {
+  if (!c) return MIA_ERR_MODEL_NOT_LOADED;
+  mia_ctx* ctx = c->ctx;
+  MIA_CHECK_ARG(ctx, c->kind == 1, "dac_decode_batch: handle is not a DAC model");
+  MIA_CHECK_ARG(ctx, n_utt >= 1 && n_utt <= 64, "dac_decode_batch: n_utt must be 1..64 (got %d)", n_utt);
+  MIA_CHECK_ARG(ctx, codes && T && pcm && pcm_off && n_codebooks > 0 && n_codebooks <= c->n_levels, "dac_decode_batch: bad arguments");
+  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "dac_decode_batch: bad mem");
+  std::vector<BatchUtt> ut(n_utt);
+  size_t off = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    MIA_CHECK_ARG(ctx, T[u] > 0 && T[u] < (1ll << 30), "dac_decode_batch: utterance %d has no codes (T = %lld)", u, (long long)T[u]);
+    ut[u].T0 = T[u];
+    for (int i = 0; i < n_codebooks; ++i) ut[u].code_off[i] = (int64_t)(off + (size_t)i * T[u]);
+    const size_t n = (size_t)n_codebooks * T[u];
+    for (size_t k = 0; k < n && mem == MIA_MEM_HOST; ++k)
+      MIA_CHECK_ARG(ctx, codes[off + k] >= 0 && codes[off + k] < c->cb_size, "dac_decode_batch: code %d out of range in utterance %d", codes[off + k], u);
+    off += n;
+  }
+  if (int rc = batch_lengths(c, ut, nullptr, 0, pcm_off, "dac_decode_batch")) return rc;
+  const int ones[MIA_MAX_LEVELS] = {1, 1, 1, 1};
+  return decode_batch_common(c, ut, ones, n_codebooks, codes, off, nullptr, pcm, pcm_off, n_samples, mem);
 }
 
 

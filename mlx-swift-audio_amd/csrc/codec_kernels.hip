@@ -68,6 +68,14 @@ __global__ __launch_bounds__(256) void conv_gemm_f32(ConvGemmArgs g) {
   float* __restrict__ Yb = g.Y + y_seq * g.ldy;
   const float* __restrict__ Rb = g.R ? g.R + y_seq * g.ldr : nullptr;
   const float* __restrict__ R2b = g.R2 ? g.R2 + y_seq * g.ldr : nullptr;
+  // noise term of a stacked sequence: its own values, and no row at or past its length (it has no noise value).  u comes out of a
+  // vector-unit division, so both are pinned to scalar registers: left in VGPRs they took the 128 x 128 tile from 168 to 176
+  const float* __restrict__ nz = g.noise;
+  int T_lim = g.T_out;
+  if (g.noise && g.noise_seq_off) {
+    nz += __builtin_amdgcn_readfirstlane(g.noise_seq_off[u]);
+    T_lim = min(T_lim, __builtin_amdgcn_readfirstlane(T_valid));
+  }
   const int Ktot = g.taps * g.Cin;
   const int64_t ldw = g.ldw > 0 ? g.ldw : Ktot;
 
@@ -222,7 +230,7 @@ __global__ __launch_bounds__(256) void conv_gemm_f32(ConvGemmArgs g) {
         const int m = m0 + wr * 32 * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         if (m >= g.M) continue;
         const int64_t yr = (int64_t)m * g.y_row_mul + g.y_row_off + (int64_t)z * g.y_phase_step;
-        if (yr < 0 || yr >= g.T_out) continue;
+        if (yr < 0 || yr >= T_lim) continue;
         float v = acc[i][j][r] + bias;
         if (g.gelu == 1) v = gelu_erf(v);
         else if (g.gelu == 2) v = v > 0.f ? v : (__expf(v) - 1.0f);
@@ -230,7 +238,7 @@ __global__ __launch_bounds__(256) void conv_gemm_f32(ConvGemmArgs g) {
         else if (g.gelu == 4) v = v / (1.0f + __expf(-v));
         else if (g.gelu == 5) v = v > 0.f ? v : 0.01f * v;
         else if (g.gelu == 6) v = fmaxf(v, 0.f);
-        if (g.noise) v = Rb[yr * g.ldr + n] + g.noise[yr] * v;
+        if (nz) v = Rb[yr * g.ldr + n] + nz[yr] * v;
         else if (Rb) v += Rb[yr * g.ldr + n];
         if (g.out_scale != 0.f) v *= g.out_scale;
         if (R2b) v += R2b[yr * g.ldr + n];
@@ -243,9 +251,14 @@ __global__ __launch_bounds__(256) void conv_gemm_f32(ConvGemmArgs g) {
 // y[t][c] = post( bias[c] + sum_k w[k][c] * pre(x[t + (k - K/2)*dil][c]) ),  pre/post = snake with alpha_pre/alpha_post (optional)
 __global__ __launch_bounds__(256) void dwconv_snake(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ w,
                                                     const float* __restrict__ bias, const float* __restrict__ a_pre,
-                                                    const float* __restrict__ a_post, int T, int C, int K, int dil) {
+                                                    const float* __restrict__ a_post, int T, int C, int K, int dil,
+                                                    const int32_t* __restrict__ seq_len, int64_t seq_step) {
+  // blockIdx.y = stacked sequence: seq_step rows apart, taps and outputs confined to its own [0, L)
+  const int L = seq_len ? min(T, seq_len[blockIdx.y]) : T;
+  x += (int64_t)blockIdx.y * seq_step * C;
+  y += (int64_t)blockIdx.y * seq_step * C;
   const int c4n = C >> 2;
-  const int64_t total = (int64_t)T * c4n;
+  const int64_t total = (int64_t)L * c4n;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int t = (int)(e / c4n), c = (int)(e - (int64_t)t * c4n) * 4;
     float ap[4] = {0, 0, 0, 0}, rap[4] = {0, 0, 0, 0};
@@ -258,7 +271,7 @@ __global__ __launch_bounds__(256) void dwconv_snake(const float* __restrict__ x,
     for (int j = 0; j < 4; ++j) acc[j] = bias ? bias[c + j] : 0.f;
     for (int k = 0; k < K; ++k) {
       const int ts = t + (k - K / 2) * dil;
-      if (ts < 0 || ts >= T) continue;
+      if (ts < 0 || ts >= L) continue;
       const float4 v = *reinterpret_cast<const float4*>(x + (int64_t)ts * C + c);
       const float4 wk = *reinterpret_cast<const float4*>(w + (int64_t)k * C + c);
       float xv[4] = {v.x, v.y, v.z, v.w};
@@ -279,7 +292,8 @@ __global__ __launch_bounds__(256) void dwconv_snake(const float* __restrict__ x,
 
 // out[t] = tanh( bias + sum_{k,c} w[k*C + c] * snake(x[t + k - K/2][c]) )      (C -> 1 output convolution)
 __global__ __launch_bounds__(256) void conv_out1(const float* __restrict__ x, float* __restrict__ out, const float* __restrict__ w,
-                                                 const float* __restrict__ bias, const float* __restrict__ alpha, int T, int C, int K) {
+                                                 const float* __restrict__ bias, const float* __restrict__ alpha, int T, int C, int K,
+                                                 const int32_t* __restrict__ seq_len, int64_t seq_step, const int64_t* __restrict__ out_off) {
   extern __shared__ float sm[];        // w[K*C] | alpha[C] | ralpha[C]
   float* sw = sm;
   float* sa = sm + K * C;
@@ -287,12 +301,16 @@ __global__ __launch_bounds__(256) void conv_out1(const float* __restrict__ x, fl
   for (int i = threadIdx.x; i < K * C; i += 256) sw[i] = w[i];
   for (int i = threadIdx.x; i < C; i += 256) { const float a = alpha ? alpha[i] : 0.f; sa[i] = a; sr[i] = 1.0f / (a + 1e-9f); }
   __syncthreads();
+  // blockIdx.y = stacked sequence: seq_step rows apart in x, its L samples at out + out_off
+  const int L = seq_len ? min(T, seq_len[blockIdx.y]) : T;
+  x += (int64_t)blockIdx.y * seq_step * C;
+  if (out_off) out += out_off[blockIdx.y];
   const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= T) return;
+  if (t >= L) return;
   float acc = bias ? bias[0] : 0.f;
   for (int k = 0; k < K; ++k) {
     const int ts = t + k - K / 2;
-    if (ts < 0 || ts >= T) continue;
+    if (ts < 0 || ts >= L) continue;
     const float* xr = x + (int64_t)ts * C;
     for (int c = 0; c < C; c += 4) {
       const float4 v = *reinterpret_cast<const float4*>(xr + c);
@@ -308,8 +326,19 @@ __global__ __launch_bounds__(256) void conv_out1(const float* __restrict__ x, fl
 }
 
 // z[t][ch] = sum_levels ( b_l[ch] + sum_j cb_l[code_l[t / stride_l]][j] * Weff_l[ch][j] )
-__global__ __launch_bounds__(256) void embed_codes(EmbedArgs a, float* __restrict__ z, int T, int C) {
-  const int64_t total = (int64_t)T * C;
+__global__ __launch_bounds__(256) void embed_codes(EmbedArgs a, float* __restrict__ z, int T, int C, const int32_t* __restrict__ seq_len,
+                                                   int64_t seq_step) {
+  // blockIdx.y = stacked sequence: its L rows at row blockIdx.y * seq_step of z, its levels' codes through the offset table
+  const int L = seq_len ? min(T, seq_len[blockIdx.y]) : T;
+  z += (int64_t)blockIdx.y * seq_step * C;
+  if (a.seq_code_off) {
+#pragma unroll
+    for (int l = 0; l < MIA_MAX_LEVELS; ++l) {
+      const int64_t o = a.seq_code_off[blockIdx.y * MIA_MAX_LEVELS + l];
+      a.codes[l] = o < 0 ? nullptr : a.codes_base + o;
+    }
+  }
+  const int64_t total = (int64_t)L * C;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int t = (int)(e / C), ch = (int)(e - (int64_t)t * C);
     float acc = 0.f;
@@ -327,9 +356,14 @@ __global__ __launch_bounds__(256) void embed_codes(EmbedArgs a, float* __restric
 }
 
 // x[t][:] += noise[t] * dot(x[t][:], w)      one wave per row
-__global__ __launch_bounds__(256) void noise_mod1(float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ noise, int T, int C) {
+__global__ __launch_bounds__(256) void noise_mod1(float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ noise, int T, int C,
+                                                  const int32_t* __restrict__ seq_len, int64_t seq_step, const int32_t* __restrict__ noise_off) {
+  // blockIdx.y = stacked sequence: seq_step rows apart in x, its L noise values at noise + noise_off
+  const int L = seq_len ? min(T, seq_len[blockIdx.y]) : T;
+  x += (int64_t)blockIdx.y * seq_step * C;
+  if (noise_off) noise += noise_off[blockIdx.y];
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (t >= T) return;
+  if (t >= L) return;
   float* xr = x + (int64_t)t * C;
   float s = 0.f;
   for (int c = lane; c < C; c += 64) s = fmaf(xr[c], w[c], s);
@@ -422,7 +456,9 @@ const char* codec_conv_gemm_check(const ConvGemmArgs& g) {
   if (g.Cin % 32) return "conv_gemm: Cin must be a multiple of 32";
   if (g.ldx % 4 || ((uintptr_t)g.X & 15) || ((uintptr_t)g.W & 15)) return "conv_gemm: X rows / W must be 16-byte aligned";
   if (g.noise && !g.R) return "conv_gemm: noise modulation needs the residual input";
-  if (g.n_seq < 1 || (g.n_seq > 1 && (g.x_seq_step < g.T_in || g.y_seq_step <= 0 || g.noise || g.x_phase_step))) return "conv_gemm: bad stacked-sequence arguments";
+  if (g.n_seq < 1 || (g.n_seq > 1 && (g.x_seq_step < g.T_in || g.y_seq_step <= 0 || g.x_phase_step))) return "conv_gemm: bad stacked-sequence arguments";
+  if ((g.n_seq > 1 && g.noise && !g.noise_seq_off) || (g.noise_seq_off && (!g.noise || !g.seq_len || g.y_row_mul != 1 || g.y_row_off || g.T_out != g.T_in)))
+    return "conv_gemm: stacked noise needs noise_seq_off and seq_len on a row-for-row mapping";
   if ((int64_t)g.M * g.x_row_mul + (int64_t)g.taps * g.dil > 0x7fffffffLL) return "conv_gemm: row index exceeds 31 bits";
   if (((int64_t)g.M * g.x_row_mul + (int64_t)g.taps * g.dil + g.pad + g.T_in) * g.ldx > 0x7fffffffLL) return "conv_gemm: row offset exceeds 31 bits";
   return nullptr;
@@ -476,34 +512,37 @@ int codec_conv_gemm_launch(const ConvGemmArgs& g, int phases_per_seq, hipStream_
 }
 
 int codec_dwconv_launch(const float* x, float* y, const float* w, const float* bias, const float* a_pre, const float* a_post, int T, int C,
-                        int K, int dil, hipStream_t s) {
-  if (C % 4) return -1;
-  t_alg_bytes += 2.0 * T * C * 4.0 + (double)K * C * 4.0;
+                        int K, int dil, hipStream_t s, const SeqArgs& q) {
+  if (C % 4 || q.n < 1 || (q.n > 1 && !q.len)) return -1;
+  t_alg_bytes += 2.0 * T * C * 4.0 * q.n + (double)K * C * 4.0;
   const int64_t total = (int64_t)T * (C / 4);
   const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
-  hipLaunchKernelGGL(dwconv_snake, dim3(grid), dim3(256), 0, s, x, y, w, bias, a_pre, a_post, T, C, K, dil);
+  hipLaunchKernelGGL(dwconv_snake, dim3(grid, q.n), dim3(256), 0, s, x, y, w, bias, a_pre, a_post, T, C, K, dil, q.len, q.step ? q.step : (int64_t)T);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int codec_conv_out1_launch(const float* x, float* out, const float* w, const float* bias, const float* alpha, int T, int C, int K, hipStream_t s) {
-  if (C % 4) return -1;
-  t_alg_bytes += (double)T * C * 4.0 + (double)T * 4.0;
+int codec_conv_out1_launch(const float* x, float* out, const float* w, const float* bias, const float* alpha, int T, int C, int K, hipStream_t s,
+                           const SeqArgs& q) {
+  if (C % 4 || q.n < 1 || (q.n > 1 && !(q.len && q.out_off))) return -1;
+  t_alg_bytes += ((double)T * C * 4.0 + (double)T * 4.0) * q.n;
   const size_t lds = (size_t)(K * C + 2 * C) * 4;
-  hipLaunchKernelGGL(conv_out1, dim3((T + 255) / 256), dim3(256), lds, s, x, out, w, bias, alpha, T, C, K);
+  hipLaunchKernelGGL(conv_out1, dim3((T + 255) / 256, q.n), dim3(256), lds, s, x, out, w, bias, alpha, T, C, K, q.len, q.step ? q.step : (int64_t)T, q.out_off);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int codec_embed_launch(const EmbedArgs& a, float* z, int T, int C, hipStream_t s) {
+int codec_embed_launch(const EmbedArgs& a, float* z, int T, int C, hipStream_t s, const SeqArgs& q) {
+  if (q.n < 1 || (q.n > 1 && !(q.len && a.seq_code_off && a.codes_base))) return -1;
   const int64_t total = (int64_t)T * C;
-  t_alg_bytes += (double)total * 4.0;
+  t_alg_bytes += (double)total * 4.0 * q.n;
   const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
-  hipLaunchKernelGGL(embed_codes, dim3(grid), dim3(256), 0, s, a, z, T, C);
+  hipLaunchKernelGGL(embed_codes, dim3(grid, q.n), dim3(256), 0, s, a, z, T, C, q.len, q.step ? q.step : (int64_t)T);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int codec_noise1_launch(float* x, const float* w, const float* noise, int T, int C, hipStream_t s) {
-  t_alg_bytes += 2.0 * T * C * 4.0 + (double)T * 4.0;
-  hipLaunchKernelGGL(noise_mod1, dim3((T + 3) / 4), dim3(256), 0, s, x, w, noise, T, C);
+int codec_noise1_launch(float* x, const float* w, const float* noise, int T, int C, hipStream_t s, const SeqArgs& q) {
+  if (q.n < 1 || (q.n > 1 && !(q.len && q.noise_off))) return -1;
+  t_alg_bytes += (2.0 * T * C * 4.0 + (double)T * 4.0) * q.n;
+  hipLaunchKernelGGL(noise_mod1, dim3((T + 3) / 4, q.n), dim3(256), 0, s, x, w, noise, T, C, q.len, q.step ? q.step : (int64_t)T, q.noise_off);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -312,15 +312,23 @@ class OrpheusTTS:
         sentence with the same uniforms / noise.  uniforms [n, max_new_tokens]; noises: one array per sentence or None."""
         gens = self.lm.generate_batch(input_ids_list, uniforms, temperature=temperature, top_p=top_p, rep_penalty=1.3,
                                       rep_window=REPETITION_CONTEXT_SIZE, max_new_tokens=max_new_tokens, stop_ids=(END_TOKEN,))
-        out = []
+        out = [(gen, np.zeros(0, np.float32)) for gen in gens]
         lim = self.snac.cfg.codebook_size
+        todo = []                                    # (sentence, codes, noise) of every sentence that has codes
         for b, gen in enumerate(gens):
             codes = parse_output(list(input_ids_list[b]) + gen)
             if not codes[0]:
-                out.append((gen, np.zeros(0, np.float32)))
                 continue
             n = len(codes[0])
             codes = [[min(max(c, 0), lim - 1) for c in lv] for lv in codes]
             nz = None if noises is None or noises[b] is None else np.ascontiguousarray(noises[b][:self.snac.noise_len(4 * n)], np.float32)
-            out.append((gen, self.snac.decode(codes, nz)))
+            todo.append((b, codes, nz))
+        # one stacked SNAC pass per group (SNACDecoder.decode_batch, at most 64 utterances); noise is all-or-none inside a call
+        for with_noise in (False, True):
+            grp = [t for t in todo if (t[2] is not None) == with_noise]
+            for i in range(0, len(grp), 64):
+                part = grp[i:i + 64]
+                pcms = self.snac.decode_batch([c for _, c, _ in part], [z for _, _, z in part] if with_noise else None)
+                for (b, _, _), pcm in zip(part, pcms):
+                    out[b] = (gens[b], pcm)
         return out
