@@ -167,6 +167,15 @@ int mia_dequant_affine(mia_ctx* ctx, const uint32_t* wq, const void* scales, con
 int mia_op_attention_f32(mia_ctx* ctx, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, float* out,
                          int64_t ldo, int B, int T, int H, float scale);
 
+/* The LM's single-token grouped-query attention over a KV cache it fills itself (the kernels behind attentionWithCacheUpdate,
+ * TTS/Orpheus/BuildingBlocks/TransformerBlock.swift:91-99), without a model around it.  q [Hq][dh], k / v [Hkv][T][dh] in `dtype`
+ * (MIA_BF16 | MIA_F16; rows taken as already rotated), HOST pointers.  The rows go through the prompt pass's cache writer for the given
+ * cache mode -- bits 0: the 16-bit cache (KVCacheSimple); bits 4 | 8: QuantizedKVCache(groupSize: 64, bits:) (:182-201), see
+ * mia_lm_set_kv_quant -- and that mode's attention kernel runs q at position T - 1 over keys [0, T).  out fp32 [Hq][dh].
+ * dh 64 | 128, Hq % Hkv == 0, T <= 8192.  bits outside {0, 4, 8}: MIA_ERR_INVALID_ARGUMENT; another head_dim: MIA_ERR_UNSUPPORTED. */
+int mia_op_kvq_attention(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int dh, int bits,
+                         int dtype);
+
 /* ---- Whisper ---------------------------------------------------------------------------------- */
 /* Model dimensions == ModelDimensions (STT/Whisper/Config/WhisperConfig.swift:9-86), read by the caller
  * from config.json. */
@@ -459,6 +468,22 @@ int mia_lm_generate(mia_lm* lm, const int32_t* prompt, int n_prompt, const mia_l
 int mia_lm_set_batch(mia_lm* lm, int max_batch);
 int mia_lm_generate_batch(mia_lm* lm, const int32_t* prompts, const int32_t* prompt_offsets, int n_seq, const mia_lm_sampler* sampler,
                           const float* uniforms, int32_t* out_tokens, int32_t* n_out);
+/* Quantised KV cache: OrpheusModel.newCache(quantized:groupSize:bits:) (TTS/Orpheus/BuildingBlocks/TransformerBlock.swift:182-201,
+ * re-exported at :236-241) returns QuantizedKVCache(groupSize: 64, bits: 4) instead of KVCacheSimple, and attentionWithCacheUpdate
+ * (:91-99) routes every attention call of the layer to it.  bits 4 | 8, group_size 64: each K row (after RoPE) and V row is rounded
+ * to the handle's 16-bit type as before, then kept per 64 consecutive elements of the head dimension as codes (uint32, little end
+ * first) plus one (scale, bias) pair in that 16-bit type: scale = (max - min) / (2^bits - 1) (1 for a constant group), bias = min,
+ * code = clamp(rint((x - bias) / scale), 0, 2^bits - 1) with the ROUNDED pair, value read back = scale * code + bias in fp32.
+ * Attention then sees only values read back, the current token's row included.  MLX's rule restated from its public documentation,
+ * unpinned against MLX; its nudge that makes zero exactly representable is not reproduced.  The 16-bit caches are not allocated in
+ * this mode: 0.28x (4 bit) / 0.53x (8 bit) of their bytes.  bits 0 restores them.  The call re-allocates the per-sequence state at the
+ * current capacity (either order with mia_lm_set_batch), drops the step graph and resets every sequence; cache contents are not
+ * converted.  Every other entry point works unchanged in either mode.  bits outside {0, 4, 8}: MIA_ERR_INVALID_ARGUMENT;
+ * group_size != 64: MIA_ERR_UNSUPPORTED; nothing is launched or allocated then. */
+int mia_lm_set_kv_quant(mia_lm* lm, int bits, int group_size);
+/* Test hook: rows [pos0, pos0 + n) of every kv head of (layer, seq) as fp32 [Hkv][n][dh] -- scale * code + bias in quantised mode, the
+ * 16-bit values widened otherwise.  Host pointers; layer / seq / rows outside the handle: MIA_ERR_INVALID_ARGUMENT. */
+int mia_lm_read_kv(mia_lm* lm, int layer, int seq, int pos0, int n, float* k_out, float* v_out);
 /* CosyVoice2 RAS sampling parameters (TTS/CosyVoice2/LLM/Qwen2LM.swift:433-488 defaults: top_p 0.8, top_k 25, win 10, tau 0.1;
  * eos = speech_token_size (6561); min_len / max_len = 2x / 20x the text length, :368-372). */
 typedef struct { float top_p; int32_t top_k; int32_t win; float tau; int32_t eos; int32_t min_len; int32_t max_len; } mia_ras_params;

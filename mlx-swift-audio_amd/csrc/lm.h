@@ -1,5 +1,6 @@
 // lm.h -- host-side interface between the LM decode sources: lm.hip (step kernels, prompt pass, step graph, entry points),
-// lm_sample.hip (the top-p and RAS samplers) and lm_load.hip (checkpoint loader, state buffers, packed-weight attach).
+// lm_sample.hip (the top-p and RAS samplers), lm_load.hip (checkpoint loader, state buffers, packed-weight attach) and lm_kvq.hip
+// (the quantised KV cache: its prompt-pass quantiser and its attention).
 #pragma once
 #include <vector>
 
@@ -48,7 +49,10 @@ struct mia_lm {
   float* inv_freq = nullptr;    // [dh/2]
   std::vector<LmLayer> layers;
   // state
-  void* k_cache = nullptr; void* v_cache = nullptr;   // [L][Hkv][max_ctx][dh]
+  void* k_cache = nullptr; void* v_cache = nullptr;   // [L][B][Hkv][max_ctx][dh]; null while the cache is quantised
+  // quantised cache (mia_lm_set_kv_quant, lm_kvq.hip): codes [L][B][Hkv][max_ctx][dh * kv_bits / 32], pairs [L][B][Hkv][max_ctx][dh / 64]
+  int kv_bits = 0;              // 0 = 16-bit cache, 4 | 8
+  uint32_t* kq_codes = nullptr; uint32_t* vq_codes = nullptr; uint32_t* kq_pairs = nullptr; uint32_t* vq_pairs = nullptr;
   float* x = nullptr; void* h = nullptr; float* qkv_part = nullptr; void* q = nullptr; void* att = nullptr; void* act = nullptr;
   float* partial = nullptr; float* logits = nullptr;
   float* ss = nullptr;          // [2][hidden / 16][B]: per-tile partial sums of squares of the residual stream (SK_RESID producers)
@@ -84,6 +88,27 @@ size_t lm_sample_ws_bytes();
 constexpr int LM_RAS_MAX_VOCAB = 8192;
 void lm_sample_ras_launch(hipStream_t s, const float* logits, int V, int32_t* tokens, int32_t* out_tokens, const float* uniforms, LmState* st, const RasParams& rp,
                           int max_ctx, int B);
+
+// ---- lm.hip: the two launch sites that branch on the cache mode (layer l of the handle's caches; the op ABI calls them on a bare handle) ----
+// q|k|v rows of the prompt pass -> RoPE -> q rows + the layer's K/V rows at rowmap's (sequence, position)
+void lm_launch_rope_cache(mia_lm* m, int layer, const float* qkv, const float* bias, void* q, const int2* rowmap, int M);
+// fused: rows = sequences (row b uses state b and the b-th cache of the layer); otherwise rows = (sequence, position) pairs of rowmap
+int lm_launch_attention(mia_lm* m, bool fused, int rows, const void* q, int layer, void* att, const int2* rowmap, const float* part, int S, const float* bias);
+
+// ---- lm_kvq.hip ----
+// one layer's packed cache (all sequences) and what its kernels need of the model
+struct LmKvq {
+  int dtype, dh, bits, Hq, Hkv, max_ctx;
+  uint32_t* kq; uint32_t* vq; uint32_t* kp; uint32_t* vp;
+  const LmState* st; const float* inv_freq;
+};
+// null when (bits, group_size, head_dim) is supported, else the message and, in *code, MIA_ERR_INVALID_ARGUMENT / MIA_ERR_UNSUPPORTED
+const char* lm_kvq_check(int bits, int group_size, int head_dim, int* code);
+void lm_kvq_launch_rope_cache(hipStream_t s, const LmKvq& a, const float* part, const float* bias, uint16_t* qout, const int2* rowmap, int M);
+void lm_kvq_launch_attention(hipStream_t s, const LmKvq& a, bool fused, int rows, const uint16_t* q, uint16_t* out, const int2* rowmap, const float* part, int S,
+                             const float* bias);
+// host: n_rows packed rows -> fp32 [n_rows][dh] (scale * code + bias)
+void lm_kvq_read_rows(const uint32_t* codes, const uint32_t* pairs, int64_t n_rows, int dh, int bits, int dtype, float* out);
 
 // ---- lm_load.hip ----
 // every per-sequence buffer, for B sequences side by side (rows of the skinny GEMMs; caches [L][B][Hkv][max_ctx][dh]); drops the step graph

@@ -328,12 +328,38 @@ __global__ __launch_bounds__(256) void lm_swiglu_rows(const float* __restrict__ 
 
 // ---- host side ------------------------------------------------------------------------------------
 
-// one launch site for the eight (dtype, head_dim, fused) instances
-int lm_launch_attention(mia_lm* m, bool fused, int rows, const void* q, uint16_t* kc, uint16_t* vc, void* att, const int2* rowmap, const float* part, int S, const float* bias) {
-  // fused: rows = sequences (row b uses state b and the b-th cache of the layer); otherwise rows = positions of one sequence
-  const int64_t seq_stride = (int64_t)m->cfg.n_kv_heads * m->cfg.max_ctx * m->cfg.head_dim;
+}  // namespace
+
+// the layer's packed cache, all sequences of the handle
+static LmKvq lm_kvq_layer(const mia_lm* m, int layer) {
+  const mia_lm_config& c = m->cfg;
+  const size_t rows = ((size_t)layer * m->B_cap) * c.n_kv_heads * c.max_ctx, wpr = (size_t)c.head_dim * m->kv_bits / 32, gpr = c.head_dim / 64;
+  return LmKvq{m->dtype, c.head_dim, m->kv_bits, c.n_heads, c.n_kv_heads, c.max_ctx, m->kq_codes + rows * wpr, m->vq_codes + rows * wpr,
+               m->kq_pairs + rows * gpr, m->vq_pairs + rows * gpr, m->state, m->inv_freq};
+}
+
+void lm_launch_rope_cache(mia_lm* m, int layer, const float* qkv, const float* bias, void* q, const int2* rowmap, int M) {
   const mia_lm_config& c = m->cfg;
   hipStream_t s = m->ctx->stream;
+  if (m->kv_bits) { lm_kvq_launch_rope_cache(s, lm_kvq_layer(m, layer), qkv, bias, (uint16_t*)q, rowmap, M); return; }
+  const bool f16 = m->dtype == MIA_F16;
+  const int dh = c.head_dim;
+  const int64_t seq_stride = (int64_t)c.n_kv_heads * c.max_ctx * dh;
+  uint16_t* kc = (uint16_t*)m->k_cache + (size_t)layer * m->B_cap * seq_stride;
+  uint16_t* vc = (uint16_t*)m->v_cache + (size_t)layer * m->B_cap * seq_stride;
+  const int n_el = (c.n_heads + c.n_kv_heads) * (dh / 2) + c.n_kv_heads * dh;
+  LAUNCH_T(lm_rope_cache, dim3((n_el + 255) / 256, M), dim3(256), 0, qkv, 1, bias, m->inv_freq, (uint16_t*)q, kc, vc, rowmap, c.n_heads, c.n_kv_heads, dh, c.max_ctx, seq_stride);
+}
+
+// one launch site for the eight (dtype, head_dim, fused) instances of the 16-bit cache; the packed cache's are lm_kvq.hip's
+int lm_launch_attention(mia_lm* m, bool fused, int rows, const void* q, int layer, void* att, const int2* rowmap, const float* part, int S, const float* bias) {
+  // fused: rows = sequences (row b uses state b and the b-th cache of the layer); otherwise rows = (sequence, position) pairs
+  const mia_lm_config& c = m->cfg;
+  hipStream_t s = m->ctx->stream;
+  if (m->kv_bits) { lm_kvq_launch_attention(s, lm_kvq_layer(m, layer), fused, rows, (const uint16_t*)q, (uint16_t*)att, rowmap, part, S, bias); return 0; }
+  const int64_t seq_stride = (int64_t)c.n_kv_heads * c.max_ctx * c.head_dim;
+  uint16_t* kc = (uint16_t*)m->k_cache + (size_t)layer * m->B_cap * seq_stride;
+  uint16_t* vc = (uint16_t*)m->v_cache + (size_t)layer * m->B_cap * seq_stride;
   const int dh = c.head_dim;
   const size_t lds = (size_t)(c.max_ctx + ATT_NW * dh + 2 * ATT_NW + 3 * dh) * 4;
   const float scale = 1.0f / sqrtf((float)dh);
@@ -345,6 +371,8 @@ int lm_launch_attention(mia_lm* m, bool fused, int rows, const void* q, uint16_t
 #undef ATT_GO
   return 0;
 }
+
+namespace {
 
 // (the samplers read each sequence's prompt length from its state: a captured and a directly launched step issue the same arguments)
 int lm_enqueue_step(mia_lm* m, bool sampling, const mia_lm_sampler& sp, const RasParams* ras = nullptr, int nb = 1) {
@@ -375,24 +403,21 @@ int lm_enqueue_step(mia_lm* m, bool sampling, const mia_lm_sampler& sp, const Ra
     return skinny_gemm_launch(a, mode, m->dtype, s);
   };
   LAUNCH_T(lm_embed_norm, dim3(nb), dim3(256), 0, m->tokens, (const uint16_t*)m->embed, (const uint16_t*)m->gen_embed, m->embeds, m->layers[0].in_norm, m->x, (uint16_t*)m->h, m->state, D, c.rms_eps, (const int2*)nullptr, c.max_ctx, c.vocab, m->gen_rows);
-  const size_t layer_stride = (size_t)m->B_cap * c.n_kv_heads * c.max_ctx * dh;
   for (int l = 0; l < c.n_layers; ++l) {
     const LmLayer& L = m->layers[l];
-    uint16_t* kc = (uint16_t*)m->k_cache + (size_t)l * layer_stride;
-    uint16_t* vc = (uint16_t*)m->v_cache + (size_t)l * layer_stride;
     const float* next_norm = l + 1 < c.n_layers ? m->layers[l + 1].in_norm : m->final_norm;
     const float* next_norm_c = l + 1 < c.n_layers ? m->layers[l + 1].in_norm_c : m->final_norm_c;
     if (fused_norm) {
       // layer 0 reads the embedding kernel's (normalised) h; later layers the previous down-proj's x * norm weight + its sums of squares
       if (skinny(m->h, D, L.wqkv, L.wqkv_f, nullptr, m->qkv_part, 0, Nqkv, D, m->S_qkv, SK_PARTIAL, &L.q_qkv, l > 0 ? ss_d : nullptr, nullptr, nullptr, L.in_rs)) return -1;
-      lm_launch_attention(m, true, nb, nullptr, kc, vc, m->att, nullptr, m->qkv_part, m->S_qkv, L.bqkv);      // RoPE + cache row + attention
+      lm_launch_attention(m, true, nb, nullptr, l, m->att, nullptr, m->qkv_part, m->S_qkv, L.bqkv);      // RoPE + cache row + attention
       if (skinny(m->att, Nq, L.wo, L.wo_f, nullptr, m->h, D, D, Nq, 1, SK_RESID, &L.q_o, nullptr, L.post_norm_c, ss_o)) return -1;
       if (skinny(m->h, D, L.wgu, L.wgu_f, nullptr, m->act, c.inter, 2 * c.inter, D, 1, SK_SWIGLU, &L.q_gu, ss_o, nullptr, nullptr, L.post_rs)) return -1;
       if (skinny(m->act, c.inter, L.wdown, L.wdown_f, nullptr, m->h, D, D, c.inter, 1, SK_RESID, &L.q_down, nullptr, next_norm_c, ss_d)) return -1;
       continue;
     }
     if (skinny(m->h, D, L.wqkv, L.wqkv_f, nullptr, m->qkv_part, 0, Nqkv, D, m->S_qkv, SK_PARTIAL, &L.q_qkv)) return -1;
-    lm_launch_attention(m, true, nb, nullptr, kc, vc, m->att, nullptr, m->qkv_part, m->S_qkv, L.bqkv);      // RoPE + cache row + attention
+    lm_launch_attention(m, true, nb, nullptr, l, m->att, nullptr, m->qkv_part, m->S_qkv, L.bqkv);      // RoPE + cache row + attention
     if (skinny(m->att, Nq, L.wo, L.wo_f, nullptr, m->partial, 0, D, Nq, m->S_o, SK_PARTIAL, &L.q_o)) return -1;
     LAUNCH_T(lm_reduce_norm, dim3(nb), dim3(256), 0, m->partial, m->S_o, L.post_norm, m->x, (uint16_t*)m->h, D, c.rms_eps, nb);
     if (skinny(m->h, D, L.wgu, L.wgu_f, nullptr, m->act, c.inter, 2 * c.inter, D, 1, SK_SWIGLU, &L.q_gu)) return -1;
@@ -456,8 +481,6 @@ int lm_prefill_rows(mia_lm* m, const std::vector<int2>& rows, const std::vector<
     return mia_gemm_launch(g, m->dtype, s);
   };
   const int P = (int)rows.size();
-  const int64_t seq_stride = (int64_t)c.n_kv_heads * c.max_ctx * dh;
-  const size_t layer_stride = (size_t)m->B_cap * seq_stride;
   for (int r0 = 0; r0 < P; r0 += PF_ROWS) {
     const int M = std::min(PF_ROWS, P - r0);
     // (pageable source: the copy is staged before the call returns, and the stream orders it behind the previous chunk's kernels)
@@ -466,13 +489,10 @@ int lm_prefill_rows(mia_lm* m, const std::vector<int2>& rows, const std::vector<
              m->state, D, c.rms_eps, (const int2*)rowmap, c.max_ctx, c.vocab, m->gen_rows);
     for (int l = 0; l < c.n_layers; ++l) {
       const LmLayer& L = m->layers[l];
-      uint16_t* kc = (uint16_t*)m->k_cache + (size_t)l * layer_stride;
-      uint16_t* vc = (uint16_t*)m->v_cache + (size_t)l * layer_stride;
       if (gemm(h, D, L.wqkv, nullptr, qkv, Nqkv, M, nullptr)) return MIA_ERR_DEVICE;
-      const int n_el = (c.n_heads + c.n_kv_heads) * (dh / 2) + Nk;
-      LAUNCH_T(lm_rope_cache, dim3((n_el + 255) / 256, M), dim3(256), 0, qkv, 1, L.bqkv, m->inv_freq, q, kc, vc, (const int2*)rowmap, c.n_heads, c.n_kv_heads, dh, c.max_ctx, seq_stride);
+      lm_launch_rope_cache(m, l, qkv, L.bqkv, q, rowmap, M);
       if (l + 1 == c.n_layers) break;            // past its K/V rows the last layer feeds only the head, which the prompt pass skips
-      lm_launch_attention(m, false, M, q, kc, vc, att, rowmap, nullptr, 0, nullptr);
+      lm_launch_attention(m, false, M, q, l, att, rowmap, nullptr, 0, nullptr);
       if (gemm(att, Nq, L.wo, nullptr, x, D, M, x)) return MIA_ERR_DEVICE;                // x += att . Wo^T
       LAUNCH_T(lm_reduce_norm, dim3(M), dim3(256), 0, (const float*)nullptr, 0, L.post_norm, x, h, D, c.rms_eps, 1);
       if (gemm(h, D, L.wgu, nullptr, gu, 2 * I, M, nullptr)) return MIA_ERR_DEVICE;
@@ -573,6 +593,61 @@ extern "C" int mia_lm_set_batch(mia_lm* m, int max_batch) {
   if (max_batch == m->B_cap) return MIA_OK;
   if (lm_alloc_state(m, max_batch)) return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "lm_set_batch: state buffers for %d sequences", max_batch);
   MIA_HIP(ctx, hipDeviceSynchronize());
+  return MIA_OK;
+}
+
+// QuantizedKVCache(groupSize:bits:) in place of KVCacheSimple (OrpheusModel.newCache, TransformerBlock.swift:182-201): bits 4 | 8 keeps K/V
+// as codes + per-64 (scale, bias) pairs (lm_kvq.hip), bits 0 restores the 16-bit caches.  Re-allocates the per-sequence state at the
+// current capacity (either order with mia_lm_set_batch), drops the step graph and resets every sequence; cache contents are not converted.
+extern "C" int mia_lm_set_kv_quant(mia_lm* m, int bits, int group_size) {
+  if (!m) return MIA_ERR_MODEL_NOT_LOADED;
+  mia_ctx* ctx = m->ctx;
+  int code = MIA_OK;
+  if (const char* e = lm_kvq_check(bits, group_size, m->cfg.head_dim, &code)) return mia_fail(ctx, code, "lm_set_kv_quant: %s (bits %d, group_size %d)", e, bits, group_size);
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const int before = m->kv_bits;
+  m->kv_bits = bits;
+  if (lm_alloc_state(m, m->B_cap)) {
+    m->kv_bits = before;
+    (void)lm_alloc_state(m, m->B_cap);
+    return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "lm_set_kv_quant: state buffers for %d sequences", m->B_cap);
+  }
+  MIA_HIP(ctx, hipDeviceSynchronize());
+  return MIA_OK;
+}
+
+// test hook: rows [pos0, pos0 + n) of every kv head of (layer, seq) as fp32 [Hkv][n][dh] -- scale * code + bias from the packed cache,
+// widened from the 16-bit one.  Host pointers.
+extern "C" int mia_lm_read_kv(mia_lm* m, int layer, int seq, int pos0, int n, float* k_out, float* v_out) {
+  if (!m) return MIA_ERR_MODEL_NOT_LOADED;
+  mia_ctx* ctx = m->ctx;
+  const mia_lm_config& c = m->cfg;
+  MIA_CHECK_ARG(ctx, k_out && v_out, "lm_read_kv: null output");
+  MIA_CHECK_ARG(ctx, layer >= 0 && layer < c.n_layers && seq >= 0 && seq < m->B_cap, "lm_read_kv: layer %d / sequence %d out of range (%d layers, capacity %d)", layer, seq, c.n_layers, m->B_cap);
+  MIA_CHECK_ARG(ctx, pos0 >= 0 && n > 0 && pos0 <= c.max_ctx - n, "lm_read_kv: rows [%d, %d + %d) outside [0, %d)", pos0, pos0, n, c.max_ctx);
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const int dh = c.head_dim;
+  const size_t wpr = m->kv_bits ? (size_t)dh * m->kv_bits / 32 : (size_t)dh / 2, gpr = dh / 64;      // dwords per row
+  std::vector<uint32_t> rows((size_t)n * wpr), pairs((size_t)n * gpr);
+  for (int kv = 0; kv < 2; ++kv)
+    for (int hd = 0; hd < c.n_kv_heads; ++hd) {
+      const size_t r0 = (((size_t)layer * m->B_cap + seq) * c.n_kv_heads + hd) * c.max_ctx + pos0;
+      float* out = (kv ? v_out : k_out) + (size_t)hd * n * dh;
+      if (m->kv_bits) {
+        MIA_HIP(ctx, hipMemcpy(rows.data(), (kv ? m->vq_codes : m->kq_codes) + r0 * wpr, rows.size() * 4, hipMemcpyDeviceToHost));
+        MIA_HIP(ctx, hipMemcpy(pairs.data(), (kv ? m->vq_pairs : m->kq_pairs) + r0 * gpr, pairs.size() * 4, hipMemcpyDeviceToHost));
+        lm_kvq_read_rows(rows.data(), pairs.data(), n, dh, m->kv_bits, m->dtype, out);
+      } else {
+        MIA_HIP(ctx, hipMemcpy(rows.data(), (const uint32_t*)(kv ? m->v_cache : m->k_cache) + r0 * wpr, rows.size() * 4, hipMemcpyDeviceToHost));
+        const uint16_t* src = (const uint16_t*)rows.data();
+        for (size_t i = 0; i < (size_t)n * dh; ++i) {
+          if (m->dtype == MIA_F16) { _Float16 hh; memcpy(&hh, &src[i], 2); out[i] = (float)hh; }
+          else { const uint32_t u = (uint32_t)src[i] << 16; memcpy(&out[i], &u, 4); }
+        }
+      }
+    }
   return MIA_OK;
 }
 

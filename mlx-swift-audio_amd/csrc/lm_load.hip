@@ -77,8 +77,12 @@ int lm_alloc_state(mia_lm* m, int B) {
     m->state_allocs.push_back(p);
     return p;
   };
-  const size_t kv = (size_t)c.n_layers * B * c.n_kv_heads * c.max_ctx * dh * 2;
-  m->k_cache = dev(kv); m->v_cache = dev(kv);
+  // K/V: the 16-bit caches, or (mia_lm_set_kv_quant) code dwords + one (scale, bias) dword per 64 values -- never both
+  const size_t kv_rows = (size_t)c.n_layers * B * c.n_kv_heads * c.max_ctx;
+  const size_t kv = m->kv_bits ? 0 : kv_rows * dh * 2, kvq = kv_rows * dh * m->kv_bits / 8, kvp = m->kv_bits ? kv_rows * (dh / 64) * 4 : 0;
+  m->k_cache = m->v_cache = nullptr; m->kq_codes = m->vq_codes = m->kq_pairs = m->vq_pairs = nullptr;
+  if (m->kv_bits) { m->kq_codes = (uint32_t*)dev(kvq); m->vq_codes = (uint32_t*)dev(kvq); m->kq_pairs = (uint32_t*)dev(kvp); m->vq_pairs = (uint32_t*)dev(kvp); }
+  else { m->k_cache = dev(kv); m->v_cache = dev(kv); }
   m->x = (float*)dev((size_t)B * D * 4); m->h = dev((size_t)B * D * 2);
   m->qkv_part = (float*)dev((size_t)4 * B * (Nq + 2 * Nk) * 4); m->q = dev((size_t)B * Nq * 2); m->att = dev((size_t)B * Nq * 2); m->act = dev((size_t)B * c.inter * 2);
   m->ss = (float*)dev((size_t)2 * ((D + 15) / 16) * B * 4);
@@ -87,7 +91,9 @@ int lm_alloc_state(mia_lm* m, int B) {
   m->state = (LmState*)dev(sizeof(LmState) * B); m->smx = dev(lm_sample_ws_bytes() * B);
   m->embeds = (float*)dev((size_t)B * c.max_ctx * D * 4); m->out_tokens = (int32_t*)dev((size_t)B * c.max_ctx * 4);
   if (!ok) return -1;
-  (void)hipMemset(m->k_cache, 0, kv); (void)hipMemset(m->v_cache, 0, kv); (void)hipMemset(m->state, 0, sizeof(LmState) * B);
+  if (m->kv_bits) { (void)hipMemset(m->kq_codes, 0, kvq); (void)hipMemset(m->vq_codes, 0, kvq); (void)hipMemset(m->kq_pairs, 0, kvp); (void)hipMemset(m->vq_pairs, 0, kvp); }
+  else { (void)hipMemset(m->k_cache, 0, kv); (void)hipMemset(m->v_cache, 0, kv); }
+  (void)hipMemset(m->state, 0, sizeof(LmState) * B);
   m->B_cap = B;
   return 0;
 }

@@ -63,3 +63,70 @@ extern "C" int mia_op_attention_f32(mia_ctx* ctx, const float* q, int64_t ldq, c
   if (mia_attn_f32_launch(a, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_attention_f32: launch failed");
   return MIA_OK;
 }
+
+// The LM's single-token GQA attention over a cache it fills itself, without a model around it: K / V rows [Hkv][T][dh] (16 bit, taken
+// as already rotated) go through the prompt pass's cache writer -- lm_rope_cache, or lm_kvq_rope_cache for bits 4 | 8 (QuantizedKVCache,
+// TransformerBlock.swift:182-201) -- with all rotation angles zero, which leaves a 16-bit value unchanged; then the non-fused attention
+// kernel of that cache mode runs q [Hq][dh] at position T - 1 over keys [0, T).  out fp32 [Hq][dh].  Host pointers.
+#include "lm.h"
+extern "C" int mia_op_kvq_attention(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int dh, int bits, int dtype) {
+  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, q && k && v && out, "op_kvq_attention: null pointer");
+  MIA_CHECK_ARG(ctx, dtype == MIA_BF16 || dtype == MIA_F16, "op_kvq_attention: dtype must be MIA_BF16 or MIA_F16");
+  MIA_CHECK_ARG(ctx, Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq <= 1024 && T > 0 && T <= 8192, "op_kvq_attention: bad shape (Hq %% Hkv == 0, 1 <= T <= 8192)");
+  int code = MIA_OK;
+  if (const char* e = lm_kvq_check(bits, 64, dh, &code)) return mia_fail(ctx, code, "op_kvq_attention: %s (bits %d, head_dim %d)", e, bits, dh);
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  const int Nq = Hq * dh, Nk = Hkv * dh, N = Nq + 2 * Nk;
+  auto widen = [&](uint16_t x) -> float {
+    if (dtype == MIA_F16) { _Float16 h; memcpy(&h, &x, 2); return (float)h; }
+    const uint32_t u = (uint32_t)x << 16; float f; memcpy(&f, &u, 4); return f;
+  };
+  // the q|k|v rows a prompt pass would hand the cache writer: row t = [q (last row only) | K[.][t] | V[.][t]]
+  std::vector<float> part((size_t)T * N, 0.f);
+  std::vector<int2> rowmap(T);
+  const uint16_t* q16 = (const uint16_t*)q; const uint16_t* k16 = (const uint16_t*)k; const uint16_t* v16 = (const uint16_t*)v;
+  for (int i = 0; i < Nq; ++i) part[(size_t)(T - 1) * N + i] = widen(q16[i]);
+  for (int t = 0; t < T; ++t) {
+    rowmap[t] = make_int2(0, t);
+    for (int h = 0; h < Hkv; ++h)
+      for (int d = 0; d < dh; ++d) {
+        part[(size_t)t * N + Nq + h * dh + d] = widen(k16[((size_t)h * T + t) * dh + d]);
+        part[(size_t)t * N + Nq + Nk + h * dh + d] = widen(v16[((size_t)h * T + t) * dh + d]);
+      }
+  }
+  const size_t rows = (size_t)Hkv * T;
+  const size_t b_part = align_up(part.size() * 4, 256), b_map = align_up((size_t)T * sizeof(int2), 256), b_freq = align_up((size_t)dh / 2 * 4, 256),
+               b_q = align_up((size_t)T * Nq * 2, 256), b_att = align_up((size_t)Nq * 2, 256), b_st = align_up(sizeof(LmState), 256),
+               b_codes = align_up(bits ? rows * dh * bits / 8 : rows * dh * 2, 256), b_pairs = align_up(rows * (dh / 64) * 4, 256);
+  char* ws = (char*)mia_workspace(ctx, b_part + b_map + b_freq + b_q + b_att + b_st + 2 * b_codes + 2 * b_pairs);
+  if (!ws) return MIA_ERR_OUT_OF_MEMORY;
+  hipStream_t s = ctx->stream;
+  char* p = ws;
+  float* d_part = (float*)p; p += b_part;
+  int2* d_map = (int2*)p; p += b_map;
+  float* d_freq = (float*)p; p += b_freq;
+  uint16_t* d_q = (uint16_t*)p; p += b_q;
+  uint16_t* d_att = (uint16_t*)p; p += b_att;
+  LmState* d_st = (LmState*)p; p += b_st;
+  char* d_kc = p; p += b_codes;
+  char* d_vc = p; p += b_codes;
+  char* d_kp = p; p += b_pairs;
+  char* d_vp = p;
+  MIA_HIP(ctx, hipMemcpyAsync(d_part, part.data(), part.size() * 4, hipMemcpyHostToDevice, s));
+  MIA_HIP(ctx, hipMemcpyAsync(d_map, rowmap.data(), (size_t)T * sizeof(int2), hipMemcpyHostToDevice, s));
+  MIA_HIP(ctx, hipMemsetAsync(d_freq, 0, b_freq + b_q + b_att + b_st, s));
+  mia_lm sh;                      // a bare handle: what the two launch sites read of one
+  sh.ctx = ctx; sh.dtype = dtype; sh.kv_bits = bits; sh.B_cap = 1; sh.state = d_st; sh.inv_freq = d_freq;
+  sh.cfg.n_layers = 1; sh.cfg.n_heads = Hq; sh.cfg.n_kv_heads = Hkv; sh.cfg.head_dim = dh; sh.cfg.max_ctx = T;
+  if (bits) { sh.kq_codes = (uint32_t*)d_kc; sh.vq_codes = (uint32_t*)d_vc; sh.kq_pairs = (uint32_t*)d_kp; sh.vq_pairs = (uint32_t*)d_vp; }
+  else { sh.k_cache = d_kc; sh.v_cache = d_vc; }
+  lm_launch_rope_cache(&sh, 0, d_part, nullptr, d_q, d_map, T);
+  lm_launch_attention(&sh, false, 1, d_q + (size_t)(T - 1) * Nq, 0, d_att, d_map + (T - 1), nullptr, 0, nullptr);
+  if (hipGetLastError() != hipSuccess) return mia_fail(ctx, MIA_ERR_DEVICE, "op_kvq_attention: launch failed");
+  std::vector<uint16_t> att(Nq);
+  MIA_HIP(ctx, hipMemcpyAsync(att.data(), d_att, (size_t)Nq * 2, hipMemcpyDeviceToHost, s));
+  MIA_HIP(ctx, hipStreamSynchronize(s));
+  for (int i = 0; i < Nq; ++i) out[i] = widen(att[i]);
+  return MIA_OK;
+}

@@ -183,6 +183,30 @@ CausalLM.set_batch = _set_batch
 CausalLM.generate_batch = _generate_batch
 
 
+def _new_cache(self, quantized: bool = False, group_size: int = 64, bits: int = 4) -> None:
+    """OrpheusModel.newCache(quantized:groupSize:bits:) (TransformerBlock.swift:182-201): quantized=True keeps K/V as 4- / 8-bit codes plus
+    a (scale, bias) pair per 64 values (mia_lm_set_kv_quant), False restores the 16-bit caches.  Every sequence is reset either way."""
+    lib = self.ctx.lib
+    lib.mia_lm_set_kv_quant.restype = C.c_int
+    lib.mia_lm_set_kv_quant.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    self.ctx.check(lib.mia_lm_set_kv_quant(self.h, int(bits) if quantized else 0, int(group_size)))
+
+
+def _read_kv(self, layer: int, seq: int, pos0: int, n: int) -> tuple[np.ndarray, np.ndarray]:
+    """Test hook (mia_lm_read_kv): cache rows [pos0, pos0 + n) of (layer, seq) as fp32 (k, v), each [n_kv_heads, n, head_dim]."""
+    lib = self.ctx.lib
+    lib.mia_lm_read_kv.restype = C.c_int
+    lib.mia_lm_read_kv.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    k = np.empty((self.cfg.n_kv_heads, max(int(n), 0), self.cfg.head_dim), np.float32)
+    v = np.empty_like(k)
+    self.ctx.check(lib.mia_lm_read_kv(self.h, int(layer), int(seq), int(pos0), int(n), k.ctypes.data, v.ctypes.data))
+    return k, v
+
+
+CausalLM.new_cache = _new_cache
+CausalLM.read_kv = _read_kv
+
+
 def _generate_ras(self, prompt_embeds, uniforms, min_len, max_len, eos, top_p=0.8, top_k=25, win=10, tau=0.1) -> list[int]:
     """mia_lm_generate_ras: embedding-row prompt -> RAS-sampled ids (stops at `eos` once min_len ids are out, or at max_len)."""
     lib = self.ctx.lib
@@ -289,8 +313,10 @@ class OrpheusTTS:
     """generateChunk (TTS/Orpheus/TTSEngine/OrpheusTTS.swift:224-373) from token ids onward: LM sampling loop ->
     parseOutput -> SNAC decode.  Text tokenisation / voice prefix / sentence splitting stay with the caller (CPU text code)."""
 
-    def __init__(self, lm: CausalLM, snac):
+    def __init__(self, lm: CausalLM, snac, kv_bits: int | None = None):
         self.lm, self.snac = lm, snac
+        if kv_bits is not None:                      # newCache(quantized: kv_bits != 0, bits: kv_bits); None leaves the handle's mode alone
+            lm.new_cache(quantized=kv_bits != 0, bits=kv_bits or 4)
 
     def generate_chunk(self, input_ids, uniforms, noise=None, temperature=0.6, top_p=0.8, max_new_tokens=MAX_TOKEN_COUNT):
         gen = self.lm.generate(input_ids, uniforms, temperature=temperature, top_p=top_p, rep_penalty=1.3,

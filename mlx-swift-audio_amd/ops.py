@@ -40,3 +40,17 @@ def linear(ctx: _lib.Context, x: np.ndarray, w: np.ndarray, bias=None, residual=
                                     None if r is None else r.ctypes.data, N, y.ctypes.data, N, M, N, K,
                                     1 if act == "gelu" else 0, dtype, 1 if out_f32 else 0, variant, _lib.MEM_HOST))
     return y if out_f32 else from16(y, dtype)
+
+
+def kvq_attention(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.ndarray, bits: int = 4, dtype: int = _lib.BF16) -> np.ndarray:
+    """mia_op_kvq_attention: the LM's single-token GQA attention for the last of T positions over a cache the op fills from k / v
+    [Hkv, T, dh] (fp32 here, rounded to `dtype`): bits 0 = the 16-bit cache, 4 | 8 = the quantised one.  q [Hq, dh]; returns fp32 [Hq, dh]."""
+    lib = ctx.lib
+    lib.mia_op_kvq_attention.restype = C.c_int
+    lib.mia_op_kvq_attention.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6
+    Hq, dh = q.shape
+    Hkv, T, _ = k.shape
+    q16, k16, v16 = to16(q, dtype), to16(k, dtype), to16(v, dtype)
+    out = np.empty((Hq, dh), np.float32)
+    ctx.check(lib.mia_op_kvq_attention(ctx.h, q16.ctypes.data, k16.ctypes.data, v16.ctypes.data, out.ctypes.data, Hq, Hkv, T, dh, int(bits), dtype))
+    return out
