@@ -235,6 +235,25 @@ void mia_whisper_free(mia_whisper* w);
  * context (= another HIP stream) of the same device -- for decoding different batches concurrently (the reference has one model per
  * actor; this is the serving-side counterpart).  Free every clone before the handle it was cloned from. */
 mia_whisper* mia_whisper_clone(mia_whisper* src, mia_ctx* ctx);
+/* MLX-affine quantised decoder weights for the decode step (group 64; 4- or 8-bit codes): the reference's default engine loads Whisper
+ * in 4 bit and keeps every quantised module packed (STT/Whisper/WhisperModel.swift:189-196).  mia_whisper_attach_quantized takes the
+ * decoder matrices the step reads as stored -- `<p>.weight` (MIA_U32 codes [N][K * bits / 32], little end first), `<p>.scales`,
+ * `<p>.biases` ([N][K/64]; f16, bf16 or f32, one type for all) for p = decoder.blocks.L.{attn.{query,key,value,out},
+ * cross_attn.{query,out}, mlp1, mlp2} and decoder.token_embedding -- onto a handle loaded from the de-quantised checkpoint; other
+ * tensors (the encoder, cross_attn.{key,value}) are ignored and stay on the 16-bit copy.  n_text_state must be a multiple of 128.  One
+ * attach per handle, on the handle that owns the weights and before it is cloned.  Errors: MIA_ERR_INVALID_ARGUMENT for anything wrong
+ * with the call (a missing or mis-shaped tensor, bits, group size, a clone, a handle with clones, a second attach), MIA_ERR_OUT_OF_MEMORY
+ * when the device refuses the buffers, MIA_ERR_DEVICE when an upload fails; after any of them the handle is unchanged.  mia_whisper_use_packed(w, 1) makes the decode step (mia_whisper_decode_greedy, mia_whisper_align,
+ * mia_whisper_detect_language) stream the packed codes and multiply them as MLX's kernels do (per group: scale * sum(code * x) + bias *
+ * sum(x), fp32 group sums, no weight rounded); 0 (the default) restores the 16-bit step exactly.  A clone inherits the packed weights and
+ * the switch of the handle it was cloned from. */
+int mia_whisper_attach_quantized(mia_whisper* w, const mia_tensor_view* tensors, int n_tensors, int group_size, int bits);
+int mia_whisper_use_packed(mia_whisper* w, int on);
+/* Test hook: the host repack of one packed Linear [N][K] (K % 128 == 0) into the fragment-ordered arrays the packed step kernels read:
+ * wfrag [ceil(N/16)][K/128][bits/4][64][4] uint32, stfrag [ceil(N/16)][K/128][16][4] float = (scale, bias - MAG * scale) per group, MAG =
+ * 1024 (MIA_F16 compute) or 128 (MIA_BF16), x 17 for 8 bit.  Host memory in and out; needs no device. */
+int mia_quant_repack(const uint32_t* codes, const void* scales, const void* biases, int N, int K, int bits, int scale_dtype,
+                     int compute_dtype, uint32_t* wfrag, float* stfrag);
 /* Test hook: force the encoder GEMM tile variant (0 / 1: 128^2 register / LDS-DMA staged, 2: 256^2 two-buffer, 3: automatic
  * (default), 4: 256^2 8-phase).  Results are identical up to fp32 summation order; anything else is MIA_ERR_INVALID_ARGUMENT. */
 int mia_whisper_set_gemm_variant(mia_whisper* w, int variant);

@@ -114,11 +114,22 @@ def expand_checkpoint(ctx: _lib.Context, tensors: dict[str, np.ndarray], bits: i
     return out
 
 
-def load_whisper_checkpoint(ctx: _lib.Context, model_dir: str):
-    """WhisperModel.load's file half (WhisperModel.swift:175-206): config.json + model.safetensors -> (ModelDimensions, dense tensors)."""
+def packed_tensors(tensors: dict[str, np.ndarray]) -> dict[str, np.ndarray]:
+    """The raw `<p>.weight` / `<p>.scales` / `<p>.biases` triples of a checkpoint's quantised modules (what expand_checkpoint de-quantises)."""
+    return {n: a for n, a in tensors.items()
+            if n.endswith((".weight", ".scales", ".biases")) and n.rsplit(".", 1)[0] + ".scales" in tensors}
+
+
+def load_whisper_checkpoint(ctx: _lib.Context, model_dir: str, keep_packed: bool = False):
+    """WhisperModel.load's file half (WhisperModel.swift:175-206): config.json + model.safetensors -> (ModelDimensions, dense tensors).
+    keep_packed: a third value, the raw packed tensors of the quantised modules (empty for a dense checkpoint), for
+    WhisperModel.attach_quantized -- the reference keeps them packed (WhisperModel.swift:189-196)."""
     import os
     dims = load_model_dimensions(os.path.join(model_dir, "config.json"))
-    return dims, expand_checkpoint(ctx, read_safetensors(os.path.join(model_dir, "model.safetensors")))
+    raw = read_safetensors(os.path.join(model_dir, "model.safetensors"))
+    if keep_packed:
+        return dims, expand_checkpoint(ctx, raw), packed_tensors(raw)
+    return dims, expand_checkpoint(ctx, raw)
 
 
 def quantize_affine(w: np.ndarray, group_size: int = 64, bits: int = 4, scale_dtype=np.float16):

@@ -7,6 +7,9 @@ int dec_launch_embed_ln(mia_whisper* w, const LNW& ln, hipStream_t s);
 int dec_launch_reduce_ln(mia_whisper* w, int S, const float* bias, const LNW& ln, hipStream_t s);
 // Whisper step: a.A in activation fragment order, a.W in weight fragment order (LinearW::wf)
 int dec_launch_skinny(mia_whisper* w, const SkinnyArgs& a, int mode, hipStream_t s);
+// the same on packed 4- / 8-bit weights (skinny_frag_quant.hip; LinearW::qw / qst): a.W is ignored, K % (128 S) == 0, modes SK_QKV /
+// SK_OUT16 / SK_PARTIAL / SK_OUTF32, no carried LayerNorm (a.ss_in / a.c1 must be null)
+int dec_launch_skinny_q(mia_whisper* w, const SkinnyArgs& a, const uint32_t* wfrag, const float* stfrag, int bits, int mode, hipStream_t s);
 // c1[n] = sum_k W[n][k] gamma[k], c2[n] = sum_k W[n][k] beta[k] for a row-major 16-bit [N][K] matrix (fp32 sums in k order)
 int dec_launch_lnfold(const void* w16, int N, int K, const float* gamma, const float* beta, float* c1, float* c2, int dtype, hipStream_t s, const float* bias = nullptr);
 // qk_out (optional): pre-softmax scores of the heads with head_slot[h] >= 0 -> qk_out[b][slot][pos[b]][key] (word-timestamp alignment)

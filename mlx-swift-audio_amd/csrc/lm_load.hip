@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "lm.h"
+#include "quant_repack.h"
 #include "skinny.h"
 
 namespace {
@@ -209,49 +210,12 @@ extern "C" mia_lm* mia_lm_load(mia_ctx* ctx, const mia_lm_config* cfg, const mia
 // ---- MLX-affine 4-bit weights for the decode step (OrpheusWeightLoader.swift:28-60: the reference's default checkpoints are q4, group 64) ----
 namespace {
 
-struct Q4Src { const uint32_t* w; const uint16_t* s; const uint16_t* b; };   // one Linear as stored: packed [N][K*bits/32], scales / biases [N][K/64]
-
-float q16_to_f32(uint16_t v, int sdt) {
-  if (sdt == MIA_F16) { _Float16 h; memcpy(&h, &v, 2); return (float)h; }
-  const uint32_t u = (uint32_t)v << 16; float f; memcpy(&f, &u, 4); return f;
-}
-
-// rows[i] = (tensor index, row): the fused matrix's row i.  Builds the fragment-ordered arrays (layout and arithmetic: skinny_gemm_qi)
-// and uploads them.  bits 4 | 8; mag = the 16-bit float the codes are OR-ed into (128 for bf16, 1024 for f16 compute).
+// rows[i] = (tensor index, row): the fused matrix's row i.  Builds the fragment-ordered arrays (quant_repack.h; layout and arithmetic:
+// skinny_gemm_qi) and uploads them.  bits 4 | 8; mag = the 16-bit float the codes are OR-ed into (128 for bf16, 1024 for f16 compute).
 bool q_repack(LmLoader& L, const std::vector<Q4Src>& src, const std::vector<std::pair<int, int>>& rows, int K, int bits, int sdt, float mag, Q4W& out) {
-  const int N = (int)rows.size(), tiles = (N + 15) / 16, nblk = K / 128, np = bits / 4, cpw = 32 / bits, wpr = K / cpw, gpr = K / 64;
-  std::vector<uint32_t> wf((size_t)tiles * nblk * np * 64 * 4);
-  std::vector<float> st((size_t)tiles * nblk * 16 * 4);
-  const float tmul = mag * (np == 2 ? 17.0f : 1.0f);
-  for (int t = 0; t < tiles; ++t)
-    for (int r = 0; r < 16; ++r) {
-      const int n = std::min(t * 16 + r, N - 1);                      // the last tile repeats its final row (never stored)
-      const Q4Src& q = src[rows[n].first];
-      const uint32_t* wrow = q.w + (size_t)rows[n].second * wpr;
-      const uint16_t* srow = q.s + (size_t)rows[n].second * gpr;
-      const uint16_t* brow = q.b + (size_t)rows[n].second * gpr;
-      auto code = [&](int k) -> uint32_t { return (wrow[k / cpw] >> ((k % cpw) * bits)) & ((1u << bits) - 1u); };   // MLX packing: little end first
-      for (int b = 0; b < nblk; ++b) {
-        for (int c = 0; c < 4; ++c)
-          for (int stp = 0; stp < 4; ++stp) {
-            const int k0 = b * 128 + 32 * stp + 8 * c;
-            for (int p = 0; p < np; ++p) {
-              uint32_t word = 0;
-              for (int i = 0; i < 4; ++i) {
-                const uint32_t q0 = (code(k0 + 2 * i) >> (4 * p)) & 15u, q1 = (code(k0 + 2 * i + 1) >> (4 * p)) & 15u;
-                word |= (q0 << (4 * i)) | (q1 << (16 + 4 * i));
-              }
-              wf[((((size_t)t * nblk + b) * np + p) * 64 + 16 * c + r) * 4 + stp] = word;
-            }
-          }
-        for (int g = 0; g < 2; ++g) {
-          const float sc = q16_to_f32(srow[2 * b + g], sdt), bi = q16_to_f32(brow[2 * b + g], sdt);
-          float* d = &st[(((size_t)t * nblk + b) * 16 + r) * 4 + 2 * g];
-          d[0] = sc;
-          d[1] = (float)((double)bi - (double)tmul * (double)sc);
-        }
-      }
-    }
+  std::vector<uint32_t> wf;
+  std::vector<float> st;
+  q_repack_host(src, rows, K, bits, sdt, mag, wf, st);
   out.wfrag = (uint32_t*)L.dev(wf.size() * 4);
   out.stfrag = (float*)L.dev(st.size() * 4);
   if (!out.wfrag || !out.stfrag) { if (L.err.empty()) L.err = "hipMalloc failed for the packed weights"; return false; }
@@ -289,7 +253,7 @@ extern "C" int mia_lm_attach_quantized(mia_lm* m, const mia_tensor_view* tensors
     if (!ok) { if (L.err.empty()) L.err = "'" + p + "' is not a " + std::to_string(bits) + "-bit group-64 Linear of the expected shape (scales / biases must be f16 or bf16)"; return false; }
     if (sdt == 0) sdt = s->dtype;
     if (sdt != s->dtype) { if (L.err.empty()) L.err = "mixed scale dtypes"; return false; }
-    q = Q4Src{(const uint32_t*)w->data, (const uint16_t*)s->data, (const uint16_t*)b->data};
+    q = Q4Src{(const uint32_t*)w->data, s->data, b->data};
     return true;
   };
   auto seq = [](int tensor, int n, std::vector<std::pair<int, int>>& rows) { for (int i = 0; i < n; ++i) rows.push_back({tensor, i}); };

@@ -1,0 +1,72 @@
+// quant_repack.hip -- host repack of packed MLX-affine Linears into fragment order (quant_repack.h); no device code.
+#include "quant_repack.h"
+
+#include <string.h>
+
+#include <algorithm>
+
+#include "../../include/mia.h"
+
+namespace {
+
+float q_to_f32(const void* p, size_t i, int sdt) {
+  if (sdt == MIA_F32) return ((const float*)p)[i];
+  const uint16_t v = ((const uint16_t*)p)[i];
+  if (sdt == MIA_F16) { _Float16 h; memcpy(&h, &v, 2); return (float)h; }
+  const uint32_t u = (uint32_t)v << 16; float f; memcpy(&f, &u, 4); return f;
+}
+
+}  // namespace
+
+void q_repack_host(const std::vector<Q4Src>& src, const std::vector<std::pair<int, int>>& rows, int K, int bits, int sdt, float mag,
+                   std::vector<uint32_t>& wf, std::vector<float>& st) {
+  const int N = (int)rows.size(), tiles = (N + 15) / 16, nblk = K / 128, np = bits / 4, cpw = 32 / bits, wpr = K / cpw, gpr = K / 64;
+  wf.assign((size_t)tiles * nblk * np * 64 * 4, 0u);
+  st.assign((size_t)tiles * nblk * 16 * 4, 0.f);
+  const float tmul = mag * (np == 2 ? 17.0f : 1.0f);
+  for (int t = 0; t < tiles; ++t)
+    for (int r = 0; r < 16; ++r) {
+      const int n = std::min(t * 16 + r, N - 1);                      // the last tile repeats its final row (never stored)
+      const Q4Src& q = src[rows[n].first];
+      const uint32_t* wrow = q.w + (size_t)rows[n].second * wpr;
+      const size_t g0 = (size_t)rows[n].second * gpr;
+      auto code = [&](int k) -> uint32_t { return (wrow[k / cpw] >> ((k % cpw) * bits)) & ((1u << bits) - 1u); };   // MLX packing: little end first
+      for (int b = 0; b < nblk; ++b) {
+        for (int c = 0; c < 4; ++c)
+          for (int stp = 0; stp < 4; ++stp) {
+            const int k0 = b * 128 + 32 * stp + 8 * c;
+            for (int p = 0; p < np; ++p) {
+              uint32_t word = 0;
+              for (int i = 0; i < 4; ++i) {
+                const uint32_t q0 = (code(k0 + 2 * i) >> (4 * p)) & 15u, q1 = (code(k0 + 2 * i + 1) >> (4 * p)) & 15u;
+                word |= (q0 << (4 * i)) | (q1 << (16 + 4 * i));
+              }
+              wf[((((size_t)t * nblk + b) * np + p) * 64 + 16 * c + r) * 4 + stp] = word;
+            }
+          }
+        for (int g = 0; g < 2; ++g) {
+          const float sc = q_to_f32(q.s, g0 + 2 * b + g, sdt), bi = q_to_f32(q.b, g0 + 2 * b + g, sdt);
+          float* d = &st[(((size_t)t * nblk + b) * 16 + r) * 4 + 2 * g];
+          d[0] = sc;
+          d[1] = (float)((double)bi - (double)tmul * (double)sc);
+        }
+      }
+    }
+}
+
+// Test hook (include/mia.h): the repack alone, host memory in and out -- needs no device.
+extern "C" int mia_quant_repack(const uint32_t* codes, const void* scales, const void* biases, int N, int K, int bits, int scale_dtype,
+                                int compute_dtype, uint32_t* wfrag, float* stfrag) {
+  if (!codes || !scales || !biases || !wfrag || !stfrag || N <= 0 || K <= 0 || K % 128 != 0 || (bits != 4 && bits != 8)) return MIA_ERR_INVALID_ARGUMENT;
+  if (scale_dtype != MIA_F16 && scale_dtype != MIA_BF16 && scale_dtype != MIA_F32) return MIA_ERR_INVALID_ARGUMENT;
+  if (compute_dtype != MIA_F16 && compute_dtype != MIA_BF16) return MIA_ERR_INVALID_ARGUMENT;
+  std::vector<Q4Src> src{Q4Src{codes, scales, biases}};
+  std::vector<std::pair<int, int>> rows;
+  for (int i = 0; i < N; ++i) rows.push_back({0, i});
+  std::vector<uint32_t> wf;
+  std::vector<float> st;
+  q_repack_host(src, rows, K, bits, scale_dtype, compute_dtype == MIA_F16 ? 1024.0f : 128.0f, wf, st);
+  memcpy(wfrag, wf.data(), wf.size() * 4);
+  memcpy(stfrag, st.data(), st.size() * 4);
+  return MIA_OK;
+}

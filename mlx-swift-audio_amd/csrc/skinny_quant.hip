@@ -1,5 +1,6 @@
 // skinny_quant.hip -- the LM step's skinny GEMM on packed 4- / 8-bit weights (skinny.h: skinny_gemm_q_launch).
 #include "skinny_device.h"
+#include "skinny_quant_device.h"
 
 // ------------------------------------------------------------------------------------------------
 // The same skinny GEMM on MLX-affine quantised weights (group 64: w = scale * code + bias; 4- or 8-bit codes), multiplied PACKED: the
@@ -27,12 +28,6 @@
 // Results agree with the 16-bit step on the de-quantised checkpoint to the rounding of the de-quantised weights to 16 bit (this form
 // does not round them at all); tests/test_lm_gpu.py compares both with the fp32 oracle.
 // ------------------------------------------------------------------------------------------------
-struct QFrag { const uint32_t* wfrag; const float* stfrag; };
-
-template <typename T> struct QMagic;
-template <> struct QMagic<BF16> { static constexpr uint32_t pair = 0x43004300u; static constexpr uint32_t one = 0x3f803f80u; };   // 128 + q; 1.0
-template <> struct QMagic<F16> { static constexpr uint32_t pair = 0x64006400u; static constexpr uint32_t one = 0x3c003c00u; };    // 1024 + q; 1.0
-
 // Epilogue of the transposed accumulator layout (activations are the MFMA's row operand here): lane (r, c) holds
 // C[m = m0 + 16 mt + 4 c + i][n = n0 + 16 t + r], i = 0..3 -- one output column per lane, so scale / offset are per-lane scalars.
 template <typename T, int MODE, int NT>

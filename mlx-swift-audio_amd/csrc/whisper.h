@@ -27,6 +27,9 @@ struct LinearW {
   float* c1 = nullptr;
   float* c2 = nullptr;
   float ln_rs = 1.f;       // consumers of a CARRIED operand: 1 / the pre-scale folded into c1 and into the producer's gain (LNW::gc)
+  // decoder only, after mia_whisper_attach_quantized: the same matrix as MLX-affine codes in fragment order (skinny_quant.hip: wfrag / stfrag)
+  uint32_t* qw = nullptr;
+  float* qst = nullptr;
   int N = 0, K = 0;
 };
 
@@ -65,6 +68,7 @@ struct DecodeParams {  // immutable per graph (kernel argument, by value)
   int trace;                    // test hook (mia_whisper_trace_logits): the step also copies the traced clips' logits out
   int head_single;              // test hook (mia_whisper_set_debug bit 1): one-workgroup head even at temperature 0
   int split_ln;                 // test hook (mia_whisper_set_debug bit 2): no LayerNorm carried across the GEMMs (reduce + LayerNorm chain)
+  int packed;                   // mia_whisper_use_packed: 0, or the bit width (4 | 8) of the packed weights the step's GEMMs read
 };
 
 struct mia_whisper {
@@ -87,6 +91,10 @@ struct mia_whisper {
   void* tok_emb_f = nullptr;          // the same in MFMA-fragment order (the logits GEMM of the decode step)
   float* emb_c1 = nullptr;            // fp32 [V]: the token embedding folded with decoder.ln (LinearW::c1 / c2 of the logits GEMM)
   float* emb_c2 = nullptr;
+  uint32_t* emb_qw = nullptr;         // mia_whisper_attach_quantized: the token embedding as packed codes in fragment order (the logits GEMM;
+  float* emb_qst = nullptr;           // the embedding gather keeps the 16-bit table)
+  int q_bits = 0;                     // 4 | 8 once packed decoder weights are attached, 0 = none
+  int use_packed = 0;                 // mia_whisper_use_packed: the step's GEMMs read the packed weights
   float* dec_pos = nullptr;           // [n_text_ctx][D]
   std::vector<DecBlockW> dec;
   LNW dec_ln;

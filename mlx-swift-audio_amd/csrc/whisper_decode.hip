@@ -70,14 +70,17 @@ int enqueue_step(mia_whisper* w, const DecodeParams& p, const AlignHook* hook = 
     a.w_keep = w->weight_sharing;
     if (stat_in) { a.ss_in = stat_in; a.ss_tiles = D / 16; a.ss_dim = D; a.eps = 1e-5f; a.c1 = c1 ? c1 : lw.c1; a.c2 = c2 ? c2 : lw.c2; a.rs_scale = lw.ln_rs; }
     if (mode == SK_RESID) { a.xres = w->dx; a.nw = next_ln->gc; a.ss_out = stat_out; }
+    if (p.packed) return dec_launch_skinny_q(w, a, lw.qw, lw.qst, p.packed, mode, s);      // mia_whisper_use_packed (skinny_frag_quant.hip)
     return dec_launch_skinny(w, a, mode, s);
   };
-  const int S_d = pick_split(D, 2), S_4d = pick_split(4 * D, 4);   // x 4 waves of intra-workgroup split-K each
+  // x 4 waves of intra-workgroup split-K each; the packed kernels split K in 128-input blocks
+  const int S_d = p.packed ? pick_split(D / 4, 2) : pick_split(D, 2), S_4d = p.packed ? pick_split(D, 4) : pick_split(4 * D, 4);
   // LayerNorm carried across the chain (skinny.h): the three residual-writing projections of a layer (self-attention out, cross-attention
   // out, fc2) add into x, store x * gamma of the NEXT LayerNorm as the next GEMM's operand plus per-tile (sum x, sum x^2); the GEMM that
   // consumes it applies mean / rstd / beta through its folded constants.  Used for the two attention output projections (8 of the 12
   // reduce + LayerNorm launches of a step go); fc2 keeps the split form (below).
-  const bool fused_ln = D % 32 == 0 && D <= 2048 && w->dec[0].qkv.c1 != nullptr && !p.split_ln;    // D <= 2048: the consumer sums at most 128 tiles (LnStat)
+  // (packed weights: the packed kernels have no carried-LayerNorm epilogues, the step runs the reduce + LayerNorm chain)
+  const bool fused_ln = D % 32 == 0 && D <= 2048 && w->dec[0].qkv.c1 != nullptr && !p.split_ln && !p.packed;    // D <= 2048: the consumer sums at most 128 tiles (LnStat)
   float* st_a = w->dstat;                                          // two alternating buffers: a producer never overwrites what its
   float* st_b = w->dstat + (size_t)(D / 16) * w->cap_B * 2;        // own consumer is still reading (the chain is strictly serial anyway)
   // (the split greedy head embeds the next position itself: only the very first step needs this launch, done by the caller)
@@ -124,7 +127,7 @@ int enqueue_step(mia_whisper* w, const DecodeParams& p, const AlignHook* hook = 
     dec_launch_reduce_ln(w, S_4d, b.mlp2.b, next_ln, s);
   }
   {  // logits = ln(x) . E^T (tied embedding, TextDecoder.swift:93)
-    LinearW e; e.w = w->tok_emb; e.wf = w->tok_emb_f; e.N = p.V; e.K = D; e.c1 = w->emb_c1; e.c2 = w->emb_c2;
+    LinearW e; e.w = w->tok_emb; e.wf = w->tok_emb_f; e.N = p.V; e.K = D; e.c1 = w->emb_c1; e.c2 = w->emb_c2; e.qw = w->emb_qw; e.qst = w->emb_qst;
     if (skinny(dh, D, e, false, w->logits, p.V, 1, MIA_ACT_NONE, SK_OUTF32)) return -1;
   }
   if (p.trace && !hook && dec_launch_trace(w, s)) return -1;
@@ -162,6 +165,7 @@ int whisper_decode(mia_whisper* w, const mia_decode_opts* o, int32_t* tokens, in
   p.timestamps = o->timestamps ? 1 : 0; p.max_tokens = o->max_tokens;
   p.max_initial_ts = o->max_initial_timestamp_index; p.max_new_tokens = o->max_new_tokens;
   p.trace = w->trace ? 1 : 0; p.head_single = (w->debug_flags & 2) ? 1 : 0; p.split_ln = (w->debug_flags & 4) ? 1 : 0;
+  p.packed = w->use_packed ? w->q_bits : 0;
   if (w->trace)
     for (int i = 0; i < w->trace_n; ++i) MIA_CHECK_ARG(ctx, w->trace_clip_ids[i] < w->cur_B, "decode: traced clip %d is not in this batch of %d", w->trace_clip_ids[i], w->cur_B);
 
@@ -433,7 +437,7 @@ extern "C" int mia_whisper_align(mia_whisper* w, const int32_t* tokens, int stri
   MIA_HIP(ctx, hipStreamSynchronize(s));       // host vectors above go out of use
 
   DecodeParams p{};
-  p.B = B; p.V = d.n_vocab; p.D = d.n_text_state; p.H = H; p.L = L; p.n_ctx = C;
+  p.B = B; p.V = d.n_vocab; p.D = d.n_text_state; p.H = H; p.L = L; p.n_ctx = C; p.packed = w->use_packed ? w->q_bits : 0;
   AlignHook hook; hook.qk = d_qk; hook.head_slot = d_slot; hook.n_slots = n_heads; hook.n_tok = d_ntok; hook.probs = d_probs; hook.eot = eot;
   // teacher-forced pass, one position per step (clips that have consumed their last token idle at it)
   for (int step = 0; step < max_tok; ++step)

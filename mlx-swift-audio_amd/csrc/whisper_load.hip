@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "decode.h"
+#include "quant_repack.h"
 
 namespace {
 
@@ -309,7 +310,111 @@ extern "C" mia_whisper* mia_whisper_clone(mia_whisper* src, mia_ctx* ctx) {
   w->ctx = ctx; w->dims = root->dims; w->dtype = root->dtype; w->kpad_conv1 = root->kpad_conv1;
   w->conv1 = root->conv1; w->conv2 = root->conv2; w->enc_pos = root->enc_pos; w->enc = root->enc; w->ln_post = root->ln_post;
   w->tok_emb = root->tok_emb; w->tok_emb_f = root->tok_emb_f; w->emb_c1 = root->emb_c1; w->emb_c2 = root->emb_c2; w->dec_pos = root->dec_pos; w->dec = root->dec; w->dec_ln = root->dec_ln;
+  w->emb_qw = root->emb_qw; w->emb_qst = root->emb_qst; w->q_bits = root->q_bits; w->use_packed = src->use_packed;      // (LinearW::qw / qst came with w->dec)
   w->parent = root;
   root->n_clones += 1;
   return w;
+}
+
+// ---- MLX-affine 4- / 8-bit weights for the decode step (WhisperModel.swift:189-196: the reference's default engine loads Whisper in 4 bit,
+// group 64, and multiplies packed).  tensors: `<p>.weight` (MIA_U32 codes [N][K * bits / 32]), `<p>.scales`, `<p>.biases` ([N][K / 64]; f16,
+// bf16 or f32, one type for all) of every decoder matrix the step reads -- decoder.blocks.L.{attn.{query,key,value,out},
+// cross_attn.{query,out}, mlp1, mlp2} and decoder.token_embedding.  Encoder tensors and cross_attn.{key,value} are ignored: they run at
+// 1500 rows per clip in the encode call (MFMA-bound) on the 16-bit copy.  Nothing of the handle changes unless every matrix was repacked
+// and uploaded.  A bad argument or tensor list is MIA_ERR_INVALID_ARGUMENT; a refused hipMalloc MIA_ERR_OUT_OF_MEMORY, a failed upload
+// MIA_ERR_DEVICE.
+extern "C" int mia_whisper_attach_quantized(mia_whisper* w, const mia_tensor_view* tensors, int n_tensors, int group_size, int bits) {
+  if (!w) return MIA_ERR_MODEL_NOT_LOADED;
+  mia_ctx* ctx = w->ctx;
+  MIA_CHECK_ARG(ctx, tensors && n_tensors > 0 && group_size == 64 && (bits == 4 || bits == 8), "whisper_attach_quantized: tensors required, group size 64, 4 or 8 bits");
+  MIA_CHECK_ARG(ctx, !w->parent, "whisper_attach_quantized: this handle is a clone (attach to the handle that owns the weights, before cloning)");
+  MIA_CHECK_ARG(ctx, w->n_clones == 0, "whisper_attach_quantized: %d clone(s) share these weights; attach before cloning", w->n_clones);
+  MIA_CHECK_ARG(ctx, w->q_bits == 0, "whisper_attach_quantized: packed weights are already attached to this handle (load a fresh handle to replace them)");
+  const int D = w->dims.n_text_state, V = w->dims.n_vocab;
+  MIA_CHECK_ARG(ctx, D % 128 == 0, "whisper_attach_quantized: n_text_state must be a multiple of 128 (the packed kernels take 128-input blocks)");
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  std::map<std::string, const mia_tensor_view*> by_name;
+  for (int i = 0; i < n_tensors; ++i) if (tensors[i].name && tensors[i].data) by_name[tensors[i].name] = &tensors[i];
+  std::string err;
+  int sdt = -1;
+  auto get = [&](const std::string& p, int N, int K, Q4Src& q) -> bool {
+    const mia_tensor_view* t[3];
+    const char* suffix[3] = {".weight", ".scales", ".biases"};
+    for (int i = 0; i < 3; ++i) {
+      auto it = by_name.find(p + suffix[i]);
+      if (it == by_name.end()) { if (err.empty()) err = "missing tensor '" + p + suffix[i] + "'"; return false; }
+      t[i] = it->second;
+    }
+    const mia_tensor_view *wt = t[0], *s = t[1], *b = t[2];
+    const bool ok = wt->dtype == MIA_U32 && wt->ndim == 2 && wt->shape[0] == N && wt->shape[1] == (int64_t)K * bits / 32 && s->ndim == 2 && s->shape[0] == N &&
+                    s->shape[1] == K / 64 && b->ndim == 2 && b->shape[0] == N && b->shape[1] == K / 64 && s->dtype == b->dtype &&
+                    (s->dtype == MIA_F16 || s->dtype == MIA_BF16 || s->dtype == MIA_F32);
+    if (!ok) { if (err.empty()) err = "'" + p + "' is not a " + std::to_string(bits) + "-bit group-64 Linear of the expected shape (scales / biases: f16, bf16 or f32)"; return false; }
+    if (sdt < 0) sdt = s->dtype;
+    if (sdt != s->dtype) { if (err.empty()) err = "mixed scale dtypes"; return false; }
+    q = Q4Src{(const uint32_t*)wt->data, s->data, b->data};
+    return true;
+  };
+  const float mag = w->dtype == MIA_F16 ? 1024.0f : 128.0f;
+  std::vector<void*> fresh;                      // joins w->allocs only when everything is in place
+  int code = MIA_ERR_INVALID_ARGUMENT;           // what a failure is reported as: a bad tensor list, unless the device refused
+  struct QPair { uint32_t* qw = nullptr; float* qst = nullptr; };
+  // parts stacked along N as the dense loader stacks them (Loader::linear)
+  auto pack = [&](const std::vector<std::string>& parts, int N_each, int K, QPair& out) -> bool {
+    std::vector<Q4Src> src(parts.size());
+    std::vector<std::pair<int, int>> rows;
+    for (size_t i = 0; i < parts.size(); ++i) {
+      if (!get(parts[i], N_each, K, src[i])) return false;
+      for (int n = 0; n < N_each; ++n) rows.push_back({(int)i, n});
+    }
+    std::vector<uint32_t> wf;
+    std::vector<float> st;
+    q_repack_host(src, rows, K, bits, sdt, mag, wf, st);
+    void* dw = nullptr; void* ds = nullptr;
+    if (hipMalloc(&dw, wf.size() * 4) != hipSuccess) { code = MIA_ERR_OUT_OF_MEMORY; err = "hipMalloc failed for the packed weights"; return false; }
+    fresh.push_back(dw);
+    if (hipMalloc(&ds, st.size() * 4) != hipSuccess) { code = MIA_ERR_OUT_OF_MEMORY; err = "hipMalloc failed for the packed weights"; return false; }
+    fresh.push_back(ds);
+    if (hipMemcpy(dw, wf.data(), wf.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(ds, st.data(), st.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+      code = MIA_ERR_DEVICE; err = "upload of the packed weights failed";
+      return false;
+    }
+    out.qw = (uint32_t*)dw; out.qst = (float*)ds;
+    return true;
+  };
+  const int L = (int)w->dec.size();
+  std::vector<QPair> qp((size_t)L * 6);
+  QPair emb;
+  bool ok = true;
+  for (int l = 0; l < L && ok; ++l) {
+    const std::string p = "decoder.blocks." + std::to_string(l);
+    QPair* q = &qp[(size_t)l * 6];
+    ok = pack({p + ".attn.query", p + ".attn.key", p + ".attn.value"}, D, D, q[0]) && pack({p + ".attn.out"}, D, D, q[1]) &&
+         pack({p + ".cross_attn.query"}, D, D, q[2]) && pack({p + ".cross_attn.out"}, D, D, q[3]) &&
+         pack({p + ".mlp1"}, 4 * D, D, q[4]) && pack({p + ".mlp2"}, D, 4 * D, q[5]);
+  }
+  ok = ok && pack({"decoder.token_embedding"}, V, D, emb);
+  if (ok && hipDeviceSynchronize() != hipSuccess) { ok = false; code = MIA_ERR_DEVICE; err = "device error during upload"; }
+  if (!ok) {
+    for (void* p : fresh) (void)hipFree(p);
+    return mia_fail(ctx, code, "whisper_attach_quantized: %s", err.c_str());
+  }
+  for (int l = 0; l < L; ++l) {
+    DecBlockW& b = w->dec[l];
+    LinearW* lw[6] = {&b.qkv, &b.out, &b.cq, &b.cout, &b.mlp1, &b.mlp2};
+    for (int i = 0; i < 6; ++i) { lw[i]->qw = qp[(size_t)l * 6 + i].qw; lw[i]->qst = qp[(size_t)l * 6 + i].qst; }
+  }
+  w->emb_qw = emb.qw; w->emb_qst = emb.qst;
+  w->allocs.insert(w->allocs.end(), fresh.begin(), fresh.end());
+  w->q_bits = bits;
+  return MIA_OK;
+}
+
+// The step's GEMMs read the packed weights (1) or the 16-bit copy (0, the default).  Packed loads follow mia_whisper_set_weight_sharing
+// like the 16-bit ones.  Takes effect at the next decode (the step graph is re-captured: DecodeParams::packed).
+extern "C" int mia_whisper_use_packed(mia_whisper* w, int on) {
+  if (!w) return MIA_ERR_MODEL_NOT_LOADED;
+  MIA_CHECK_ARG(w->ctx, !on || w->q_bits != 0, "whisper_use_packed: no packed weights attached (mia_whisper_attach_quantized)");
+  w->use_packed = on ? 1 : 0;
+  return MIA_OK;
 }

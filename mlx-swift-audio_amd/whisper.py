@@ -193,6 +193,52 @@ class WhisperModel:
         lib.mia_whisper_set_weight_sharing.argtypes = [C.c_void_p, C.c_int]
         self.ctx.check(lib.mia_whisper_set_weight_sharing(self.h, int(concurrent_readers)))
 
+    def attach_quantized(self, tensors: dict[str, np.ndarray], bits: int | None = None, group_size: int = 64) -> None:
+        """mia_whisper_attach_quantized: `tensors` holds the decoder matrices of the step as the checkpoint stores them -- `<p>.weight`
+        uint32 codes, `<p>.scales` / `<p>.biases` float16, float32 or bf16 (uint16 arrays tagged .st_dtype == "BF16", as
+        checkpoint.read_safetensors returns them); anything else in the dict (dense tensors, the encoder) is left out.  bits: inferred
+        from the packed width when not given, as checkpoint.expand_checkpoint does.  The handle must have been loaded from the
+        de-quantised tensors of the same checkpoint."""
+        lib = self.ctx.lib
+        lib.mia_whisper_attach_quantized.restype = C.c_int
+        lib.mia_whisper_attach_quantized.argtypes = [C.c_void_p, C.POINTER(_TensorView), C.c_int, C.c_int, C.c_int]
+        packed = {}
+        for name, arr in tensors.items():
+            base = name.rsplit(".", 1)[0]
+            if name.endswith((".weight", ".scales", ".biases")) and base + ".scales" in tensors and base.startswith("decoder."):
+                packed[name] = arr
+        if bits is None:
+            for name, arr in packed.items():
+                if name.endswith(".weight"):
+                    bits = (32 * arr.shape[-1]) // (packed[name[:-7] + ".scales"].shape[-1] * group_size)
+                    break
+        views = (_TensorView * max(len(packed), 1))()
+        keep = []
+        for i, (name, arr) in enumerate(packed.items()):
+            a = np.ascontiguousarray(arr)
+            if a.dtype == np.uint32:
+                dt = _lib.U32
+            elif a.dtype == np.float16:
+                dt = _lib.F16
+            elif a.dtype == np.float32:
+                dt = _lib.F32
+            elif a.dtype == np.uint16 and getattr(arr, "st_dtype", "BF16") == "BF16":
+                dt = _lib.BF16
+            else:
+                raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, f"attach_quantized: '{name}' must be uint32 codes or f16 / bf16 / f32 scales / biases (got {a.dtype})")
+            keep.append(a)
+            shp = (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim)))
+            views[i] = _TensorView(name.encode(), dt, a.ndim, shp, a.ctypes.data)
+        self.ctx.check(lib.mia_whisper_attach_quantized(self.h, views, len(packed), int(group_size), int(bits or 0)))
+
+    def use_packed(self, on: bool) -> None:
+        """mia_whisper_use_packed: the decode step (decode, align, detect_language) reads the attached packed weights (True) or the 16-bit
+        copy (False, the default).  A clone inherits the switch of the handle it is made from."""
+        lib = self.ctx.lib
+        lib.mia_whisper_use_packed.restype = C.c_int
+        lib.mia_whisper_use_packed.argtypes = [C.c_void_p, C.c_int]
+        self.ctx.check(lib.mia_whisper_use_packed(self.h, 1 if on else 0))
+
     def set_encode_stream(self, hip_stream: int | None) -> None:
         """mia_whisper_set_encode_stream: run the encoder half of every window on another HIP stream (raw pointer, e.g.
         torch.cuda.Stream(...).cuda_stream); None restores the single-stream form."""
