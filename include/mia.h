@@ -428,11 +428,21 @@ int64_t mia_dac_code_len(mia_codec* c, int64_t n_samples);
 int mia_dac_encode(mia_codec* c, const float* pcm, int64_t n_samples, int n_quantizers, int32_t* codes, int64_t codes_capacity,
                    int64_t* n_steps, int mem);
 
-/* ---- autoregressive LMs (Llama-3 / Qwen2 blocks) ------------------------------------------------ */
+/* ---- autoregressive LMs (Llama-3 / Qwen2 / Qwen3 blocks) ---------------------------------------- */
 /* OrpheusConfig (TTS/Orpheus/BuildingBlocks/TransformerBlock.swift:16-34) / Qwen2Config (TTS/CosyVoice2/LLM/Qwen2LM.swift:15-43).
  * Tensors use the Hugging Face key schema both ports load: model.embed_tokens.weight, model.layers.N.self_attn.{q,k,v,o}_proj.weight
  * (+ .bias for q,k,v when qkv_bias), model.layers.N.mlp.{gate,up,down}_proj.weight, model.layers.N.{input,post_attention}_layernorm.weight,
- * model.norm.weight, lm_head.weight (absent when tie_embeddings). */
+ * model.norm.weight, lm_head.weight (absent when tie_embeddings).
+ * Optional tensors switch behaviour by their presence (the struct below keeps its layout):
+ *  - llm_decoder.{weight,bias}, speech_embedding.weight: the CosyVoice2 head and speech embedding (mia_lm_generate_ras).
+ *  - model.layers.N.self_attn.q_norm.weight and .k_norm.weight, [head_dim] each: Qwen3's per-head RMSNorm of every query and key head
+ *    (Qwen3Attention, STT/FunASR/Layers/Qwen3Model.swift:32-35,57-59,88-95; eps = rms_eps).  Applied in fp32 between the projection
+ *    (+ bias, if any) and RoPE, y = x * rsqrt(mean(x^2 over head_dim) + eps) * w, inside the two kernels that finish q|k|v (no extra
+ *    launch); V is untouched.  Both tensors in every layer or in none: one of a pair, some layers only, or a wrong length fail the load
+ *    with a message naming the tensor.  A handle without them launches exactly the kernels it launched before.  n_heads * head_dim need
+ *    not equal hidden (Qwen3-0.6B: 16 x 128 against 1024; Qwen3Config's Swift default head_dim is 64, the published config says 128 --
+ *    both widths are supported).  mia_lm_set_kv_quant(bits != 0) on such a handle is MIA_ERR_UNSUPPORTED (the reference's Qwen3 decoder
+ *    uses KVCacheSimple only, FunASRSTT.swift:120); packed step weights (mia_lm_attach_quantized) work as on any handle. */
 typedef struct {
   int32_t vocab, hidden, inter, n_layers, n_heads, n_kv_heads, head_dim, max_ctx;
   float rms_eps, rope_theta;
@@ -518,6 +528,24 @@ int mia_lm_generate_ras(mia_lm* lm, const float* prompt_embeds, int n_prompt, co
  * mia_lm_generate_ras(prompt b, rp[b], uniforms row b).  Host pointers. */
 int mia_lm_generate_ras_batch(mia_lm* lm, const float* prompt_embeds, const int32_t* prompt_offsets, int n_seq, const mia_ras_params* rp,
                               const float* uniforms, int n_uniforms, int32_t* out_tokens, int out_stride, int32_t* n_out);
+/* Fun-ASR's decoder loop (STT/FunASR/FunASRSTT.swift:118-156 with FunASRConfig.temperature 0, its default: sampleNextToken takes
+ * MLX.argMax, FunASRModel.swift:160-163) on device.  prompt_embeds: float32 [n_prompt][hidden], the merged prompt
+ * [text ... sos | audio embeddings | eos ... text] (FunASRModel.mergeEmbeddings, :71-141; gathered by the caller).  The rows go through
+ * the batched prompt pass and the first step; every step then takes the argmax of the fp32 logits over the whole vocabulary (lowest
+ * index on an exact tie, as MLX.argMax), embeds it through model.embed_tokens and projects through the tied embedding or lm_head.weight.
+ * A sequence ends when it draws one of stop_ids (n_stop in 1..4) -- that id is NOT written to out_tokens and not counted in n_out
+ * (:151-155) -- or after max_new_tokens ids.  out_tokens holds max_new_tokens ids.  The sampler is a node of the captured step graph; no
+ * uniforms are involved.  The reference's temperature > 0 branch (top-k 50, then top-p 0.95) is not built.  MIA_ERR_INVALID_ARGUMENT,
+ * before anything is launched: a null pointer, n_prompt <= 0, n_prompt + max_new_tokens > max_ctx, n_stop outside 1..4, a stop id
+ * outside the vocabulary, a handle with llm_decoder / speech_embedding tensors.  Host pointers. */
+int mia_lm_generate_greedy(mia_lm* lm, const float* prompt_embeds, int n_prompt, const int32_t* stop_ids, int n_stop,
+                           int max_new_tokens, int32_t* out_tokens, int32_t* n_out);
+/* mia_lm_generate_greedy for n_seq utterances side by side (after mia_lm_set_batch; n_seq above the capacity is
+ * MIA_ERR_INVALID_ARGUMENT): prompt_embeds = the rows of all prompts back to back [prompt_offsets[n_seq]][hidden]; out_tokens
+ * [n_seq][out_stride], out_stride >= max_new_tokens; n_out [n_seq].  Utterance b's ids equal mia_lm_generate_greedy(prompt b) on the
+ * same handle capacity.  Host pointers. */
+int mia_lm_generate_greedy_batch(mia_lm* lm, const float* prompt_embeds, const int32_t* prompt_offsets, int n_seq,
+                                 const int32_t* stop_ids, int n_stop, int max_new_tokens, int32_t* out_tokens, int out_stride, int32_t* n_out);
 /* One sampleNextToken call on caller-provided logits (host pointers). */
 int mia_sample_top_p(mia_ctx* ctx, const float* logits, int V, const int32_t* history, int n_hist, float rep_penalty,
                      float temperature, float top_p, float uniform, int32_t* out);

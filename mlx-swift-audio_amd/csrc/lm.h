@@ -1,12 +1,12 @@
 // lm.h -- host-side interface between the LM decode sources: lm.hip (step kernels, prompt pass, step graph, entry points),
-// lm_sample.hip (the top-p and RAS samplers), lm_load.hip (checkpoint loader, state buffers, packed-weight attach) and lm_kvq.hip
+// lm_sample.hip (the top-p, RAS and greedy samplers), lm_load.hip (checkpoint loader, state buffers, packed-weight attach) and lm_kvq.hip
 // (the quantised KV cache: its prompt-pass quantiser and its attention).
 #pragma once
 #include <vector>
 
 #include "mia_internal.h"
 
-struct LmState { int pos; int n_hist; int finished; int n_gen; int n_embeds; int n_out; int u_cursor; int n_prompt; int min_len; int max_len; };   // min/max_len: RAS loop, per sequence
+struct LmState { int pos; int n_hist; int finished; int n_gen; int n_embeds; int n_out; int u_cursor; int n_prompt; int min_len; int max_len; };   // min/max_len: RAS and greedy loops, per sequence
 
 struct RasParams { float top_p; int top_k; int win; float tau; int eos; int min_len; int max_len; int n_uniforms; };
 
@@ -47,6 +47,9 @@ struct mia_lm {
   int32_t* out_tokens = nullptr;  // [max_ctx] emitted tokens of the RAS loop
   float* final_norm = nullptr; float* final_norm_c = nullptr; float final_rs = 1.f;
   float* inv_freq = nullptr;    // [dh/2]
+  // Qwen3: per-head RMSNorm gains of q and k, fp32 [n_layers][2][dh] (q_norm | k_norm), applied between the split-K sum (+ bias) and RoPE;
+  // null = the checkpoint has none (Llama-3 / Qwen2) and the handle launches the kernel instances without the norm
+  float* qk_norm = nullptr;
   std::vector<LmLayer> layers;
   // state
   void* k_cache = nullptr; void* v_cache = nullptr;   // [L][B][Hkv][max_ctx][dh]; null while the cache is quantised
@@ -61,8 +64,8 @@ struct mia_lm {
   float* uniforms = nullptr;    // [max_ctx]
   void* smx = nullptr;            // top-p sampler scratch, lm_sample_ws_bytes() per sequence (slice records + radix slabs)
   LmState* state = nullptr;
-  hipGraphExec_t graph = nullptr;       // one decode step (forward / top-p sampler / RAS sampler), re-captured when its sampler arguments change
-  int graph_mode = -1;                  // 0 forward, 1 top-p, 2 RAS
+  hipGraphExec_t graph = nullptr;       // one decode step (forward / top-p / RAS / greedy sampler), re-captured when its sampler arguments change
+  int graph_mode = -1;                  // LM_STEP_* below
   int debug_flags = 0;                  // test hook (mia_lm_set_debug): bit 0 = no hipGraph, bit 1 = no batched prompt pass
   mia_lm_sampler graph_sampler{};
   RasParams graph_ras{};
@@ -76,6 +79,9 @@ struct mia_lm {
   std::vector<void*> state_allocs;
 };
 
+// what ends a decode step: nothing (the host reads the logits), the top-p sampler, the RAS sampler, the greedy argmax
+enum { LM_STEP_FORWARD = 0, LM_STEP_TOP_P = 1, LM_STEP_RAS = 2, LM_STEP_GREEDY = 3 };
+
 // launch a kernel template's F16 or BF16 instance; expects `const bool f16` and `hipStream_t s` in scope
 #define LAUNCH_T(kern, grid, block, lds, ...) do { if (f16) hipLaunchKernelGGL((kern<F16>), grid, block, lds, s, __VA_ARGS__); else hipLaunchKernelGGL((kern<BF16>), grid, block, lds, s, __VA_ARGS__); } while (0)
 
@@ -88,6 +94,11 @@ size_t lm_sample_ws_bytes();
 constexpr int LM_RAS_MAX_VOCAB = 8192;
 void lm_sample_ras_launch(hipStream_t s, const float* logits, int V, int32_t* tokens, int32_t* out_tokens, const float* uniforms, LmState* st, const RasParams& rp,
                           int max_ctx, int B);
+// greedy sampler, two launches: argmax per vocabulary slice, then one wave per sequence picks the winner (lowest index on exact ties),
+// tests it against sp.stop_ids and appends it to tokens / out_tokens.  The prompt is embedding rows (LmState::n_embeds), the budget is
+// LmState::max_len.  ws: the top-p workspace (lm_sample_ws_bytes() per sequence)
+void lm_sample_greedy_launch(hipStream_t s, const float* logits, int V, int32_t* tokens, int32_t* out_tokens, LmState* st, void* ws, const mia_lm_sampler& sp,
+                             int max_ctx, int B);
 
 // ---- lm.hip: the two launch sites that branch on the cache mode (layer l of the handle's caches; the op ABI calls them on a bare handle) ----
 // q|k|v rows of the prompt pass -> RoPE -> q rows + the layer's K/V rows at rowmap's (sequence, position)

@@ -2,7 +2,8 @@
 //
 // Replaces, per token, OrpheusModel / OrpheusLMHeadModel (TTS/Orpheus/BuildingBlocks/TransformerBlock.swift:70-105,129-139,
 // 165-180,223-233), Llama3RoPE (TTS/Shared/Llama3RoPE.swift:27-66,104-114), SwiGLUMLP (TTS/Shared/SwiGLUMLP.swift:27-29),
-// Qwen2Attention / Qwen2 blocks (TTS/CosyVoice2/LLM/Qwen2LM.swift:48-151); the samplers that end a step are lm_sample.hip.
+// Qwen2Attention / Qwen2 blocks (TTS/CosyVoice2/LLM/Qwen2LM.swift:48-151), Qwen3Attention with its per-head q / k RMSNorm
+// (STT/FunASR/Layers/Qwen3Model.swift:72-109); the samplers that end a step are lm_sample.hip.
 //
 // Decode at batch 1 is HBM-bound on the weights (Orpheus-3B: 6.6 GB bf16 per token).  Every projection is the skinny
 // MFMA GEMM of skinny_rowmajor.hip (weights HBM -> VGPR once, split-K partials summed in a fixed order by the consumer
@@ -123,10 +124,16 @@ __global__ __launch_bounds__(256) void lm_reduce_norm(const float* __restrict__ 
 
 // q|k|v = sum_s partial[s] + bias; RoPE (split-half pairs (i, i+dh/2), angle = pos * inv_freq[i]) on q and k; q -> qout,
 // k, v -> cache[kv head][pos][:]          one thread per rotation pair / per v element; blockIdx.y = row of the batched prompt pass
-template <typename T>
+// QKN (Qwen3Attention, STT/FunASR/Layers/Qwen3Model.swift:88-95): every q and k head goes through an RMSNorm over head_dim between the
+// sum (+ bias) and the rotation, y = x * rsqrt(mean(x^2) + eps) * w with qkn = [q_norm | k_norm] gains [2][dh]; all fp32, the one 16-bit
+// rounding stays where it is.  A head's dh/2 pairs are dh/2 consecutive threads, each holding both halves of its pair, and the segments
+// are aligned to dh/2 (32 | 64) inside the 256-thread block, so the sum of squares is an xor-shuffle over those lanes: n_pairs is a
+// multiple of dh/2, a segment never mixes with the V lanes of its wave, and every lane of the wave runs the shuffles.
+template <typename T, bool QKN>
 __global__ __launch_bounds__(256) void lm_rope_cache(const float* __restrict__ part, int S, const float* __restrict__ bias, const float* __restrict__ inv_freq,
                                                      uint16_t* __restrict__ qout, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc,
-                                                     const int2* __restrict__ rowmap, int Hq, int Hkv, int dh, int max_ctx, int64_t seq_stride) {
+                                                     const int2* __restrict__ rowmap, int Hq, int Hkv, int dh, int max_ctx, int64_t seq_stride,
+                                                     const float* __restrict__ qkn, float qk_eps) {
   const int Nq = Hq * dh, Nk = Hkv * dh, N = Nq + 2 * Nk;
   const int half = dh >> 1;
   const int pos = rowmap[blockIdx.y].y;
@@ -143,10 +150,19 @@ __global__ __launch_bounds__(256) void lm_rope_cache(const float* __restrict__ p
     for (int k = 0; k < 4; ++k) if (k < S) a += p[k];
     return a;
   };
+  float n0 = 0.f, n1 = 0.f, rstd = 0.f;
+  if constexpr (QKN) {           // ahead of the divergence below, so that every lane of the wave reaches the shuffles
+    if (e < n_pairs) { const int head = e / half, i = e - head * half; n0 = val(head * dh + i); n1 = val(head * dh + i + half); }
+    float ss = n0 * n0 + n1 * n1;
+    for (int o = 1; o < half; o <<= 1) ss += __shfl_xor(ss, o, 64);
+    rstd = rsqrtf(ss / (float)dh + qk_eps);
+  }
   if (e < n_pairs) {
     const int head = e / half, i = e - head * half;       // head < Hq: query head, else key head
     const int base = head * dh;                           // q and k sections are contiguous: [q heads | k heads]
-    const float x0 = val(base + i), x1 = val(base + i + half);
+    float x0, x1;
+    if constexpr (QKN) { const float* w = qkn + (head < Hq ? 0 : dh); x0 = n0 * rstd * w[i]; x1 = n1 * rstd * w[i + half]; }
+    else { x0 = val(base + i); x1 = val(base + i + half); }
     float sn, cs;
     sincosf((float)pos * inv_freq[i], &sn, &cs);
     const float y0 = x0 * cs - x1 * sn, y1 = x1 * cs + x0 * sn;
@@ -156,8 +172,8 @@ __global__ __launch_bounds__(256) void lm_rope_cache(const float* __restrict__ p
       k[i] = T::from_f32(y0); k[i + half] = T::from_f32(y1);
     }
   } else if (e < n_pairs + Nk) {
-    const int j = e - n_pairs, head = j / dh, d = j - head * dh;
-    vc[((int64_t)head * max_ctx + pos) * dh + d] = T::from_f32(val(Nq + Nk + j));
+    const int j = e - n_pairs, vh = j / dh, d = j - vh * dh;
+    vc[((int64_t)vh * max_ctx + pos) * dh + d] = T::from_f32(val(Nq + Nk + j));
   }
 }
 
@@ -169,12 +185,13 @@ constexpr int ATT_NW = 16;
 // FUSED (the decode step): the workgroup first finishes its own q head and its K/V head's new row from the split-K slices of the
 // q|k|v GEMM (sum + bias + RoPE, exactly lm_rope_cache's arithmetic and 16-bit rounding), keeps them in LDS, and the first query
 // head of each group writes the K/V row to the cache -- one kernel less per layer; the new row is used from LDS because the
-// writer may be another workgroup.
-template <typename T, int DH, bool FUSED>
+// writer may be another workgroup.  QKN (FUSED only): lm_rope_cache's per-head RMSNorm of q and k before the rotation -- with DH 128 the q
+// pairs are wave 0 and the k pairs wave 1, with DH 64 the two halves of wave 0; `tid < DH` is uniform over a wave, so every lane shuffles.
+template <typename T, int DH, bool FUSED, bool QKN>
 __global__ __launch_bounds__(64 * ATT_NW) void lm_attention(const uint16_t* __restrict__ q, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc,
                                                     uint16_t* __restrict__ out, const LmState* __restrict__ st, int Hq, int Hkv, int max_ctx, float scale, int pos0,
                                                     const float* __restrict__ part, int S, const float* __restrict__ bias, const float* __restrict__ inv_freq,
-                                                    int B, int64_t seq_stride, const int2* __restrict__ rowmap) {
+                                                    int B, int64_t seq_stride, const int2* __restrict__ rowmap, const float* __restrict__ qkn, float qk_eps) {
   extern __shared__ float sc[];            // [max_ctx] scores, then red[ATT_NW][DH] + red2[2 * ATT_NW] (+ FUSED: q, k, v rows [3][DH])
   const int seq = FUSED ? (int)blockIdx.y : rowmap[blockIdx.y].x;          // FUSED: row = sequence; prompt pass: row -> (sequence, position)
   st += seq; kc += (int64_t)seq * seq_stride; vc += (int64_t)seq * seq_stride;
@@ -210,7 +227,15 @@ __global__ __launch_bounds__(64 * ATT_NW) void lm_attention(const uint16_t* __re
       const bool is_k = tid >= half;
       const int i = is_k ? tid - half : tid;
       const int base = is_k ? Nq + kvh * DH : h * DH;
-      const float x0 = val(base + i), x1 = val(base + i + half);
+      float x0 = val(base + i), x1 = val(base + i + half);
+      if constexpr (QKN) {
+        float ss = x0 * x0 + x1 * x1;
+#pragma unroll
+        for (int o = 1; o < half; o <<= 1) ss += __shfl_xor(ss, o, 64);
+        const float rstd = rsqrtf(ss / (float)DH + qk_eps);
+        const float* w = qkn + (is_k ? DH : 0);
+        x0 = x0 * rstd * w[i]; x1 = x1 * rstd * w[i + half];
+      }
       float sn, cs;
       sincosf((float)pos * inv_freq[i], &sn, &cs);
       const uint16_t r0 = T::from_f32(x0 * cs - x1 * sn), r1 = T::from_f32(x1 * cs + x0 * sn);
@@ -348,10 +373,16 @@ void lm_launch_rope_cache(mia_lm* m, int layer, const float* qkv, const float* b
   uint16_t* kc = (uint16_t*)m->k_cache + (size_t)layer * m->B_cap * seq_stride;
   uint16_t* vc = (uint16_t*)m->v_cache + (size_t)layer * m->B_cap * seq_stride;
   const int n_el = (c.n_heads + c.n_kv_heads) * (dh / 2) + c.n_kv_heads * dh;
-  LAUNCH_T(lm_rope_cache, dim3((n_el + 255) / 256, M), dim3(256), 0, qkv, 1, bias, m->inv_freq, (uint16_t*)q, kc, vc, rowmap, c.n_heads, c.n_kv_heads, dh, c.max_ctx, seq_stride);
+  const float* qkn = m->qk_norm ? m->qk_norm + (size_t)layer * 2 * dh : nullptr;
+  const dim3 grid((n_el + 255) / 256, M);
+#define ROPE_GO(TT, NN) hipLaunchKernelGGL((lm_rope_cache<TT, NN>), grid, dim3(256), 0, s, qkv, 1, bias, m->inv_freq, (uint16_t*)q, kc, vc, rowmap, c.n_heads, c.n_kv_heads, dh, c.max_ctx, seq_stride, qkn, c.rms_eps)
+  if (qkn) { if (f16) ROPE_GO(F16, true); else ROPE_GO(BF16, true); }
+  else     { if (f16) ROPE_GO(F16, false); else ROPE_GO(BF16, false); }
+#undef ROPE_GO
 }
 
-// one launch site for the eight (dtype, head_dim, fused) instances of the 16-bit cache; the packed cache's are lm_kvq.hip's
+// one launch site for the twelve (dtype, head_dim, fused, q/k norm) instances of the 16-bit cache -- the norm exists in the fused form only:
+// the prompt pass's q and k rows were normalised by lm_rope_cache; the packed cache's are lm_kvq.hip's
 int lm_launch_attention(mia_lm* m, bool fused, int rows, const void* q, int layer, void* att, const int2* rowmap, const float* part, int S, const float* bias) {
   // fused: rows = sequences (row b uses state b and the b-th cache of the layer); otherwise rows = (sequence, position) pairs
   const mia_lm_config& c = m->cfg;
@@ -364,18 +395,23 @@ int lm_launch_attention(mia_lm* m, bool fused, int rows, const void* q, int laye
   const size_t lds = (size_t)(c.max_ctx + ATT_NW * dh + 2 * ATT_NW + 3 * dh) * 4;
   const float scale = 1.0f / sqrtf((float)dh);
   const dim3 grid(c.n_heads, rows), block(64 * ATT_NW);
-#define ATT_GO(TT, DD, FF) hipLaunchKernelGGL((lm_attention<TT, DD, FF>), grid, block, lds, s, (const uint16_t*)q, kc, vc, (uint16_t*)att, m->state, c.n_heads, c.n_kv_heads, c.max_ctx, scale, 0, part, S, bias, m->inv_freq, rows, seq_stride, rowmap)
+  const float* qkn = fused && m->qk_norm ? m->qk_norm + (size_t)layer * 2 * dh : nullptr;
+#define ATT_GO_N(TT, DD, FF, NN) hipLaunchKernelGGL((lm_attention<TT, DD, FF, NN>), grid, block, lds, s, (const uint16_t*)q, kc, vc, (uint16_t*)att, m->state, c.n_heads, c.n_kv_heads, c.max_ctx, scale, 0, part, S, bias, m->inv_freq, rows, seq_stride, rowmap, qkn, c.rms_eps)
+#define ATT_GO(TT, DD, FF) ATT_GO_N(TT, DD, FF, false)
   const bool f16 = m->dtype == MIA_F16;
-  if (dh == 128) { if (fused) { if (f16) ATT_GO(F16, 128, true); else ATT_GO(BF16, 128, true); } else { if (f16) ATT_GO(F16, 128, false); else ATT_GO(BF16, 128, false); } }
+  if (qkn) { if (dh == 128) { if (f16) ATT_GO_N(F16, 128, true, true); else ATT_GO_N(BF16, 128, true, true); } else { if (f16) ATT_GO_N(F16, 64, true, true); else ATT_GO_N(BF16, 64, true, true); } }
+  else if (dh == 128) { if (fused) { if (f16) ATT_GO(F16, 128, true); else ATT_GO(BF16, 128, true); } else { if (f16) ATT_GO(F16, 128, false); else ATT_GO(BF16, 128, false); } }
   else           { if (fused) { if (f16) ATT_GO(F16, 64, true); else ATT_GO(BF16, 64, true); } else { if (f16) ATT_GO(F16, 64, false); else ATT_GO(BF16, 64, false); } }
 #undef ATT_GO
+#undef ATT_GO_N
   return 0;
 }
 
 namespace {
 
 // (the samplers read each sequence's prompt length from its state: a captured and a directly launched step issue the same arguments)
-int lm_enqueue_step(mia_lm* m, bool sampling, const mia_lm_sampler& sp, const RasParams* ras = nullptr, int nb = 1) {
+// mode: LM_STEP_* (what ends the step); sp: the top-p sampler's arguments, or the greedy one's stop ids; ras: the RAS sampler's
+int lm_enqueue_step(mia_lm* m, int mode, const mia_lm_sampler& sp, const RasParams* ras = nullptr, int nb = 1) {
   hipStream_t s = m->ctx->stream;
   const mia_lm_config& c = m->cfg;
   const int D = c.hidden, dh = c.head_dim, Nq = c.n_heads * dh, Nk = c.n_kv_heads * dh, Nqkv = Nq + 2 * Nk;
@@ -426,8 +462,9 @@ int lm_enqueue_step(mia_lm* m, bool sampling, const mia_lm_sampler& sp, const Ra
   }
   const int HV = m->head_vocab > 0 ? m->head_vocab : c.vocab;
   if (skinny(m->h, D, m->lm_head, m->lm_head_f, m->head_bias, m->logits, HV, HV, D, 1, SK_OUTF32, &m->q_head, fused_norm && c.n_layers > 0 ? ss_d : nullptr, nullptr, nullptr, m->final_rs)) return -1;
-  if (ras) lm_sample_ras_launch(s, m->logits, HV, m->tokens, m->out_tokens, m->uniforms, m->state, *ras, c.max_ctx, nb);
-  else if (sampling) lm_sample_launch(s, m->logits, HV, m->tokens, m->hist, m->uniforms, m->state, m->smx, sp, -1, c.max_ctx, nb);
+  if (mode == LM_STEP_RAS) lm_sample_ras_launch(s, m->logits, HV, m->tokens, m->out_tokens, m->uniforms, m->state, *ras, c.max_ctx, nb);
+  else if (mode == LM_STEP_TOP_P) lm_sample_launch(s, m->logits, HV, m->tokens, m->hist, m->uniforms, m->state, m->smx, sp, -1, c.max_ctx, nb);
+  else if (mode == LM_STEP_GREEDY) lm_sample_greedy_launch(s, m->logits, HV, m->tokens, m->out_tokens, m->state, m->smx, sp, c.max_ctx, nb);
   else hipLaunchKernelGGL(lm_advance, dim3(nb), dim3(1), 0, s, m->state);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -519,13 +556,13 @@ int lm_graph(mia_lm* m, int mode, const mia_lm_sampler& sp, const RasParams* ras
   mia_ctx* ctx = m->ctx;
   if (m->debug_flags & 1) return 1;                  // test hook (mia_lm_set_debug): launch every step directly
   mia_lm_sampler key{}; RasParams rkey{};
-  if (mode == 1) key = sp;
-  if (mode == 2) rkey = *ras;
+  if (mode == LM_STEP_TOP_P || mode == LM_STEP_GREEDY) key = sp;
+  if (mode == LM_STEP_RAS) rkey = *ras;
   if (m->graph && m->graph_mode == mode && m->graph_nb == nb && memcmp(&m->graph_sampler, &key, sizeof(key)) == 0 && memcmp(&m->graph_ras, &rkey, sizeof(rkey)) == 0) return 0;
   if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; }
   hipGraph_t g = nullptr;
   MIA_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-  const int erc = lm_enqueue_step(m, mode != 0, sp, mode == 2 ? ras : nullptr, nb);
+  const int erc = lm_enqueue_step(m, mode, sp, ras, nb);
   hipError_t ce = hipStreamEndCapture(ctx->stream, &g);
   if (erc != 0 || ce != hipSuccess || !g) { if (g) (void)hipGraphDestroy(g); return mia_fail(ctx, MIA_ERR_DEVICE, "lm: step graph capture failed"); }
   hipError_t ie = hipGraphInstantiate(&m->graph, g, nullptr, nullptr, 0);
@@ -566,7 +603,7 @@ extern "C" int mia_lm_forward(mia_lm* m, const int32_t* ids, int n, float* last_
   MIA_HIP(ctx, hipMemcpyAsync(m->tokens + st.pos, ids, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
   MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   mia_lm_sampler none{};
-  const int gr = lm_graph(m, 0, none);
+  const int gr = lm_graph(m, LM_STEP_FORWARD, none);
   if (gr < 0) return gr;
   int done = 0;
   if (n - 1 >= PF_MIN_ROWS && lm_prefill_supported(m)) {        // all but the last position: K/V only, batched
@@ -575,7 +612,7 @@ extern "C" int mia_lm_forward(mia_lm* m, const int32_t* ids, int n, float* last_
   }
   for (int i = done; i < n; ++i) {
     if (gr == 0) MIA_HIP(ctx, hipGraphLaunch(m->graph, ctx->stream));
-    else if (lm_enqueue_step(m, false, none)) return mia_fail(ctx, MIA_ERR_DEVICE, "lm_forward: launch failed");
+    else if (lm_enqueue_step(m, LM_STEP_FORWARD, none)) return mia_fail(ctx, MIA_ERR_DEVICE, "lm_forward: launch failed");
   }
   if (last_logits) MIA_HIP(ctx, hipMemcpyAsync(last_logits, m->logits, (size_t)m->cfg.vocab * 4, hipMemcpyDeviceToHost, ctx->stream));
   MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -604,6 +641,8 @@ extern "C" int mia_lm_set_kv_quant(mia_lm* m, int bits, int group_size) {
   mia_ctx* ctx = m->ctx;
   int code = MIA_OK;
   if (const char* e = lm_kvq_check(bits, group_size, m->cfg.head_dim, &code)) return mia_fail(ctx, code, "lm_set_kv_quant: %s (bits %d, group_size %d)", e, bits, group_size);
+  // (the reference's Qwen3 decoder runs on KVCacheSimple only, FunASRSTT.swift:120; lm_kvq.hip's kernels do not carry the q/k norm)
+  if (bits != 0 && m->qk_norm) return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "lm_set_kv_quant: a quantised KV cache on a handle with q_norm / k_norm tensors is not supported");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const int before = m->kv_bits;
@@ -656,16 +695,17 @@ namespace {
 
 // One validated call of a generate entry point.  The samplers tie the two forms together: the top-p kernels count a prompt of ids
 // (LmState::n_prompt) and append the drawn ids to `tokens` (n_gen of them); the RAS kernel counts a prompt of embedding rows (n_embeds)
-// and emits to `out_tokens` (n_out ids).  A single-sequence call is n_seq = 1 with offsets {0, n_prompt}.
+// and emits to `out_tokens` (n_out ids), and so does the greedy kernel (embedding rows in, no uniforms).  A single-sequence call is
+// n_seq = 1 with offsets {0, n_prompt}.
 struct LmGenCall {
   const char* name;                       // entry point, for error messages
   int n_seq;
   const int32_t* offsets;                 // [n_seq + 1]: sequence b's prompt is ids / rows [offsets[b], offsets[b + 1])
   const int32_t* ids = nullptr;           // top-p: the prompts' ids ...
   const mia_lm_sampler* sp = nullptr;     // ... and the sampler
-  const float* embeds = nullptr;          // RAS: the prompts' embedding rows [.][hidden] ...
-  const mia_ras_params* ras = nullptr;    // ... and [n_seq] parameters (min_len / max_len per sequence, the rest equal)
-  const float* uniforms = nullptr;        // sequence b draws from uniforms[b * u_stride + i], i < n_uniforms (staged up to max_ctx of them)
+  const float* embeds = nullptr;          // RAS / greedy: the prompts' embedding rows [.][hidden] ...
+  const mia_ras_params* ras = nullptr;    // ... RAS: [n_seq] parameters (min_len / max_len per sequence, the rest equal)
+  const float* uniforms = nullptr;        // sequence b draws from uniforms[b * u_stride + i], i < n_uniforms (staged up to max_ctx of them); greedy: none
   int u_stride = 0, n_uniforms = 0;
   int max_new = 0;                        // the most steps any sequence runs past its prompt
   // A prompt with at least this many positions before its last one goes through the batched prompt pass; a shorter one walks the step.
@@ -686,14 +726,16 @@ int lm_generate_run(mia_lm* m, const LmGenCall& g) {
   std::vector<LmState> st(B);
   for (int b = 0; b < B; ++b) {
     st[b] = LmState{};
-    if (g.ras) {
-      st[b].n_embeds = n_prompt(b); st[b].min_len = g.ras[b].min_len; st[b].max_len = g.ras[b].max_len;
+    if (g.embeds) {
+      st[b].n_embeds = n_prompt(b);
+      if (g.ras) { st[b].min_len = g.ras[b].min_len; st[b].max_len = g.ras[b].max_len; }
+      else st[b].max_len = g.max_new;
       MIA_HIP(ctx, hipMemcpyAsync(m->embeds + (size_t)b * C * D, g.embeds + (size_t)g.offsets[b] * D, (size_t)n_prompt(b) * D * 4, hipMemcpyHostToDevice, s));
     } else {
       st[b].n_prompt = n_prompt(b);
       MIA_HIP(ctx, hipMemcpyAsync(m->tokens + (size_t)b * C, g.ids + g.offsets[b], (size_t)n_prompt(b) * 4, hipMemcpyHostToDevice, s));
     }
-    MIA_HIP(ctx, hipMemcpyAsync(m->uniforms + (size_t)b * C, g.uniforms + (size_t)b * g.u_stride, (size_t)nu * 4, hipMemcpyHostToDevice, s));
+    if (g.uniforms) MIA_HIP(ctx, hipMemcpyAsync(m->uniforms + (size_t)b * C, g.uniforms + (size_t)b * g.u_stride, (size_t)nu * 4, hipMemcpyHostToDevice, s));
   }
   MIA_HIP(ctx, hipMemcpyAsync(m->state, st.data(), sizeof(LmState) * B, hipMemcpyHostToDevice, s));
   MIA_HIP(ctx, hipStreamSynchronize(s));
@@ -701,7 +743,8 @@ int lm_generate_run(mia_lm* m, const LmGenCall& g) {
   if (g.ras) r = RasParams{g.ras[0].top_p, g.ras[0].top_k, g.ras[0].win, g.ras[0].tau, g.ras[0].eos, 0, 0, nu};   // (the length bounds travel in the state: one graph serves every text length)
   else sp = *g.sp;
   const RasParams* rp = g.ras ? &r : nullptr;
-  const int gr = lm_graph(m, g.ras ? 2 : 1, sp, rp, B);
+  const int mode = g.ras ? LM_STEP_RAS : g.embeds ? LM_STEP_GREEDY : LM_STEP_TOP_P;
+  const int gr = lm_graph(m, mode, sp, rp, B);
   if (gr < 0) return gr;
   // prompts: everything but a prompt's last position through the batched prompt pass (K/V only; the rows of all prompts share its
   // GEMMs), the last position takes the first step.  A prompt that does not take the pass walks the step instead -- its sampler idles
@@ -726,7 +769,7 @@ int lm_generate_run(mia_lm* m, const LmGenCall& g) {
   const int total = walk + g.max_new;
   for (int step = 0; step < total; ++step) {
     if (gr == 0) MIA_HIP(ctx, hipGraphLaunch(m->graph, s));
-    else if (lm_enqueue_step(m, true, sp, rp, B)) return mia_fail(ctx, MIA_ERR_DEVICE, "%s: launch failed", g.name);
+    else if (lm_enqueue_step(m, mode, sp, rp, B)) return mia_fail(ctx, MIA_ERR_DEVICE, "%s: launch failed", g.name);
     if ((step & 15) == 15) {                               // after every 16th launched step: a finished sequence's further steps are no-ops
       if (const int rc = read_state()) return rc;
       bool all = true;
@@ -736,8 +779,8 @@ int lm_generate_run(mia_lm* m, const LmGenCall& g) {
   }
   if (const int rc = read_state()) return rc;
   for (int b = 0; b < B; ++b) {
-    const int n = g.ras ? st[b].n_out : st[b].n_gen;
-    const int32_t* src = g.ras ? m->out_tokens + (size_t)b * C : m->tokens + (size_t)b * C + n_prompt(b);
+    const int n = g.embeds ? st[b].n_out : st[b].n_gen;
+    const int32_t* src = g.embeds ? m->out_tokens + (size_t)b * C : m->tokens + (size_t)b * C + n_prompt(b);
     g.n_out[b] = n;
     if (n > 0) MIA_HIP(ctx, hipMemcpyAsync(g.out + (size_t)b * g.out_stride, src, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   }
@@ -829,5 +872,58 @@ extern "C" int mia_lm_generate_ras_batch(mia_lm* m, const float* prompt_embeds, 
   LmGenCall g{"lm_generate_ras_batch", n_seq, prompt_offsets};
   g.embeds = prompt_embeds; g.ras = rp; g.uniforms = uniforms; g.u_stride = g.n_uniforms = n_uniforms; g.max_new = max_len;
   g.out = out_tokens; g.out_stride = out_stride; g.n_out = n_out;
+  return lm_generate_run(m, g);
+}
+
+// ---- greedy decode from a prompt of embedding rows (Fun-ASR's decoder loop, STT/FunASR/FunASRSTT.swift:118-156) ----
+namespace {
+
+int lm_greedy_check(mia_lm* m, const char* name, const int32_t* stop_ids, int n_stop, int max_new_tokens, mia_lm_sampler* sp) {
+  mia_ctx* ctx = m->ctx;
+  MIA_CHECK_ARG(ctx, !m->gen_embed && m->head_vocab == 0, "%s: the handle has speech_embedding / llm_decoder tensors (its loop is mia_lm_generate_ras)", name);
+  MIA_CHECK_ARG(ctx, n_stop >= 1 && n_stop <= 4, "%s: n_stop must be 1..4 (got %d)", name, n_stop);
+  MIA_CHECK_ARG(ctx, max_new_tokens > 0, "%s: max_new_tokens must be positive", name);
+  *sp = mia_lm_sampler{};
+  sp->n_stop = n_stop;
+  for (int i = 0; i < n_stop; ++i) {
+    MIA_CHECK_ARG(ctx, stop_ids[i] >= 0 && stop_ids[i] < m->cfg.vocab, "%s: stop id %d out of vocabulary", name, stop_ids[i]);
+    sp->stop_ids[i] = stop_ids[i];
+  }
+  return MIA_OK;
+}
+
+}  // namespace
+
+// The two greedy entries give a prompt of two or more rows to the batched prompt pass (pf_min_rows 1), alone or in a batch: sequence b of
+// mia_lm_generate_greedy_batch goes through exactly the kernels of its single call.
+extern "C" int mia_lm_generate_greedy(mia_lm* m, const float* prompt_embeds, int n_prompt, const int32_t* stop_ids, int n_stop, int max_new_tokens,
+                                      int32_t* out_tokens, int32_t* n_out) {
+  if (!m) return MIA_ERR_MODEL_NOT_LOADED;
+  mia_ctx* ctx = m->ctx;
+  MIA_CHECK_ARG(ctx, prompt_embeds && stop_ids && out_tokens && n_out, "lm_generate_greedy: null arguments");
+  mia_lm_sampler sp;
+  if (const int rc = lm_greedy_check(m, "lm_generate_greedy", stop_ids, n_stop, max_new_tokens, &sp)) return rc;
+  MIA_CHECK_ARG(ctx, n_prompt > 0 && n_prompt <= m->cfg.max_ctx - max_new_tokens, "lm_generate_greedy: prompt %d + max_new_tokens %d exceeds max_ctx %d", n_prompt, max_new_tokens, m->cfg.max_ctx);
+  const int32_t offsets[2] = {0, n_prompt};
+  LmGenCall g{"lm_generate_greedy", 1, offsets};
+  g.embeds = prompt_embeds; g.sp = &sp; g.max_new = max_new_tokens; g.out = out_tokens; g.n_out = n_out;
+  return lm_generate_run(m, g);
+}
+
+extern "C" int mia_lm_generate_greedy_batch(mia_lm* m, const float* prompt_embeds, const int32_t* prompt_offsets, int n_seq, const int32_t* stop_ids, int n_stop,
+                                            int max_new_tokens, int32_t* out_tokens, int out_stride, int32_t* n_out) {
+  if (!m) return MIA_ERR_MODEL_NOT_LOADED;
+  mia_ctx* ctx = m->ctx;
+  MIA_CHECK_ARG(ctx, prompt_embeds && prompt_offsets && stop_ids && out_tokens && n_out, "lm_generate_greedy_batch: null arguments");
+  MIA_CHECK_ARG(ctx, n_seq >= 1 && n_seq <= m->B_cap, "lm_generate_greedy_batch: n_seq %d exceeds the batch set with mia_lm_set_batch (%d)", n_seq, m->B_cap);
+  mia_lm_sampler sp;
+  if (const int rc = lm_greedy_check(m, "lm_generate_greedy_batch", stop_ids, n_stop, max_new_tokens, &sp)) return rc;
+  MIA_CHECK_ARG(ctx, out_stride >= max_new_tokens, "lm_generate_greedy_batch: out_stride %d must hold max_new_tokens %d ids", out_stride, max_new_tokens);
+  for (int b = 0; b < n_seq; ++b) {
+    const int np_ = prompt_offsets[b + 1] - prompt_offsets[b];
+    MIA_CHECK_ARG(ctx, np_ > 0 && np_ <= m->cfg.max_ctx - max_new_tokens, "lm_generate_greedy_batch: prompt %d: length %d + max_new_tokens exceeds max_ctx", b, np_);
+  }
+  LmGenCall g{"lm_generate_greedy_batch", n_seq, prompt_offsets};
+  g.embeds = prompt_embeds; g.sp = &sp; g.max_new = max_new_tokens; g.out = out_tokens; g.out_stride = out_stride; g.n_out = n_out;
   return lm_generate_run(m, g);
 }

@@ -1,4 +1,4 @@
-// lm_load.hip -- the LM handle's life cycle: mia_lm_load (16-bit upload of a Llama-3 / Qwen2 checkpoint, fused q|k|v and gate|up
+// lm_load.hip -- the LM handle's life cycle: mia_lm_load (16-bit upload of a Llama-3 / Qwen2 / Qwen3 checkpoint, fused q|k|v and gate|up
 // matrices, fragment-order copies for the decode step), the per-sequence state buffers, mia_lm_free, and the MLX-affine 4- / 8-bit
 // packed weights of the step (mia_lm_attach_quantized: host repack into the layout skinny_quant.hip reads).
 #include <algorithm>
@@ -158,9 +158,19 @@ extern "C" mia_lm* mia_lm_load(mia_ctx* ctx, const mia_lm_config* cfg, const mia
     m->inv_freq = L.up32(inv);
   }
   m->layers.resize(c.n_layers);
+  // Qwen3's per-head q / k RMSNorm (STT/FunASR/Layers/Qwen3Model.swift:32-35,57-59) is switched by tensor presence, like the CosyVoice2
+  // head above: both gains [head_dim] in every layer, or none in any
+  std::vector<float> qkn;
   for (int l = 0; l < c.n_layers && L.err.empty(); ++l) {
     const std::string p = "model.layers." + std::to_string(l);
     LmLayer& ly = m->layers[l];
+    {
+      const std::string qn = p + ".self_attn.q_norm.weight", kn = p + ".self_attn.k_norm.weight";
+      const bool has_q = L.find(qn, false) != nullptr, has_k = L.find(kn, false) != nullptr;
+      if (has_q != has_k) L.err = "missing tensor '" + (has_q ? kn : qn) + "' (q_norm and k_norm come as a pair)";
+      else if (l > 0 && has_q != !qkn.empty()) L.err = "tensor '" + qn + "' is " + (has_q ? "present" : "missing") + ": q_norm / k_norm must be in every layer or in none";
+      else if (has_q && L.to_f32(qn, t, dh, 0) && L.to_f32(kn, t2, dh, 0)) { qkn.insert(qkn.end(), t.begin(), t.end()); qkn.insert(qkn.end(), t2.begin(), t2.end()); }
+    }
     if (L.to_f32(p + ".input_layernorm.weight", t, D, 0)) { ly.in_norm = L.up32(t); ly.in_norm_c = L.carried(t, &ly.in_rs, ly.in_norm); }
     if (L.to_f32(p + ".post_attention_layernorm.weight", t, D, 0)) { ly.post_norm = L.up32(t); ly.post_norm_c = L.carried(t, &ly.post_rs, ly.post_norm); }
     std::vector<float> qkv((size_t)(Nq + 2 * Nk) * D);
@@ -183,6 +193,7 @@ extern "C" mia_lm* mia_lm_load(mia_ctx* ctx, const mia_lm_config* cfg, const mia
     }
     if (L.to_f32(p + ".mlp.down_proj.weight", t, D, c.inter)) ly.wdown = L.up16(t);
   }
+  if (L.err.empty() && !qkn.empty()) m->qk_norm = L.up32(qkn);
   if (!L.err.empty()) return fail(m, L.err);
   {  // fragment-order copies for the decode step (one device repack per matrix)
     bool ok = true;

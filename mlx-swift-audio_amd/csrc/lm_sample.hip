@@ -1,8 +1,9 @@
-// lm_sample.hip -- the LM decode step's two samplers on gfx950: the Orpheus top-p sampler (OrpheusTTS.swift:375-470: repetition penalty ->
-// temperature -> top-p -> categorical), also standalone as mia_sample_top_p, and the RAS sampler of CosyVoice2 (Qwen2LM.swift:295-321,
-// 433-488).  Stochastic stage: every categorical draw takes an explicit uniform (inverse CDF over the kept tokens); the reference draws
-// from MLX's unseeded RNG, so parity is on the kept set / distribution, not on the stream.  The rest of the LM code sees the two
-// launchers, the top-p workspace size and the RAS vocabulary bound (lm.h).
+// lm_sample.hip -- the LM decode step's samplers on gfx950: the Orpheus top-p sampler (OrpheusTTS.swift:375-470: repetition penalty ->
+// temperature -> top-p -> categorical), also standalone as mia_sample_top_p, the RAS sampler of CosyVoice2 (Qwen2LM.swift:295-321,
+// 433-488) and the greedy argmax of Fun-ASR's decoder (FunASRModel.swift:160-163).  Stochastic stages: every categorical draw takes an
+// explicit uniform (inverse CDF over the kept tokens); the reference draws from MLX's unseeded RNG, so parity is on the kept set /
+// distribution, not on the stream.  The rest of the LM code sees the three launchers, the top-p workspace size and the RAS vocabulary
+// bound (lm.h).
 #include <cmath>
 
 #include "lm.h"
@@ -671,6 +672,64 @@ __global__ __launch_bounds__(1024) void lm_sample_ras(const float* __restrict__ 
   }
 }
 
+// ---- greedy (Fun-ASR: FunASRConfig.temperature 0 -> sampleNextToken takes MLX.argMax, STT/FunASR/FunASRModel.swift:160-163) ----
+// argmax over the whole vocabulary, lowest index on exact ties: GRD_G workgroups per sequence each reduce one contiguous slice (one
+// workgroup walking 151 936 logits is what one CU streams; see the top-p sampler above), then one wave per sequence picks among the slice
+// winners and does the loop's bookkeeping (FunASRSTT.swift:132-156): a stop id ends the sequence and is neither emitted nor counted.
+constexpr int GRD_G = 32;
+struct GreedyWs { float v[GRD_G]; int i[GRD_G]; };      // per sequence, at the head of its top-p workspace
+static_assert(sizeof(GreedyWs) <= sizeof(SmxWs), "the greedy sampler borrows the top-p sampler's per-sequence workspace");
+
+// (value, index) order: higher value first, then lower index; an index past the vocabulary marks "nothing yet" (all NaN / -inf slices)
+__device__ __forceinline__ void grd_take(float& v, int& i, float v2, int i2) { if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; } }
+__device__ __forceinline__ void grd_wave(float& v, int& i) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const float v2 = __shfl_xor(v, o, 64); const int i2 = __shfl_xor(i, o, 64); grd_take(v, i, v2, i2); }
+}
+__device__ __forceinline__ bool grd_drawing(const LmState& s) { return !(s.pos + 1 < s.n_embeds || s.finished); }
+
+__global__ __launch_bounds__(256) void lm_greedy_part(const float* __restrict__ logits, int V, const LmState* __restrict__ st, char* __restrict__ ws, size_t ws_stride) {
+  __shared__ float shv[4];
+  __shared__ int shi[4];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  if (!grd_drawing(st[b])) return;                       // still consuming the prompt, or done (uniform over the workgroup)
+  logits += (int64_t)b * V;
+  const int sl = (V + GRD_G - 1) / GRD_G, lo = min(V, (int)blockIdx.x * sl), hi = min(V, lo + sl);
+  float v = -INFINITY; int i = 0x7fffffff;
+  for (int k = lo + tid; k < hi; k += 256) grd_take(v, i, logits[k], k);
+  grd_wave(v, i);
+  if ((tid & 63) == 0) { shv[tid >> 6] = v; shi[tid >> 6] = i; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w) grd_take(v, i, shv[w], shi[w]);
+    GreedyWs* g = (GreedyWs*)(ws + (size_t)b * ws_stride);
+    g->v[blockIdx.x] = v; g->i[blockIdx.x] = i;
+  }
+}
+
+__global__ __launch_bounds__(64) void lm_greedy_pick(int V, int32_t* __restrict__ tokens, int32_t* __restrict__ out_tokens, LmState* __restrict__ st,
+                                                     const char* __restrict__ ws, size_t ws_stride, mia_lm_sampler sp, int max_ctx) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  st += b; tokens += (int64_t)b * max_ctx; out_tokens += (int64_t)b * max_ctx;
+  const int pos = st->pos, n_prompt = st->n_embeds, cur_len = pos + 1;
+  if (!grd_drawing(*st)) { if (lane == 0 && !st->finished) st->pos = pos + 1; return; }
+  const GreedyWs* g = (const GreedyWs*)(ws + (size_t)b * ws_stride);
+  float v = lane < GRD_G ? g->v[lane] : -INFINITY;
+  int i = lane < GRD_G ? g->i[lane] : 0x7fffffff;
+  grd_wave(v, i);
+  if (lane != 0) return;
+  const int pick = i < V ? i : 0;                        // a row without one ordered value (all NaN) must still give an id inside the table
+  bool stop = false;
+  for (int k = 0; k < sp.n_stop; ++k) stop = stop || pick == sp.stop_ids[k];
+  st->n_gen += 1;
+  if (stop) { st->finished = 1; return; }
+  const int step_i = cur_len - n_prompt;
+  if (cur_len < max_ctx) tokens[cur_len] = pick;         // embedding input of the next step (model.embed_tokens[pick])
+  out_tokens[st->n_out] = pick; st->n_out += 1;
+  if (step_i + 1 >= st->max_len || cur_len + 1 >= max_ctx) st->finished = 1;
+  st->pos = pos + 1;
+}
+
 }  // namespace
 
 static_assert(LM_RAS_MAX_VOCAB == 1024 * RAS_NPT, "lm.h states the RAS kernel's register-resident vocabulary");
@@ -692,6 +751,12 @@ void lm_sample_launch(hipStream_t s, float* logits, int V, int32_t* tokens, int3
 void lm_sample_ras_launch(hipStream_t s, const float* logits, int V, int32_t* tokens, int32_t* out_tokens, const float* uniforms, LmState* st, const RasParams& rp,
                           int max_ctx, int B) {
   hipLaunchKernelGGL(lm_sample_ras, dim3(B), dim3(1024), 0, s, logits, V, tokens, out_tokens, uniforms, st, rp, max_ctx);
+}
+
+void lm_sample_greedy_launch(hipStream_t s, const float* logits, int V, int32_t* tokens, int32_t* out_tokens, LmState* st, void* ws, const mia_lm_sampler& sp,
+                             int max_ctx, int B) {
+  hipLaunchKernelGGL(lm_greedy_part, dim3(GRD_G, B), dim3(256), 0, s, logits, V, (const LmState*)st, (char*)ws, sizeof(SmxWs));
+  hipLaunchKernelGGL(lm_greedy_pick, dim3(B), dim3(64), 0, s, V, tokens, out_tokens, st, (const char*)ws, sizeof(SmxWs), sp, max_ctx);
 }
 
 // standalone sampler on caller-provided logits (OrpheusTTS.sampleNextToken, OrpheusTTS.swift:375-470)

@@ -252,6 +252,52 @@ def _generate_ras_batch(self, prompt_embeds, uniforms, min_lens, max_lens, eos, 
 CausalLM.generate_ras_batch = _generate_ras_batch
 
 
+def _stop_array(stop_ids) -> np.ndarray:
+    return np.ascontiguousarray(list(stop_ids), np.int32)
+
+
+def _generate_greedy(self, prompt_embeds, stop_ids, max_new_tokens: int) -> list[int]:
+    """mia_lm_generate_greedy: embedding-row prompt [n, hidden] -> argmax ids (lowest index on ties) until one of `stop_ids` (1..4 of them;
+    the stop id is not returned) or `max_new_tokens` ids."""
+    lib = self.ctx.lib
+    if not getattr(lib, "_greedy_declared", False):
+        lib.mia_lm_generate_greedy.restype = C.c_int
+        lib.mia_lm_generate_greedy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        lib._greedy_declared = True
+    x = np.ascontiguousarray(prompt_embeds, np.float32).reshape(-1, self.cfg.hidden)
+    stop = _stop_array(stop_ids)
+    out = np.zeros(max(int(max_new_tokens), 1), np.int32)
+    n = C.c_int32(0)
+    self.ctx.check(lib.mia_lm_generate_greedy(self.h, x.ctypes.data, x.shape[0], stop.ctypes.data, stop.size, int(max_new_tokens), out.ctypes.data, C.byref(n)))
+    return out[:n.value].tolist()
+
+
+def _generate_greedy_batch(self, prompt_embeds, stop_ids, max_new_tokens: int) -> list[list[int]]:
+    """mia_lm_generate_greedy_batch: one embedding-row prompt per utterance, decoded side by side (set_batch(n) first); utterance b's ids
+    equal generate_greedy(prompt_embeds[b], ...) on the same handle capacity."""
+    lib = self.ctx.lib
+    if not getattr(lib, "_greedy_batch_declared", False):
+        lib.mia_lm_generate_greedy_batch.restype = C.c_int
+        lib.mia_lm_generate_greedy_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        lib._greedy_batch_declared = True
+    n_seq = len(prompt_embeds)
+    xs = [np.ascontiguousarray(x, np.float32).reshape(-1, self.cfg.hidden) for x in prompt_embeds]
+    offs = np.zeros(n_seq + 1, np.int32)
+    np.cumsum([x.shape[0] for x in xs], out=offs[1:])
+    flat = np.ascontiguousarray(np.concatenate(xs, axis=0))
+    stop = _stop_array(stop_ids)
+    stride = max(int(max_new_tokens), 1)
+    out = np.zeros((n_seq, stride), np.int32)
+    n = np.zeros(n_seq, np.int32)
+    self.ctx.check(lib.mia_lm_generate_greedy_batch(self.h, flat.ctypes.data, offs.ctypes.data, n_seq, stop.ctypes.data, stop.size, int(max_new_tokens),
+                                                    out.ctypes.data, stride, n.ctypes.data))
+    return [out[b, :n[b]].tolist() for b in range(n_seq)]
+
+
+CausalLM.generate_greedy = _generate_greedy
+CausalLM.generate_greedy_batch = _generate_greedy_batch
+
+
 def sample_next_token(ctx: _lib.Context, logits: np.ndarray, history, uniform: float, temperature=0.6, top_p=0.8, rep_penalty=1.3) -> int:
     """sampleNextToken(logits:history:temperature:topP:repetitionPenalty:) with an explicit uniform for the categorical draw."""
     _declare(ctx.lib)
@@ -307,6 +353,33 @@ class Qwen2LM:
         x = self.lm_input(text, prompt_text, prompt_speech_tokens)
         min_len, max_len = int(len(text) * min_token_text_ratio), int(len(text) * max_token_text_ratio)
         return self.lm.generate_ras(x, uniforms, min_len, max_len, self.speech_token_size, top_p, top_k, win, tau)
+
+
+def merge_embeddings(text_embeddings: np.ndarray, input_ids, audio_embeddings: np.ndarray, sos_id: int, eos_id: int) -> np.ndarray:
+    """FunASRModel.mergeEmbeddings (STT/FunASR/FunASRModel.swift:71-141) for one utterance, on rows already looked up:
+    [text up to and including the first sos | audio rows | text from the first eos on]; the text rows alone when a marker is missing."""
+    ids = [int(t) for t in input_ids]
+    text = np.asarray(text_embeddings, np.float32)
+    if sos_id not in ids or eos_id not in ids:
+        return np.ascontiguousarray(text)
+    sos, eos = ids.index(sos_id), ids.index(eos_id)
+    return np.ascontiguousarray(np.concatenate([text[:sos + 1], np.asarray(audio_embeddings, np.float32), text[eos:]], axis=0))
+
+
+class FunASRDecoder:
+    """The decoder half of Fun-ASR (STT/FunASR/FunASRSTT.swift:111-156): prompt ids + audio embeddings -> greedy token ids on a Qwen3
+    CausalLM.  The audio rows (SenseVoice encoder + adaptor output, [n, hidden]) are an input; embed_weight is the checkpoint's
+    model.embed_tokens.weight (the host gathers the prompt's text rows from it, no arithmetic)."""
+
+    def __init__(self, lm: CausalLM, embed_weight: np.ndarray):
+        self.lm, self.embed = lm, embed_weight
+
+    def merge_embeddings(self, input_ids, audio_embeddings, sos_id: int, eos_id: int) -> np.ndarray:
+        text = np.asarray(self.embed[np.asarray(list(input_ids), np.int64)], np.float32)
+        return merge_embeddings(text, input_ids, audio_embeddings, sos_id, eos_id)
+
+    def transcribe_tokens(self, input_ids, audio_embeddings, sos_id: int, eos_id: int, stop_ids, max_tokens: int = 512) -> list[int]:
+        return self.lm.generate_greedy(self.merge_embeddings(input_ids, audio_embeddings, sos_id, eos_id), stop_ids, max_tokens)
 
 
 class OrpheusTTS:

@@ -332,6 +332,7 @@ class LMConfig:
     rope_old_ctx: int = 8192
     qkv_bias: bool = False
     tie_embeddings: bool = True
+    qk_norm: bool = False           # Qwen3: per-head RMSNorm of q and k before RoPE (self_attn.q_norm / k_norm, weight [head_dim])
 
 
 LM_CONFIGS = {
@@ -344,6 +345,12 @@ LM_CONFIGS = {
     "llama-micro": LMConfig(3000, 256, 512, 2, 4, 2, 64, 256),
     "llama-micro128": LMConfig(3000, 256, 512, 2, 2, 1, 128, 256),
     "qwen-micro": LMConfig(3000, 128, 384, 2, 2, 1, 64, 256, 1e-6, 1e6, False, 1.0, 1.0, 4.0, 8192, True, True),
+    # Qwen3Config (STT/FunASR/Layers/Qwen3Model.swift): Fun-ASR's decoder.  The Swift default for head_dim is 64, the published Qwen3-0.6B
+    # config.json says 128 (16 heads x 128 against hidden 1024): both widths are supported, and n_heads * head_dim != hidden in all three.
+    # The two micro shapes have n_heads * head_dim = 256 = 2 x hidden on purpose; qwen3-0.6b is for tools/bench_funasr_lm.py only.
+    "qwen3-micro": LMConfig(3000, 128, 384, 2, 4, 2, 64, 256, 1e-6, 1e6, False, 1.0, 1.0, 4.0, 8192, False, True, True),
+    "qwen3-micro128": LMConfig(3000, 128, 384, 2, 2, 1, 128, 256, 1e-6, 1e6, False, 1.0, 1.0, 4.0, 8192, False, True, True),
+    "qwen3-0.6b": LMConfig(151936, 1024, 3072, 28, 16, 8, 128, 2048, 1e-6, 1e6, False, 1.0, 1.0, 4.0, 8192, False, True, True),
 }
 
 
@@ -378,6 +385,9 @@ def lm_weights(cfg: LMConfig, seed: int = 0, round_to: str | None = None, dtype=
             vec(p + ".self_attn.q_proj.bias", cfg.n_heads * dh, 0.0, 0.1)
             vec(p + ".self_attn.k_proj.bias", cfg.n_kv_heads * dh, 0.0, 0.1)
             vec(p + ".self_attn.v_proj.bias", cfg.n_kv_heads * dh, 0.0, 0.1)
+        if cfg.qk_norm:
+            vec(p + ".self_attn.q_norm.weight", dh, 1.0, 0.1)
+            vec(p + ".self_attn.k_norm.weight", dh, 1.0, 0.1)
         mat(p + ".mlp.gate_proj.weight", cfg.inter, D)
         mat(p + ".mlp.up_proj.weight", cfg.inter, D)
         mat(p + ".mlp.down_proj.weight", D, cfg.inter)
