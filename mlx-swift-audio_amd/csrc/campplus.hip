@@ -270,9 +270,7 @@ int run_lin(mia_ctx* ctx, const Lin& l, const float* X, int64_t ldx, int T_in, f
   ConvGemmArgs g;
   g.X = X; g.ldx = ldx; g.T_in = T_in; g.W = l.w; g.bias = l.bias; g.Y = Y; g.ldy = ldy; g.T_out = T_out;
   g.M = T_out; g.N = l.cout; g.Cin = l.cin; g.taps = l.taps; g.dil = dil; g.pad = pad; g.x_row_mul = stride; g.gelu = act;
-  if (const char* e = codec_conv_gemm_check(g)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "campplus: %s", e);
-  if (codec_conv_gemm_launch(g, 1, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "campplus: GEMM launch failed");
-  return MIA_OK;
+  return codec_conv_gemm_run(ctx, g, 1, "campplus");
 }
 
 void run_conv2(hipStream_t s, const Conv2& c, const float* x, int H_in, int W, const float* res, float* y, int H_out, int stride_h, int relu,
@@ -292,8 +290,7 @@ int run_fbank(mia_campplus* m, const float* x, int64_t n, int F, float* frames, 
   ConvGemmArgs g;
   g.X = frames; g.ldx = FB_K; g.T_in = F; g.W = m->dft; g.Y = spec; g.ldy = 2 * FB_NBP; g.T_out = F;
   g.M = F; g.N = 2 * FB_NBP; g.Cin = FB_K; g.taps = 1;
-  if (const char* e = codec_conv_gemm_check(g)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "campplus fbank: %s", e);
-  if (codec_conv_gemm_launch(g, 1, s)) return mia_fail(ctx, MIA_ERR_DEVICE, "campplus fbank: GEMM launch failed");
+  if (int rc = codec_conv_gemm_run(ctx, g, 1, "campplus fbank")) return rc;
   hipLaunchKernelGGL(fbank_finish, dim3((unsigned)(((int64_t)F * FB_NMEL + 255) / 256)), dim3(256), 0, s, spec, m->fb_w, m->fb_meta, fb, F);
   if (mean_norm) hipLaunchKernelGGL(fbank_mean_sub, dim3(FB_NMEL), dim3(256), 0, s, fb, F);
   return hipGetLastError() == hipSuccess ? MIA_OK : mia_fail(ctx, MIA_ERR_DEVICE, "campplus fbank: launch failed");

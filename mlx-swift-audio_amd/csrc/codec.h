@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/mia.h"
+#include "mia_internal.h"
 
 // Tap-structured fp32 GEMM: Y[row(m)][n] = epi( sum_{tap,c} pre(X[m + tap*dil - pad][c]) * W[n][tap*Cin + c] + bias[n] )
 //   row(m) = m*y_row_mul + y_row_off + z*y_phase_step (rows outside [0,T_out) are dropped); z = grid.z phase, W += z*w_phase_stride
@@ -70,6 +71,13 @@ const char* codec_conv_gemm_check(const ConvGemmArgs& g);
 // algorithmic bytes of the fp32 conv / elementwise launches issued by the calling host thread since the last reset (profiling aid)
 double codec_alg_bytes(bool reset);
 int codec_conv_gemm_launch(const ConvGemmArgs& g, int phases, hipStream_t s);
+// the checked launch every host file goes through: the arguments are checked, the GEMM goes to the context's stream, and a failure of either
+// is recorded as "<who>: <text>"
+static inline int codec_conv_gemm_run(mia_ctx* ctx, const ConvGemmArgs& g, int phases, const char* who) {
+  if (const char* e = codec_conv_gemm_check(g)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s: %s", who, e);
+  if (codec_conv_gemm_launch(g, phases, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "%s: conv_gemm launch failed", who);
+  return MIA_OK;
+}
 int codec_dwconv_launch(const float* x, float* y, const float* w, const float* bias, const float* a_pre, const float* a_post, int T, int C,
                         int K, int dil, hipStream_t s, const SeqArgs& q = SeqArgs());
 int codec_conv_out1_launch(const float* x, float* out, const float* w, const float* bias, const float* alpha, int T, int C, int K, hipStream_t s,

@@ -284,9 +284,7 @@ struct Run {
     g.X = X; g.ldx = ldx; g.T_in = M; g.W = l.w; g.bias = l.b; g.Y = Y; g.ldy = ldy; g.T_out = M * nseq; g.R = R; g.ldr = ldy;
     g.M = M; g.N = l.N; g.Cin = l.K; g.taps = l.taps; g.pad = pad; g.gelu = act;
     if (nseq > 1) { g.x_phase_step = M; g.y_phase_step = M; g.phase_len = phase_len; }
-    if (const char* e = codec_conv_gemm_check(g)) return fail(MIA_ERR_INVALID_ARGUMENT, e);
-    if (codec_conv_gemm_launch(g, nseq, s)) return fail(MIA_ERR_DEVICE, "gemm launch failed");
-    return true;
+    return (rc = codec_conv_gemm_run(f->ctx, g, nseq, "flow")) == MIA_OK;
   }
   bool ln(const Norm& n, const float* x, float* y, int M, int D, float eps) {
     if (rc != MIA_OK) return false;
@@ -474,23 +472,9 @@ void mia_flow_free(mia_flow* f) {
 static int flow_prepare(mia_flow* f, int Tt, int S, Bufs& b, int U = 1) {
   const int T = Tt * f->cfg.upsample_stride;
   const size_t need = carve(f, Tt, U * T, S, nullptr, U);
-  if (need > f->arena_floats) {
-    MIA_HIP(f->ctx, hipStreamSynchronize(f->ctx->stream));
-    if (f->arena) (void)hipFree(f->arena);
-    f->arena = nullptr; f->arena_floats = 0;
-    if (hipMalloc((void**)&f->arena, need * 4) != hipSuccess) return mia_fail(f->ctx, MIA_ERR_OUT_OF_MEMORY, "flow: scratch hipMalloc failed");
-    f->arena_floats = need;
-  }
+  if (int rc = mia_grow(f->ctx, f->arena, f->arena_floats, need, "flow: scratch hipMalloc failed")) return rc;
   carve(f, Tt, U * T, S, &b, U);
-  const size_t ids = (size_t)U * Tt + 4 * (size_t)U;
-  if (ids > f->ids_cap) {
-    MIA_HIP(f->ctx, hipStreamSynchronize(f->ctx->stream));
-    if (f->d_ids) (void)hipFree(f->d_ids);
-    f->d_ids = nullptr; f->ids_cap = 0;
-    if (hipMalloc((void**)&f->d_ids, ids * 4 + 64) != hipSuccess) return mia_fail(f->ctx, MIA_ERR_OUT_OF_MEMORY, "flow: hipMalloc failed");
-    f->ids_cap = ids;
-  }
-  return MIA_OK;
+  return mia_grow(f->ctx, f->d_ids, f->ids_cap, (size_t)U * Tt + 4 * (size_t)U, "flow: hipMalloc failed");
 }
 
 static int upload_tokens(mia_flow* f, int32_t* dst, const int32_t* prompt_token, int n_prompt, const int32_t* token, int n_token, int mem) {

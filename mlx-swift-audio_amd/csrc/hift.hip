@@ -16,13 +16,13 @@
 // The sine source replays the reference's float32 operation order with unfused multiplies/adds (its phases reach ~1e5 rad, where
 // a different association changes the waveform visibly); the Gaussian it draws is an explicit input.
 #include <cmath>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "codec.h"
 #include "mia_device.h"
 #include "mia_internal.h"
+#include "tensor_loader.h"
 
 namespace {
 
@@ -199,30 +199,8 @@ struct mia_hift {
 
 namespace {
 
-struct HLoader {
-  mia_hift* c;
-  std::map<std::string, const mia_tensor_view*> by_name;
-  std::string err;
-
-  bool f32(const std::string& n, std::vector<float>& out, std::initializer_list<int64_t> shp) {
-    auto it = by_name.find(n);
-    if (it == by_name.end()) { if (err.empty()) err = "missing tensor '" + n + "'"; return false; }
-    const mia_tensor_view* t = it->second;
-    if (t->dtype != MIA_F32) { if (err.empty()) err = "tensor '" + n + "' must be float32"; return false; }
-    int64_t numel = 1; bool ok = t->ndim == (int)shp.size(); int i = 0;
-    for (int64_t s : shp) { if (ok && t->shape[i] != s) ok = false; ++i; }
-    for (int k = 0; k < t->ndim; ++k) numel *= t->shape[k];
-    if (!ok) { if (err.empty()) err = "tensor '" + n + "' has an unexpected shape"; return false; }
-    out.assign((const float*)t->data, (const float*)t->data + numel);
-    return true;
-  }
-  float* up(const std::vector<float>& v) {
-    void* p = nullptr;
-    if (hipMalloc(&p, v.size() * 4 + 64) != hipSuccess) { if (err.empty()) err = "hipMalloc failed"; return nullptr; }
-    c->allocs.push_back(p);
-    if (hipMemcpy(p, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess && err.empty()) err = "hipMemcpy failed";
-    return (float*)p;
-  }
+struct HLoader : TensorLoader {
+  const mia_hift_config* cfg = nullptr;
   // Conv1d weight [Cout][K][Cin] -> tap-GEMM weights [Cout][K][Cp] (input channels zero-padded to a multiple of 32)
   bool conv(const std::string& p, int Cout, int K, int Cin, int dil, int pad, int stride, Conv& o) {
     std::vector<float> w, b;
@@ -267,7 +245,7 @@ struct HLoader {
     return true;
   }
   bool resblock(const std::string& p, int C, int k, ResBlock& rb) {
-    const mia_hift_config& g = c->cfg;
+    const mia_hift_config& g = *cfg;
     for (int i = 0; i < g.n_dilations; ++i) {
       const int d = g.dilations[i];
       const std::string si = std::to_string(i);
@@ -301,9 +279,7 @@ int run_conv(mia_hift* h, const Conv& c, const float* X, int64_t T_in, float* Y,
   g.Y = Y; g.ldy = o.ldy ? o.ldy : c.N; g.T_out = (int)T_out; g.R = o.R; g.R2 = o.R2; g.ldr = c.N; g.out_scale = o.scale;
   g.M = (int)T_out; g.N = c.N; g.Cin = c.Cin; g.taps = c.taps; g.dil = c.dil; g.pad = c.pad; g.x_row_mul = c.stride; g.gelu = o.act;
   seq_args(g, q, T_in, T_out);
-  if (const char* e = codec_conv_gemm_check(g)) return mia_fail(h->ctx, MIA_ERR_INVALID_ARGUMENT, "hift: %s", e);
-  if (codec_conv_gemm_launch(g, 1, h->ctx->stream)) return mia_fail(h->ctx, MIA_ERR_DEVICE, "hift: conv launch failed");
-  return MIA_OK;
+  return codec_conv_gemm_run(h->ctx, g, 1, "hift");
 }
 
 // transposed conv: Y rows [row_shift, row_shift + T_out) of a buffer with T_out + row_shift rows (per sequence)
@@ -313,9 +289,7 @@ int run_convt(mia_hift* h, const Conv& c, const float* X, int64_t T_in, float* Y
   g.M = (int)T_in + c.taps - 1; g.N = c.N; g.Cin = c.Cin; g.taps = c.taps; g.dil = 1; g.pad = c.taps - 1;
   g.Y = Y + (int64_t)row_shift * c.N; g.ldy = c.N; g.T_out = (int)T_out; g.y_row_mul = c.stride; g.y_row_off = -c.pad; g.y_phase_step = 1;
   seq_args(g, q, T_in, T_out + row_shift);
-  if (const char* e = codec_conv_gemm_check(g)) return mia_fail(h->ctx, MIA_ERR_INVALID_ARGUMENT, "hift: %s", e);
-  if (codec_conv_gemm_launch(g, c.stride, h->ctx->stream)) return mia_fail(h->ctx, MIA_ERR_DEVICE, "hift: convT launch failed");
-  return MIA_OK;
+  return codec_conv_gemm_run(h->ctx, g, c.stride, "hift");
 }
 
 // HiFiGANResBlock (HiFiGAN.swift:117-130).  x: input (left untouched), xt: scratch, res: running result; the last pair writes
@@ -382,13 +356,7 @@ int carve(mia_hift* h, const Plan& p, Scratch& sc) {
                     al(U * p.big), al(U * p.big), al(U * p.big), al(U * p.big), al(U * 8)};
   size_t tot = 0;
   for (size_t s : sizes) tot += s;
-  if (tot > h->arena_floats) {
-    (void)hipStreamSynchronize(h->ctx->stream);
-    if (h->arena) (void)hipFree(h->arena);
-    h->arena = nullptr; h->arena_floats = 0;
-    if (hipMalloc((void**)&h->arena, tot * 4) != hipSuccess) return mia_fail(h->ctx, MIA_ERR_OUT_OF_MEMORY, "hift: scratch hipMalloc failed");
-    h->arena_floats = tot;
-  }
+  if (int rc = mia_grow(h->ctx, h->arena, h->arena_floats, tot, "hift: scratch hipMalloc failed")) return rc;
   float* q = h->arena;
   float** dst[] = {&sc.mel_raw, &sc.melp, &sc.fa, &sc.fb, &sc.f0, &sc.P, &sc.s, &sc.noise, &sc.cache, &sc.stft, &sc.post, &sc.fr, &sc.pcm,
                    &sc.big[0], &sc.big[1], &sc.big[2], &sc.big[3]};
@@ -521,8 +489,7 @@ mia_hift* mia_hift_load(mia_ctx* ctx, const mia_hift_config* cfg, const mia_tens
   mia_hift* h = new mia_hift();
   h->ctx = ctx; h->cfg = g; h->H = g.nb_harmonics + 1; h->Cp_mel = (g.in_channels + 31) / 32 * 32;
   h->up = 4; for (int i = 0; i < g.n_ups; ++i) h->up *= g.up_rates[i];
-  HLoader L; L.c = h;
-  for (int i = 0; i < n_tensors; ++i) if (tensors[i].name) L.by_name[tensors[i].name] = &tensors[i];
+  HLoader L; L.cfg = &h->cfg; L.allocs = &h->allocs; L.index(tensors, n_tensors);
   const int B = g.base_channels;
   bool ok = true;
   static const int cond_idx[5] = {0, 2, 4, 6, 8};

@@ -79,6 +79,20 @@ inline int mia_fail(mia_ctx* ctx, int code, const char* fmt, ...) {
 // Ensure the ctx workspace holds at least `bytes`; returns nullptr on failure (ctx->err set).
 void* mia_workspace(mia_ctx* ctx, size_t bytes);
 
+// Grow-only device buffer of a handle: make p hold at least n elements (+ 64 B of slack), keeping it when it already does.  The old
+// buffer is freed behind a stream synchronisation, and p / cap are cleared BEFORE the allocation, so that a failed one leaves an empty
+// buffer on record and the next call allocates again instead of launching on a null pointer.  Contents are not carried over.
+template <class P>
+static int mia_grow(mia_ctx* ctx, P*& p, size_t& cap, size_t n, const char* msg) {
+  if (n <= cap) return MIA_OK;
+  (void)hipStreamSynchronize(ctx->stream);
+  if (p) (void)hipFree(p);
+  p = nullptr; cap = 0;
+  if (hipMalloc((void**)&p, n * sizeof(P) + 64) != hipSuccess) { p = nullptr; return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "%s", msg); }
+  cap = n;
+  return MIA_OK;
+}
+
 inline size_t mia_dtype_size(int dt) { return dt == MIA_F32 ? 4 : 2; }
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

@@ -11,7 +11,6 @@
 //   FSQ: round(tanh(W x + b) * 0.999) + 1 in base 3 (rintf = half-to-even like MLX round)
 #include <cmath>
 #include <mutex>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -19,6 +18,7 @@
 #include "mia_device.h"
 #include "mia_internal.h"
 #include "ops.h"
+#include "tensor_loader.h"
 
 namespace {
 
@@ -175,31 +175,9 @@ struct mia_s3tok {
 
 namespace {
 
-struct S3Loader {
-  mia_s3tok* m;
-  std::map<std::string, const mia_tensor_view*> by_name;
-  std::string err;
-  bool get(const std::string& n, std::vector<float>& out, std::initializer_list<int64_t> shp) {
-    auto it = by_name.find(n);
-    if (it == by_name.end()) { if (err.empty()) err = "missing tensor '" + n + "'"; return false; }
-    const mia_tensor_view* t = it->second;
-    if (t->dtype != MIA_F32) { if (err.empty()) err = "tensor '" + n + "' must be float32"; return false; }
-    bool ok = t->ndim == (int)shp.size(); int i = 0; int64_t numel = 1;
-    for (int64_t s : shp) { if (ok && t->shape[i] != s) ok = false; ++i; }
-    for (int k = 0; k < t->ndim; ++k) numel *= t->shape[k];
-    if (!ok) { if (err.empty()) err = "tensor '" + n + "' has an unexpected shape"; return false; }
-    out.assign((const float*)t->data, (const float*)t->data + numel);
-    return true;
-  }
-  float* up(const std::vector<float>& v) {
-    void* p = nullptr;
-    if (hipMalloc(&p, v.size() * 4 + 64) != hipSuccess) { if (err.empty()) err = "hipMalloc failed"; return nullptr; }
-    m->allocs.push_back(p);
-    (void)hipMemcpy(p, v.data(), v.size() * 4, hipMemcpyHostToDevice);
-    return (float*)p;
-  }
-  float* vec(const std::string& n, int64_t len) { std::vector<float> v; return get(n, v, {len}) ? up(v) : nullptr; }
-  float* mat(const std::string& n, int64_t r, int64_t c) { std::vector<float> v; return get(n, v, {r, c}) ? up(v) : nullptr; }
+struct S3Loader : TensorLoader {
+  float* vec(const std::string& n, int64_t len) { std::vector<float> v; return f32(n, v, {len}) ? up(v) : nullptr; }
+  float* mat(const std::string& n, int64_t r, int64_t c) { std::vector<float> v; return f32(n, v, {r, c}) ? up(v) : nullptr; }
 };
 
 }  // namespace
@@ -222,12 +200,11 @@ extern "C" mia_s3tok* mia_s3tok_load(mia_ctx* ctx, const mia_s3_config* cfg, con
   if (D <= 0 || H * 64 != D || M % 32 || D % 32 || cfg->n_audio_layer <= 0 || D > 4096) return fail(nullptr, "unsupported dims (state = 64*heads, n_mels % 32 == 0)");
   if (hipSetDevice(ctx->device) != hipSuccess) return fail(nullptr, "hipSetDevice failed");
   mia_s3tok* m = new mia_s3tok(); m->ctx = ctx; m->cfg = *cfg;
-  S3Loader L; L.m = m;
-  for (int i = 0; i < n_tensors; ++i) if (tensors[i].name && tensors[i].data) L.by_name[tensors[i].name] = &tensors[i];
+  S3Loader L; L.allocs = &m->allocs; L.index(tensors, n_tensors);
   {  // Conv1d weights [Cout][3][Cin] are already tap-major rows
     std::vector<float> v;
-    if (L.get("encoder.conv1.weight", v, {D, 3, M})) m->conv1_w = L.up(v);
-    if (L.get("encoder.conv2.weight", v, {D, 3, D})) m->conv2_w = L.up(v);
+    if (L.f32("encoder.conv1.weight", v, {D, 3, M})) m->conv1_w = L.up(v);
+    if (L.f32("encoder.conv2.weight", v, {D, 3, D})) m->conv2_w = L.up(v);
     m->conv1_b = L.vec("encoder.conv1.bias", D); m->conv2_b = L.vec("encoder.conv2.bias", D);
   }
   m->blocks.resize(cfg->n_audio_layer);
@@ -237,8 +214,8 @@ extern "C" mia_s3tok* mia_s3tok_load(mia_ctx* ctx, const mia_s3_config* cfg, con
     b.attn_ln_g = L.vec(p + ".attn_ln.weight", D); b.attn_ln_b = L.vec(p + ".attn_ln.bias", D);
     b.mlp_ln_g = L.vec(p + ".mlp_ln.weight", D); b.mlp_ln_b = L.vec(p + ".mlp_ln.bias", D);
     std::vector<float> q, k, v, bq, bv;
-    if (L.get(p + ".attn.query.weight", q, {D, D}) && L.get(p + ".attn.key.weight", k, {D, D}) && L.get(p + ".attn.value.weight", v, {D, D}) &&
-        L.get(p + ".attn.query.bias", bq, {D}) && L.get(p + ".attn.value.bias", bv, {D})) {
+    if (L.f32(p + ".attn.query.weight", q, {D, D}) && L.f32(p + ".attn.key.weight", k, {D, D}) && L.f32(p + ".attn.value.weight", v, {D, D}) &&
+        L.f32(p + ".attn.query.bias", bq, {D}) && L.f32(p + ".attn.value.bias", bv, {D})) {
       std::vector<float> w((size_t)3 * D * D), bb((size_t)3 * D, 0.f);
       memcpy(w.data(), q.data(), q.size() * 4); memcpy(w.data() + q.size(), k.data(), k.size() * 4); memcpy(w.data() + 2 * q.size(), v.data(), v.size() * 4);
       memcpy(bb.data(), bq.data(), D * 4); memcpy(bb.data() + 2 * D, bv.data(), D * 4);
@@ -247,7 +224,7 @@ extern "C" mia_s3tok* mia_s3tok_load(mia_ctx* ctx, const mia_s3_config* cfg, con
     b.wo = L.mat(p + ".attn.out.weight", D, D); b.bo = L.vec(p + ".attn.out.bias", D);
     {  // depthwise FSMN kernel [D][31][1] -> [31][D]
       std::vector<float> f;
-      if (L.get(p + ".attn.fsmn_block.weight", f, {D, 31, 1})) {
+      if (L.f32(p + ".attn.fsmn_block.weight", f, {D, 31, 1})) {
         std::vector<float> t((size_t)31 * D);
         for (int c = 0; c < D; ++c) for (int kk = 0; kk < 31; ++kk) t[(size_t)kk * D + c] = f[(size_t)c * 31 + kk];
         b.fsmn = L.up(t);
@@ -262,11 +239,7 @@ extern "C" mia_s3tok* mia_s3tok_load(mia_ctx* ctx, const mia_s3_config* cfg, con
   return m;
 }
 
-static int s3_gemm(mia_s3tok* m, const ConvGemmArgs& g) {
-  if (const char* e = codec_conv_gemm_check(g)) return mia_fail(m->ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
-  if (codec_conv_gemm_launch(g, 1, m->ctx->stream)) return mia_fail(m->ctx, MIA_ERR_DEVICE, "s3tok: gemm launch failed");
-  return MIA_OK;
-}
+static int s3_gemm(mia_s3tok* m, const ConvGemmArgs& g) { return codec_conv_gemm_run(m->ctx, g, 1, "s3tok"); }
 
 // one clip of T mel frames (T <= 3000: longer audio is windowed by the caller, S3Tokenizer.swift:497-650)
 static int s3_encode_clip(mia_s3tok* m, const float* d_mel, int64_t ld_mel, int T, int32_t* d_ids, int* n_tok) {
@@ -276,13 +249,7 @@ static int s3_encode_clip(mia_s3tok* m, const float* d_mel, int64_t ld_mel, int 
   // scratch carve (floats): x0 [(T+2)*NM] | c1 [(T1+2)*D] | x [T2*D] | h [T2*D] | qkv [T2*3D] | att [T2*D] | g [T2*4D]
   const size_t n_x0 = (size_t)(T + 2) * NM, n_c1 = (size_t)(T1 + 2) * D, n_td = (size_t)T2 * D;
   const size_t need = n_x0 + n_c1 + n_td * 2 + n_td * 3 + n_td + n_td * 4 + 1024;
-  if (need > m->scratch_floats) {
-    MIA_HIP(ctx, hipStreamSynchronize(s));
-    if (m->scratch) (void)hipFree(m->scratch);
-    m->scratch = nullptr;
-    if (hipMalloc((void**)&m->scratch, need * 4) != hipSuccess) return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "s3tok: scratch hipMalloc failed");
-    m->scratch_floats = need;
-  }
+  if (int rc = mia_grow(ctx, m->scratch, m->scratch_floats, need, "s3tok: scratch hipMalloc failed")) return rc;
   float* x0 = m->scratch; float* c1 = x0 + n_x0; float* x = c1 + n_c1; float* h = x + n_td; float* qkv = h + n_td; float* att = qkv + 3 * n_td; float* gbuf = att + n_td;
   hipLaunchKernelGGL(s3_transpose_pad, dim3(256), dim3(256), 0, s, d_mel, ld_mel, x0, T, NM);
   MIA_HIP(ctx, hipMemsetAsync(c1, 0, (size_t)D * 4, s));                                  // leading zero row of the conv2 input
@@ -337,13 +304,7 @@ extern "C" int mia_s3tok_encode(mia_s3tok* m, const float* mel, const int32_t* m
     MIA_HIP(ctx, hipMemcpyAsync(ws, mel, bytes, hipMemcpyHostToDevice, ctx->stream));
     d_mel = (const float*)ws;
   }
-  if ((size_t)tokens_stride > m->ids_cap) {
-    MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (m->d_ids) (void)hipFree(m->d_ids);
-    m->d_ids = nullptr;
-    if (hipMalloc((void**)&m->d_ids, (size_t)tokens_stride * 4 + 64) != hipSuccess) return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "s3tok: hipMalloc failed");
-    m->ids_cap = tokens_stride;
-  }
+  if (int rc = mia_grow(ctx, m->d_ids, m->ids_cap, (size_t)tokens_stride, "s3tok: hipMalloc failed")) return rc;
   for (int b = 0; b < B; ++b) {
     const int L = mel_len[b];
     MIA_CHECK_ARG(ctx, L > 0 && L <= T, "s3tok_encode: mel_len[%d] = %d out of range", b, L);
