@@ -143,7 +143,8 @@ int mia_dp_gather_tokens(mia_ctx* ctx, const int32_t* local_tokens, const int32_
 /* y = act(x W^T + b) + r : the dense contraction behind every MLXNN Linear on the path
  * (e.g. STT/Whisper/Layers/MultiHeadAttention.swift:40-58,134; ResidualAttentionBlock.swift:91).
  *   x [M][lda] and w [N][K] in `dtype` (MIA_BF16|MIA_F16), y [M][ldy] in `dtype` or fp32 (out_f32),
- *   bias fp32 [N] or NULL, r fp32 [M][ldr] or NULL, act 0 = none / 1 = exact-erf GELU.  K % 64 == 0.
+ *   bias fp32 [N] or NULL, r fp32 [M][ldr] or NULL, act 0 = none / 1 = exact-erf GELU / act 2 = ReLU (PositionwiseFeedForward,
+ *   Codec/S3Gen/Transformer/PositionwiseFeedForward.swift; runs on the 128^2 tiles whatever the variant).  K % 64 == 0.
  *   variant 0 = register-staged tiles, 1 = LDS-DMA staged tiles (default elsewhere).  Buffers live in `mem`. */
 int mia_op_linear(mia_ctx* ctx, const void* x, int64_t lda, const void* w, const float* bias, const float* r, int64_t ldr,
                   void* y, int64_t ldy, int M, int N, int K, int act, int dtype, int out_f32, int variant, int mem);
@@ -166,6 +167,27 @@ int mia_dequant_affine(mia_ctx* ctx, const uint32_t* wq, const void* scales, con
  * Codec/S3Gen/Matcha/MatchaTransformer.swift:58-66): q / k / v float32 [B*T][ld*] with head h in columns h*64 .. h*64+63. */
 int mia_op_attention_f32(mia_ctx* ctx, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, float* out,
                          int64_t ldo, int B, int T, int H, float scale);
+
+/* 16-bit scaled-dot-product attention, head dim 128, full (non-causal) softmax in fp32 on the matrix cores: Fun-ASR's
+ * MultiHeadAttentionSANM and FunASRMultiHeadAttention (STT/FunASR/Layers/MultiHeadAttentionSANM.swift:155-162, :245-251).
+ *   q / k / v [B*T][ld*] in `dtype` (MIA_BF16 | MIA_F16) with head h in columns h*128 .. h*128+127, each with its own pointer and row
+ *   stride (multiples of 8 elements, 16-byte aligned), so a fused [M][3 D] q|k|v buffer and three separate ones both fit; out [B*T][ldo]
+ *   in `dtype`; scale = d_k^-0.5.  Any T >= 1.  seq_len (int32 [B], nullable, in `mem`): keys at or beyond seq_len[b] are masked, rows of
+ *   `out` at or beyond it are left as they are, and sequence b's rows equal its own B = 1, T = seq_len[b] call bit for bit.
+ *   Deterministic (fixed summation order).  Buffers live in `mem`. */
+int mia_op_attention_h128(mia_ctx* ctx, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out,
+                          int64_t ldo, int B, int T, int H, float scale, const int32_t* seq_len, int dtype, int mem);
+
+/* The SANM memory (forwardFSMN, STT/FunASR/Layers/MultiHeadAttentionSANM.swift:90-116) added into an fp32 stream:
+ *   x[t][c] += v[t][c] + sum_k w[k][c] * v[t + k - left][c], rows outside the sequence read as zero; left = (K - 1) / 2 + sanm_shift
+ *   must lie in [0, K - 1].  x fp32 [B*T][ldx], v [B*T][ldv] in `dtype` (the v third of a q|k|v buffer), w fp32 [K][D], D % 4 == 0,
+ *   seq_len int32 [B] or NULL (no tap crosses a sequence's end; rows at or beyond it are untouched).  Buffers live in `mem`. */
+int mia_op_fsmn_add(mia_ctx* ctx, float* x, int64_t ldx, const void* v, int64_t ldv, const float* w, int B, int T, int D, int K, int left,
+                    const int32_t* seq_len, int dtype, int mem);
+
+/* The log-mel stage of Fun-ASR's front end alone (funASRLogMelSpectrogram, STT/FunASR/FunASRAudio.swift:57-94), the test tap of
+ * mia_sensevoice_features: mel_out float32 [sum_b (1 + L_b / 160)][80], natural log, the clips' frames back to back.  offs HOST. */
+int mia_op_funasr_logmel(mia_ctx* ctx, const float* pcm, const int64_t* offs, int B, float* mel_out, int mem);
 
 /* The LM's single-token grouped-query attention over a KV cache it fills itself (the kernels behind attentionWithCacheUpdate,
  * TTS/Orpheus/BuildingBlocks/TransformerBlock.swift:91-99), without a model around it.  q [Hq][dh], k / v [Hkv][T][dh] in `dtype`
@@ -549,6 +571,39 @@ int mia_lm_generate_greedy_batch(mia_lm* lm, const float* prompt_embeds, const i
 /* One sampleNextToken call on caller-provided logits (host pointers). */
 int mia_sample_top_p(mia_ctx* ctx, const float* logits, int V, const int32_t* history, int n_hist, float rep_penalty,
                      float temperature, float top_p, float uniform, int32_t* out);
+
+/* ---- Fun-ASR audio half: fbank + LFR + CMVN front end, SenseVoice SANM encoder, audio adaptor ------------------ */
+/* FunASRModel.encodeAudio (STT/FunASR/FunASRModel.swift:41-58): waveform -> the audio rows mia_lm_generate_greedy's prompt takes.
+ * SenseVoiceEncoderConfig + AudioAdaptorConfig (STT/FunASR/Config/FunASRConfig.swift:79-214).  Head dim is 128 in both stacks
+ * (encoder_dim = n_heads * 128, llm_dim = adaptor_heads * 128); the adaptor blocks' ffn is llm_dim / 4; n_encoders0 = 1. */
+typedef struct mia_sensevoice mia_sensevoice;
+typedef struct { int32_t input_dim, encoder_dim, n_heads, ffn_dim, kernel_size, sanm_shift,
+                 n_encoders0, n_encoders, n_tp_encoders;
+                 int32_t adaptor_k, llm_dim, adaptor_ffn_dim, adaptor_layers, adaptor_heads; } mia_sensevoice_config;
+/* float32 tensors under the reference's Module keys: audio_encoder.{encoders0,encoders,tp_encoders}.N.{norm1,norm2}.{weight,bias},
+ * ....self_attn.{linear_q_k_v,linear_out}.{weight,bias}, ....self_attn.fsmn_block.weight ([D][1][K] as in the checkpoint or [D][K][1] as
+ * FunASRModel.sanitize leaves it), ....feed_forward.{w_1,w_2}.{weight,bias}, audio_encoder.{after_norm,tp_norm}.{weight,bias},
+ * audio_adaptor.{linear1,linear2}.{weight,bias}, audio_adaptor.blocks.N.self_attn.{linear_q,linear_k,linear_v,linear_out}.{weight,bias},
+ * audio_adaptor.blocks.N.{norm1,norm2}.{weight,bias}, audio_adaptor.blocks.N.feed_forward.{w_1,w_2}.{weight,bias}.  Linear weights are
+ * rounded to `dtype` (MIA_BF16 | MIA_F16); norms, biases and FSMN taps stay fp32.  NULL on failure: mia_last_error(ctx) names the
+ * missing or mis-shaped tensor, or the config rule that failed (e.g. a sanm_shift that leaves a negative right context). */
+mia_sensevoice* mia_sensevoice_load(mia_ctx* ctx, const mia_sensevoice_config* cfg, const mia_tensor_view* tensors, int n_tensors, int dtype);
+void mia_sensevoice_free(mia_sensevoice* sv);
+/* preprocessAudio (STT/FunASR/FunASRAudio.swift:197-216) for B clips of 16 kHz float32 audio laid back to back (offs: HOST int64 [B+1],
+ * every clip longer than 200 samples): Hamming-window log-mel (1 + L/160 frames, natural log), LFR (7 frames stacked, every 6th kept:
+ * t_lfr = ceil(frames / 6)), per-utterance CMVN.  feats_out float32 [sum t_lfr][stride] (stride >= 560), the clips' rows back to back;
+ * t_lfr_out HOST int32 [B].  pcm / feats_out live in `mem`. */
+int mia_sensevoice_features(mia_ctx* ctx, const float* pcm, const int64_t* offs, int B, float* feats_out, int32_t* t_lfr_out, int64_t stride, int mem);
+/* Rows feats_out must hold for these clips (offs as above); < 0 on a bad argument. */
+int64_t mia_sensevoice_feature_rows(const int64_t* offs, int B);
+/* SenseVoiceEncoder + AudioAdaptor on B utterances stacked back to back: feats float32 [sum t_lfr[b]][input_dim]; t_lfr HOST int32 [B].
+ * enc_out (nullable, the test tap) float32 [sum t_lfr[b]][encoder_dim]: the encoder's output after tp_norm.  emb_out float32
+ * [sum n_out[b]][llm_dim] with n_out[b] = (t_lfr[b] - 1) / adaptor_k + 1 (HOST int32 [B]).  Every GEMM runs over all utterances at once;
+ * utterance b's rows equal its own B = 1 call bit for bit.  feats / enc_out / emb_out live in `mem`. */
+int mia_sensevoice_encode(mia_sensevoice* sv, const float* feats, const int32_t* t_lfr, int B, float* enc_out, float* emb_out, int32_t* n_out, int mem);
+/* mia_sensevoice_features -> mia_sensevoice_encode with nothing leaving the device in between: emb_out float32 [sum n_out[b]][llm_dim]
+ * (capacity: mia_sensevoice_feature_rows rows is always enough), n_out HOST int32 [B].  pcm / emb_out live in `mem`. */
+int mia_sensevoice_encode_audio(mia_sensevoice* sv, const float* pcm, const int64_t* offs, int B, float* emb_out, int32_t* n_out, int mem);
 
 /* ---- S3Tokenizer (speech -> 25 Hz token ids) ---------------------------------------------------- */
 /* S3TokenizerModelConfig / V3 (Codec/S3Tokenizer/S3TokenizerConfig.swift:9-90): V2 = 6 blocks, V3 = 12. */

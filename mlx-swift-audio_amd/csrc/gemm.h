@@ -5,7 +5,7 @@
 
 #include "../../include/mia.h"
 
-enum { MIA_ACT_NONE = 0, MIA_ACT_GELU = 1 };
+enum { MIA_ACT_NONE = 0, MIA_ACT_GELU = 1, MIA_ACT_RELU = 2 };   // RELU: the 128^2 kernels only (variants 3 / 4 are run as 1)
 enum { MIA_EPI_STD = 0, MIA_EPI_QKV_VT = 1, MIA_EPI_HEADMAJOR = 2 };
 
 // C[bz][m][n] = act(sum_k A[bz][m][k] * W[n][k] + bias[n]) + R[bz][m][n]

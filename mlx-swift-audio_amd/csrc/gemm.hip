@@ -25,7 +25,7 @@ constexpr int TILE_BYTES = BM * BK * 2;  // 16 KB per operand tile
 
 template <typename T>
 __device__ __forceinline__ float apply_act(float v, int act) {
-  return act == MIA_ACT_GELU ? gelu_erf(v) : v;
+  return act == MIA_ACT_GELU ? gelu_erf(v) : act == MIA_ACT_RELU ? fmaxf(v, 0.f) : v;
 }
 
 // Tile order inside the contiguous block-id range an XCD receives: groups of GROUP_M row-panels walked column-major, so the
@@ -859,6 +859,8 @@ int launch_t(const GemmArgs& g, hipStream_t s) {
   if (g.variant == 0) return launch_ts<T, 0>(g, s);
   if (g.variant == 1) return launch_ts<T, 1>(g, s);
   if (g.variant == 2) return launch_256<T>(g, s);
+  // ReLU lives in apply_act (variants 0 - 2); the 8-phase kernel selects GELU by template flag and has no ReLU form: auto and 4 take 1
+  if (g.act == MIA_ACT_RELU) return launch_ts<T, 1>(g, s);
   // the 8-phase kernel addresses A and W through 32-bit byte offsets from the (per-batch) base and needs two K-tiles
   const bool ok8 = g.K >= 2 * BK && (int64_t)g.M * g.lda * 2 < (1ll << 32) && (int64_t)g.N * g.K * 2 < (1ll << 32);
   if (g.variant == 4) return ok8 ? launch_8ph<T>(g, s) : launch_256<T>(g, s);
@@ -873,7 +875,7 @@ int launch_t(const GemmArgs& g, hipStream_t s) {
 
 static bool gemm_uses_8ph(const GemmArgs& g) {
   const bool ok8 = g.K >= 2 * BK && (int64_t)g.M * g.lda * 2 < (1ll << 32) && (int64_t)g.N * g.K * 2 < (1ll << 32);
-  if (!ok8) return false;
+  if (!ok8 || g.act == MIA_ACT_RELU) return false;
   if (g.variant == 4) return true;
   if (g.variant != 3) return false;
   // a LayerNorm hand-over pair runs on this kernel at EVERY size: its arithmetic (16-bit x * gamma operand, statistics applied in the
@@ -898,6 +900,7 @@ bool mia_gemm_ln_ok(const GemmArgs& g) {
 const char* mia_gemm_check(const GemmArgs& g) {
   if ((g.ln_gamma || g.ln_stat) && !mia_gemm_ln_ok(g)) return "gemm: the LayerNorm hand-over fields need the 8-phase kernel's row epilogues (mia_gemm_ln_ok)";
   if (g.M <= 0 || g.N <= 0 || g.K <= 0) return "gemm: M, N, K must be > 0";
+  if (g.act < MIA_ACT_NONE || g.act > MIA_ACT_RELU) return "gemm: act must be 0 (none), 1 (GELU) or 2 (ReLU)";
   if (g.K % BK != 0) return "gemm: K must be a multiple of 64";
   if (g.lda % 8 != 0) return "gemm: lda must be a multiple of 8 elements (16-byte rows)";
   if (((uintptr_t)g.A & 15) || ((uintptr_t)g.W & 15)) return "gemm: A and W must be 16-byte aligned";

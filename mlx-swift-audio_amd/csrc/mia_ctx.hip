@@ -51,6 +51,7 @@ extern "C" void mia_destroy(mia_ctx* ctx) {
   }
   for (void* p : ctx->table_allocs) (void)hipFree(p);
   if (ctx->s3gen_mel) free(ctx->s3gen_mel);
+  if (ctx->funasr_tables) free(ctx->funasr_tables);
   mia_resampler_free(ctx);
   for (auto& r : ctx->prof) { (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); }
   for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -107,7 +108,7 @@ void mia_prof_end(mia_ctx* ctx, int rec) {
   (void)hipEventRecord(ctx->prof[rec].stop, ctx->stream);
 }
 
-static const char* kProfNames[MIA_PROF_NCLASSES] = {"logmel", "enc_gemm", "enc_attention", "enc_norm", "decode", "crosskv_gemm", "mel_gather"};
+static const char* kProfNames[MIA_PROF_NCLASSES] = {"logmel", "enc_gemm", "enc_attention", "enc_norm", "decode", "crosskv_gemm", "mel_gather", "fsmn"};
 
 extern "C" int mia_profile_enable(mia_ctx* ctx, int on) {
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;

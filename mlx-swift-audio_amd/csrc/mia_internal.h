@@ -33,6 +33,7 @@ struct mia_ctx {
   std::vector<MelTables> mel_tables;
   std::vector<void*> table_allocs;   // other cached device tables (freed at destroy), e.g. the 24 kHz 80-mel front end
   void* s3gen_mel = nullptr;         // S3GenMelTables* (mel_s3gen.hip), lives in table_allocs' lifetime
+  void* funasr_tables = nullptr;     // Fun-ASR front-end tables (funasr_frontend.hip), malloc'ed; device parts in table_allocs
   mia_resampler_cache* resampler = nullptr;   // per-ratio polyphase filters of mia_resample_sinc (resample.hip); device tables in table_allocs
   // optional HIP-event profiling of kernel classes (mia_profile_*): bench.py's roofline figures come from here
   bool prof_on = false;
@@ -47,7 +48,7 @@ struct mia_ctx {
 };
 
 enum { MIA_PROF_LOGMEL = 0, MIA_PROF_ENC_GEMM = 1, MIA_PROF_ENC_ATTN = 2, MIA_PROF_ENC_NORM = 3, MIA_PROF_DECODE = 4,
-       MIA_PROF_CROSSKV_GEMM = 5, MIA_PROF_MEL_GATHER = 6, MIA_PROF_NCLASSES = 7 };
+       MIA_PROF_CROSSKV_GEMM = 5, MIA_PROF_MEL_GATHER = 6, MIA_PROF_FSMN = 7, MIA_PROF_NCLASSES = 8 };
 
 // RAII-less helpers: if profiling is on, bracket the launches between begin/end with events on the ctx stream
 int mia_prof_begin(mia_ctx* ctx, int cls, double work);   // returns record index or -1

@@ -32,3 +32,30 @@ struct AttnF32Args {
 };
 const char* mia_attn_f32_check(const AttnF32Args& a);
 int mia_attn_f32_launch(const AttnF32Args& a, hipStream_t s);
+
+// ---- attn128.hip (16-bit MFMA flash attention, d_h = 128, full attention) ---------------------------
+struct Attn128Args {
+  const void* q = nullptr; int64_t ldq = 0;     // 16-bit [B*T][ldq], head h in columns h*128 .. h*128+127
+  const void* k = nullptr; int64_t ldk = 0;
+  const void* v = nullptr; int64_t ldv = 0;
+  void* out = nullptr; int64_t ldo = 0;         // 16-bit [B*T][ldo]
+  int B = 1, T = 0, H = 0;
+  float scale = 0.08838834764831845f;           // d_k^-0.5
+  const int32_t* seq_len = nullptr;   // device [B], optional, AttnF32Args::seq_len's contract: keys at or beyond seq_len[b] are masked and a
+                                      // sequence's rows equal its own B = 1, T = seq_len[b] call bit for bit; rows beyond it are not written
+  int dtype = MIA_BF16;
+};
+const char* mia_attn128_check(const Attn128Args& a);
+int mia_attn128_launch(const Attn128Args& a, hipStream_t s);
+
+// ---- fsmn.hip (SANM memory: x += v + depthwise conv over time of v) -----------------------------------
+struct FsmnArgs {
+  float* x = nullptr; int64_t ldx = 0;          // fp32 residual stream [B*T][ldx]
+  const void* v = nullptr; int64_t ldv = 0;     // 16-bit values [B*T][ldv] (the v third of a fused q | k | v buffer: ldv = 3 D)
+  const float* w = nullptr;                     // taps [K][D]
+  int B = 1, T = 0, D = 0, K = 0, left = 0;     // tap k reads row t + k - left
+  const int32_t* seq_len = nullptr;             // device [B], optional: taps stop at the sequence's own length, rows beyond it are left alone
+  int dtype = MIA_BF16;
+};
+const char* mia_fsmn_check(const FsmnArgs& a);
+int mia_fsmn_launch(const FsmnArgs& a, hipStream_t s);

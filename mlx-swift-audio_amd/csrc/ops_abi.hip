@@ -64,6 +64,79 @@ extern "C" int mia_op_attention_f32(mia_ctx* ctx, const float* q, int64_t ldq, c
   return MIA_OK;
 }
 
+// 16-bit scaled-dot-product attention, head dim 128, full softmax (attn128.hip): q / k / v [B*T][ld] with head h in columns h*128.., out [B*T][ldo]
+// in `dtype`; seq_len int32 [B] or NULL.  Buffers live in `mem`; with host pointers every operand is copied on its own, so q, k and v may
+// be three views of one fused buffer.
+extern "C" int mia_op_attention_h128(mia_ctx* ctx, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out,
+                                     int64_t ldo, int B, int T, int H, float scale, const int32_t* seq_len, int dtype, int mem) {
+  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "op_attention_h128: bad mem");
+  MIA_CHECK_ARG(ctx, q && k && v && out && B > 0 && T > 0 && H > 0 && (int64_t)B * T < (1ll << 31), "op_attention_h128: bad argument");
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  Attn128Args a;
+  a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.B = B; a.T = T; a.H = H; a.scale = scale; a.dtype = dtype;
+  const int64_t rows = (int64_t)B * T, D = (int64_t)H * 128;
+  size_t ob = 0;
+  if (mem == MIA_MEM_DEVICE) {
+    a.q = q; a.k = k; a.v = v; a.out = out; a.seq_len = seq_len;
+  } else {
+    MIA_CHECK_ARG(ctx, ldq >= D && ldk >= D && ldv >= D && ldo >= D, "op_attention_h128: row strides must be >= H * 128");
+    const size_t qb = (size_t)((rows - 1) * ldq + D) * 2, kb = (size_t)((rows - 1) * ldk + D) * 2, vb = (size_t)((rows - 1) * ldv + D) * 2;
+    ob = (size_t)((rows - 1) * ldo + D) * 2;
+    const size_t o_k = align_up(qb, 256), o_v = o_k + align_up(kb, 256), o_o = o_v + align_up(vb, 256), o_s = o_o + align_up(ob, 256);
+    char* ws = (char*)mia_workspace(ctx, o_s + align_up((size_t)B * 4, 256));
+    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
+    MIA_HIP(ctx, hipMemcpyAsync(ws, q, qb, hipMemcpyHostToDevice, ctx->stream));
+    MIA_HIP(ctx, hipMemcpyAsync(ws + o_k, k, kb, hipMemcpyHostToDevice, ctx->stream));
+    MIA_HIP(ctx, hipMemcpyAsync(ws + o_v, v, vb, hipMemcpyHostToDevice, ctx->stream));
+    MIA_HIP(ctx, hipMemcpyAsync(ws + o_o, out, ob, hipMemcpyHostToDevice, ctx->stream));      // rows beyond seq_len keep the caller's bytes
+    if (seq_len) MIA_HIP(ctx, hipMemcpyAsync(ws + o_s, seq_len, (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
+    a.q = ws; a.k = ws + o_k; a.v = ws + o_v; a.out = ws + o_o; a.seq_len = seq_len ? (const int32_t*)(ws + o_s) : nullptr;
+  }
+  if (const char* e = mia_attn128_check(a)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
+  if (mia_attn128_launch(a, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_attention_h128: launch failed");
+  if (mem == MIA_MEM_HOST) {
+    MIA_HIP(ctx, hipMemcpyAsync(out, a.out, ob, hipMemcpyDeviceToHost, ctx->stream));
+    MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return MIA_OK;
+}
+
+// The SANM memory (fsmn.hip): x[t][c] += v[t][c] + sum_k w[k][c] v[t + k - left][c] per sequence of a [B][T] stack.
+extern "C" int mia_op_fsmn_add(mia_ctx* ctx, float* x, int64_t ldx, const void* v, int64_t ldv, const float* w, int B, int T, int D, int K, int left,
+                               const int32_t* seq_len, int dtype, int mem) {
+  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "op_fsmn_add: bad mem");
+  MIA_CHECK_ARG(ctx, x && v && w && B > 0 && T > 0 && D > 0 && K > 0 && (int64_t)B * T < (1ll << 31), "op_fsmn_add: bad argument");
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  FsmnArgs a;
+  a.ldx = ldx; a.ldv = ldv; a.B = B; a.T = T; a.D = D; a.K = K; a.left = left; a.dtype = dtype;
+  const int64_t rows = (int64_t)B * T;
+  size_t xb = 0;
+  if (mem == MIA_MEM_DEVICE) {
+    a.x = x; a.v = v; a.w = w; a.seq_len = seq_len;
+  } else {
+    MIA_CHECK_ARG(ctx, ldx >= D && ldv >= D, "op_fsmn_add: row strides must be >= D");
+    xb = (size_t)((rows - 1) * ldx + D) * 4;
+    const size_t vb = (size_t)((rows - 1) * ldv + D) * 2, wb = (size_t)K * D * 4;
+    const size_t o_v = align_up(xb, 256), o_w = o_v + align_up(vb, 256), o_s = o_w + align_up(wb, 256);
+    char* ws = (char*)mia_workspace(ctx, o_s + align_up((size_t)B * 4, 256));
+    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
+    MIA_HIP(ctx, hipMemcpyAsync(ws, x, xb, hipMemcpyHostToDevice, ctx->stream));
+    MIA_HIP(ctx, hipMemcpyAsync(ws + o_v, v, vb, hipMemcpyHostToDevice, ctx->stream));
+    MIA_HIP(ctx, hipMemcpyAsync(ws + o_w, w, wb, hipMemcpyHostToDevice, ctx->stream));
+    if (seq_len) MIA_HIP(ctx, hipMemcpyAsync(ws + o_s, seq_len, (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
+    a.x = (float*)ws; a.v = ws + o_v; a.w = (const float*)(ws + o_w); a.seq_len = seq_len ? (const int32_t*)(ws + o_s) : nullptr;
+  }
+  if (const char* e = mia_fsmn_check(a)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
+  if (mia_fsmn_launch(a, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_fsmn_add: launch failed");
+  if (mem == MIA_MEM_HOST) {
+    MIA_HIP(ctx, hipMemcpyAsync(x, a.x, xb, hipMemcpyDeviceToHost, ctx->stream));
+    MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return MIA_OK;
+}
+
 // The LM's single-token GQA attention over a cache it fills itself, without a model around it: K / V rows [Hkv][T][dh] (16 bit, taken
 // as already rotated) go through the prompt pass's cache writer -- lm_rope_cache, or lm_kvq_rope_cache for bits 4 | 8 (QuantizedKVCache,
 // TransformerBlock.swift:182-201) -- with all rotation angles zero, which leaves a 16-bit value unchanged; then the non-fused attention

@@ -350,6 +350,8 @@ LM_CONFIGS = {
     # The two micro shapes have n_heads * head_dim = 256 = 2 x hidden on purpose; qwen3-0.6b is for tools/bench_funasr_lm.py only.
     "qwen3-micro": LMConfig(3000, 128, 384, 2, 4, 2, 64, 256, 1e-6, 1e6, False, 1.0, 1.0, 4.0, 8192, False, True, True),
     "qwen3-micro128": LMConfig(3000, 128, 384, 2, 2, 1, 128, 256, 1e-6, 1e6, False, 1.0, 1.0, 4.0, 8192, False, True, True),
+    # hidden 256 = sensevoice-micro's llm_dim: the decoder of the micro Fun-ASR pipeline
+    "qwen3-micro256": LMConfig(3000, 256, 512, 2, 4, 2, 64, 256, 1e-6, 1e6, False, 1.0, 1.0, 4.0, 8192, False, True, True),
     "qwen3-0.6b": LMConfig(151936, 1024, 3072, 28, 16, 8, 128, 2048, 1e-6, 1e6, False, 1.0, 1.0, 4.0, 8192, False, True, True),
 }
 
@@ -678,4 +680,53 @@ def campplus_weights(seed: int = 0) -> dict[str, np.ndarray]:
     bn("out_nonlinear.0", ch)
     conv("dense.linear", (192, 1, 2 * ch))
     bn("dense.nonlinear.0", 192, affine=False)
+    return w
+
+
+# ---- Fun-ASR audio half (SenseVoice encoder + adaptor) --------------------------------------------------------------
+def sensevoice_weights(cfg, seed: int = 0, round_to: str | None = None) -> dict[str, np.ndarray]:
+    """Random-init SenseVoice encoder + audio adaptor under the reference's Module keys (funasr.SenseVoiceConfig).  Linear weights
+    N(0, 1 / fan_in), rounded to `round_to`; LayerNorm gains 1 + 0.1 N and biases 0.1 N (non-degenerate); FSMN taps 0.3 N in the
+    checkpoint's [D][1][K] layout, so the memory term is of the attention output's size."""
+    w: dict[str, np.ndarray] = {}
+
+    def t(name, shape, std, base=0.0):
+        rng = np.random.Generator(np.random.PCG64(_key_seed(name, seed)))
+        w[name] = (base + rng.standard_normal(shape, dtype=np.float32) * np.float32(std)).astype(np.float32)
+
+    def lin(p, o, i):
+        t(p + ".weight", (o, i), 1.0 / math.sqrt(i))
+        w[p + ".weight"] = round_array(w[p + ".weight"], round_to)
+        t(p + ".bias", (o,), 0.1)
+
+    def ln(p, d):
+        t(p + ".weight", (d,), 0.1, 1.0)
+        t(p + ".bias", (d,), 0.1)
+
+    def ffn(p, d, f):
+        lin(p + ".w_1", f, d)
+        lin(p + ".w_2", d, f)
+
+    D, L = cfg.encoder_dim, cfg.llm_dim
+    for stack, n in (("encoders0", cfg.n_encoders0), ("encoders", cfg.n_encoders), ("tp_encoders", cfg.n_tp_encoders)):
+        for i in range(n):
+            p = f"audio_encoder.{stack}.{i}"
+            din = cfg.input_dim if stack == "encoders0" and i == 0 else D
+            ln(p + ".norm1", din)
+            lin(p + ".self_attn.linear_q_k_v", 3 * D, din)
+            lin(p + ".self_attn.linear_out", D, D)
+            t(p + ".self_attn.fsmn_block.weight", (D, 1, cfg.kernel_size), 0.3)
+            ln(p + ".norm2", D)
+            ffn(p + ".feed_forward", D, cfg.ffn_dim)
+    ln("audio_encoder.after_norm", D)
+    ln("audio_encoder.tp_norm", D)
+    lin("audio_adaptor.linear1", cfg.adaptor_ffn_dim, D * cfg.adaptor_k)
+    lin("audio_adaptor.linear2", L, cfg.adaptor_ffn_dim)
+    for i in range(cfg.adaptor_layers):
+        p = f"audio_adaptor.blocks.{i}"
+        ln(p + ".norm1", L)
+        for nm in ("linear_q", "linear_k", "linear_v", "linear_out"):
+            lin(f"{p}.self_attn.{nm}", L, L)
+        ln(p + ".norm2", L)
+        ffn(p + ".feed_forward", L, L // 4)
     return w
