@@ -152,7 +152,8 @@ int mia_op_linear(mia_ctx* ctx, const void* x, int64_t lda, const void* w, const
 /* fp32 Conv1d / Linear, the contraction behind every MLXNN Conv1d / Linear of the codec, flow and vocoder stages
  * (e.g. Codec/S3Gen/S3GenDecoder.swift:40-48, Codec/S3Gen/Matcha/MatchaTransformer.swift:36-56), time-major, DEVICE pointers:
  *   y[t][n] = act(b[n] + sum_{k,c} x[t*stride + k*dil - pad][c] * w[n][k][c]) (+ r[t][n]);  x [T_in][ldx], w [N][taps][Cin] (Cin % 32 == 0),
- *   act 0 none / 1 exact-erf GELU / 2 ELU / 3 abs / 4 SiLU / 5 leaky-ReLU(0.01).  Rows outside [0, T_in) read as zero. */
+ *   act 0 none / 1 exact-erf GELU / 2 ELU / 3 abs / 4 SiLU / 5 leaky-ReLU(0.01) / 6 ReLU.  Rows outside [0, T_in) read as zero.
+ *   ldx % 4 == 0, ldx >= Cin, ldy >= N, x and w 16-byte aligned; anything else is MIA_ERR_INVALID_ARGUMENT. */
 int mia_op_conv1d_f32(mia_ctx* ctx, const float* x, int64_t ldx, int T_in, const float* w, const float* bias, const float* r, float* y,
                       int64_t ldy, int T_out, int N, int Cin, int taps, int stride, int dil, int pad, int act);
 
@@ -167,6 +168,48 @@ int mia_dequant_affine(mia_ctx* ctx, const uint32_t* wq, const void* scales, con
  * Codec/S3Gen/Matcha/MatchaTransformer.swift:58-66): q / k / v float32 [B*T][ld*] with head h in columns h*64 .. h*64+63. */
 int mia_op_attention_f32(mia_ctx* ctx, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, float* out,
                          int64_t ldo, int B, int T, int H, float scale);
+
+/* Test hook: the tap-structured fp32 GEMM behind mia_op_conv1d_f32 with every argument of its internal launch exposed, so each mode the
+ * codec, flow and vocoder programs use (transposed convolutions as output phases, snake / leaky-ReLU prologues, noise and residual
+ * epilogues, stacked sequences) can be compared with a reference on its own.  DEVICE pointers, enqueued on the context's stream.
+ * For grid phase z in [0, phases) and stacked sequence u in [0, n_seq):
+ *   Y[u*y_seq_step + row(m)][n] = epi( sum_{tap,c} pre(X[u*x_seq_step + z*x_phase_step + m*x_row_mul + tap*dil - pad][c])
+ *                                                  * W[z*w_phase_stride + n*ldw + tap*Cin + c] + bias[n] ),   m in [0, M), n in [0, N)
+ *   row(m) = m*y_row_mul + y_row_off + z*y_phase_step; rows outside [0, T_out) are dropped.  X rows (relative to the sequence / phase
+ *   base) outside [0, T_valid) read as zero, T_valid = min(T_in, seq_len[u]) | min(T_in, phase_len[z]) | T_in.
+ *   pre: alpha != NULL: snake x + ralpha[c] * sin^2(alpha[c] x), ralpha NULL -> 1 / (alpha[c] + 1e-9); else lrelu_slope > 0: leaky ReLU.
+ *   epi(v): v = act(v) (codes of mia_op_conv1d_f32, 6 = ReLU); noise ? v = R + noise[row] * v : v += R; out_scale != 0: v *= out_scale;
+ *   v += R2; tanh_out: v = tanh(v).  R / R2 have row stride ldr and Y's row mapping.  With n_seq > 1 and noise, sequence u's noise value
+ *   for row r is noise[noise_seq_off[u] + r] and rows at or past seq_len[u] are not written.
+ * Cin % 32 == 0, ldx % 4 == 0, ldx >= Cin, ldw == 0 (dense, taps*Cin) or a multiple of 4 >= taps*Cin; X and W 16-byte aligned. */
+typedef struct {
+  const float* X; int64_t ldx; int32_t T_in;
+  const float* W; int64_t ldw; int64_t w_phase_stride;
+  const float* bias;
+  const float* alpha; const float* ralpha;
+  float lrelu_slope;
+  float* Y; int64_t ldy; int32_t T_out;
+  int32_t y_row_mul, y_row_off, y_phase_step;
+  const float* R; const float* R2; int64_t ldr;
+  const float* noise;
+  float out_scale;
+  int32_t M, N, Cin, taps, dil, pad;
+  int32_t x_row_mul;
+  int32_t act;
+  int32_t tanh_out;
+  const int32_t* phase_len; int32_t x_phase_step;
+  int32_t n_seq; int64_t x_seq_step, y_seq_step;
+  const int32_t* seq_len; const int32_t* noise_seq_off;
+} mia_conv_gemm_desc;
+int mia_op_conv_gemm_f32(mia_ctx* ctx, const mia_conv_gemm_desc* d, int phases);
+
+/* Test hook: mia_op_attention_f32 with the remaining modes of the fp32 attention kernel.  p [T][ldp] (nullable) = positional keys shared
+ * by the batch, with bias_u / bias_v [H][64]: score(i, j) = ((q_i + u) . k_j + (q_i + v) . p_j) * scale (RelPositionMultiHeadedAttention,
+ * Codec/S3Gen/Transformer/Attention.swift:143-195).  seq_len int32 [B] (nullable): keys at or beyond seq_len[b] are masked, and sequence
+ * b's rows below it equal its own B = 1 call bit for bit.  chunk > 0: query i sees keys j < (i / chunk + 1) * chunk.  DEVICE pointers. */
+int mia_op_attention_f32_ex(mia_ctx* ctx, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const float* p,
+                            int64_t ldp, const float* bias_u, const float* bias_v, float* out, int64_t ldo, int B, int T, int H, float scale,
+                            const int32_t* seq_len, int chunk);
 
 /* 16-bit scaled-dot-product attention, head dim 128, full (non-causal) softmax in fp32 on the matrix cores: Fun-ASR's
  * MultiHeadAttentionSANM and FunASRMultiHeadAttention (STT/FunASR/Layers/MultiHeadAttentionSANM.swift:155-162, :245-251).

@@ -8,6 +8,7 @@
 
 // Tap-structured fp32 GEMM: Y[row(m)][n] = epi( sum_{tap,c} pre(X[m + tap*dil - pad][c]) * W[n][tap*Cin + c] + bias[n] )
 //   row(m) = m*y_row_mul + y_row_off + z*y_phase_step (rows outside [0,T_out) are dropped); z = grid.z phase, W += z*w_phase_stride
+// (mia_conv_gemm_desc in include/mia.h mirrors this struct field for field: the test hook mia_op_conv_gemm_f32 copies it and launches)
 struct ConvGemmArgs {
   const float* X = nullptr; int64_t ldx = 0; int T_in = 0;
   const float* W = nullptr; int64_t w_phase_stride = 0;

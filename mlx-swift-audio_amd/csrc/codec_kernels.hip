@@ -455,12 +455,15 @@ const char* codec_conv_gemm_check(const ConvGemmArgs& g) {
   if (g.M <= 0 || g.N <= 0 || g.Cin <= 0 || g.taps <= 0) return "conv_gemm: bad shape";
   if (g.Cin % 32) return "conv_gemm: Cin must be a multiple of 32";
   if (g.ldx % 4 || ((uintptr_t)g.X & 15) || ((uintptr_t)g.W & 15)) return "conv_gemm: X rows / W must be 16-byte aligned";
+  if (g.ldw && (g.ldw % 4 || g.ldw < (int64_t)g.taps * g.Cin)) return "conv_gemm: W row stride must be a multiple of 4 floats and cover taps * Cin";
   if (g.noise && !g.R) return "conv_gemm: noise modulation needs the residual input";
   if (g.n_seq < 1 || (g.n_seq > 1 && (g.x_seq_step < g.T_in || g.y_seq_step <= 0 || g.x_phase_step))) return "conv_gemm: bad stacked-sequence arguments";
   if ((g.n_seq > 1 && g.noise && !g.noise_seq_off) || (g.noise_seq_off && (!g.noise || !g.seq_len || g.y_row_mul != 1 || g.y_row_off || g.T_out != g.T_in)))
     return "conv_gemm: stacked noise needs noise_seq_off and seq_len on a row-for-row mapping";
-  if ((int64_t)g.M * g.x_row_mul + (int64_t)g.taps * g.dil > 0x7fffffffLL) return "conv_gemm: row index exceeds 31 bits";
-  if (((int64_t)g.M * g.x_row_mul + (int64_t)g.taps * g.dil + g.pad + g.T_in) * g.ldx > 0x7fffffffLL) return "conv_gemm: row offset exceeds 31 bits";
+  // the kernel's 32-bit row arithmetic runs over whole tiles (rows up to M rounded up to 128) and subtracts pad, which may be negative
+  const int64_t row_max = ((int64_t)g.M + 127) * g.x_row_mul + (int64_t)g.taps * g.dil + std::abs((int64_t)g.pad);
+  if (row_max > 0x7fffffffLL) return "conv_gemm: row index exceeds 31 bits";
+  if ((row_max + g.T_in) * g.ldx > 0x7fffffffLL) return "conv_gemm: row offset exceeds 31 bits";
   return nullptr;
 }
 

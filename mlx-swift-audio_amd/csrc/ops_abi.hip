@@ -38,6 +38,16 @@ extern "C" int mia_op_linear(mia_ctx* ctx, const void* x, int64_t lda, const voi
 
 // fp32 Conv1d / Linear on the exact-fp32 matrix cores (device pointers only): y[t][n] = act(b[n] + sum_{k,c} x[t*stride + k*dil - pad][c] w[n][k][c]) (+ r)
 #include "codec.h"
+// what the public fp32 GEMM entry points add to codec_conv_gemm_check: the kernel clamps row offsets, so its loads and stores stay inside
+// X / Y / R only when a row holds all Cin channels / N columns, and a public caller has no layer program in front of it that guarantees so
+static const char* conv_gemm_abi_check(const ConvGemmArgs& g, int phases) {
+  if (!g.X || !g.W || !g.Y) return "null pointer";
+  if (phases <= 0 || g.T_in <= 0 || g.T_out <= 0 || g.dil <= 0 || g.x_row_mul <= 0) return "bad argument";
+  if (g.ldx < g.Cin || g.ldy < g.N || ((g.R || g.R2) && g.ldr < g.N)) return "row strides must cover the row";
+  if (g.gelu < 0 || g.gelu > 6) return "unknown activation";
+  return nullptr;
+}
+
 extern "C" int mia_op_conv1d_f32(mia_ctx* ctx, const float* x, int64_t ldx, int T_in, const float* w, const float* bias, const float* r, float* y,
                                  int64_t ldy, int T_out, int N, int Cin, int taps, int stride, int dil, int pad, int act) {
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
@@ -46,22 +56,47 @@ extern "C" int mia_op_conv1d_f32(mia_ctx* ctx, const float* x, int64_t ldx, int 
   ConvGemmArgs g;
   g.X = x; g.ldx = ldx; g.T_in = T_in; g.W = w; g.bias = bias; g.Y = y; g.ldy = ldy; g.T_out = T_out; g.R = r; g.ldr = ldy;
   g.M = T_out; g.N = N; g.Cin = Cin; g.taps = taps; g.dil = dil; g.pad = pad; g.x_row_mul = stride; g.gelu = act;
+  if (const char* e = conv_gemm_abi_check(g, 1)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "op_conv1d_f32: %s", e);
   if (const char* e = codec_conv_gemm_check(g)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
   if (codec_conv_gemm_launch(g, 1, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_conv1d_f32: launch failed");
   return MIA_OK;
 }
 
-// fp32 scaled-dot-product attention, head dim 64, full (unmasked) softmax; device pointers (MLXFast.scaledDotProductAttention as used by
-// Codec/S3Gen/Matcha/MatchaTransformer.swift:58-66): q/k/v [B*T][ld] with head h in columns h*64.., out [B*T][ldo].
-extern "C" int mia_op_attention_f32(mia_ctx* ctx, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, float* out,
-                                    int64_t ldo, int B, int T, int H, float scale) {
+// the tap GEMM with every launch argument exposed (test hook; the formula is at the top of codec.h and in include/mia.h)
+extern "C" int mia_op_conv_gemm_f32(mia_ctx* ctx, const mia_conv_gemm_desc* d, int phases) {
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, d, "op_conv_gemm_f32: null descriptor");
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  ConvGemmArgs g;
+  g.X = d->X; g.ldx = d->ldx; g.T_in = d->T_in; g.W = d->W; g.ldw = d->ldw; g.w_phase_stride = d->w_phase_stride; g.bias = d->bias;
+  g.alpha = d->alpha; g.ralpha = d->ralpha; g.lrelu_slope = d->lrelu_slope; g.Y = d->Y; g.ldy = d->ldy; g.T_out = d->T_out;
+  g.y_row_mul = d->y_row_mul; g.y_row_off = d->y_row_off; g.y_phase_step = d->y_phase_step; g.R = d->R; g.R2 = d->R2; g.ldr = d->ldr;
+  g.noise = d->noise; g.out_scale = d->out_scale; g.M = d->M; g.N = d->N; g.Cin = d->Cin; g.taps = d->taps; g.dil = d->dil; g.pad = d->pad;
+  g.x_row_mul = d->x_row_mul; g.gelu = d->act; g.tanh_out = d->tanh_out; g.phase_len = d->phase_len; g.x_phase_step = d->x_phase_step;
+  g.n_seq = d->n_seq; g.x_seq_step = d->x_seq_step; g.y_seq_step = d->y_seq_step; g.seq_len = d->seq_len; g.noise_seq_off = d->noise_seq_off;
+  if (const char* e = conv_gemm_abi_check(g, phases)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "op_conv_gemm_f32: %s", e);
+  return codec_conv_gemm_run(ctx, g, phases, "op_conv_gemm_f32");
+}
+
+// fp32 attention, head dim 64, with every mode of attn_f32.hip (test hook): positional keys p with bias_u / bias_v, seq_len, chunk; device
+// pointers, q/k/v [B*T][ld] with head h in columns h*64.., out [B*T][ldo]
+extern "C" int mia_op_attention_f32_ex(mia_ctx* ctx, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                       const float* p, int64_t ldp, const float* bias_u, const float* bias_v, float* out, int64_t ldo, int B, int T,
+                                       int H, float scale, const int32_t* seq_len, int chunk) {
+  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, chunk >= 0 && (int64_t)B * T < (1ll << 31), "op_attention_f32: bad argument");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   AttnF32Args a;
   a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldk; a.v = v; a.ldv = ldv; a.out = out; a.ldo = ldo; a.B = B; a.T = T; a.H = H; a.scale = scale;
-  if (const char* e = mia_attn_f32_check(a)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
+  a.p = p; a.ldp = ldp; a.bias_u = bias_u; a.bias_v = bias_v; a.seq_len = seq_len; a.chunk = chunk;
+  if (const char* e = mia_attn_f32_check(a)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);     // B, T, H > 0 and the null checks live there
   if (mia_attn_f32_launch(a, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_attention_f32: launch failed");
   return MIA_OK;
+}
+// full (unmasked) softmax (MLXFast.scaledDotProductAttention as used by Codec/S3Gen/Matcha/MatchaTransformer.swift:58-66)
+extern "C" int mia_op_attention_f32(mia_ctx* ctx, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, float* out,
+                                    int64_t ldo, int B, int T, int H, float scale) {
+  return mia_op_attention_f32_ex(ctx, q, ldq, k, ldk, v, ldv, nullptr, 0, nullptr, nullptr, out, ldo, B, T, H, scale, nullptr, 0);
 }
 
 // 16-bit scaled-dot-product attention, head dim 128, full softmax (attn128.hip): q / k / v [B*T][ld] with head h in columns h*128.., out [B*T][ldo]

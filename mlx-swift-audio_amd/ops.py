@@ -90,3 +90,124 @@ def kvq_attention(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.ndarray
     out = np.empty((Hq, dh), np.float32)
     ctx.check(lib.mia_op_kvq_attention(ctx.h, q16.ctypes.data, k16.ctypes.data, v16.ctypes.data, out.ctypes.data, Hq, Hkv, T, dh, int(bits), dtype))
     return out
+
+
+# ---- fp32 tap GEMM and fp32 attention (device pointers; the test hooks expose every launch argument) -------------------------------
+class ConvGemmDesc(C.Structure):
+    """mia_conv_gemm_desc (include/mia.h), field for field."""
+    _fields_ = [("X", C.c_void_p), ("ldx", C.c_int64), ("T_in", C.c_int32),
+                ("W", C.c_void_p), ("ldw", C.c_int64), ("w_phase_stride", C.c_int64),
+                ("bias", C.c_void_p), ("alpha", C.c_void_p), ("ralpha", C.c_void_p), ("lrelu_slope", C.c_float),
+                ("Y", C.c_void_p), ("ldy", C.c_int64), ("T_out", C.c_int32),
+                ("y_row_mul", C.c_int32), ("y_row_off", C.c_int32), ("y_phase_step", C.c_int32),
+                ("R", C.c_void_p), ("R2", C.c_void_p), ("ldr", C.c_int64), ("noise", C.c_void_p), ("out_scale", C.c_float),
+                ("M", C.c_int32), ("N", C.c_int32), ("Cin", C.c_int32), ("taps", C.c_int32), ("dil", C.c_int32), ("pad", C.c_int32),
+                ("x_row_mul", C.c_int32), ("act", C.c_int32), ("tanh_out", C.c_int32),
+                ("phase_len", C.c_void_p), ("x_phase_step", C.c_int32),
+                ("n_seq", C.c_int32), ("x_seq_step", C.c_int64), ("y_seq_step", C.c_int64),
+                ("seq_len", C.c_void_p), ("noise_seq_off", C.c_void_p)]
+
+
+_DESC_F32 = ("X", "W", "bias", "alpha", "ralpha", "Y", "R", "R2", "noise")
+_DESC_I32 = ("phase_len", "seq_len", "noise_seq_off")
+_DESC_DEFAULTS = dict(y_row_mul=1, dil=1, taps=1, x_row_mul=1, n_seq=1)
+
+
+def _declare_f32(lib):
+    if getattr(lib, "_f32_ops_declared", False):
+        return
+    vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
+    lib.mia_op_conv1d_f32.restype = i32
+    lib.mia_op_conv1d_f32.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, i64] + [i32] * 8
+    lib.mia_op_conv_gemm_f32.restype = i32
+    lib.mia_op_conv_gemm_f32.argtypes = [vp, C.POINTER(ConvGemmDesc), i32]
+    lib.mia_op_attention_f32.restype = i32
+    lib.mia_op_attention_f32.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, f32]
+    lib.mia_op_attention_f32_ex.restype = i32
+    lib.mia_op_attention_f32_ex.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, i32, f32, vp, i32]
+    lib._f32_ops_declared = True
+
+
+def _dev(a, np_dtype=np.float32):
+    """A torch CUDA tensor as it is (views included: its data_ptr and row stride are what the op sees), a numpy array uploaded."""
+    import torch
+    if a is None:
+        return None
+    if isinstance(a, torch.Tensor):
+        assert a.is_cuda, "device tensors only"
+        return a
+    return torch.from_numpy(np.ascontiguousarray(a, np_dtype)).cuda()
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _ld(t, ld):
+    return int(ld) if ld is not None else (int(t.stride(0)) if t is not None and t.dim() == 2 else 0)
+
+
+def _run(ctx, call):
+    """torch's uploads are complete before the op is enqueued on the context's stream, and the op before the result is read."""
+    import torch
+    torch.cuda.synchronize()
+    try:
+        ctx.check(call())
+    finally:
+        ctx.synchronize()
+
+
+def conv1d_f32(ctx: _lib.Context, x, w, y, *, Cin: int, taps: int = 1, stride: int = 1, dil: int = 1, pad: int = 0, act: int = 0, bias=None,
+               r=None, T_in: int | None = None, T_out: int | None = None, N: int | None = None, ldx: int | None = None,
+               ldy: int | None = None) -> np.ndarray:
+    """mia_op_conv1d_f32: x [T_in, ldx], w [N, taps*Cin], y [rows, ldy] (its contents are what unwritten elements keep; a device tensor is written in place), r in
+    y's layout.  Returns y's whole buffer."""
+    _declare_f32(ctx.lib)
+    dx, dw, dy, db, dr = _dev(x), _dev(w), _dev(y), _dev(bias), _dev(r)
+    _run(ctx, lambda: ctx.lib.mia_op_conv1d_f32(ctx.h, _ptr(dx), _ld(dx, ldx), int(dx.shape[0] if T_in is None else T_in), _ptr(dw), _ptr(db),
+                                                 _ptr(dr), _ptr(dy), _ld(dy, ldy), int(dy.shape[0] if T_out is None else T_out),
+                                                 int(dw.shape[0] if N is None else N), int(Cin), int(taps), int(stride), int(dil), int(pad), int(act)))
+    return dy.cpu().numpy()
+
+
+def conv_gemm_f32(ctx: _lib.Context, phases: int = 1, **d) -> np.ndarray:
+    """mia_op_conv_gemm_f32: keyword arguments are the fields of mia_conv_gemm_desc, arrays for its pointers (X, Y, R, R2 two-dimensional:
+    ldx / ldy / ldr default to their row strides; Y's contents are what unwritten elements keep, a device tensor is written in place).
+    Returns Y's whole buffer."""
+    _declare_f32(ctx.lib)
+    unknown = set(d) - {n for n, _ in ConvGemmDesc._fields_}
+    assert not unknown, f"not a mia_conv_gemm_desc field: {sorted(unknown)}"
+    t = {k: _dev(d.get(k)) for k in _DESC_F32}
+    t.update({k: _dev(d.get(k), np.int32) for k in _DESC_I32})
+    desc = ConvGemmDesc()
+    for name, _ in ConvGemmDesc._fields_:
+        if name in t:
+            setattr(desc, name, _ptr(t[name]))
+        elif name in ("ldx", "ldy", "ldr"):
+            setattr(desc, name, _ld(t[{"ldx": "X", "ldy": "Y", "ldr": "R"}[name]] if name != "ldr" or t["R"] is not None else t["R2"], d.get(name)))
+        else:
+            setattr(desc, name, d.get(name, _DESC_DEFAULTS.get(name, 0)))
+    _run(ctx, lambda: ctx.lib.mia_op_conv_gemm_f32(ctx.h, C.byref(desc), int(phases)))
+    return None if t["Y"] is None else t["Y"].cpu().numpy()
+
+
+def attention_f32_ex(ctx: _lib.Context, q, k, v, out, B: int, T: int, H: int, scale: float = 0.125, p=None, bias_u=None, bias_v=None,
+                     seq_len=None, chunk: int = 0, ldq=None, ldk=None, ldv=None, ldp=None, ldo=None, plain: bool = False) -> np.ndarray:
+    """mia_op_attention_f32_ex (plain: mia_op_attention_f32): q / k / v [B*T, ld] (three views of one fused device buffer are fine), head h
+    in columns h*64..; out [B*T, ldo], its contents are what unwritten elements keep (a device tensor is written in place).  Returns out's whole buffer."""
+    _declare_f32(ctx.lib)
+    dq, dk, dv, do, dp, du, dbv = _dev(q), _dev(k), _dev(v), _dev(out), _dev(p), _dev(bias_u), _dev(bias_v)
+    ds = _dev(seq_len, np.int32)
+    head = (ctx.h, _ptr(dq), _ld(dq, ldq), _ptr(dk), _ld(dk, ldk), _ptr(dv), _ld(dv, ldv))
+    if plain:
+        assert p is None and seq_len is None and not chunk
+        _run(ctx, lambda: ctx.lib.mia_op_attention_f32(*head, _ptr(do), _ld(do, ldo), int(B), int(T), int(H), float(scale)))
+    else:
+        _run(ctx, lambda: ctx.lib.mia_op_attention_f32_ex(*head, _ptr(dp), _ld(dp, ldp), _ptr(du), _ptr(dbv), _ptr(do), _ld(do, ldo), int(B), int(T),
+                                                           int(H), float(scale), _ptr(ds), int(chunk)))
+    return do.cpu().numpy()
+
+
+def attention_f32(ctx: _lib.Context, q, k, v, out, B: int, T: int, H: int, scale: float = 0.125, **ld) -> np.ndarray:
+    """mia_op_attention_f32: full softmax(q k^T scale) v per head, head dim 64; see attention_f32_ex."""
+    return attention_f32_ex(ctx, q, k, v, out, B, T, H, scale, plain=True, **ld)
