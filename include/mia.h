@@ -241,6 +241,14 @@ int mia_op_funasr_logmel(mia_ctx* ctx, const float* pcm, const int64_t* offs, in
 int mia_op_kvq_attention(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int dh, int bits,
                          int dtype);
 
+/* The prompt pass's tiled causal grouped-query attention (lm_prefill_attn.hip, see mia_lm_set_prompt_attention) without a model around
+ * it.  k / v [Hkv][T][dh] in `dtype` (MIA_BF16 | MIA_F16; rows taken as already rotated) go through the prompt pass's 16-bit cache
+ * writer; q [n][Hq][dh] holds the rows at positions T - n .. T - 1, and the row at position p attends to keys [0, p] (n < T: queries
+ * that start behind cached keys).  out fp32 [n][Hq][dh]: the kernel's 16-bit output widened.  HOST pointers.  dh 64 | 128,
+ * Hq % Hkv == 0, 1 <= n <= T <= 8192; anything else is MIA_ERR_INVALID_ARGUMENT, another head_dim MIA_ERR_UNSUPPORTED. */
+int mia_op_lm_prompt_attention(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int n, int dh,
+                               int dtype);
+
 /* ---- Whisper ---------------------------------------------------------------------------------- */
 /* Model dimensions == ModelDimensions (STT/Whisper/Config/WhisperConfig.swift:9-86), read by the caller
  * from config.json. */
@@ -541,6 +549,15 @@ int mia_lm_use_q4(mia_lm* lm, int on);
 /* Test hook: bit 0 = launch every step's kernels directly (no hipGraph), bit 1 = feed prompts token by token (no batched prompt
  * pass).  Results agree up to fp32 summation order. */
 int mia_lm_set_debug(mia_lm* lm, int flags);
+/* Which attention kernel the batched prompt pass runs (every entry point that feeds a prompt: mia_lm_forward, mia_lm_generate and its
+ * batch / RAS / greedy forms).  0 (default): the single-token kernel, one workgroup per (query head, prompt row).  1: the tiled causal
+ * grouped-query kernel of lm_prefill_attn.hip -- Q K^T and P V on the matrix cores, the query heads of a KV group sharing each staged
+ * K / V tile -- for every run on the 16-bit cache; meant for long prompts (OuteTTS repeats its ~1 900-token speaker profile for every
+ * sentence, TTS/OuteTTS/OuteTTS.swift:327-340).  With mia_lm_set_kv_quant(bits != 0) active the prompt pass keeps the packed cache's row
+ * kernel whatever the mode; the decode step is the same in both modes.  The modes agree to the 16-bit rounding of the attention
+ * probabilities, not bit for bit; within mode 1 a row's result does not depend on the chunk or batch it sits in.  Any other mode:
+ * MIA_ERR_INVALID_ARGUMENT. */
+int mia_lm_set_prompt_attention(mia_lm* lm, int mode);
 void mia_lm_free(mia_lm* lm);
 int mia_lm_reset(mia_lm* lm);
 /* model(ids, cache) then logits[0,-1] (OrpheusTTS.swift:245-251,289): appends n ids to the KV cache, returns the fp32

@@ -1,6 +1,6 @@
 // lm.h -- host-side interface between the LM decode sources: lm.hip (step kernels, prompt pass, step graph, entry points),
 // lm_sample.hip (the top-p, RAS and greedy samplers), lm_load.hip (checkpoint loader, state buffers, packed-weight attach) and lm_kvq.hip
-// (the quantised KV cache: its prompt-pass quantiser and its attention).
+// (the quantised KV cache: its prompt-pass quantiser and its attention); lm_prefill_attn.hip (the prompt pass's tiled causal attention) reads it too.
 #pragma once
 #include <vector>
 
@@ -67,6 +67,7 @@ struct mia_lm {
   hipGraphExec_t graph = nullptr;       // one decode step (forward / top-p / RAS / greedy sampler), re-captured when its sampler arguments change
   int graph_mode = -1;                  // LM_STEP_* below
   int debug_flags = 0;                  // test hook (mia_lm_set_debug): bit 0 = no hipGraph, bit 1 = no batched prompt pass
+  int prompt_attn = 0;                  // mia_lm_set_prompt_attention: 0 = the row kernel (lm_attention), 1 = lm_prefill_attn.hip on the 16-bit cache
   mia_lm_sampler graph_sampler{};
   RasParams graph_ras{};
   int S_qkv = 1, S_o = 1, S_down = 1;
@@ -120,6 +121,23 @@ void lm_kvq_launch_attention(hipStream_t s, const LmKvq& a, bool fused, int rows
                              const float* bias);
 // host: n_rows packed rows -> fp32 [n_rows][dh] (scale * code + bias)
 void lm_kvq_read_rows(const uint32_t* codes, const uint32_t* pairs, int64_t n_rows, int dh, int bits, int dtype, float* out);
+
+// ---- lm_prefill_attn.hip: tiled causal GQA attention of a prompt-pass chunk over one layer's 16-bit cache ----
+struct LmPromptAttn {
+  const uint16_t* q = nullptr;            // [M][Hq * dh], rotated
+  const uint16_t* kc = nullptr; const uint16_t* vc = nullptr;   // the layer's caches [B_cap][Hkv][max_ctx][dh], the chunk's rows already written
+  uint16_t* out = nullptr;                // [M][Hq * dh]
+  const int4* tiles = nullptr; int n_tiles = 0;   // device: (sequence, first position, first row, positions <= query tile) per query tile
+  int Hq = 0, Hkv = 0, dh = 0, max_ctx = 0;
+  int64_t seq_stride = 0;                 // Hkv * max_ctx * dh
+  int dtype = MIA_BF16;
+};
+// positions per query tile for this head grouping (128, 64 or 32)
+int lm_prefill_attn_qtile(int Hq, int Hkv);
+// the chunk's rows (every sequence's positions ascending and contiguous) cut into runs and the runs into query tiles
+void lm_prefill_attn_tiles(const int2* rows, int M, int qtile, std::vector<int4>& tiles);
+const char* lm_prefill_attn_check(const LmPromptAttn& a);
+int lm_prefill_attn_launch(const LmPromptAttn& a, hipStream_t s);
 
 // ---- lm_load.hip ----
 // every per-sequence buffer, for B sequences side by side (rows of the skinny GEMMs; caches [L][B][Hkv][max_ctx][dh]); drops the step graph

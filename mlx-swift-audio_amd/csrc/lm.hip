@@ -10,7 +10,8 @@
 // kernel); RMSNorm / RoPE / KV-cache write / GQA attention / SwiGLU / sampling are fused around it; one hipGraph per token.
 // The prompt is consumed one position per step through the same graph (identical maths to a causal prefill).
 // This file: the step's row kernels next to their launch sites, the batched prompt pass, the step graph and the entry points; the
-// loader and the packed-weight attach are lm_load.hip, and lm.h is what the three sources share.
+// loader and the packed-weight attach are lm_load.hip, the prompt pass's optional tiled attention is lm_prefill_attn.hip
+// (mia_lm_set_prompt_attention), and lm.h is what the sources share.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -495,10 +496,10 @@ int lm_prefill_rows(mia_lm* m, const std::vector<int2>& rows, const std::vector<
   const bool f16 = m->dtype == MIA_F16;
   const size_t b_x = align_up((size_t)PF_ROWS * D * 4, 256), b_h = align_up((size_t)PF_ROWS * D * 2, 256), b_qkv = align_up((size_t)PF_ROWS * Nqkv * 4, 256),
                b_q = align_up((size_t)PF_ROWS * Nq * 2, 256), b_gu = align_up((size_t)PF_ROWS * 2 * I * 4, 256), b_act = align_up((size_t)PF_ROWS * I * 2, 256),
-               b_map = align_up((size_t)PF_ROWS * sizeof(int2), 256);
+               b_map = align_up((size_t)PF_ROWS * sizeof(int2), 256), b_tiles = align_up((size_t)PF_ROWS * sizeof(int4), 256);
   if (!m->pf_buf) {
     void* p = nullptr;
-    if (hipMalloc(&p, b_x + b_h + b_qkv + 2 * b_q + b_gu + b_act + b_map) != hipSuccess) return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "lm: prompt-pass buffers");
+    if (hipMalloc(&p, b_x + b_h + b_qkv + 2 * b_q + b_gu + b_act + b_map + b_tiles) != hipSuccess) return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "lm: prompt-pass buffers");
     m->allocs.push_back(p); m->pf_buf = (char*)p;
   }
   char* b = m->pf_buf;
@@ -509,7 +510,12 @@ int lm_prefill_rows(mia_lm* m, const std::vector<int2>& rows, const std::vector<
   uint16_t* att = (uint16_t*)b; b += b_q;
   float* gu = (float*)b; b += b_gu;
   uint16_t* act = (uint16_t*)b; b += b_act;
-  int2* rowmap = (int2*)b;
+  int2* rowmap = (int2*)b; b += b_map;
+  int4* tiles = (int4*)b;                          // query tiles of the chunk (prompt_attn 1 only)
+  // mia_lm_set_prompt_attention(1): the chunk's attention is lm_prefill_attn.hip's tiled kernel; the packed cache keeps lm_kvq's row kernel
+  const bool tiled = m->prompt_attn == 1 && !m->kv_bits;
+  const int qtile = lm_prefill_attn_qtile(c.n_heads, c.n_kv_heads);
+  std::vector<std::vector<int4>> chunk_tiles(tiled ? (rows.size() + PF_ROWS - 1) / PF_ROWS : 0);    // alive until the call returns, like `rows`
   auto gemm = [&](const void* A, int K, const void* W, const float* bias, float* C, int N, int M, const float* R) {
     GemmArgs g;
     g.A = A; g.lda = K; g.W = W; g.bias = bias; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K; g.out_f32 = 1;
@@ -524,12 +530,24 @@ int lm_prefill_rows(mia_lm* m, const std::vector<int2>& rows, const std::vector<
     MIA_HIP(ctx, hipMemcpyAsync(rowmap, rows.data() + r0, (size_t)M * sizeof(int2), hipMemcpyHostToDevice, s));
     LAUNCH_T(lm_embed_norm, dim3(M), dim3(256), 0, m->tokens, (const uint16_t*)m->embed, (const uint16_t*)m->gen_embed, m->embeds, m->layers[0].in_norm, x, h,
              m->state, D, c.rms_eps, (const int2*)rowmap, c.max_ctx, c.vocab, m->gen_rows);
+    LmPromptAttn pa;
+    if (tiled) {
+      std::vector<int4>& t = chunk_tiles[r0 / PF_ROWS];
+      lm_prefill_attn_tiles(rows.data() + r0, M, qtile, t);
+      MIA_HIP(ctx, hipMemcpyAsync(tiles, t.data(), t.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+      pa.q = q; pa.out = att; pa.tiles = tiles; pa.n_tiles = (int)t.size(); pa.Hq = c.n_heads; pa.Hkv = c.n_kv_heads; pa.dh = dh; pa.max_ctx = c.max_ctx;
+      pa.seq_stride = (int64_t)c.n_kv_heads * c.max_ctx * dh; pa.dtype = m->dtype;
+    }
     for (int l = 0; l < c.n_layers; ++l) {
       const LmLayer& L = m->layers[l];
       if (gemm(h, D, L.wqkv, nullptr, qkv, Nqkv, M, nullptr)) return MIA_ERR_DEVICE;
       lm_launch_rope_cache(m, l, qkv, L.bqkv, q, rowmap, M);
       if (l + 1 == c.n_layers) break;            // past its K/V rows the last layer feeds only the head, which the prompt pass skips
-      lm_launch_attention(m, false, M, q, l, att, rowmap, nullptr, 0, nullptr);
+      if (tiled) {
+        pa.kc = (const uint16_t*)m->k_cache + (size_t)l * m->B_cap * pa.seq_stride; pa.vc = (const uint16_t*)m->v_cache + (size_t)l * m->B_cap * pa.seq_stride;
+        if (const char* e = lm_prefill_attn_check(pa)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
+        if (lm_prefill_attn_launch(pa, s)) return mia_fail(ctx, MIA_ERR_DEVICE, "lm: prompt attention launch failed");
+      } else lm_launch_attention(m, false, M, q, l, att, rowmap, nullptr, 0, nullptr);
       if (gemm(att, Nq, L.wo, nullptr, x, D, M, x)) return MIA_ERR_DEVICE;                // x += att . Wo^T
       LAUNCH_T(lm_reduce_norm, dim3(M), dim3(256), 0, (const float*)nullptr, 0, L.post_norm, x, h, D, c.rms_eps, 1);
       if (gemm(h, D, L.wgu, nullptr, gu, 2 * I, M, nullptr)) return MIA_ERR_DEVICE;
@@ -579,6 +597,15 @@ extern "C" int mia_lm_set_debug(mia_lm* m, int flags) {
   if (!m) return MIA_ERR_MODEL_NOT_LOADED;
   MIA_CHECK_ARG(m->ctx, flags >= 0 && flags <= 3, "lm_set_debug: flags must be 0..3 (got %d)", flags);
   m->debug_flags = flags;
+  return MIA_OK;
+}
+
+// which attention the batched prompt pass runs on the 16-bit cache: 0 = lm_attention, one workgroup per (query head, row) -- the default;
+// 1 = lm_prefill_attn.hip's tiled matrix-core kernel.  The step graph and the packed cache's prompt pass are not affected.
+extern "C" int mia_lm_set_prompt_attention(mia_lm* m, int mode) {
+  if (!m) return MIA_ERR_MODEL_NOT_LOADED;
+  MIA_CHECK_ARG(m->ctx, mode == 0 || mode == 1, "lm_set_prompt_attention: mode must be 0 or 1 (got %d)", mode);
+  m->prompt_attn = mode;
   return MIA_OK;
 }
 

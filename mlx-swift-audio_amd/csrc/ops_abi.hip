@@ -238,3 +238,69 @@ extern "C" int mia_op_kvq_attention(mia_ctx* ctx, const void* q, const void* k, 
   for (int i = 0; i < Nq; ++i) out[i] = widen(att[i]);
   return MIA_OK;
 }
+
+// lm_prefill_attn.hip without a model around it: K / V rows [Hkv][T][dh] (16 bit, taken as already rotated) go through the prompt pass's
+// 16-bit cache writer (lm_rope_cache with all rotation angles zero, which leaves a 16-bit value unchanged), then the tiled kernel runs the
+// q rows [n][Hq][dh] at positions T - n .. T - 1, each over keys [0, its position].  out fp32 [n][Hq][dh].  Host pointers.
+extern "C" int mia_op_lm_prompt_attention(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int n, int dh, int dtype) {
+  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, q && k && v && out, "op_lm_prompt_attention: null pointer");
+  MIA_CHECK_ARG(ctx, dtype == MIA_BF16 || dtype == MIA_F16, "op_lm_prompt_attention: dtype must be MIA_BF16 or MIA_F16");
+  MIA_CHECK_ARG(ctx, Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq <= 1024 && n >= 1 && n <= T && T <= 8192, "op_lm_prompt_attention: bad shape (Hq %% Hkv == 0, 1 <= n <= T <= 8192)");
+  if (dh != 64 && dh != 128) return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "op_lm_prompt_attention: head_dim %d (64 or 128)", dh);
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  const int Nq = Hq * dh, Nk = Hkv * dh, N = Nq + 2 * Nk;
+  auto widen = [&](uint16_t x) -> float {
+    if (dtype == MIA_F16) { _Float16 h; memcpy(&h, &x, 2); return (float)h; }
+    const uint32_t u = (uint32_t)x << 16; float f; memcpy(&f, &u, 4); return f;
+  };
+  // the q|k|v rows a prompt pass would hand the cache writer: row t = [q (last n rows only) | K[.][t] | V[.][t]]
+  std::vector<float> part((size_t)T * N, 0.f);
+  std::vector<int2> rowmap(T);
+  const uint16_t* q16 = (const uint16_t*)q; const uint16_t* k16 = (const uint16_t*)k; const uint16_t* v16 = (const uint16_t*)v;
+  for (int r = 0; r < n; ++r)
+    for (int i = 0; i < Nq; ++i) part[(size_t)(T - n + r) * N + i] = widen(q16[(size_t)r * Nq + i]);
+  for (int t = 0; t < T; ++t) {
+    rowmap[t] = make_int2(0, t);
+    for (int h = 0; h < Hkv; ++h)
+      for (int d = 0; d < dh; ++d) {
+        part[(size_t)t * N + Nq + h * dh + d] = widen(k16[((size_t)h * T + t) * dh + d]);
+        part[(size_t)t * N + Nq + Nk + h * dh + d] = widen(v16[((size_t)h * T + t) * dh + d]);
+      }
+  }
+  std::vector<int4> tiles;
+  lm_prefill_attn_tiles(rowmap.data() + (T - n), n, lm_prefill_attn_qtile(Hq, Hkv), tiles);     // rows 0 .. n - 1 of q / att below
+  const size_t b_part = align_up(part.size() * 4, 256), b_map = align_up((size_t)T * sizeof(int2), 256), b_freq = align_up((size_t)dh / 2 * 4, 256),
+               b_q = align_up((size_t)T * Nq * 2, 256), b_att = align_up((size_t)n * Nq * 2, 256), b_tiles = align_up(tiles.size() * sizeof(int4), 256),
+               b_cache = align_up((size_t)Hkv * T * dh * 2, 256);
+  char* ws = (char*)mia_workspace(ctx, b_part + b_map + b_freq + b_q + b_att + b_tiles + 2 * b_cache);
+  if (!ws) return MIA_ERR_OUT_OF_MEMORY;
+  hipStream_t s = ctx->stream;
+  char* p = ws;
+  float* d_part = (float*)p; p += b_part;
+  int2* d_map = (int2*)p; p += b_map;
+  float* d_freq = (float*)p; p += b_freq;
+  uint16_t* d_q = (uint16_t*)p; p += b_q;
+  uint16_t* d_att = (uint16_t*)p; p += b_att;
+  int4* d_tiles = (int4*)p; p += b_tiles;
+  char* d_kc = p; p += b_cache;
+  char* d_vc = p;
+  MIA_HIP(ctx, hipMemcpyAsync(d_part, part.data(), part.size() * 4, hipMemcpyHostToDevice, s));
+  MIA_HIP(ctx, hipMemcpyAsync(d_map, rowmap.data(), (size_t)T * sizeof(int2), hipMemcpyHostToDevice, s));
+  MIA_HIP(ctx, hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+  MIA_HIP(ctx, hipMemsetAsync(d_freq, 0, b_freq + b_q + b_att, s));
+  mia_lm sh;                      // a bare handle: what the cache writer reads of one
+  sh.ctx = ctx; sh.dtype = dtype; sh.B_cap = 1; sh.inv_freq = d_freq; sh.k_cache = d_kc; sh.v_cache = d_vc;
+  sh.cfg.n_layers = 1; sh.cfg.n_heads = Hq; sh.cfg.n_kv_heads = Hkv; sh.cfg.head_dim = dh; sh.cfg.max_ctx = T;
+  lm_launch_rope_cache(&sh, 0, d_part, nullptr, d_q, d_map, T);
+  LmPromptAttn a;
+  a.q = d_q + (size_t)(T - n) * Nq; a.kc = (const uint16_t*)d_kc; a.vc = (const uint16_t*)d_vc; a.out = d_att; a.tiles = d_tiles; a.n_tiles = (int)tiles.size();
+  a.Hq = Hq; a.Hkv = Hkv; a.dh = dh; a.max_ctx = T; a.seq_stride = (int64_t)Hkv * T * dh; a.dtype = dtype;
+  if (const char* e = lm_prefill_attn_check(a)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
+  if (lm_prefill_attn_launch(a, s)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_lm_prompt_attention: launch failed");
+  std::vector<uint16_t> att((size_t)n * Nq);
+  MIA_HIP(ctx, hipMemcpyAsync(att.data(), d_att, att.size() * 2, hipMemcpyDeviceToHost, s));
+  MIA_HIP(ctx, hipStreamSynchronize(s));
+  for (size_t i = 0; i < att.size(); ++i) out[i] = widen(att[i]);
+  return MIA_OK;
+}

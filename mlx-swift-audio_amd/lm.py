@@ -104,6 +104,13 @@ class CausalLM:
         lib.mia_lm_set_debug.argtypes = [C.c_void_p, C.c_int]
         self.ctx.check(lib.mia_lm_set_debug(self.h, int(flags)))
 
+    def set_prompt_attention(self, mode: int) -> None:
+        """mia_lm_set_prompt_attention: 0 = the prompt pass's row kernel (default), 1 = the tiled matrix-core kernel on the 16-bit cache."""
+        lib = self.ctx.lib
+        lib.mia_lm_set_prompt_attention.restype = C.c_int
+        lib.mia_lm_set_prompt_attention.argtypes = [C.c_void_p, C.c_int]
+        self.ctx.check(lib.mia_lm_set_prompt_attention(self.h, int(mode)))
+
     def use_q4(self, on: bool) -> None:
         lib = self.ctx.lib
         lib.mia_lm_use_q4.restype = C.c_int

@@ -92,6 +92,21 @@ def kvq_attention(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.ndarray
     return out
 
 
+def lm_prompt_attention(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.ndarray, dtype: int = _lib.BF16) -> np.ndarray:
+    """mia_op_lm_prompt_attention: the prompt pass's tiled causal GQA attention (lm_prefill_attn.hip) over a 16-bit cache the op fills
+    from k / v [Hkv, T, dh] (fp32 here, rounded to `dtype`).  q [n, Hq, dh]: the rows at positions T - n .. T - 1, the row at p sees
+    keys [0, p]; returns fp32 [n, Hq, dh]."""
+    lib = ctx.lib
+    lib.mia_op_lm_prompt_attention.restype = C.c_int
+    lib.mia_op_lm_prompt_attention.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6
+    n, Hq, dh = q.shape
+    Hkv, T, _ = k.shape
+    q16, k16, v16 = to16(q, dtype), to16(k, dtype), to16(v, dtype)
+    out = np.empty((n, Hq, dh), np.float32)
+    ctx.check(lib.mia_op_lm_prompt_attention(ctx.h, q16.ctypes.data, k16.ctypes.data, v16.ctypes.data, out.ctypes.data, Hq, Hkv, T, n, dh, dtype))
+    return out
+
+
 # ---- fp32 tap GEMM and fp32 attention (device pointers; the test hooks expose every launch argument) -------------------------------
 class ConvGemmDesc(C.Structure):
     """mia_conv_gemm_desc (include/mia.h), field for field."""

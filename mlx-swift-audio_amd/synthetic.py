@@ -338,6 +338,9 @@ class LMConfig:
 LM_CONFIGS = {
     # OrpheusConfig (TransformerBlock.swift:16-34) == Llama-3.2-3B with the Orpheus vocabulary
     "orpheus-3b": LMConfig(156940, 3072, 8192, 28, 24, 8, 128, 2048),
+    # OuteTTSModelConfig (TTS/OuteTTS/OuteTTSModel.swift): a Llama-3.2-1B backbone -- Llama-3 RoPE scaling, tied head.  The reference reads
+    # the vocabulary size from the checkpoint's config.json; 128 256 (Llama-3.2's) is an assumption, tools/bench_outetts.py takes --vocab
+    "llama-3.2-1b": LMConfig(128256, 2048, 8192, 16, 32, 8, 64, 8192),
     # Qwen2Config defaults (Qwen2LM.swift:15-43): the CosyVoice2-0.5B backbone
     "qwen2-0.5b": LMConfig(151936, 896, 4864, 24, 14, 2, 64, 2048, 1e-6, 1e6, False, 1.0, 1.0, 4.0, 8192, True, True),
     # mid-size shape for the packed-q4 step: K = 1024 / 2048 give several 128-input blocks per wave, 4-wave workgroups and cross-workgroup splits
