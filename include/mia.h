@@ -249,6 +249,39 @@ int mia_op_kvq_attention(mia_ctx* ctx, const void* q, const void* k, const void*
 int mia_op_lm_prompt_attention(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int n, int dh,
                                int dtype);
 
+/* Test hook: the LM decode step's skinny GEMMs (csrc/skinny.h: skinny_gemm_launch on 16-bit weights, skinny_gemm_q_launch on packed 4- /
+ * 8-bit weights) with every launch argument exposed, so each kernel form the two launchers choose from the shape can be compared with a
+ * reference on its own.  DEVICE pointers, enqueued on the context's stream.  A [M][lda] and the 16-bit outputs are in `dtype`
+ * (MIA_BF16 | MIA_F16); acc[m][n] = sum_k A[m][k] W[n][k] in fp32, summed in a fixed order that depends on the shape only.
+ *   mode 1 (OUTF32):  out fp32 [M][ldo] = acc (* rstd[m]) + bias[n]
+ *   mode 2 (PARTIAL): out fp32 [S][M][N], slice s = the K range [s K/S, (s+1) K/S) of acc (* rstd[m]); no bias
+ *   mode 4 (SWIGLU):  W rows interleaved gate / up: out 16-bit [M][ldo], out[m][n/2] = silu(g) * u of v = acc (* rstd) + bias; S = 1
+ *   mode 5 (RESID):   xres fp32 [M][N] += acc + bias; out 16-bit [M][ldo] = xres * nw[n]; ss_out[n/16][m] (fp32 [N/16][M]) = the sum of
+ *                     xres^2 over the tile's 16 columns; S = 1, N % 16 == 0, ldo % 4 == 0
+ *   ss_in != NULL (fp32 [ss_tiles][M], 1 <= ss_tiles <= 512): rstd[m] = rsqrt(sum_t ss_in[t][m] / ss_dim + eps) * rs_scale; else rstd = 1.
+ * Weights: wfrag == NULL: W [N][K] row-major in `dtype`, K % (32 S) == 0; w_frag != 0 makes the op repack W into weight fragment order
+ *   (dec_launch_repack_wfrag, into the context workspace) and run the fragment-order loads -- results are identical.  wfrag != NULL:
+ *   the packed form, wfrag / stfrag as mia_quant_repack builds them for `bits` (4 | 8) and compute type `dtype`, K % (128 S) == 0.
+ * M_cap (0 = M): the rows the caller's buffers are sized for.  The packed launcher picks its kernel form from max(M, M_cap), so that a
+ *   row's result does not depend on how many rows the call carries (the LM step passes the handle's batch capacity).
+ * lda % 8 == 0, lda >= K, ldo >= N (N / 2 for mode 4); S > 1 only in mode 2; A, W, wfrag, stfrag, out, xres and nw 16-byte aligned, bias
+ * too in mode 5 (the other modes read it, like ss_in, one float at a time; ss_out is written so); W and the packed arrays below 4 GiB,
+ * A too with 16-bit weights (32-bit byte offsets in the kernels).  Anything else, modes 0 and 3 and non-positive sizes included, is
+ * MIA_ERR_INVALID_ARGUMENT and launches nothing. */
+typedef struct {
+  const void* A; int64_t lda;
+  const void* W;
+  const uint32_t* wfrag; const float* stfrag; int32_t bits;
+  int32_t w_frag;
+  const float* bias;
+  void* out; int64_t ldo;
+  int32_t M, N, K, S, mode, dtype;
+  float* xres; const float* nw; float* ss_out;
+  const float* ss_in; int32_t ss_tiles, ss_dim; float eps, rs_scale;
+  int32_t M_cap;
+} mia_skinny_desc;
+int mia_op_skinny_gemm(mia_ctx* ctx, const mia_skinny_desc* d);
+
 /* ---- Whisper ---------------------------------------------------------------------------------- */
 /* Model dimensions == ModelDimensions (STT/Whisper/Config/WhisperConfig.swift:9-86), read by the caller
  * from config.json. */

@@ -435,7 +435,7 @@ int lm_enqueue_step(mia_lm* m, int mode, const mia_lm_sampler& sp, const RasPara
     SkinnyArgs a{(const uint16_t*)A, lda, (const uint16_t*)W, bias, out, ldo, nullptr, nullptr, nullptr, nb, N, K, S, MIA_ACT_NONE, 0, 0, 0};
     if (ss_in) { a.ss_in = ss_in; a.ss_tiles = ss_tiles; a.ss_dim = D; a.eps = c.rms_eps; a.rs_scale = rs_scale; }
     if (mode == SK_RESID) { a.xres = m->x; a.nw = nw; a.ss_out = ss_out; }
-    if (m->q4 && qw && qw->wfrag) return skinny_gemm_q_launch(a, qw->wfrag, qw->stfrag, m->q_bits, mode, m->dtype, s);
+    if (m->q4 && qw && qw->wfrag) return skinny_gemm_q_launch(a, qw->wfrag, qw->stfrag, m->q_bits, mode, m->dtype, s, m->B_cap);      // the form follows the capacity (skinny.h)
     if (Wf) { a.W = (const uint16_t*)Wf; a.w_frag = 1; }      // same K order and partition as the row-major form: identical results
     return skinny_gemm_launch(a, mode, m->dtype, s);
   };

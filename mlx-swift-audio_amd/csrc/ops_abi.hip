@@ -78,6 +78,57 @@ extern "C" int mia_op_conv_gemm_f32(mia_ctx* ctx, const mia_conv_gemm_desc* d, i
   return codec_conv_gemm_run(ctx, g, phases, "op_conv_gemm_f32");
 }
 
+// The LM step's skinny GEMMs with every launch argument exposed (test hook; formulas in skinny.h and include/mia.h).  The launchers'
+// own checks cover what lm.hip cannot get wrong by construction; a public caller has no model in front of it, so the sizes, strides,
+// pointers and alignments the kernels rely on are checked here.
+#include "skinny.h"
+static const char* skinny_abi_check(const mia_skinny_desc& d) {
+  if (d.dtype != MIA_BF16 && d.dtype != MIA_F16) return "dtype must be MIA_BF16 or MIA_F16";
+  if (d.mode != SK_OUTF32 && d.mode != SK_PARTIAL && d.mode != SK_SWIGLU && d.mode != SK_RESID) return "mode must be 1 (OUTF32), 2 (PARTIAL), 4 (SWIGLU) or 5 (RESID)";
+  if (!d.A || !d.out) return "null pointer";
+  if (d.wfrag ? !d.stfrag : !d.W) return "null weights";
+  if (d.lda < d.K) return "lda must cover the row";
+  if (d.mode != SK_PARTIAL && d.S != 1) return "only PARTIAL takes S > 1";      // the other epilogues own their output: one K slice only
+  if ((d.mode == SK_OUTF32 || d.mode == SK_RESID) && d.ldo < d.N) return "ldo must cover the row";
+  if (d.mode == SK_SWIGLU && d.ldo < d.N / 2) return "ldo must cover the row";
+  if (d.mode == SK_RESID && (!d.xres || !d.nw || !d.ss_out)) return "RESID needs xres, nw and ss_out";
+  if (d.M_cap < 0) return "bad M_cap";
+  auto misaligned = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
+  if (misaligned(d.A) || misaligned(d.W) || misaligned(d.wfrag) || misaligned(d.stfrag) || misaligned(d.out) || misaligned(d.xres) || misaligned(d.nw) ||
+      (d.mode == SK_RESID && misaligned(d.bias)))
+    return "operands must be 16-byte aligned";
+  // (non-positive sizes and what the kernels hold in 32 bits -- operands of 4 GiB or more -- are refused by the launchers themselves)
+  return nullptr;
+}
+
+extern "C" int mia_op_skinny_gemm(mia_ctx* ctx, const mia_skinny_desc* d) {
+  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, d, "op_skinny_gemm: null descriptor");
+  if (const char* e = skinny_abi_check(*d)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "op_skinny_gemm: %s", e);
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  SkinnyArgs a{(const uint16_t*)d->A, d->lda, (const uint16_t*)d->W, d->bias, d->out, d->ldo, nullptr, nullptr, nullptr, d->M, d->N, d->K, d->S, MIA_ACT_NONE, 0, 0, 0};
+  a.xres = d->xres; a.nw = d->nw; a.ss_out = d->ss_out;
+  a.ss_in = d->ss_in; a.ss_tiles = d->ss_tiles; a.ss_dim = d->ss_dim; a.eps = d->eps; a.rs_scale = d->rs_scale;
+  int rc;
+  if (d->wfrag) rc = skinny_gemm_q_launch(a, d->wfrag, d->stfrag, d->bits, d->mode, d->dtype, ctx->stream, d->M_cap);
+  else {
+    if (d->w_frag) {
+      // (before the repack allocates and launches anything: what the launcher would refuse afterwards)
+      MIA_CHECK_ARG(ctx, d->N > 0 && d->K > 0 && d->K % 32 == 0 && ((uint64_t)d->N + 15) / 16 * 16 * (uint64_t)d->K * 2 <= 0xffffffffull,
+                    "op_skinny_gemm: N, K must be positive, K a multiple of 32, W below 4 GiB");
+      void* wf = mia_workspace(ctx, (size_t)((d->N + 15) / 16) * 16 * d->K * 2);
+      if (!wf) return MIA_ERR_OUT_OF_MEMORY;
+      if (dec_launch_repack_wfrag(d->W, wf, d->N, d->K, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_skinny_gemm: fragment repack failed");
+      a.W = (const uint16_t*)wf; a.w_frag = 1;
+    }
+    rc = skinny_gemm_launch(a, d->mode, d->dtype, ctx->stream);
+  }
+  if (rc) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "op_skinny_gemm: the launcher refused the arguments (K %d, S %d, lda %lld, N %d, ldo %lld, mode %d, bits %d, ss_tiles %d)",
+                          d->K, d->S, (long long)d->lda, d->N, (long long)d->ldo, d->mode, d->bits, d->ss_tiles);
+  if (hipGetLastError() != hipSuccess) return mia_fail(ctx, MIA_ERR_DEVICE, "op_skinny_gemm: launch failed");
+  return MIA_OK;
+}
+
 // fp32 attention, head dim 64, with every mode of attn_f32.hip (test hook): positional keys p with bias_u / bias_v, seq_len, chunk; device
 // pointers, q/k/v [B*T][ld] with head h in columns h*64.., out [B*T][ldo]
 extern "C" int mia_op_attention_f32_ex(mia_ctx* ctx, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,

@@ -71,6 +71,21 @@ inline float mia_carry_prescale(const float* gain, int n, int dtype) {
 int dec_launch_repack_wfrag(const void* src, void* dst, int N, int K, hipStream_t s);
 // row-major activations (the LM step; skinny_rowmajor.hip), dtype = MIA_BF16 | MIA_F16; modes SK_OUTF32 / SK_PARTIAL / SK_SWIGLU / SK_RESID.
 // SK_SWIGLU: W rows interleaved gate/up, out[m][n/2] = silu(g)*u (16-bit)
+// Both launchers also refuse (-1) non-positive sizes and a W (16 bit: an A too) or packed code array of 4 GiB or more: the kernels address
+// them through buffer resources with 32-bit sizes and byte offsets (WFragBuf), and a loader can get there (a 262144 x 8192 vocabulary
+// head is exactly 4 GiB).
+// The kernel form is chosen from the shape alone; tests/_skinny_cases.py restates the rule (dispatch16) -- change the two together.
 int skinny_gemm_launch(const SkinnyArgs& a, int mode, int dtype, hipStream_t s);
 // MLX-affine 4- / 8-bit weights in fragment order (skinny_quant.hip: skinny_gemm_qi); modes SK_OUTF32 / SK_PARTIAL / SK_SWIGLU / SK_RESID
-int skinny_gemm_q_launch(const SkinnyArgs& a, const uint32_t* wfrag, const float* stfrag, int bits, int mode, int dtype, hipStream_t s);
+// M_cap: the rows the caller's handle can hold (0 = M).  The launcher chooses between kernel forms that split K differently -- four
+// tiles per wave above 16 rows, the one-wave vocabulary head up to 16 -- and so sum in a different order.  It chooses from
+// max(M, M_cap): with M_cap = the handle's batch capacity a row's result does not depend on how many rows this call carries
+// (lm.hip: lm_enqueue_step).  Without it the form follows M, and these shapes change their K split between M <= 16 and M > 16:
+//   * ceil(N / 64) * S >= 192 with K / S / 128 in {2, 6, 9, 10, 14, ...} (several waves below, one above; Qwen3-0.6B q|k|v: N 4096, K 1024, S 4;
+//     Orpheus-3B q|k|v: N 5120, K 3072, S 4);
+//   * ceil(N / 64) * S >= 192 with K / S / 128 == 4: four waves above 16 rows, two below;
+//   * the OUTF32 head with N >= 65536 and K / 128 a multiple of 4: one wave up to 16 rows, four above (Qwen3-0.6B, Llama-3.2-1B,
+//     Orpheus-3B vocabulary heads).
+// tests/test_skinny_gpu.py asserts the derived bound only across the boundary for those, and bit-equality of rows everywhere else.
+// (form rule restated in tests/_skinny_cases.py: dispatch_q)
+int skinny_gemm_q_launch(const SkinnyArgs& a, const uint32_t* wfrag, const float* stfrag, int bits, int mode, int dtype, hipStream_t s, int M_cap = 0);

@@ -187,22 +187,24 @@ __global__ __launch_bounds__(64 * NW) void skinny_gemm_qi(SkinnyArgs a, QFrag q)
 }
 
 template <typename T, bool M16, int NP>
-static void skinny_qi_launch_m(const SkinnyArgs& a, const QFrag& q, int mode, hipStream_t s) {
+static void skinny_qi_launch_m(const SkinnyArgs& a, const QFrag& q, int mode, hipStream_t s, int M_cap) {
   const int tiles = (a.N + 15) / 16, nblk = a.K / 128;
   const int zb = (a.M + 31) / 32;
+  // the FORM follows the rows the handle can hold (M_cap, skinny.h), the grid the rows of this call
+  const int Mf = M_cap > a.M ? M_cap : a.M, zf = (Mf + 31) / 32;
   const int per_split = nblk / a.S;               // 128-input blocks per cross-workgroup split
   // 4 tiles per wave only when one tile per wave would put more than ~16 waves on every SIMD anyway (the vocabulary-wide head): the
   // activation fragments and group sums are then reused four times.  Otherwise one tile per wave and as many waves per workgroup
   // (1..4, splitting the K range) as keep 2+ blocks per wave -- the kernel hides its memory latency by occupancy.
   // ... and whenever more than 16 rows are multiplied: every wave then loads 32 activation rows per K-step (8 KB per 128-input block against
   // 1 KB of codes), which four tiles share (32 sequences side by side, Orpheus-3B: 4 900 tokens/s with one tile per wave, 11 000 with four)
-  const bool nt4 = (int64_t)tiles * a.S * zb >= 16384 || (a.M > 16 && (int64_t)((tiles + 3) / 4) * a.S * zb >= 192);
+  const bool nt4 = (int64_t)tiles * a.S * zf >= 16384 || (Mf > 16 && (int64_t)((tiles + 3) / 4) * a.S * zf >= 192);
   int nw = 1;
   for (int cand : {4, 3, 2}) if (per_split % cand == 0 && (per_split / cand >= 2 || cand == 2)) { nw = cand; break; }
   // the vocabulary-wide head at <= 16 rows: 4 tiles per ONE-wave workgroup, the whole K range in the wave (no LDS reduction, a quarter
   // of the workgroups) -- Orpheus-3B, V 156 940: 75.4 us as 9 809 four-wave workgroups, 72.6 as one-wave ones, 67.8 in this form
   // (4 tiles x 4 waves: 107.6)
-  const bool head41 = mode == SK_OUTF32 && tiles >= 4096 && a.M <= 16;
+  const bool head41 = mode == SK_OUTF32 && tiles >= 4096 && Mf <= 16;
 #define QI_GO(MODE_, NT_, NW_) hipLaunchKernelGGL((skinny_gemm_qi<T, MODE_, NT_, NW_, M16, NP>), dim3((tiles + NT_ - 1) / NT_, a.S, zb), dim3(64 * NW_), 0, s, a, q)
 #define QI_LAUNCH(MODE_)                                                                                   \
   do {                                                                                                     \
@@ -226,20 +228,24 @@ static void skinny_qi_launch_m(const SkinnyArgs& a, const QFrag& q, int mode, hi
 }
 
 template <typename T>
-static void skinny_qi_launch_t(const SkinnyArgs& a, const QFrag& q, int bits, int mode, hipStream_t s) {
-  if (bits == 8) { if (a.M <= 16) skinny_qi_launch_m<T, true, 2>(a, q, mode, s); else skinny_qi_launch_m<T, false, 2>(a, q, mode, s); }
-  else { if (a.M <= 16) skinny_qi_launch_m<T, true, 1>(a, q, mode, s); else skinny_qi_launch_m<T, false, 1>(a, q, mode, s); }
+static void skinny_qi_launch_t(const SkinnyArgs& a, const QFrag& q, int bits, int mode, hipStream_t s, int M_cap) {
+  if (bits == 8) { if (a.M <= 16) skinny_qi_launch_m<T, true, 2>(a, q, mode, s, M_cap); else skinny_qi_launch_m<T, false, 2>(a, q, mode, s, M_cap); }
+  else { if (a.M <= 16) skinny_qi_launch_m<T, true, 1>(a, q, mode, s, M_cap); else skinny_qi_launch_m<T, false, 1>(a, q, mode, s, M_cap); }
 }
 
 // quantised form of skinny_gemm_launch: a.W is ignored, the weights come from the fragment-ordered arrays (see skinny_gemm_qi)
-int skinny_gemm_q_launch(const SkinnyArgs& a, const uint32_t* wfrag, const float* stfrag, int bits, int mode, int dtype, hipStream_t s) {
-  if (a.K % (128 * a.S) != 0 || a.lda % 8 != 0 || !wfrag || !stfrag) return -1;
+// (the form rule -- skinny_qi_launch_m / _t -- is restated in tests/_skinny_cases.py: dispatch_q; change the two together)
+int skinny_gemm_q_launch(const SkinnyArgs& a, const uint32_t* wfrag, const float* stfrag, int bits, int mode, int dtype, hipStream_t s, int M_cap) {
+  if (a.M <= 0 || a.N <= 0 || a.K <= 0 || a.S <= 0 || a.K % (128 * a.S) != 0 || a.lda % 8 != 0 || !wfrag || !stfrag) return -1;
   if (bits != 4 && bits != 8) return -1;
+  // the kernel's buffer resources and byte offsets are 32 bit: codes [tiles][K / 128][bits / 4] KB (the (scale, offset) array is smaller;
+  // A is loaded through 64-bit pointers here and needs no such limit)
+  if ((uint64_t)((a.N + 15) / 16) * (uint64_t)(a.K / 128) * 1024 * (uint64_t)(bits / 4) > 0xffffffffull) return -1;
   if (mode != SK_OUTF32 && mode != SK_PARTIAL && mode != SK_SWIGLU && mode != SK_RESID) return -1;
   if (mode == SK_SWIGLU && (a.N & 3)) return -1;
   if (mode == SK_RESID && (a.S != 1 || (a.N & 15) || !a.xres || !a.nw || !a.ss_out)) return -1;
   if (a.ss_in && (a.ss_tiles <= 0 || a.ss_tiles > 512 || a.ss_dim <= 0)) return -1;    // skinny_rstd_prepare sums at most 512 tiles
   const QFrag q{wfrag, stfrag};
-  if (dtype == MIA_F16) skinny_qi_launch_t<F16>(a, q, bits, mode, s); else skinny_qi_launch_t<BF16>(a, q, bits, mode, s);
+  if (dtype == MIA_F16) skinny_qi_launch_t<F16>(a, q, bits, mode, s, M_cap); else skinny_qi_launch_t<BF16>(a, q, bits, mode, s, M_cap);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

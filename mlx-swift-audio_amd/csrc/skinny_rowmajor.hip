@@ -217,7 +217,8 @@ __global__ __launch_bounds__(64 * NW) void dec_skinny_flat(SkinnyArgs a) {
 template <typename T, int MODE>
 static bool skinny_flat_try(const SkinnyArgs& a, hipStream_t s) {
   const int tiles = (a.N + 15) / 16, zb = (a.M + 31) / 32;
-  const int64_t wgs = (int64_t)tiles * a.S * zb;
+  // (the row blocks do not enter the form: a row's result must not depend on how many rows the call carries -- the LM step has one block)
+  const int64_t wgs = (int64_t)tiles * a.S;
   if (a.K % (128 * a.S) != 0 || wgs > 1024 || a.K / a.S < 512) return false;
   const int per_split = a.K / a.S;
   const dim3 grid(tiles, a.S, zb);
@@ -246,7 +247,8 @@ static void skinny_launch_t(const SkinnyArgs& a, int mode, hipStream_t s) {
   }
   dim3 grid((a.N + 15) / 16, a.S, (a.M + 31) / 32);
   // few workgroups and a long K per wave -> split K over 4 waves of the workgroup (K per wave stays a multiple of 32)
-  const bool wide = (int64_t)grid.x * grid.y * grid.z <= 1024 && a.K % (128 * a.S) == 0 && a.K / a.S >= 512;
+  // (counted per 32-row block, as in skinny_flat_try: with grid.z in the count a row of a 33-row call was summed in another order than alone)
+  const bool wide = (int64_t)grid.x * grid.y <= 1024 && a.K % (128 * a.S) == 0 && a.K / a.S >= 512;
 #define SK_LAUNCH(MODE_)                                                                                              \
   do {                                                                                                                \
     if (wide) hipLaunchKernelGGL((dec_skinny_gemm<T, MODE_, 1, 2, 4>), grid, dim3(256), 0, s, a);                      \
@@ -265,8 +267,11 @@ static void skinny_launch_t(const SkinnyArgs& a, int mode, hipStream_t s) {
 #undef SK_LAUNCH
 }
 
+// (the form rule below -- skinny_flat_try and skinny_launch_t -- is restated in tests/_skinny_cases.py: dispatch16; change the two together)
 int skinny_gemm_launch(const SkinnyArgs& a, int mode, int dtype, hipStream_t s) {
-  if (a.K % (32 * a.S) != 0 || a.lda % 8 != 0) return -1;
+  if (a.M <= 0 || a.N <= 0 || a.K <= 0 || a.S <= 0 || a.K % (32 * a.S) != 0 || a.lda % 8 != 0) return -1;
+  // WFragBuf holds sizes and byte offsets in 32 bits (fragment order pads the rows to 16)
+  if ((uint64_t)((a.N + 15) / 16) * 16 * (uint64_t)a.K * 2 > 0xffffffffull || (uint64_t)a.M * (uint64_t)a.lda * 2 > 0xffffffffull) return -1;
   if (mode != SK_OUTF32 && mode != SK_PARTIAL && mode != SK_SWIGLU && mode != SK_RESID) return -1;    // the LM step's modes
   if (mode == SK_SWIGLU && (a.N & 3)) return -1;
   if (mode == SK_RESID && (a.S != 1 || (a.N & 15) || (a.ldo & 3) || !a.xres || !a.nw || !a.ss_out)) return -1;

@@ -226,3 +226,61 @@ def attention_f32_ex(ctx: _lib.Context, q, k, v, out, B: int, T: int, H: int, sc
 def attention_f32(ctx: _lib.Context, q, k, v, out, B: int, T: int, H: int, scale: float = 0.125, **ld) -> np.ndarray:
     """mia_op_attention_f32: full softmax(q k^T scale) v per head, head dim 64; see attention_f32_ex."""
     return attention_f32_ex(ctx, q, k, v, out, B, T, H, scale, plain=True, **ld)
+
+
+# ---- the LM step's skinny GEMMs (device tensors; the test hook exposes every launch argument) ---------------------------------------
+class SkinnyDesc(C.Structure):
+    """mia_skinny_desc (include/mia.h), field for field."""
+    _fields_ = [("A", C.c_void_p), ("lda", C.c_int64), ("W", C.c_void_p),
+                ("wfrag", C.c_void_p), ("stfrag", C.c_void_p), ("bits", C.c_int32), ("w_frag", C.c_int32),
+                ("bias", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int64),
+                ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("S", C.c_int32), ("mode", C.c_int32), ("dtype", C.c_int32),
+                ("xres", C.c_void_p), ("nw", C.c_void_p), ("ss_out", C.c_void_p),
+                ("ss_in", C.c_void_p), ("ss_tiles", C.c_int32), ("ss_dim", C.c_int32), ("eps", C.c_float), ("rs_scale", C.c_float),
+                ("M_cap", C.c_int32)]
+
+
+SK_OUT16, SK_OUTF32, SK_PARTIAL, SK_QKV, SK_SWIGLU, SK_RESID = range(6)
+_SKINNY_PTRS = ("A", "W", "wfrag", "stfrag", "bias", "out", "xres", "nw", "ss_out", "ss_in")
+
+
+def quant_repack(codes: np.ndarray, scales: np.ndarray, biases: np.ndarray, bits: int, scale_dtype: int, compute_dtype: int):
+    """mia_quant_repack (host): one packed Linear (quantize_affine's three arrays; bf16 scales as uint16 bit patterns) -> (wfrag, stfrag)."""
+    lib = _lib.load()
+    lib.mia_quant_repack.restype = C.c_int
+    lib.mia_quant_repack.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    codes, scales, biases = np.ascontiguousarray(codes, np.uint32), np.ascontiguousarray(scales), np.ascontiguousarray(biases)
+    N, K = codes.shape[0], codes.shape[1] * (32 // bits)
+    tiles = (N + 15) // 16
+    wf = np.zeros((tiles, K // 128, bits // 4, 64, 4), np.uint32)
+    st = np.zeros((tiles, K // 128, 16, 4), np.float32)
+    rc = lib.mia_quant_repack(codes.ctypes.data, scales.ctypes.data, biases.ctypes.data, N, K, int(bits), int(scale_dtype), int(compute_dtype),
+                              wf.ctypes.data, st.ctypes.data)
+    if rc != 0:
+        raise _lib.MiaError(rc, "quant_repack: bad argument")
+    return wf, st
+
+
+def skinny_gemm(ctx: _lib.Context, **d) -> None:
+    """mia_op_skinny_gemm: keyword arguments are the fields of mia_skinny_desc, torch device tensors (views included) or None for its
+    pointers; lda / ldo default to the row strides of two-dimensional A / out, S to 1, rs_scale to 1.  Outputs are written in place."""
+    lib = ctx.lib
+    if not getattr(lib, "_skinny_declared", False):
+        lib.mia_op_skinny_gemm.restype = C.c_int
+        lib.mia_op_skinny_gemm.argtypes = [C.c_void_p, C.POINTER(SkinnyDesc)]
+        lib._skinny_declared = True
+    unknown = set(d) - {n for n, _ in SkinnyDesc._fields_}
+    assert not unknown, f"not a mia_skinny_desc field: {sorted(unknown)}"
+    desc = SkinnyDesc()
+    for name, _ in SkinnyDesc._fields_:
+        v = d.get(name)
+        if name in _SKINNY_PTRS:
+            assert v is None or v.is_cuda, "device tensors only"
+            setattr(desc, name, _ptr(v))
+        elif name == "lda":
+            desc.lda = _ld(d.get("A"), v)
+        elif name == "ldo":
+            desc.ldo = _ld(d.get("out"), v)
+        else:
+            setattr(desc, name, {"S": 1, "rs_scale": 1.0}.get(name, 0) if v is None else v)
+    _run(ctx, lambda: lib.mia_op_skinny_gemm(ctx.h, C.byref(desc)))

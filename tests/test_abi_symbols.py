@@ -19,7 +19,7 @@ def test_header_symbols_exported():
     import mlx_swift_audio_amd as m
     lib = m._lib.load()
     names = _declared()
-    assert len(names) >= 15
+    assert len(names) >= 15 and {"mia_op_skinny_gemm", "mia_op_conv_gemm_f32", "mia_quant_repack"} <= set(names)
     for n in names:
         assert hasattr(lib, n), f"{n} declared in include/mia.h but not exported by libmia.so"
     assert lib.mia_version().startswith(b"mia ")

@@ -479,3 +479,37 @@ def test_packed_step_mid_size_batch_32(ctx, bits):
                                     # on the same capacity (same kernel chain; mia.h, mia_lm_generate_batch)
         assert model.generate(prompts[b], ub[b], **kw) == q[b], b
     model.close()
+
+
+def test_packed_step_rows_do_not_depend_on_batch_occupancy(ctx):
+    """On a capacity-32 handle a sequence decoded alone (1 row) and next to 16 others (17 rows) must get the same arithmetic.  The packed
+    launcher picks between forms that split K differently (four tiles per wave above 16 rows: skinny.h, skinny_gemm_q_launch); with a
+    Qwen3-0.6B-like q|k|v (N 4096, K 1024, 4 cross-workgroup splits) a form taken from the rows of the call sums K in two waves alone and
+    in one wave in the batch, and the 16-bit K / V rows written from those fp32 sums differ.  lm_enqueue_step passes the capacity instead.
+    Sequence 0's ids and every K / V cache row of both layers are compared bit for bit (mia_lm_read_kv)."""
+    import mlx_swift_audio_amd as m
+    from mlx_swift_audio_amd import lm as HL
+    cfg = S.LMConfig(512, 1024, 512, 2, 16, 8, 128, 64)
+    packed, dense = _quantized_checkpoint(cfg, seed=31, bits=4)
+    model = HL.CausalLM.load(ctx, cfg, dense, m.F16)
+    model.attach_q4(packed, bits=4)
+    model.set_debug(2)              # prompts token by token through the packed step
+    model.set_batch(32)
+    rng = np.random.default_rng(8)
+    prompts = [rng.integers(0, cfg.vocab, 14).tolist() for _ in range(17)]
+    u = rng.random((17, 10)).astype(np.float32)
+    kw = dict(temperature=0.8, top_p=0.9, rep_penalty=1.1, rep_window=8, max_new_tokens=10, stop_ids=(cfg.vocab - 1,))
+
+    def rows(n_seq):
+        ids = model.generate_batch(prompts[:n_seq], u[:n_seq], **kw)[0]
+        n = len(prompts[0]) + len(ids) - 1
+        return ids, [np.concatenate(model.read_kv(l, 0, 0, n)) for l in range(cfg.n_layers)]
+
+    ids1, kv1 = rows(1)
+    ids17, kv17 = rows(17)
+    assert ids1 == ids17
+    for l in range(cfg.n_layers):
+        assert np.isfinite(kv1[l]).all() and np.abs(kv1[l]).max() > 0
+        diff = int((kv1[l] != kv17[l]).sum())
+        assert diff == 0, f"layer {l}: {diff} of {kv1[l].size} K / V values of sequence 0 depend on how many sequences the call carries"
+    model.close()
