@@ -149,6 +149,31 @@ int mia_dp_gather_tokens(mia_ctx* ctx, const int32_t* local_tokens, const int32_
 int mia_op_linear(mia_ctx* ctx, const void* x, int64_t lda, const void* w, const float* bias, const float* r, int64_t ldr,
                   void* y, int64_t ldy, int M, int N, int K, int act, int dtype, int out_f32, int variant, int mem);
 
+/* Test hook: mia_op_linear (no residual, no activation) with the two special store layouts of the Whisper encoder / decoder GEMMs.  Rows
+ * are tokens of stacked clips, m = b*T + t with M = B*T, columns are head channels, n = h*64 + d.
+ *   epi 1 (QKV_VT), N == 3*H*64 (q | k | v thirds), T % 4 == 0, Tpad % 4 == 0, Tpad >= T, ldy % 4 == 0, ldy >= 2*H*64:
+ *     columns n < 2*H*64 (q | k) go to y[m][n], row stride ldy; the V third goes transposed per head to
+ *     vt[((b*H + h)*64 + d)*Tpad + t] (vt [B][H][64][Tpad]).  Columns t >= T of vt and columns >= 2*H*64 of y are never written.
+ *   epi 2 (HEADMAJOR), N == H*64: y[((b*H + h)*T + t)*64 + d] (y [B][H][T][64]; ldy and vt are unused).
+ * out_f32 != 0 and batch != 1 exist to be refused (the special epilogues store 16 bit and take the flattened M = B*T form).
+ * variant as mia_op_linear, plus 2 = 256^2 tiles, 4 = 256^2 8-phase tiles, 3 = auto.  y and vt 8-byte aligned.  Buffers live in `mem`;
+ * with host pointers y and vt are uploaded before the launch, so the bytes the GEMM does not write come back as they were.  Anything
+ * else is MIA_ERR_INVALID_ARGUMENT and launches nothing. */
+int mia_op_linear_epi(mia_ctx* ctx, const void* x, int64_t lda, const void* w, const float* bias, void* y, int64_t ldy, void* vt, int M, int N,
+                      int K, int epi, int T, int H, int Tpad, int batch, int dtype, int out_f32, int variant, int mem);
+
+/* Test hook: the Whisper encoder's self-attention (head dim 64, full softmax((q k^T) / 8) v, fp32 softmax; qkvAttention,
+ * STT/Whisper/Layers/MultiHeadAttention.swift:85-135) in the layout the fused QKV GEMM (epi 1 above) leaves behind:
+ *   qk [B*T][ld_qk] in `dtype` (MIA_BF16 | MIA_F16), q of head h in columns h*64.., k in columns H*64 + h*64..; vt [B][H][64][Tpad], V
+ *   transposed per head; out [B*T][ld_out] in `dtype`, columns >= H*64 of a row are left as they are.
+ *   vt columns [T, align_up(T, 64)) are read and multiplied by a zero weight, so they must hold finite values (the model zeroes vt once
+ *   and the GEMM never writes them); columns at or beyond align_up(T, 64) are never read.
+ * Tpad % 64 == 0, Tpad >= T, ld_qk % 8 == 0, ld_qk >= 2*H*64, ld_out % 4 == 0, ld_out >= H*64, B*T < 2^31; qk and vt 16-byte aligned, out
+ * 8-byte aligned.  Anything else is MIA_ERR_INVALID_ARGUMENT and launches nothing.  Deterministic.  Buffers live in `mem`; with host
+ * pointers every operand is copied on its own and out is uploaded first. */
+int mia_op_attention_h64(mia_ctx* ctx, const void* qk, int64_t ld_qk, const void* vt, void* out, int64_t ld_out, int B, int T, int H, int Tpad,
+                         int dtype, int mem);
+
 /* fp32 Conv1d / Linear, the contraction behind every MLXNN Conv1d / Linear of the codec, flow and vocoder stages
  * (e.g. Codec/S3Gen/S3GenDecoder.swift:40-48, Codec/S3Gen/Matcha/MatchaTransformer.swift:36-56), time-major, DEVICE pointers:
  *   y[t][n] = act(b[n] + sum_{k,c} x[t*stride + k*dil - pad][c] * w[n][k][c]) (+ r[t][n]);  x [T_in][ldx], w [N][taps][Cin] (Cin % 32 == 0),

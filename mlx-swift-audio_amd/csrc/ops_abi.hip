@@ -36,6 +36,97 @@ extern "C" int mia_op_linear(mia_ctx* ctx, const void* x, int64_t lda, const voi
   return MIA_OK;
 }
 
+// mia_op_linear with the two special store layouts of gemm.hip (test hook): epi 1 = MIA_EPI_QKV_VT (q|k rows into y, V transposed per head
+// into vt), epi 2 = MIA_EPI_HEADMAJOR (y [B][H][T][64]).  mia_gemm_check is the gatekeeper; what it leaves to the model in front of it -- that
+// m = b*T + t covers whole clips and that the row stride covers the q|k row, i.e. that every store lands inside y / vt -- is checked here.
+extern "C" int mia_op_linear_epi(mia_ctx* ctx, const void* x, int64_t lda, const void* w, const float* bias, void* y, int64_t ldy, void* vt, int M,
+                                 int N, int K, int epi, int T, int H, int Tpad, int batch, int dtype, int out_f32, int variant, int mem) {
+  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, x && w && y && (vt || epi != MIA_EPI_QKV_VT), "op_linear_epi: null pointer");
+  MIA_CHECK_ARG(ctx, dtype == MIA_BF16 || dtype == MIA_F16, "op_linear_epi: dtype must be MIA_BF16 or MIA_F16");
+  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "op_linear_epi: bad mem");
+  MIA_CHECK_ARG(ctx, epi == MIA_EPI_QKV_VT || epi == MIA_EPI_HEADMAJOR, "op_linear_epi: epi must be 1 (QKV_VT) or 2 (HEADMAJOR)");
+  MIA_CHECK_ARG(ctx, variant >= 0 && variant <= 4, "op_linear_epi: variant must be 0 .. 4");
+  MIA_CHECK_ARG(ctx, M > 0 && N > 0 && K > 0 && T > 0 && H > 0 && lda >= K, "op_linear_epi: bad shape");
+  MIA_CHECK_ARG(ctx, M % T == 0, "op_linear_epi: M must be B * T");
+  const int64_t B = M / T, D2 = 2 * (int64_t)H * 64;
+  if (epi == MIA_EPI_QKV_VT) {
+    MIA_CHECK_ARG(ctx, ldy >= D2, "op_linear_epi: ldy must cover the q|k row (2 * H * 64)");
+    MIA_CHECK_ARG(ctx, Tpad >= T, "op_linear_epi: Tpad must be >= T");
+    MIA_CHECK_ARG(ctx, (((uintptr_t)y | (uintptr_t)vt) & 7) == 0 || mem == MIA_MEM_HOST, "op_linear_epi: y and vt must be 8-byte aligned");
+  } else {
+    MIA_CHECK_ARG(ctx, ((uintptr_t)y & 7) == 0 || mem == MIA_MEM_HOST, "op_linear_epi: y must be 8-byte aligned");
+  }
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  GemmArgs g;
+  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldy; g.out_f32 = out_f32 ? 1 : 0; g.variant = variant; g.batch = batch;
+  g.epi = epi; g.T = T; g.H = H; g.Tpad = Tpad;
+  const size_t xb = (size_t)M * lda * 2, wb = (size_t)N * K * 2, bb = bias ? (size_t)N * 4 : 0;
+  const size_t yb = epi == MIA_EPI_QKV_VT ? (size_t)(((int64_t)M - 1) * ldy + D2) * 2 : (size_t)B * H * T * 64 * 2;
+  const size_t vb = epi == MIA_EPI_QKV_VT ? (size_t)B * H * 64 * Tpad * 2 : 0;
+  if (mem == MIA_MEM_DEVICE) {
+    g.A = x; g.W = w; g.C = y; g.C2 = vt; g.bias = bias;
+  } else {
+    const size_t o_w = align_up(xb, 256), o_y = o_w + align_up(wb, 256), o_v = o_y + align_up(yb, 256), o_b = o_v + align_up(vb, 256);
+    char* ws = (char*)mia_workspace(ctx, o_b + align_up(bb, 256));
+    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
+    g.A = ws; g.W = ws + o_w; g.C = ws + o_y; g.C2 = vb ? ws + o_v : nullptr; g.bias = bias ? (const float*)(ws + o_b) : nullptr;
+  }
+  if (const char* e = mia_gemm_check(g)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);     // before anything is copied or launched
+  if (mem == MIA_MEM_HOST) {
+    MIA_HIP(ctx, hipMemcpyAsync((void*)g.A, x, xb, hipMemcpyHostToDevice, ctx->stream));
+    MIA_HIP(ctx, hipMemcpyAsync((void*)g.W, w, wb, hipMemcpyHostToDevice, ctx->stream));
+    if (bias) MIA_HIP(ctx, hipMemcpyAsync((void*)g.bias, bias, bb, hipMemcpyHostToDevice, ctx->stream));
+    MIA_HIP(ctx, hipMemcpyAsync(g.C, y, yb, hipMemcpyHostToDevice, ctx->stream));                      // untouched bytes survive the round trip
+    if (vb) MIA_HIP(ctx, hipMemcpyAsync(g.C2, vt, vb, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (mia_gemm_launch(g, dtype, ctx->stream) != 0) return mia_fail(ctx, MIA_ERR_DEVICE, "op_linear_epi: launch failed");
+  if (mem == MIA_MEM_HOST) {
+    MIA_HIP(ctx, hipMemcpyAsync(y, g.C, yb, hipMemcpyDeviceToHost, ctx->stream));
+    if (vb) MIA_HIP(ctx, hipMemcpyAsync(vt, g.C2, vb, hipMemcpyDeviceToHost, ctx->stream));
+    MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return MIA_OK;
+}
+
+// The Whisper encoder's attention (attention.hip) in its native layout (test hook): qk [B*T][ld_qk] with q of head h in columns h*64.. and k
+// in columns H*64 + h*64.., vt [B][H][64][Tpad] (what MIA_EPI_QKV_VT stores), out [B*T][ld_out].  mia_enc_attention_check covers what the
+// kernel's loads need; the sizes a model guarantees by construction (strides that cover the row, a 32-bit row count) are checked here.
+extern "C" int mia_op_attention_h64(mia_ctx* ctx, const void* qk, int64_t ld_qk, const void* vt, void* out, int64_t ld_out, int B, int T, int H,
+                                    int Tpad, int dtype, int mem) {
+  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "op_attention_h64: bad mem");
+  MIA_CHECK_ARG(ctx, qk && vt && out, "op_attention_h64: null pointer");
+  MIA_CHECK_ARG(ctx, dtype == MIA_BF16 || dtype == MIA_F16, "op_attention_h64: dtype must be MIA_BF16 or MIA_F16");
+  if (const char* e = mia_enc_attention_check(B, T, H, Tpad, ld_qk, ld_out)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
+  const int64_t rows = (int64_t)B * T, D = (int64_t)H * 64;
+  MIA_CHECK_ARG(ctx, rows < (1ll << 31) && (int64_t)B * H * ((T + 127) / 128) < (1ll << 31), "op_attention_h64: B * T must stay below 2^31");
+  MIA_CHECK_ARG(ctx, ld_qk >= 2 * D && ld_out >= D, "op_attention_h64: row strides must cover the row (ld_qk >= 2 * H * 64, ld_out >= H * 64)");
+  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || ((((uintptr_t)qk | (uintptr_t)vt) & 15) == 0 && ((uintptr_t)out & 7) == 0),
+                "op_attention_h64: qk and vt must be 16-byte aligned, out 8-byte aligned");
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  const void* d_qk = qk; const void* d_vt = vt; void* d_out = out;
+  size_t ob = 0;
+  if (mem == MIA_MEM_HOST) {
+    const size_t qb = (size_t)((rows - 1) * ld_qk + 2 * D) * 2, vb = (size_t)B * H * 64 * Tpad * 2;
+    ob = (size_t)((rows - 1) * ld_out + D) * 2;
+    const size_t o_v = align_up(qb, 256), o_o = o_v + align_up(vb, 256);
+    char* ws = (char*)mia_workspace(ctx, o_o + align_up(ob, 256));
+    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
+    MIA_HIP(ctx, hipMemcpyAsync(ws + o_o, out, ob, hipMemcpyHostToDevice, ctx->stream));      // unwritten elements keep the caller's bytes
+    MIA_HIP(ctx, hipMemcpyAsync(ws, qk, qb, hipMemcpyHostToDevice, ctx->stream));
+    MIA_HIP(ctx, hipMemcpyAsync(ws + o_v, vt, vb, hipMemcpyHostToDevice, ctx->stream));
+    d_qk = ws; d_vt = ws + o_v; d_out = ws + o_o;
+  }
+  if (mia_enc_attention_launch(d_qk, ld_qk, d_vt, d_out, ld_out, B, T, H, Tpad, dtype, ctx->stream))
+    return mia_fail(ctx, MIA_ERR_DEVICE, "op_attention_h64: launch failed");
+  if (mem == MIA_MEM_HOST) {
+    MIA_HIP(ctx, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, ctx->stream));
+    MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return MIA_OK;
+}
+
 // fp32 Conv1d / Linear on the exact-fp32 matrix cores (device pointers only): y[t][n] = act(b[n] + sum_{k,c} x[t*stride + k*dil - pad][c] w[n][k][c]) (+ r)
 #include "codec.h"
 // what the public fp32 GEMM entry points add to codec_conv_gemm_check: the kernel clamps row offsets, so its loads and stores stay inside

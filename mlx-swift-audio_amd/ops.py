@@ -63,6 +63,94 @@ def attention_h128(ctx: _lib.Context, qkv: np.ndarray, B: int, T: int, H: int, s
     return from16(out, dtype)
 
 
+EPI_QKV_VT, EPI_HEADMAJOR = 1, 2
+
+
+def _declare_enc(lib):
+    if getattr(lib, "_enc_ops_declared", False):
+        return
+    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
+    lib.mia_op_linear_epi.restype = i32
+    lib.mia_op_linear_epi.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp] + [i32] * 12
+    lib.mia_op_attention_h64.restype = i32
+    lib.mia_op_attention_h64.argtypes = [vp, vp, i64, vp, vp, i64] + [i32] * 6
+    lib._enc_ops_declared = True
+
+
+def bits16(a: np.ndarray, dtype: int) -> np.ndarray:
+    """fp32 values rounded to `dtype`, as uint16 bit patterns."""
+    return to16(a, dtype).view(np.uint16)
+
+
+def from_bits16(a: np.ndarray, dtype: int) -> np.ndarray:
+    return from16(a.view(np.float16) if dtype == _lib.F16 else a, dtype)
+
+
+def enc_attention_buffers(q: np.ndarray, k: np.ndarray, v: np.ndarray, B: int, T: int, H: int, Tpad: int, ld_qk: int, pad_fill: float, dtype: int):
+    """The encoder attention's native operands from q / k / v [B*T, H*64] fp32 (rounded to `dtype`), as uint16 bit patterns:
+    qk [B*T, ld_qk] = q | k | padding columns holding `pad_fill`; vt [B, H, 64, Tpad] with columns [T, align_up(T, 64)) zero (the model's
+    contract) and columns at or beyond align_up(T, 64) holding `pad_fill`."""
+    D = H * 64
+    assert q.shape == k.shape == v.shape == (B * T, D)
+    qk = bits16(np.full((B * T, ld_qk), pad_fill, np.float32), dtype)
+    qk[:, :D], qk[:, D:2 * D] = bits16(q, dtype), bits16(k, dtype)
+    vt = bits16(np.full((B, H, 64, Tpad), pad_fill, np.float32), dtype)
+    vt[..., T:min(Tpad, (T + 63) // 64 * 64)] = 0
+    vt[..., :T] = bits16(v, dtype).reshape(B, T, H, 64).transpose(0, 2, 3, 1)
+    return qk, vt
+
+
+def attention_h64(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.ndarray, B: int, T: int, H: int, *, Tpad: int | None = None,
+                  ld_qk: int | None = None, ld_out: int | None = None, fill: float = 0.0, pad_fill: float = 0.0,
+                  dtype: int = _lib.BF16) -> np.ndarray:
+    """mia_op_attention_h64 (the Whisper encoder's attention, head dim 64) on q / k / v [B*T, H*64] fp32, rounded to `dtype` and laid out
+    by enc_attention_buffers; Tpad defaults to align_up(T, 64), ld_qk to 2*H*64, ld_out to H*64.  out starts as `fill` everywhere.
+    Returns fp32 [B*T, ld_out], the whole buffer."""
+    _declare_enc(ctx.lib)
+    D = H * 64
+    Tpad = (T + 63) // 64 * 64 if Tpad is None else Tpad
+    ld_qk = 2 * D if ld_qk is None else ld_qk
+    ld_out = D if ld_out is None else ld_out
+    qk, vt = enc_attention_buffers(q, k, v, B, T, H, Tpad, ld_qk, pad_fill, dtype)
+    out = bits16(np.full((B * T, ld_out), fill, np.float32), dtype)
+    ctx.check(ctx.lib.mia_op_attention_h64(ctx.h, qk.ctypes.data, ld_qk, vt.ctypes.data, out.ctypes.data, ld_out, B, T, H, Tpad, dtype, _lib.MEM_HOST))
+    return from_bits16(out, dtype)
+
+
+def attention_h64_device(ctx: _lib.Context, qk, vt, out, B: int, T: int, H: int, Tpad: int, ld_qk: int, ld_out: int, dtype: int) -> None:
+    """mia_op_attention_h64 on torch device tensors (16-bit elements), in place."""
+    _declare_enc(ctx.lib)
+    assert qk.is_cuda and vt.is_cuda and out.is_cuda
+    _run(ctx, lambda: ctx.lib.mia_op_attention_h64(ctx.h, _ptr(qk), ld_qk, _ptr(vt), _ptr(out), ld_out, B, T, H, Tpad, dtype, _lib.MEM_DEVICE))
+
+
+def linear_epi(ctx: _lib.Context, x: np.ndarray, w: np.ndarray, bias, y: np.ndarray, vt, *, epi: int, T: int, H: int, Tpad: int = 0,
+               ldy: int | None = None, dtype: int = _lib.BF16, variant: int = 3, out_f32: bool = False, batch: int = 1, N: int | None = None):
+    """mia_op_linear_epi: x [M, K], w [N, K] fp32 (rounded to `dtype` here), bias fp32 [N] or None; y and vt are uint16 arrays holding the
+    destinations' initial bit patterns (QKV_VT: y [M, ldy], vt [B, H, 64, Tpad]; HEADMAJOR: y [B, H, T, 64], vt None) and are not
+    modified.  Returns (y_bits, vt_bits, y_f32, vt_f32): the destinations after the GEMM as bit patterns and widened (vt: None, None for
+    HEADMAJOR)."""
+    _declare_enc(ctx.lib)
+    M, K = x.shape
+    x16, w16 = to16(x, dtype), to16(w, dtype)
+    b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+    yo = np.array(y, np.uint16, order="C")
+    vo = None if vt is None else np.array(vt, np.uint16, order="C")
+    ldy = int(ldy if ldy is not None else (yo.shape[1] if yo.ndim == 2 else H * 64))
+    ctx.check(ctx.lib.mia_op_linear_epi(ctx.h, x16.ctypes.data, K, w16.ctypes.data, None if b is None else b.ctypes.data, yo.ctypes.data, ldy,
+                                        None if vo is None else vo.ctypes.data, M, int(w.shape[0] if N is None else N), K, int(epi), int(T), int(H),
+                                        int(Tpad), int(batch), dtype, 1 if out_f32 else 0, int(variant), _lib.MEM_HOST))
+    return yo, vo, from_bits16(yo, dtype), None if vo is None else from_bits16(vo, dtype)
+
+
+def linear_epi_device(ctx: _lib.Context, x, w, bias, y, vt, *, M: int, N: int, K: int, epi: int, T: int, H: int, Tpad: int, ldy: int,
+                      dtype: int, variant: int = 3) -> None:
+    """mia_op_linear_epi on torch device tensors (x, w, y, vt 16-bit elements, bias fp32), in place."""
+    _declare_enc(ctx.lib)
+    _run(ctx, lambda: ctx.lib.mia_op_linear_epi(ctx.h, _ptr(x), K, _ptr(w), _ptr(bias), _ptr(y), ldy, _ptr(vt), M, N, K, int(epi), T, H, Tpad, 1,
+                                                dtype, 0, int(variant), _lib.MEM_DEVICE))
+
+
 def fsmn_add(ctx: _lib.Context, x: np.ndarray, v: np.ndarray, w: np.ndarray, left: int, B: int = 1, seq_len=None,
              dtype: int = _lib.BF16) -> np.ndarray:
     """mia_op_fsmn_add: x [B*T, D] fp32 + the SANM memory of v [B*T, D] (rounded to `dtype`) under taps w [K, D]; returns the new x."""
