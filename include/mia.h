@@ -173,6 +173,11 @@ int mia_op_linear_epi(mia_ctx* ctx, const void* x, int64_t lda, const void* w, c
  * pointers every operand is copied on its own and out is uploaded first. */
 int mia_op_attention_h64(mia_ctx* ctx, const void* qk, int64_t ld_qk, const void* vt, void* out, int64_t ld_out, int B, int T, int H, int Tpad,
                          int dtype, int mem);
+/* The same with the kernel form chosen by the caller (tests, measurements): variant 0 = 128 queries per workgroup, register-staged K / V^T;
+ * 1 = 128 queries, LDS-DMA ring; 2 = 256 queries (64 per wave), LDS-DMA ring; -1 = what mia_op_attention_h64 launches at this shape (2 for
+ * T >= 1024 when ceil(T / 256) * H * B >= 480, else 1).  Every form runs at every T and computes the same bits. */
+int mia_op_attention_h64_variant(mia_ctx* ctx, const void* qk, int64_t ld_qk, const void* vt, void* out, int64_t ld_out, int B, int T, int H,
+                                 int Tpad, int dtype, int variant, int mem);
 
 /* fp32 Conv1d / Linear, the contraction behind every MLXNN Conv1d / Linear of the codec, flow and vocoder stages
  * (e.g. Codec/S3Gen/S3GenDecoder.swift:40-48, Codec/S3Gen/Matcha/MatchaTransformer.swift:36-56), time-major, DEVICE pointers:

@@ -14,6 +14,12 @@ int mia_norm_launch(const float* x, int64_t ldx, const float* gamma, const float
 const char* mia_enc_attention_check(int B, int T, int H, int Tpad, int64_t ld_qk, int64_t ld_out);
 int mia_enc_attention_launch(const void* qk, int64_t ld_qk, const void* vt, void* out, int64_t ld_out, int B, int T, int H,
                              int Tpad, int dtype, hipStream_t s);
+// The kernel forms (attention.hip): queries per workgroup x K / V^T staging.  All compute the same bits.  mia_enc_attention_launch picks
+// by shape (MIA_ATT_DMA256 for T >= 1024 on a grid of >= 480 of its workgroups, else MIA_ATT_DMA128); the _variant entry serves the operator-level tests and measurements, for
+// which the register-staged form every earlier release ran stays compiled.
+enum { MIA_ATT_REG128 = 0, MIA_ATT_DMA128 = 1, MIA_ATT_DMA256 = 2, MIA_ATT_NVARIANTS = 3 };
+int mia_enc_attention_launch_variant(const void* qk, int64_t ld_qk, const void* vt, void* out, int64_t ld_out, int B, int T, int H,
+                                     int Tpad, int dtype, int variant, hipStream_t s);
 
 // ---- attn_f32.hip (fp32 flash attention, d_h = 64; optional positional keys) ----------------------
 struct AttnF32Args {

@@ -92,9 +92,11 @@ extern "C" int mia_op_linear_epi(mia_ctx* ctx, const void* x, int64_t lda, const
 // The Whisper encoder's attention (attention.hip) in its native layout (test hook): qk [B*T][ld_qk] with q of head h in columns h*64.. and k
 // in columns H*64 + h*64.., vt [B][H][64][Tpad] (what MIA_EPI_QKV_VT stores), out [B*T][ld_out].  mia_enc_attention_check covers what the
 // kernel's loads need; the sizes a model guarantees by construction (strides that cover the row, a 32-bit row count) are checked here.
-extern "C" int mia_op_attention_h64(mia_ctx* ctx, const void* qk, int64_t ld_qk, const void* vt, void* out, int64_t ld_out, int B, int T, int H,
-                                    int Tpad, int dtype, int mem) {
+// variant: one of attention.hip's kernel forms (ops.h MIA_ATT_*), or -1 for the form the encoder itself launches at this shape
+static int op_attention_h64(mia_ctx* ctx, const void* qk, int64_t ld_qk, const void* vt, void* out, int64_t ld_out, int B, int T, int H,
+                            int Tpad, int dtype, int variant, int mem) {
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, variant >= -1 && variant < MIA_ATT_NVARIANTS, "op_attention_h64: unknown kernel variant");
   MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "op_attention_h64: bad mem");
   MIA_CHECK_ARG(ctx, qk && vt && out, "op_attention_h64: null pointer");
   MIA_CHECK_ARG(ctx, dtype == MIA_BF16 || dtype == MIA_F16, "op_attention_h64: dtype must be MIA_BF16 or MIA_F16");
@@ -118,13 +120,22 @@ extern "C" int mia_op_attention_h64(mia_ctx* ctx, const void* qk, int64_t ld_qk,
     MIA_HIP(ctx, hipMemcpyAsync(ws + o_v, vt, vb, hipMemcpyHostToDevice, ctx->stream));
     d_qk = ws; d_vt = ws + o_v; d_out = ws + o_o;
   }
-  if (mia_enc_attention_launch(d_qk, ld_qk, d_vt, d_out, ld_out, B, T, H, Tpad, dtype, ctx->stream))
+  if (variant < 0 ? mia_enc_attention_launch(d_qk, ld_qk, d_vt, d_out, ld_out, B, T, H, Tpad, dtype, ctx->stream)
+                  : mia_enc_attention_launch_variant(d_qk, ld_qk, d_vt, d_out, ld_out, B, T, H, Tpad, dtype, variant, ctx->stream))
     return mia_fail(ctx, MIA_ERR_DEVICE, "op_attention_h64: launch failed");
   if (mem == MIA_MEM_HOST) {
     MIA_HIP(ctx, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, ctx->stream));
     MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return MIA_OK;
+}
+extern "C" int mia_op_attention_h64(mia_ctx* ctx, const void* qk, int64_t ld_qk, const void* vt, void* out, int64_t ld_out, int B, int T, int H,
+                                    int Tpad, int dtype, int mem) {
+  return op_attention_h64(ctx, qk, ld_qk, vt, out, ld_out, B, T, H, Tpad, dtype, -1, mem);
+}
+extern "C" int mia_op_attention_h64_variant(mia_ctx* ctx, const void* qk, int64_t ld_qk, const void* vt, void* out, int64_t ld_out, int B, int T,
+                                            int H, int Tpad, int dtype, int variant, int mem) {
+  return op_attention_h64(ctx, qk, ld_qk, vt, out, ld_out, B, T, H, Tpad, dtype, variant, mem);
 }
 
 // fp32 Conv1d / Linear on the exact-fp32 matrix cores (device pointers only): y[t][n] = act(b[n] + sum_{k,c} x[t*stride + k*dil - pad][c] w[n][k][c]) (+ r)

@@ -74,6 +74,8 @@ def _declare_enc(lib):
     lib.mia_op_linear_epi.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp] + [i32] * 12
     lib.mia_op_attention_h64.restype = i32
     lib.mia_op_attention_h64.argtypes = [vp, vp, i64, vp, vp, i64] + [i32] * 6
+    lib.mia_op_attention_h64_variant.restype = i32
+    lib.mia_op_attention_h64_variant.argtypes = [vp, vp, i64, vp, vp, i64] + [i32] * 7
     lib._enc_ops_declared = True
 
 
@@ -117,11 +119,41 @@ def attention_h64(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.ndarray
     return from_bits16(out, dtype)
 
 
+ATT_REG128, ATT_DMA128, ATT_DMA256 = 0, 1, 2      # csrc/ops.h MIA_ATT_*: queries per workgroup x K / V^T staging
+ATT_VARIANTS = {"reg128": ATT_REG128, "dma128": ATT_DMA128, "dma256": ATT_DMA256}
+
+
+def attention_h64_bits(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.ndarray, B: int, T: int, H: int, *, variant: int = -1,
+                       Tpad: int | None = None, ld_qk: int | None = None, ld_out: int | None = None, fill: float = 0.0,
+                       pad_fill: float = 0.0, dtype: int = _lib.BF16) -> np.ndarray:
+    """attention_h64 through mia_op_attention_h64_variant: the kernel form is the caller's choice (-1 = the one the encoder launches at
+    this T).  Returns the raw 16-bit output buffer, uint16 [B*T, ld_out]; from_bits16 widens it."""
+    _declare_enc(ctx.lib)
+    D = H * 64
+    Tpad = (T + 63) // 64 * 64 if Tpad is None else Tpad
+    ld_qk = 2 * D if ld_qk is None else ld_qk
+    ld_out = D if ld_out is None else ld_out
+    qk, vt = enc_attention_buffers(q, k, v, B, T, H, Tpad, ld_qk, pad_fill, dtype)
+    out = bits16(np.full((B * T, ld_out), fill, np.float32), dtype)
+    ctx.check(ctx.lib.mia_op_attention_h64_variant(ctx.h, qk.ctypes.data, ld_qk, vt.ctypes.data, out.ctypes.data, ld_out, B, T, H, Tpad, dtype,
+                                                   variant, _lib.MEM_HOST))
+    return out
+
+
 def attention_h64_device(ctx: _lib.Context, qk, vt, out, B: int, T: int, H: int, Tpad: int, ld_qk: int, ld_out: int, dtype: int) -> None:
     """mia_op_attention_h64 on torch device tensors (16-bit elements), in place."""
     _declare_enc(ctx.lib)
     assert qk.is_cuda and vt.is_cuda and out.is_cuda
     _run(ctx, lambda: ctx.lib.mia_op_attention_h64(ctx.h, _ptr(qk), ld_qk, _ptr(vt), _ptr(out), ld_out, B, T, H, Tpad, dtype, _lib.MEM_DEVICE))
+
+
+def attention_h64_device_variant(ctx: _lib.Context, qk, vt, out, B: int, T: int, H: int, Tpad: int, ld_qk: int, ld_out: int, dtype: int,
+                                 variant: int) -> None:
+    """mia_op_attention_h64_variant on torch device tensors (16-bit elements), in place."""
+    _declare_enc(ctx.lib)
+    assert qk.is_cuda and vt.is_cuda and out.is_cuda
+    _run(ctx, lambda: ctx.lib.mia_op_attention_h64_variant(ctx.h, _ptr(qk), ld_qk, _ptr(vt), _ptr(out), ld_out, B, T, H, Tpad, dtype, variant,
+                                                           _lib.MEM_DEVICE))
 
 
 def linear_epi(ctx: _lib.Context, x: np.ndarray, w: np.ndarray, bias, y: np.ndarray, vt, *, epi: int, T: int, H: int, Tpad: int = 0,
