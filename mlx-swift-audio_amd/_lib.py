@@ -1,4 +1,4 @@
-"""ctypes binding of lib/libmia.so (the C ABI in include/mia.h).
+"""ctypes binding of lib/libmia.so (the C ABI in include/mia.h); the prototypes themselves are the table in _abi.py.
 
 The product path never falls back to a CPU implementation: if the library is missing this module raises
 at load time, and if no gfx950 device is present `Context()` raises.
@@ -7,6 +7,9 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import threading
+
+from . import _abi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmia.so")
@@ -32,49 +35,22 @@ class MiaError(RuntimeError):
 
 
 _lib = None
+_load_lock = threading.Lock()
 
 
 def load() -> C.CDLL:
-    """Load libmia.so; raises (loudly) when the HIP extension has not been built."""
+    """Load libmia.so and bind every prototype of _abi.PROTOTYPES, once; raises (loudly) when the HIP extension has not been built."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            f"{LIB_PATH} not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(there is no CPU fallback)")
-    lib = C.CDLL(LIB_PATH)
-    _declare(lib)
-    _lib = lib
-    return lib
-
-
-def _declare(lib: C.CDLL) -> None:
-    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-    lib.mia_version.restype = C.c_char_p
-    lib.mia_version.argtypes = []
-    lib.mia_create.restype = vp
-    lib.mia_create.argtypes = [i32]
-    lib.mia_create_on_stream.restype = vp
-    lib.mia_create_on_stream.argtypes = [i32, vp]
-    lib.mia_destroy.restype = None
-    lib.mia_destroy.argtypes = [vp]
-    lib.mia_last_error.restype = C.c_char_p
-    lib.mia_last_error.argtypes = [vp]
-    lib.mia_stream.restype = vp
-    lib.mia_stream.argtypes = [vp]
-    lib.mia_synchronize.restype = i32
-    lib.mia_synchronize.argtypes = [vp]
-    lib.mia_profile_enable.restype = i32
-    lib.mia_profile_enable.argtypes = [vp, i32]
-    lib.mia_profile_reset.restype = i32
-    lib.mia_profile_reset.argtypes = [vp]
-    lib.mia_profile_read.restype = i32
-    lib.mia_profile_read.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    for name in ("mia_logmel_whisper", "mia_logmel_s3"):
-        f = getattr(lib, name)
-        f.restype = i32
-        f.argtypes = [vp, vp, vp, i32, i32, i64, i64, vp, i32, i32]
+    with _load_lock:
+        if _lib is None:
+            if not os.path.exists(LIB_PATH):
+                raise ImportError(
+                    f"{LIB_PATH} not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
+                    "(there is no CPU fallback)")
+            lib = C.CDLL(LIB_PATH)
+            _abi.apply(lib)
+            _lib = lib
+    return _lib
 
 
 class Context:

@@ -92,14 +92,7 @@ def f32_to_bf16(a: np.ndarray) -> np.ndarray:
 
 def s3gen_mel_spectrogram(ctx: _lib.Context, y) -> np.ndarray:
     """s3genMelSpectrogram(y:) with its defaults (Codec/S3Gen/Mel/S3GenMel.swift:43-102): 24 kHz mono float32 [T] -> [80, frames]."""
-    import ctypes as C
     lib = ctx.lib
-    if not getattr(lib, "_mel24_declared", False):
-        lib.mia_mel_s3gen_frames.restype = C.c_int64
-        lib.mia_mel_s3gen_frames.argtypes = [C.c_int64]
-        lib.mia_mel_s3gen.restype = C.c_int
-        lib.mia_mel_s3gen.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int]
-        lib._mel24_declared = True
     a = np.ascontiguousarray(y, np.float32).reshape(-1)
     frames = max(int(lib.mia_mel_s3gen_frames(a.shape[0])), 0)
     out = np.empty((80, frames), np.float32)
@@ -109,17 +102,10 @@ def s3gen_mel_spectrogram(ctx: _lib.Context, y) -> np.ndarray:
 
 def resample_audio(ctx: _lib.Context, audio, from_rate: int, to_rate: int) -> np.ndarray:
     """resampleAudio (TTS/CosyVoice2/CosyVoice2TTS.swift:733-744): plain linear interpolation, ratio in float32."""
-    import ctypes as C
     a = np.ascontiguousarray(audio, np.float32).reshape(-1)
     if from_rate == to_rate:
         return a
     lib = ctx.lib
-    if not getattr(lib, "_rs_declared", False):
-        lib.mia_resample_linear_len.restype = C.c_int64
-        lib.mia_resample_linear_len.argtypes = [C.c_int64, C.c_float]
-        lib.mia_resample_linear.restype = C.c_int
-        lib.mia_resample_linear.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int]
-        lib._rs_declared = True
     ratio = float(np.float32(to_rate) / np.float32(from_rate))
     out = np.empty(int(lib.mia_resample_linear_len(a.shape[0], ratio)), np.float32)
     ctx.check(lib.mia_resample_linear(ctx.h, a.ctypes.data, a.shape[0], ratio, out.ctypes.data, _lib.MEM_HOST))

@@ -68,10 +68,6 @@ def resample(ctx: _lib.Context, audio: np.ndarray, from_rate: int, to_rate: int)
     if from_rate == to_rate:
         return a
     lib = ctx.lib
-    lib.mia_resample_sinc_len.restype = C.c_int64
-    lib.mia_resample_sinc_len.argtypes = [C.c_int64, C.c_int, C.c_int]
-    lib.mia_resample_sinc.restype = C.c_int
-    lib.mia_resample_sinc.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int]
     n = int(lib.mia_resample_sinc_len(a.size, from_rate, to_rate))
     out = np.empty(max(n, 1), np.float32)
     got = C.c_int64(0)

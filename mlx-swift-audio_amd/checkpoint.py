@@ -4,7 +4,6 @@ reference's DEFAULT checkpoints, STT/Whisper/WhisperModel.swift:144-206) into th
 De-quantisation runs on the GPU (mia_dequant_affine); nothing here falls back to the CPU."""
 from __future__ import annotations
 
-import ctypes as C
 import json
 import mmap
 import struct
@@ -82,10 +81,6 @@ def _mia_dtype(a: np.ndarray) -> int:
 def dequantize_affine(ctx: _lib.Context, wq: np.ndarray, scales: np.ndarray, biases: np.ndarray, group_size: int = 64, bits: int = 4) -> np.ndarray:
     """GPU expansion of one quantised tensor to float32 [rows, cols]."""
     lib = ctx.lib
-    if not getattr(lib, "_dq_declared", False):
-        lib.mia_dequant_affine.restype = C.c_int
-        lib.mia_dequant_affine.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
-        lib._dq_declared = True
     w = np.ascontiguousarray(wq).view(np.uint32) if wq.dtype != np.uint32 else np.ascontiguousarray(wq)
     rows = int(np.prod(w.shape[:-1]))
     cols = w.shape[-1] * (32 // bits)

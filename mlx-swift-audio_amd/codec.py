@@ -8,68 +8,20 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .whisper import _TensorView
-
-
-class _SnacCfg(C.Structure):
-    _fields_ = [("latent_dim", C.c_int32), ("decoder_dim", C.c_int32), ("n_rates", C.c_int32), ("decoder_rates", C.c_int32 * 8),
-                ("n_vq", C.c_int32), ("vq_strides", C.c_int32 * 4), ("codebook_size", C.c_int32), ("codebook_dim", C.c_int32),
-                ("noise", C.c_int32), ("depthwise", C.c_int32)]
-
-
-class _DacCfg(C.Structure):
-    _fields_ = [("latent_dim", C.c_int32), ("decoder_dim", C.c_int32), ("n_rates", C.c_int32), ("decoder_rates", C.c_int32 * 8),
-                ("n_codebooks", C.c_int32), ("codebook_size", C.c_int32), ("codebook_dim", C.c_int32)]
-
-
-class _DacEncCfg(C.Structure):
-    _fields_ = [("encoder_dim", C.c_int32), ("n_rates", C.c_int32), ("encoder_rates", C.c_int32 * 8)]
-
-
-def _declare(lib):
-    if getattr(lib, "_codec_declared", False):
-        return
-    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-    lib.mia_dac_load_encoder.restype = i32
-    lib.mia_dac_load_encoder.argtypes = [vp, C.POINTER(_DacEncCfg), C.POINTER(_TensorView), i32]
-    lib.mia_dac_code_len.restype = i64
-    lib.mia_dac_code_len.argtypes = [vp, i64]
-    lib.mia_dac_encode.restype = i32
-    lib.mia_dac_encode.argtypes = [vp, vp, i64, i32, vp, i64, C.POINTER(i64), i32]
-    lib.mia_snac_load.restype = vp
-    lib.mia_snac_load.argtypes = [vp, C.POINTER(_SnacCfg), C.POINTER(_TensorView), i32]
-    lib.mia_dac_load.restype = vp
-    lib.mia_dac_load.argtypes = [vp, C.POINTER(_DacCfg), C.POINTER(_TensorView), i32]
-    lib.mia_codec_free.restype = None
-    lib.mia_codec_free.argtypes = [vp]
-    lib.mia_codec_output_len.restype = i64
-    lib.mia_codec_output_len.argtypes = [vp, i64]
-    lib.mia_codec_noise_len.restype = i64
-    lib.mia_codec_noise_len.argtypes = [vp, i64]
-    lib.mia_snac_decode.restype = i32
-    lib.mia_snac_decode.argtypes = [vp, C.POINTER(vp), vp, i32, vp, i64, vp, i64, C.POINTER(i64), i32]
-    lib.mia_dac_decode.restype = i32
-    lib.mia_dac_decode.argtypes = [vp, vp, i32, i64, vp, i64, C.POINTER(i64), i32]
-    lib.mia_snac_decode_batch.restype = i32
-    lib.mia_snac_decode_batch.argtypes = [vp, i32, vp, vp, i32, vp, i64, vp, vp, vp, i32]
-    lib.mia_dac_decode_batch.restype = i32
-    lib.mia_dac_decode_batch.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, i32]
-    lib.mia_codec_set_stack_budget.restype = i32
-    lib.mia_codec_set_stack_budget.argtypes = [vp, i64]
-    lib._codec_declared = True
+from ._abi import DacConfig, DacEncoderConfig, SnacConfig, TensorView
 
 
 MAX_BATCH = 64          # utterances per mia_*_decode_batch call
 
 
 def _views(weights):
-    views = (_TensorView * len(weights))()
+    views = (TensorView * len(weights))()
     keep = []
     for i, (name, arr) in enumerate(weights.items()):
         a = np.ascontiguousarray(arr, np.float32)
         keep.append(a)
         shp = (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim)))
-        views[i] = _TensorView(name.encode(), _lib.F32, a.ndim, shp, a.ctypes.data)
+        views[i] = TensorView(name.encode(), _lib.F32, a.ndim, shp, a.ctypes.data)
     return views, keep
 
 
@@ -103,9 +55,8 @@ class _Codec:
 class SNACDecoder(_Codec):
     @staticmethod
     def load(ctx: _lib.Context, cfg, weights: dict[str, np.ndarray]) -> "SNACDecoder":
-        _declare(ctx.lib)
-        c = _SnacCfg(cfg.latent_dim, cfg.decoder_dim, len(cfg.decoder_rates), (C.c_int32 * 8)(*cfg.decoder_rates), len(cfg.vq_strides),
-                     (C.c_int32 * 4)(*cfg.vq_strides), cfg.codebook_size, cfg.codebook_dim, 1 if cfg.noise else 0, 1 if cfg.depthwise else 0)
+        c = SnacConfig(cfg.latent_dim, cfg.decoder_dim, len(cfg.decoder_rates), (C.c_int32 * 8)(*cfg.decoder_rates), len(cfg.vq_strides),
+                       (C.c_int32 * 4)(*cfg.vq_strides), cfg.codebook_size, cfg.codebook_dim, 1 if cfg.noise else 0, 1 if cfg.depthwise else 0)
         views, keep = _views(weights)
         h = ctx.lib.mia_snac_load(ctx.h, C.byref(c), views, len(weights))
         if not h:
@@ -150,16 +101,15 @@ class SNACDecoder(_Codec):
 class DACCodec(_Codec):
     @staticmethod
     def load(ctx: _lib.Context, cfg, weights: dict[str, np.ndarray]) -> "DACCodec":
-        _declare(ctx.lib)
-        c = _DacCfg(cfg.latent_dim, cfg.decoder_dim, len(cfg.decoder_rates), (C.c_int32 * 8)(*cfg.decoder_rates), cfg.n_codebooks,
-                    cfg.codebook_size, cfg.codebook_dim)
+        c = DacConfig(cfg.latent_dim, cfg.decoder_dim, len(cfg.decoder_rates), (C.c_int32 * 8)(*cfg.decoder_rates), cfg.n_codebooks,
+                      cfg.codebook_size, cfg.codebook_dim)
         views, keep = _views(weights)
         h = ctx.lib.mia_dac_load(ctx.h, C.byref(c), views, len(weights))
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
         codec = DACCodec(ctx, h, cfg)
         if "encoder.block.layers.0.weight_v" in weights:            # checkpoints carry the encoder; decode-only callers may drop it
-            e = _DacEncCfg(cfg.encoder_dim, len(cfg.encoder_rates), (C.c_int32 * 8)(*cfg.encoder_rates))
+            e = DacEncoderConfig(cfg.encoder_dim, len(cfg.encoder_rates), (C.c_int32 * 8)(*cfg.encoder_rates))
             ctx.check(ctx.lib.mia_dac_load_encoder(h, C.byref(e), views, len(weights)))
         return codec
 

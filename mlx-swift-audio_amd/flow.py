@@ -7,28 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .whisper import _TensorView
-
-
-class _FlowCfg(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("input_size", "output_size", "spk_embed_dim", "vocab_size", "pre_lookahead_len", "n_timesteps",
-                                         "enc_heads", "enc_linear_units", "enc_blocks", "enc_up_blocks", "upsample_stride",
-                                         "dec_in_channels", "dec_channels", "dec_heads", "dec_n_blocks", "dec_mid_blocks")] + [("cfg_rate", C.c_float)]
-
-
-def _declare(lib):
-    if getattr(lib, "_flow_declared", False):
-        return
-    vp, i32 = C.c_void_p, C.c_int
-    lib.mia_flow_load.restype = vp
-    lib.mia_flow_load.argtypes = [vp, C.POINTER(_FlowCfg), C.POINTER(_TensorView), i32]
-    lib.mia_flow_free.restype = None
-    lib.mia_flow_free.argtypes = [vp]
-    lib.mia_flow_encode.restype = i32
-    lib.mia_flow_encode.argtypes = [vp, vp, i32, vp, i32]
-    lib.mia_flow_inference.restype = i32
-    lib.mia_flow_inference.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32]
-    lib._flow_declared = True
+from ._abi import FlowConfig, TensorView
 
 
 class FlowModule:
@@ -38,16 +17,15 @@ class FlowModule:
 
     @staticmethod
     def load(ctx: _lib.Context, cfg, weights: dict[str, np.ndarray]) -> "FlowModule":
-        _declare(ctx.lib)
-        c = _FlowCfg(cfg.input_size, cfg.output_size, cfg.spk_embed_dim, cfg.vocab_size, cfg.pre_lookahead_len, cfg.n_timesteps,
-                     cfg.enc_heads, cfg.enc_linear_units, cfg.enc_blocks, cfg.enc_up_blocks, cfg.upsample_stride,
-                     cfg.dec_in_channels, cfg.dec_channels, cfg.dec_heads, cfg.dec_n_blocks, cfg.dec_mid_blocks, cfg.cfg_rate)
-        views = (_TensorView * len(weights))()
+        c = FlowConfig(cfg.input_size, cfg.output_size, cfg.spk_embed_dim, cfg.vocab_size, cfg.pre_lookahead_len, cfg.n_timesteps,
+                       cfg.enc_heads, cfg.enc_linear_units, cfg.enc_blocks, cfg.enc_up_blocks, cfg.upsample_stride,
+                       cfg.dec_in_channels, cfg.dec_channels, cfg.dec_heads, cfg.dec_n_blocks, cfg.dec_mid_blocks, cfg.cfg_rate)
+        views = (TensorView * len(weights))()
         keep = []
         for i, (name, arr) in enumerate(weights.items()):
             a = np.ascontiguousarray(arr, np.float32)
             keep.append(a)
-            views[i] = _TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
+            views[i] = TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
         h = ctx.lib.mia_flow_load(ctx.h, C.byref(c), views, len(weights))
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
@@ -76,9 +54,6 @@ class FlowModule:
         """inference(...) with the modules' chunked-synthesis switches (mia_flow_inference_streaming): finalize = False trims the encoder's
         look-ahead frames (z is then [80, T - pre_lookahead_len * upsample_stride]); *_static_chunk > 0 = streaming attention masks."""
         lib = self.ctx.lib
-        lib.mia_flow_inference_streaming.restype = C.c_int
-        lib.mia_flow_inference_streaming.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                                     C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_int]
         t = np.ascontiguousarray(token, np.int32)
         pt = np.ascontiguousarray(prompt_token, np.int32)
         pf = np.ascontiguousarray(prompt_feat, np.float32).reshape(-1, self.cfg.output_size)
@@ -102,8 +77,6 @@ class FlowModule:
         (token, prompt_token, prompt_feat, embedding, z) tuples with the shapes inference() takes; returns their mels in order, each
         bit-identical to its own inference() call."""
         lib = self.ctx.lib
-        lib.mia_flow_inference_batch.restype = C.c_int
-        lib.mia_flow_inference_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p, C.c_int]
         U = len(utterances)
         keep, mels = [], []
         ptr = lambda n: (C.c_void_p * n)()

@@ -8,9 +8,8 @@ from dataclasses import dataclass, fields, replace
 
 import numpy as np
 
-from . import _lib
+from . import _abi, _lib
 from .lm import FunASRDecoder
-from .whisper import _TensorView
 
 
 @dataclass
@@ -41,31 +40,6 @@ SENSEVOICE_CONFIGS = {
 }
 
 
-class _SvCfg(C.Structure):
-    _fields_ = [(f.name, C.c_int32) for f in fields(SenseVoiceConfig)]
-
-
-def _declare(lib):
-    if getattr(lib, "_sensevoice_declared", False):
-        return
-    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-    lib.mia_sensevoice_load.restype = vp
-    lib.mia_sensevoice_load.argtypes = [vp, C.POINTER(_SvCfg), C.POINTER(_TensorView), i32, i32]
-    lib.mia_sensevoice_free.restype = None
-    lib.mia_sensevoice_free.argtypes = [vp]
-    lib.mia_sensevoice_features.restype = i32
-    lib.mia_sensevoice_features.argtypes = [vp, vp, vp, i32, vp, vp, i64, i32]
-    lib.mia_sensevoice_feature_rows.restype = i64
-    lib.mia_sensevoice_feature_rows.argtypes = [vp, i32]
-    lib.mia_op_funasr_logmel.restype = i32
-    lib.mia_op_funasr_logmel.argtypes = [vp, vp, vp, i32, vp, i32]
-    lib.mia_sensevoice_encode.restype = i32
-    lib.mia_sensevoice_encode.argtypes = [vp, vp, vp, i32, vp, vp, vp, i32]
-    lib.mia_sensevoice_encode_audio.restype = i32
-    lib.mia_sensevoice_encode_audio.argtypes = [vp, vp, vp, i32, vp, vp, i32]
-    lib._sensevoice_declared = True
-
-
 def _stack_clips(clips):
     clips = [np.ascontiguousarray(c, np.float32).reshape(-1) for c in clips]
     offs = np.zeros(len(clips) + 1, np.int64)
@@ -80,7 +54,6 @@ def _split(rows: np.ndarray, counts) -> list[np.ndarray]:
 
 def features(ctx: _lib.Context, clips) -> list[np.ndarray]:
     """preprocessAudio (STT/FunASR/FunASRAudio.swift:197-216) per clip of 16 kHz audio: fp32 [ceil((1 + L // 160) / 6), 560] each."""
-    _declare(ctx.lib)
     pcm, offs = _stack_clips(clips)
     rows = int(ctx.lib.mia_sensevoice_feature_rows(offs.ctypes.data, len(clips)))
     if rows < 0:
@@ -93,7 +66,6 @@ def features(ctx: _lib.Context, clips) -> list[np.ndarray]:
 
 def log_mel(ctx: _lib.Context, clips) -> list[np.ndarray]:
     """funASRLogMelSpectrogram per clip (mia_op_funasr_logmel, the front end's test tap): fp32 [1 + L // 160, 80], natural log."""
-    _declare(ctx.lib)
     pcm, offs = _stack_clips(clips)
     frames = [1 + int(offs[i + 1] - offs[i]) // 160 for i in range(len(clips))]
     out = np.zeros((sum(frames), 80), np.float32)
@@ -110,14 +82,13 @@ class SenseVoiceEncoder:
     def load(ctx: _lib.Context, cfg: SenseVoiceConfig, weights: dict[str, np.ndarray], dtype: int = _lib.BF16) -> "SenseVoiceEncoder":
         """weights: float32 arrays under the reference's Module keys (audio_encoder.*, audio_adaptor.*); a quantised checkpoint goes through
         checkpoint.expand_checkpoint first."""
-        _declare(ctx.lib)
-        c = _SvCfg(*[getattr(cfg, f.name) for f in fields(SenseVoiceConfig)])
-        views = (_TensorView * max(len(weights), 1))()
+        c = _abi.SensevoiceConfig(*[getattr(cfg, f.name) for f in fields(SenseVoiceConfig)])
+        views = (_abi.TensorView * max(len(weights), 1))()
         keep = []
         for i, (name, arr) in enumerate(weights.items()):
             a = np.ascontiguousarray(arr, np.float32)
             keep.append(a)
-            views[i] = _TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
+            views[i] = _abi.TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
         h = ctx.lib.mia_sensevoice_load(ctx.h, C.byref(c), views, len(weights), dtype)
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())

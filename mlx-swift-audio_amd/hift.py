@@ -8,39 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .whisper import _TensorView
-
-
-class _HiftCfg(C.Structure):
-    _fields_ = [("in_channels", C.c_int32), ("base_channels", C.c_int32), ("nb_harmonics", C.c_int32), ("sampling_rate", C.c_int32),
-                ("n_ups", C.c_int32), ("up_rates", C.c_int32 * 4), ("up_kernels", C.c_int32 * 4),
-                ("n_res_kernels", C.c_int32), ("res_kernels", C.c_int32 * 4), ("src_res_kernels", C.c_int32 * 4),
-                ("n_dilations", C.c_int32), ("dilations", C.c_int32 * 4),
-                ("nsf_alpha", C.c_float), ("nsf_sigma", C.c_float), ("voiced_threshold", C.c_float), ("lrelu_slope", C.c_float),
-                ("audio_limit", C.c_float)]
-
-
-def _declare(lib):
-    if getattr(lib, "_hift_declared", False):
-        return
-    vp, i32 = C.c_void_p, C.c_int
-    lib.mia_hift_load.restype = vp
-    lib.mia_hift_load.argtypes = [vp, C.POINTER(_HiftCfg), C.POINTER(_TensorView), i32]
-    lib.mia_hift_free.restype = None
-    lib.mia_hift_free.argtypes = [vp]
-    lib.mia_hift_upsample_factor.restype = i32
-    lib.mia_hift_upsample_factor.argtypes = [vp]
-    lib.mia_hift_f0.restype = i32
-    lib.mia_hift_f0.argtypes = [vp, vp, i32, vp, i32]
-    lib.mia_hift_source.restype = i32
-    lib.mia_hift_source.argtypes = [vp, vp, i32, vp, vp, i32]
-    lib.mia_hift_decode.restype = i32
-    lib.mia_hift_decode.argtypes = [vp, vp, i32, vp, vp, i32]
-    lib.mia_hift_vocode.restype = i32
-    lib.mia_hift_vocode.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, i32]
-    lib.mia_hift_vocode_batch.restype = i32
-    lib.mia_hift_vocode_batch.argtypes = [vp, vp, vp, i32, vp, vp, i32]
-    lib._hift_declared = True
+from ._abi import HiftConfig, TensorView
 
 
 def _pad4(v):
@@ -56,19 +24,18 @@ class HiFTGenerator:
 
     @staticmethod
     def load(ctx: _lib.Context, cfg, weights: dict[str, np.ndarray]) -> "HiFTGenerator":
-        _declare(ctx.lib)
         if cfg.n_fft != 16 or cfg.hop != 4:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, "HiFT: only istft n_fft 16 / hop 4 is built")
-        c = _HiftCfg(cfg.in_channels, cfg.base_channels, cfg.nb_harmonics, cfg.sampling_rate, len(cfg.up_rates), _pad4(cfg.up_rates),
-                     _pad4(cfg.up_kernels), len(cfg.res_kernels), _pad4(cfg.res_kernels), _pad4(cfg.src_res_kernels),
-                     len(cfg.dilations), _pad4(cfg.dilations), cfg.nsf_alpha, cfg.nsf_sigma, cfg.voiced_threshold, cfg.lrelu_slope,
-                     cfg.audio_limit)
-        views = (_TensorView * len(weights))()
+        c = HiftConfig(cfg.in_channels, cfg.base_channels, cfg.nb_harmonics, cfg.sampling_rate, len(cfg.up_rates), _pad4(cfg.up_rates),
+                       _pad4(cfg.up_kernels), len(cfg.res_kernels), _pad4(cfg.res_kernels), _pad4(cfg.src_res_kernels),
+                       len(cfg.dilations), _pad4(cfg.dilations), cfg.nsf_alpha, cfg.nsf_sigma, cfg.voiced_threshold, cfg.lrelu_slope,
+                       cfg.audio_limit)
+        views = (TensorView * len(weights))()
         keep = []
         for i, (name, arr) in enumerate(weights.items()):
             a = np.ascontiguousarray(arr, np.float32)
             keep.append(a)
-            views[i] = _TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
+            views[i] = TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
         h = ctx.lib.mia_hift_load(ctx.h, C.byref(c), views, len(weights))
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())

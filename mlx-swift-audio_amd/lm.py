@@ -7,44 +7,13 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .whisper import _TensorView
+from ._abi import LmConfig, LmSampler, RasParams, TensorView
 
 END_TOKEN = 128258                    # OrpheusTTS.swift:75-85
 CODE_OFFSET = 128266
 AUDIO_CODE_DATA_START_MARKER = 128257
 MAX_TOKEN_COUNT = 1200
 REPETITION_CONTEXT_SIZE = 20
-
-
-class _LmCfg(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("vocab", "hidden", "inter", "n_layers", "n_heads", "n_kv_heads", "head_dim", "max_ctx")] + \
-               [("rms_eps", C.c_float), ("rope_theta", C.c_float), ("rope_llama3", C.c_int32), ("rope_factor", C.c_float),
-                ("rope_low", C.c_float), ("rope_high", C.c_float), ("rope_old_ctx", C.c_int32), ("qkv_bias", C.c_int32),
-                ("tie_embeddings", C.c_int32)]
-
-
-class _Sampler(C.Structure):
-    _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("rep_penalty", C.c_float), ("rep_window", C.c_int32),
-                ("max_new_tokens", C.c_int32), ("n_stop", C.c_int32), ("stop_ids", C.c_int32 * 4), ("reserved", C.c_int32)]
-
-
-def _declare(lib):
-    if getattr(lib, "_lm_declared", False):
-        return
-    vp, i32 = C.c_void_p, C.c_int
-    lib.mia_lm_load.restype = vp
-    lib.mia_lm_load.argtypes = [vp, C.POINTER(_LmCfg), C.POINTER(_TensorView), i32, i32]
-    lib.mia_lm_free.restype = None
-    lib.mia_lm_free.argtypes = [vp]
-    lib.mia_lm_reset.restype = i32
-    lib.mia_lm_reset.argtypes = [vp]
-    lib.mia_lm_forward.restype = i32
-    lib.mia_lm_forward.argtypes = [vp, vp, i32, vp]
-    lib.mia_lm_generate.restype = i32
-    lib.mia_lm_generate.argtypes = [vp, vp, i32, C.POINTER(_Sampler), vp, vp, vp]
-    lib.mia_sample_top_p.restype = i32
-    lib.mia_sample_top_p.argtypes = [vp, vp, i32, vp, i32, C.c_float, C.c_float, C.c_float, C.c_float, vp]
-    lib._lm_declared = True
 
 
 class CausalLM:
@@ -54,11 +23,10 @@ class CausalLM:
 
     @staticmethod
     def load(ctx: _lib.Context, cfg, weights: dict[str, np.ndarray], dtype: int = _lib.BF16) -> "CausalLM":
-        _declare(ctx.lib)
-        c = _LmCfg(cfg.vocab, cfg.hidden, cfg.inter, cfg.n_layers, cfg.n_heads, cfg.n_kv_heads, cfg.head_dim, cfg.max_ctx, cfg.rms_eps,
-                   cfg.rope_theta, 1 if cfg.rope_llama3 else 0, cfg.rope_factor, cfg.rope_low, cfg.rope_high, cfg.rope_old_ctx,
-                   1 if cfg.qkv_bias else 0, 1 if cfg.tie_embeddings else 0)
-        views = (_TensorView * len(weights))()
+        c = LmConfig(cfg.vocab, cfg.hidden, cfg.inter, cfg.n_layers, cfg.n_heads, cfg.n_kv_heads, cfg.head_dim, cfg.max_ctx, cfg.rms_eps,
+                     cfg.rope_theta, 1 if cfg.rope_llama3 else 0, cfg.rope_factor, cfg.rope_low, cfg.rope_high, cfg.rope_old_ctx,
+                     1 if cfg.qkv_bias else 0, 1 if cfg.tie_embeddings else 0)
+        views = (TensorView * len(weights))()
         keep = []
         for i, (name, arr) in enumerate(weights.items()):
             if arr.dtype == np.float16:
@@ -67,7 +35,7 @@ class CausalLM:
                 a, dt = np.ascontiguousarray(arr, np.float32), _lib.F32
             keep.append(a)
             shp = (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim)))
-            views[i] = _TensorView(name.encode(), dt, a.ndim, shp, a.ctypes.data)
+            views[i] = TensorView(name.encode(), dt, a.ndim, shp, a.ctypes.data)
         h = ctx.lib.mia_lm_load(ctx.h, C.byref(c), views, len(weights), dtype)
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
@@ -78,9 +46,7 @@ class CausalLM:
         `<name>.scales` / `<name>.biases` float16 (or uint16 arrays tagged .st_dtype == "BF16", as checkpoint.read_safetensors returns
         bf16 payloads).  The handle must have been loaded from the de-quantised tensors of the same checkpoint."""
         lib = self.ctx.lib
-        lib.mia_lm_attach_quantized.restype = C.c_int
-        lib.mia_lm_attach_quantized.argtypes = [C.c_void_p, C.POINTER(_TensorView), C.c_int, C.c_int, C.c_int]
-        views = (_TensorView * len(packed))()
+        views = (TensorView * len(packed))()
         keep = []
         for i, (name, arr) in enumerate(packed.items()):
             a = np.ascontiguousarray(arr)
@@ -94,27 +60,21 @@ class CausalLM:
                 raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, f"attach_q4: '{name}' must be uint32 codes or 16-bit scales / biases (got {a.dtype})")
             keep.append(a)
             shp = (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim)))
-            views[i] = _TensorView(name.encode(), dt, a.ndim, shp, a.ctypes.data)
+            views[i] = TensorView(name.encode(), dt, a.ndim, shp, a.ctypes.data)
         self.ctx.check(lib.mia_lm_attach_quantized(self.h, views, len(packed), group_size, bits))
 
     def set_debug(self, flags: int) -> None:
         """Test hook (mia_lm_set_debug): bit 0 = no hipGraph, bit 1 = prompts token by token (no batched prompt pass)."""
         lib = self.ctx.lib
-        lib.mia_lm_set_debug.restype = C.c_int
-        lib.mia_lm_set_debug.argtypes = [C.c_void_p, C.c_int]
         self.ctx.check(lib.mia_lm_set_debug(self.h, int(flags)))
 
     def set_prompt_attention(self, mode: int) -> None:
         """mia_lm_set_prompt_attention: 0 = the prompt pass's row kernel (default), 1 = the tiled matrix-core kernel on the 16-bit cache."""
         lib = self.ctx.lib
-        lib.mia_lm_set_prompt_attention.restype = C.c_int
-        lib.mia_lm_set_prompt_attention.argtypes = [C.c_void_p, C.c_int]
         self.ctx.check(lib.mia_lm_set_prompt_attention(self.h, int(mode)))
 
     def use_q4(self, on: bool) -> None:
         lib = self.ctx.lib
-        lib.mia_lm_use_q4.restype = C.c_int
-        lib.mia_lm_use_q4.argtypes = [C.c_void_p, C.c_int]
         self.ctx.check(lib.mia_lm_use_q4(self.h, 1 if on else 0))
 
     def close(self):
@@ -144,25 +104,15 @@ class CausalLM:
         u = np.ascontiguousarray(uniforms, np.float32)
         if u.size < max_new_tokens:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, "need one uniform per possible draw")
-        sp = _Sampler(temperature, top_p, rep_penalty, rep_window, max_new_tokens, len(stop_ids), (C.c_int32 * 4)(*(list(stop_ids) + [0] * (4 - len(stop_ids)))), 0)
+        sp = LmSampler(temperature, top_p, rep_penalty, rep_window, max_new_tokens, len(stop_ids), (C.c_int32 * 4)(*(list(stop_ids) + [0] * (4 - len(stop_ids)))), 0)
         out = np.zeros(max_new_tokens, np.int32)
         n = C.c_int32(0)
         self.ctx.check(self.ctx.lib.mia_lm_generate(self.h, a.ctypes.data, a.size, C.byref(sp), u.ctypes.data, out.ctypes.data, C.byref(n)))
         return out[:n.value].tolist()
 
 
-def _declare_batch(lib):
-    if not getattr(lib, "_lm_batch_declared", False):
-        lib.mia_lm_set_batch.restype = C.c_int
-        lib.mia_lm_set_batch.argtypes = [C.c_void_p, C.c_int]
-        lib.mia_lm_generate_batch.restype = C.c_int
-        lib.mia_lm_generate_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_Sampler), C.c_void_p, C.c_void_p, C.c_void_p]
-        lib._lm_batch_declared = True
-
-
 def _set_batch(self, max_batch: int) -> None:
     """Size the per-sequence state for up to `max_batch` (<= 32) sequences decoded side by side."""
-    _declare_batch(self.ctx.lib)
     self.ctx.check(self.ctx.lib.mia_lm_set_batch(self.h, int(max_batch)))
 
 
@@ -178,10 +128,9 @@ def _generate_batch(self, prompts, uniforms, temperature=0.6, top_p=0.8, rep_pen
     offs = np.zeros(n_seq + 1, np.int32)
     np.cumsum([len(p) for p in prompts], out=offs[1:])
     flat = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int32) for p in prompts]))
-    sp = _Sampler(temperature, top_p, rep_penalty, rep_window, max_new_tokens, len(stop_ids), (C.c_int32 * 4)(*(list(stop_ids) + [0] * (4 - len(stop_ids)))), 0)
+    sp = LmSampler(temperature, top_p, rep_penalty, rep_window, max_new_tokens, len(stop_ids), (C.c_int32 * 4)(*(list(stop_ids) + [0] * (4 - len(stop_ids)))), 0)
     out = np.zeros((n_seq, max_new_tokens), np.int32)
     n = np.zeros(n_seq, np.int32)
-    _declare_batch(self.ctx.lib)
     self.ctx.check(self.ctx.lib.mia_lm_generate_batch(self.h, flat.ctypes.data, offs.ctypes.data, n_seq, C.byref(sp), u.ctypes.data, out.ctypes.data, n.ctypes.data))
     return [out[b, :n[b]].tolist() for b in range(n_seq)]
 
@@ -194,16 +143,12 @@ def _new_cache(self, quantized: bool = False, group_size: int = 64, bits: int = 
     """OrpheusModel.newCache(quantized:groupSize:bits:) (TransformerBlock.swift:182-201): quantized=True keeps K/V as 4- / 8-bit codes plus
     a (scale, bias) pair per 64 values (mia_lm_set_kv_quant), False restores the 16-bit caches.  Every sequence is reset either way."""
     lib = self.ctx.lib
-    lib.mia_lm_set_kv_quant.restype = C.c_int
-    lib.mia_lm_set_kv_quant.argtypes = [C.c_void_p, C.c_int, C.c_int]
     self.ctx.check(lib.mia_lm_set_kv_quant(self.h, int(bits) if quantized else 0, int(group_size)))
 
 
 def _read_kv(self, layer: int, seq: int, pos0: int, n: int) -> tuple[np.ndarray, np.ndarray]:
     """Test hook (mia_lm_read_kv): cache rows [pos0, pos0 + n) of (layer, seq) as fp32 (k, v), each [n_kv_heads, n, head_dim]."""
     lib = self.ctx.lib
-    lib.mia_lm_read_kv.restype = C.c_int
-    lib.mia_lm_read_kv.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     k = np.empty((self.cfg.n_kv_heads, max(int(n), 0), self.cfg.head_dim), np.float32)
     v = np.empty_like(k)
     self.ctx.check(lib.mia_lm_read_kv(self.h, int(layer), int(seq), int(pos0), int(n), k.ctypes.data, v.ctypes.data))
@@ -217,12 +162,8 @@ CausalLM.read_kv = _read_kv
 def _generate_ras(self, prompt_embeds, uniforms, min_len, max_len, eos, top_p=0.8, top_k=25, win=10, tau=0.1) -> list[int]:
     """mia_lm_generate_ras: embedding-row prompt -> RAS-sampled ids (stops at `eos` once min_len ids are out, or at max_len)."""
     lib = self.ctx.lib
-    if not getattr(lib, "_ras_declared", False):
-        lib.mia_lm_generate_ras.restype = C.c_int
-        lib.mia_lm_generate_ras.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_Ras), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        lib._ras_declared = True
     x = np.ascontiguousarray(prompt_embeds, np.float32)
-    rp = _Ras(top_p, top_k, win, tau, eos, min_len, max_len)
+    rp = RasParams(top_p, top_k, win, tau, eos, min_len, max_len)
     u = np.ascontiguousarray(uniforms, np.float32)
     out = np.zeros(max_len + 1, np.int32)
     n = C.c_int32(0)
@@ -236,16 +177,12 @@ CausalLM.generate_ras = _generate_ras
 def _generate_ras_batch(self, prompt_embeds, uniforms, min_lens, max_lens, eos, top_p=0.8, top_k=25, win=10, tau=0.1) -> list[list[int]]:
     """mia_lm_generate_ras_batch: one embedding-row prompt, (min_len, max_len) pair and uniform row per utterance; set_batch(n) first."""
     lib = self.ctx.lib
-    if not getattr(lib, "_ras_batch_declared", False):
-        lib.mia_lm_generate_ras_batch.restype = C.c_int
-        lib.mia_lm_generate_ras_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_Ras), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        lib._ras_batch_declared = True
     n_seq = len(prompt_embeds)
     xs = [np.ascontiguousarray(x, np.float32) for x in prompt_embeds]
     offs = np.zeros(n_seq + 1, np.int32)
     np.cumsum([x.shape[0] for x in xs], out=offs[1:])
     flat = np.ascontiguousarray(np.concatenate(xs, axis=0))
-    rps = (_Ras * n_seq)(*[_Ras(top_p, top_k, win, tau, eos, int(min_lens[b]), int(max_lens[b])) for b in range(n_seq)])
+    rps = (RasParams * n_seq)(*[RasParams(top_p, top_k, win, tau, eos, int(min_lens[b]), int(max_lens[b])) for b in range(n_seq)])
     u = np.ascontiguousarray(uniforms, np.float32)
     if u.ndim != 2 or u.shape[0] != n_seq:
         raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, "uniforms must be [n_seq, n_uniforms]")
@@ -267,10 +204,6 @@ def _generate_greedy(self, prompt_embeds, stop_ids, max_new_tokens: int) -> list
     """mia_lm_generate_greedy: embedding-row prompt [n, hidden] -> argmax ids (lowest index on ties) until one of `stop_ids` (1..4 of them;
     the stop id is not returned) or `max_new_tokens` ids."""
     lib = self.ctx.lib
-    if not getattr(lib, "_greedy_declared", False):
-        lib.mia_lm_generate_greedy.restype = C.c_int
-        lib.mia_lm_generate_greedy.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        lib._greedy_declared = True
     x = np.ascontiguousarray(prompt_embeds, np.float32).reshape(-1, self.cfg.hidden)
     stop = _stop_array(stop_ids)
     out = np.zeros(max(int(max_new_tokens), 1), np.int32)
@@ -283,10 +216,6 @@ def _generate_greedy_batch(self, prompt_embeds, stop_ids, max_new_tokens: int) -
     """mia_lm_generate_greedy_batch: one embedding-row prompt per utterance, decoded side by side (set_batch(n) first); utterance b's ids
     equal generate_greedy(prompt_embeds[b], ...) on the same handle capacity."""
     lib = self.ctx.lib
-    if not getattr(lib, "_greedy_batch_declared", False):
-        lib.mia_lm_generate_greedy_batch.restype = C.c_int
-        lib.mia_lm_generate_greedy_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        lib._greedy_batch_declared = True
     n_seq = len(prompt_embeds)
     xs = [np.ascontiguousarray(x, np.float32).reshape(-1, self.cfg.hidden) for x in prompt_embeds]
     offs = np.zeros(n_seq + 1, np.int32)
@@ -307,7 +236,6 @@ CausalLM.generate_greedy_batch = _generate_greedy_batch
 
 def sample_next_token(ctx: _lib.Context, logits: np.ndarray, history, uniform: float, temperature=0.6, top_p=0.8, rep_penalty=1.3) -> int:
     """sampleNextToken(logits:history:temperature:topP:repetitionPenalty:) with an explicit uniform for the categorical draw."""
-    _declare(ctx.lib)
     lg = np.ascontiguousarray(logits, np.float32)
     h = np.ascontiguousarray(history, np.int32)
     out = C.c_int32(0)
@@ -328,11 +256,6 @@ def parse_output(tokens: list[int]) -> list[list[int]]:
         l1.append(f[b]); l2.append(f[b + 1] - 4096); l3.append(f[b + 2] - 2 * 4096); l3.append(f[b + 3] - 3 * 4096)
         l2.append(f[b + 4] - 4 * 4096); l3.append(f[b + 5] - 5 * 4096); l3.append(f[b + 6] - 6 * 4096)
     return [l1, l2, l3]
-
-
-class _Ras(C.Structure):
-    _fields_ = [("top_p", C.c_float), ("top_k", C.c_int32), ("win", C.c_int32), ("tau", C.c_float), ("eos", C.c_int32),
-                ("min_len", C.c_int32), ("max_len", C.c_int32)]
 
 
 class Qwen2LM:

@@ -6,20 +6,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._abi import ConvGemmDesc, SkinnyDesc
 from . import audio as _audio
-
-
-def _declare(lib):
-    if getattr(lib, "_ops_declared", False):
-        return
-    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-    lib.mia_op_linear.restype = i32
-    lib.mia_op_linear.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32]
-    lib.mia_op_attention_h128.restype = i32
-    lib.mia_op_attention_h128.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, C.c_float, vp, i32, i32]
-    lib.mia_op_fsmn_add.restype = i32
-    lib.mia_op_fsmn_add.argtypes = [vp, vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, vp, i32, i32]
-    lib._ops_declared = True
 
 
 def to16(a: np.ndarray, dtype: int) -> np.ndarray:
@@ -33,7 +21,6 @@ def from16(a: np.ndarray, dtype: int) -> np.ndarray:
 def linear(ctx: _lib.Context, x: np.ndarray, w: np.ndarray, bias=None, residual=None, act: str | None = None,
            dtype: int = _lib.BF16, out_f32: bool = False, variant: int = 1) -> np.ndarray:
     """y = act(x @ w.T + bias) + residual on the GPU; x [M,K], w [N,K] fp32 (rounded to `dtype` here)."""
-    _declare(ctx.lib)
     M, K = x.shape
     N = w.shape[0]
     x16, w16 = to16(x, dtype), to16(w, dtype)
@@ -50,7 +37,6 @@ def attention_h128(ctx: _lib.Context, qkv: np.ndarray, B: int, T: int, H: int, s
                    dtype: int = _lib.BF16, fill: float = 0.0) -> np.ndarray:
     """mia_op_attention_h128 on a fused q | k | v buffer [B*T, 3*H*128] (fp32 here, rounded to `dtype`): full softmax(q k^T scale) v per
     head, head dim 128.  seq_len [B] masks keys at or beyond a sequence's length; rows beyond it keep `fill`.  Returns fp32 [B*T, H*128]."""
-    _declare(ctx.lib)
     D = H * 128
     assert qkv.shape == (B * T, 3 * D)
     x16 = to16(qkv, dtype)
@@ -64,19 +50,6 @@ def attention_h128(ctx: _lib.Context, qkv: np.ndarray, B: int, T: int, H: int, s
 
 
 EPI_QKV_VT, EPI_HEADMAJOR = 1, 2
-
-
-def _declare_enc(lib):
-    if getattr(lib, "_enc_ops_declared", False):
-        return
-    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-    lib.mia_op_linear_epi.restype = i32
-    lib.mia_op_linear_epi.argtypes = [vp, vp, i64, vp, vp, vp, i64, vp] + [i32] * 12
-    lib.mia_op_attention_h64.restype = i32
-    lib.mia_op_attention_h64.argtypes = [vp, vp, i64, vp, vp, i64] + [i32] * 6
-    lib.mia_op_attention_h64_variant.restype = i32
-    lib.mia_op_attention_h64_variant.argtypes = [vp, vp, i64, vp, vp, i64] + [i32] * 7
-    lib._enc_ops_declared = True
 
 
 def bits16(a: np.ndarray, dtype: int) -> np.ndarray:
@@ -108,7 +81,6 @@ def attention_h64(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.ndarray
     """mia_op_attention_h64 (the Whisper encoder's attention, head dim 64) on q / k / v [B*T, H*64] fp32, rounded to `dtype` and laid out
     by enc_attention_buffers; Tpad defaults to align_up(T, 64), ld_qk to 2*H*64, ld_out to H*64.  out starts as `fill` everywhere.
     Returns fp32 [B*T, ld_out], the whole buffer."""
-    _declare_enc(ctx.lib)
     D = H * 64
     Tpad = (T + 63) // 64 * 64 if Tpad is None else Tpad
     ld_qk = 2 * D if ld_qk is None else ld_qk
@@ -128,7 +100,6 @@ def attention_h64_bits(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.nd
                        pad_fill: float = 0.0, dtype: int = _lib.BF16) -> np.ndarray:
     """attention_h64 through mia_op_attention_h64_variant: the kernel form is the caller's choice (-1 = the one the encoder launches at
     this T).  Returns the raw 16-bit output buffer, uint16 [B*T, ld_out]; from_bits16 widens it."""
-    _declare_enc(ctx.lib)
     D = H * 64
     Tpad = (T + 63) // 64 * 64 if Tpad is None else Tpad
     ld_qk = 2 * D if ld_qk is None else ld_qk
@@ -142,7 +113,6 @@ def attention_h64_bits(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.nd
 
 def attention_h64_device(ctx: _lib.Context, qk, vt, out, B: int, T: int, H: int, Tpad: int, ld_qk: int, ld_out: int, dtype: int) -> None:
     """mia_op_attention_h64 on torch device tensors (16-bit elements), in place."""
-    _declare_enc(ctx.lib)
     assert qk.is_cuda and vt.is_cuda and out.is_cuda
     _run(ctx, lambda: ctx.lib.mia_op_attention_h64(ctx.h, _ptr(qk), ld_qk, _ptr(vt), _ptr(out), ld_out, B, T, H, Tpad, dtype, _lib.MEM_DEVICE))
 
@@ -150,7 +120,6 @@ def attention_h64_device(ctx: _lib.Context, qk, vt, out, B: int, T: int, H: int,
 def attention_h64_device_variant(ctx: _lib.Context, qk, vt, out, B: int, T: int, H: int, Tpad: int, ld_qk: int, ld_out: int, dtype: int,
                                  variant: int) -> None:
     """mia_op_attention_h64_variant on torch device tensors (16-bit elements), in place."""
-    _declare_enc(ctx.lib)
     assert qk.is_cuda and vt.is_cuda and out.is_cuda
     _run(ctx, lambda: ctx.lib.mia_op_attention_h64_variant(ctx.h, _ptr(qk), ld_qk, _ptr(vt), _ptr(out), ld_out, B, T, H, Tpad, dtype, variant,
                                                            _lib.MEM_DEVICE))
@@ -162,7 +131,6 @@ def linear_epi(ctx: _lib.Context, x: np.ndarray, w: np.ndarray, bias, y: np.ndar
     destinations' initial bit patterns (QKV_VT: y [M, ldy], vt [B, H, 64, Tpad]; HEADMAJOR: y [B, H, T, 64], vt None) and are not
     modified.  Returns (y_bits, vt_bits, y_f32, vt_f32): the destinations after the GEMM as bit patterns and widened (vt: None, None for
     HEADMAJOR)."""
-    _declare_enc(ctx.lib)
     M, K = x.shape
     x16, w16 = to16(x, dtype), to16(w, dtype)
     b = None if bias is None else np.ascontiguousarray(bias, np.float32)
@@ -178,7 +146,6 @@ def linear_epi(ctx: _lib.Context, x: np.ndarray, w: np.ndarray, bias, y: np.ndar
 def linear_epi_device(ctx: _lib.Context, x, w, bias, y, vt, *, M: int, N: int, K: int, epi: int, T: int, H: int, Tpad: int, ldy: int,
                       dtype: int, variant: int = 3) -> None:
     """mia_op_linear_epi on torch device tensors (x, w, y, vt 16-bit elements, bias fp32), in place."""
-    _declare_enc(ctx.lib)
     _run(ctx, lambda: ctx.lib.mia_op_linear_epi(ctx.h, _ptr(x), K, _ptr(w), _ptr(bias), _ptr(y), ldy, _ptr(vt), M, N, K, int(epi), T, H, Tpad, 1,
                                                 dtype, 0, int(variant), _lib.MEM_DEVICE))
 
@@ -186,7 +153,6 @@ def linear_epi_device(ctx: _lib.Context, x, w, bias, y, vt, *, M: int, N: int, K
 def fsmn_add(ctx: _lib.Context, x: np.ndarray, v: np.ndarray, w: np.ndarray, left: int, B: int = 1, seq_len=None,
              dtype: int = _lib.BF16) -> np.ndarray:
     """mia_op_fsmn_add: x [B*T, D] fp32 + the SANM memory of v [B*T, D] (rounded to `dtype`) under taps w [K, D]; returns the new x."""
-    _declare(ctx.lib)
     rows, D = x.shape
     T = rows // B
     xo = np.array(x, np.float32, order="C")
@@ -202,8 +168,6 @@ def kvq_attention(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.ndarray
     """mia_op_kvq_attention: the LM's single-token GQA attention for the last of T positions over a cache the op fills from k / v
     [Hkv, T, dh] (fp32 here, rounded to `dtype`): bits 0 = the 16-bit cache, 4 | 8 = the quantised one.  q [Hq, dh]; returns fp32 [Hq, dh]."""
     lib = ctx.lib
-    lib.mia_op_kvq_attention.restype = C.c_int
-    lib.mia_op_kvq_attention.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6
     Hq, dh = q.shape
     Hkv, T, _ = k.shape
     q16, k16, v16 = to16(q, dtype), to16(k, dtype), to16(v, dtype)
@@ -217,8 +181,6 @@ def lm_prompt_attention(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.n
     from k / v [Hkv, T, dh] (fp32 here, rounded to `dtype`).  q [n, Hq, dh]: the rows at positions T - n .. T - 1, the row at p sees
     keys [0, p]; returns fp32 [n, Hq, dh]."""
     lib = ctx.lib
-    lib.mia_op_lm_prompt_attention.restype = C.c_int
-    lib.mia_op_lm_prompt_attention.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6
     n, Hq, dh = q.shape
     Hkv, T, _ = k.shape
     q16, k16, v16 = to16(q, dtype), to16(k, dtype), to16(v, dtype)
@@ -228,39 +190,11 @@ def lm_prompt_attention(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.n
 
 
 # ---- fp32 tap GEMM and fp32 attention (device pointers; the test hooks expose every launch argument) -------------------------------
-class ConvGemmDesc(C.Structure):
-    """mia_conv_gemm_desc (include/mia.h), field for field."""
-    _fields_ = [("X", C.c_void_p), ("ldx", C.c_int64), ("T_in", C.c_int32),
-                ("W", C.c_void_p), ("ldw", C.c_int64), ("w_phase_stride", C.c_int64),
-                ("bias", C.c_void_p), ("alpha", C.c_void_p), ("ralpha", C.c_void_p), ("lrelu_slope", C.c_float),
-                ("Y", C.c_void_p), ("ldy", C.c_int64), ("T_out", C.c_int32),
-                ("y_row_mul", C.c_int32), ("y_row_off", C.c_int32), ("y_phase_step", C.c_int32),
-                ("R", C.c_void_p), ("R2", C.c_void_p), ("ldr", C.c_int64), ("noise", C.c_void_p), ("out_scale", C.c_float),
-                ("M", C.c_int32), ("N", C.c_int32), ("Cin", C.c_int32), ("taps", C.c_int32), ("dil", C.c_int32), ("pad", C.c_int32),
-                ("x_row_mul", C.c_int32), ("act", C.c_int32), ("tanh_out", C.c_int32),
-                ("phase_len", C.c_void_p), ("x_phase_step", C.c_int32),
-                ("n_seq", C.c_int32), ("x_seq_step", C.c_int64), ("y_seq_step", C.c_int64),
-                ("seq_len", C.c_void_p), ("noise_seq_off", C.c_void_p)]
 
 
 _DESC_F32 = ("X", "W", "bias", "alpha", "ralpha", "Y", "R", "R2", "noise")
 _DESC_I32 = ("phase_len", "seq_len", "noise_seq_off")
 _DESC_DEFAULTS = dict(y_row_mul=1, dil=1, taps=1, x_row_mul=1, n_seq=1)
-
-
-def _declare_f32(lib):
-    if getattr(lib, "_f32_ops_declared", False):
-        return
-    vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
-    lib.mia_op_conv1d_f32.restype = i32
-    lib.mia_op_conv1d_f32.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, i64] + [i32] * 8
-    lib.mia_op_conv_gemm_f32.restype = i32
-    lib.mia_op_conv_gemm_f32.argtypes = [vp, C.POINTER(ConvGemmDesc), i32]
-    lib.mia_op_attention_f32.restype = i32
-    lib.mia_op_attention_f32.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, f32]
-    lib.mia_op_attention_f32_ex.restype = i32
-    lib.mia_op_attention_f32_ex.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, i32, f32, vp, i32]
-    lib._f32_ops_declared = True
 
 
 def _dev(a, np_dtype=np.float32):
@@ -297,7 +231,6 @@ def conv1d_f32(ctx: _lib.Context, x, w, y, *, Cin: int, taps: int = 1, stride: i
                ldy: int | None = None) -> np.ndarray:
     """mia_op_conv1d_f32: x [T_in, ldx], w [N, taps*Cin], y [rows, ldy] (its contents are what unwritten elements keep; a device tensor is written in place), r in
     y's layout.  Returns y's whole buffer."""
-    _declare_f32(ctx.lib)
     dx, dw, dy, db, dr = _dev(x), _dev(w), _dev(y), _dev(bias), _dev(r)
     _run(ctx, lambda: ctx.lib.mia_op_conv1d_f32(ctx.h, _ptr(dx), _ld(dx, ldx), int(dx.shape[0] if T_in is None else T_in), _ptr(dw), _ptr(db),
                                                  _ptr(dr), _ptr(dy), _ld(dy, ldy), int(dy.shape[0] if T_out is None else T_out),
@@ -309,7 +242,6 @@ def conv_gemm_f32(ctx: _lib.Context, phases: int = 1, **d) -> np.ndarray:
     """mia_op_conv_gemm_f32: keyword arguments are the fields of mia_conv_gemm_desc, arrays for its pointers (X, Y, R, R2 two-dimensional:
     ldx / ldy / ldr default to their row strides; Y's contents are what unwritten elements keep, a device tensor is written in place).
     Returns Y's whole buffer."""
-    _declare_f32(ctx.lib)
     unknown = set(d) - {n for n, _ in ConvGemmDesc._fields_}
     assert not unknown, f"not a mia_conv_gemm_desc field: {sorted(unknown)}"
     t = {k: _dev(d.get(k)) for k in _DESC_F32}
@@ -330,7 +262,6 @@ def attention_f32_ex(ctx: _lib.Context, q, k, v, out, B: int, T: int, H: int, sc
                      seq_len=None, chunk: int = 0, ldq=None, ldk=None, ldv=None, ldp=None, ldo=None, plain: bool = False) -> np.ndarray:
     """mia_op_attention_f32_ex (plain: mia_op_attention_f32): q / k / v [B*T, ld] (three views of one fused device buffer are fine), head h
     in columns h*64..; out [B*T, ldo], its contents are what unwritten elements keep (a device tensor is written in place).  Returns out's whole buffer."""
-    _declare_f32(ctx.lib)
     dq, dk, dv, do, dp, du, dbv = _dev(q), _dev(k), _dev(v), _dev(out), _dev(p), _dev(bias_u), _dev(bias_v)
     ds = _dev(seq_len, np.int32)
     head = (ctx.h, _ptr(dq), _ld(dq, ldq), _ptr(dk), _ld(dk, ldk), _ptr(dv), _ld(dv, ldv))
@@ -349,15 +280,6 @@ def attention_f32(ctx: _lib.Context, q, k, v, out, B: int, T: int, H: int, scale
 
 
 # ---- the LM step's skinny GEMMs (device tensors; the test hook exposes every launch argument) ---------------------------------------
-class SkinnyDesc(C.Structure):
-    """mia_skinny_desc (include/mia.h), field for field."""
-    _fields_ = [("A", C.c_void_p), ("lda", C.c_int64), ("W", C.c_void_p),
-                ("wfrag", C.c_void_p), ("stfrag", C.c_void_p), ("bits", C.c_int32), ("w_frag", C.c_int32),
-                ("bias", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int64),
-                ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("S", C.c_int32), ("mode", C.c_int32), ("dtype", C.c_int32),
-                ("xres", C.c_void_p), ("nw", C.c_void_p), ("ss_out", C.c_void_p),
-                ("ss_in", C.c_void_p), ("ss_tiles", C.c_int32), ("ss_dim", C.c_int32), ("eps", C.c_float), ("rs_scale", C.c_float),
-                ("M_cap", C.c_int32)]
 
 
 SK_OUT16, SK_OUTF32, SK_PARTIAL, SK_QKV, SK_SWIGLU, SK_RESID = range(6)
@@ -367,8 +289,6 @@ _SKINNY_PTRS = ("A", "W", "wfrag", "stfrag", "bias", "out", "xres", "nw", "ss_ou
 def quant_repack(codes: np.ndarray, scales: np.ndarray, biases: np.ndarray, bits: int, scale_dtype: int, compute_dtype: int):
     """mia_quant_repack (host): one packed Linear (quantize_affine's three arrays; bf16 scales as uint16 bit patterns) -> (wfrag, stfrag)."""
     lib = _lib.load()
-    lib.mia_quant_repack.restype = C.c_int
-    lib.mia_quant_repack.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     codes, scales, biases = np.ascontiguousarray(codes, np.uint32), np.ascontiguousarray(scales), np.ascontiguousarray(biases)
     N, K = codes.shape[0], codes.shape[1] * (32 // bits)
     tiles = (N + 15) // 16
@@ -385,10 +305,6 @@ def skinny_gemm(ctx: _lib.Context, **d) -> None:
     """mia_op_skinny_gemm: keyword arguments are the fields of mia_skinny_desc, torch device tensors (views included) or None for its
     pointers; lda / ldo default to the row strides of two-dimensional A / out, S to 1, rs_scale to 1.  Outputs are written in place."""
     lib = ctx.lib
-    if not getattr(lib, "_skinny_declared", False):
-        lib.mia_op_skinny_gemm.restype = C.c_int
-        lib.mia_op_skinny_gemm.argtypes = [C.c_void_p, C.POINTER(SkinnyDesc)]
-        lib._skinny_declared = True
     unknown = set(d) - {n for n, _ in SkinnyDesc._fields_}
     assert not unknown, f"not a mia_skinny_desc field: {sorted(unknown)}"
     desc = SkinnyDesc()

@@ -44,9 +44,6 @@ def gather_tokens(local_tokens, local_counts, world: int, max_shard: int | None 
 # ---- the same exchange through the C ABI (include/mia.h "data-parallel exchange"): RCCL on the context's own stream ----------------
 def dp_available(ctx) -> int:
     """1 when RCCL can be bound in this process (mia_dp_available).  mia_dp_init is a collective: vote on this across ranks first."""
-    import ctypes as C
-    ctx.lib.mia_dp_available.restype = C.c_int
-    ctx.lib.mia_dp_available.argtypes = []
     return int(ctx.lib.mia_dp_available())
 
 
@@ -54,25 +51,18 @@ def dp_unique_id(ctx) -> bytes:
     """Rank 0: the 128-byte RCCL id to hand to every other rank (mia_dp_unique_id)."""
     import ctypes as C
     buf = (C.c_char * 128)()
-    ctx.lib.mia_dp_unique_id.argtypes = [C.c_void_p, C.c_void_p]
     ctx.check(ctx.lib.mia_dp_unique_id(ctx.h, buf))
     return bytes(buf)
 
 
 def dp_init(ctx, rank: int, world: int, unique_id: bytes) -> None:
-    import ctypes as C
-    ctx.lib.mia_dp_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_char_p]
     ctx.check(ctx.lib.mia_dp_init(ctx.h, rank, world, unique_id))
 
 
 def dp_shutdown(ctx) -> None:
-    import ctypes as C
-    ctx.lib.mia_dp_shutdown.argtypes = [C.c_void_p]
     ctx.check(ctx.lib.mia_dp_shutdown(ctx.h))
 
 
 def dp_gather_tokens(ctx, local_tokens_ptr: int, local_counts_ptr: int, b_local: int, L: int, n_items: int, all_tokens_ptr: int, all_counts_ptr: int) -> None:
     """mia_dp_gather_tokens on raw device pointers (e.g. torch tensor.data_ptr()); enqueues on the context's stream."""
-    import ctypes as C
-    ctx.lib.mia_dp_gather_tokens.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     ctx.check(ctx.lib.mia_dp_gather_tokens(ctx.h, local_tokens_ptr, local_counts_ptr, b_local, L, n_items, all_tokens_ptr, all_counts_ptr))

@@ -8,24 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .whisper import _TensorView
-
-
-class _S3Cfg(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("n_mels", "n_audio_state", "n_audio_head", "n_audio_layer")]
-
-
-def _declare(lib):
-    if getattr(lib, "_s3_declared", False):
-        return
-    vp, i32 = C.c_void_p, C.c_int
-    lib.mia_s3tok_load.restype = vp
-    lib.mia_s3tok_load.argtypes = [vp, C.POINTER(_S3Cfg), C.POINTER(_TensorView), i32]
-    lib.mia_s3tok_free.restype = None
-    lib.mia_s3tok_free.argtypes = [vp]
-    lib.mia_s3tok_encode.restype = i32
-    lib.mia_s3tok_encode.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, i32]
-    lib._s3_declared = True
+from ._abi import S3Config, TensorView
 
 
 def merge_tokenized_segments(segments, overlap=4, token_rate=25):
@@ -46,14 +29,13 @@ class S3Tokenizer:
 
     @staticmethod
     def load(ctx: _lib.Context, cfg, weights: dict[str, np.ndarray]) -> "S3Tokenizer":
-        _declare(ctx.lib)
-        c = _S3Cfg(cfg.n_mels, cfg.n_audio_state, cfg.n_audio_head, cfg.n_audio_layer)
-        views = (_TensorView * len(weights))()
+        c = S3Config(cfg.n_mels, cfg.n_audio_state, cfg.n_audio_head, cfg.n_audio_layer)
+        views = (TensorView * len(weights))()
         keep = []
         for i, (name, arr) in enumerate(weights.items()):
             a = np.ascontiguousarray(arr, np.float32)
             keep.append(a)
-            views[i] = _TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
+            views[i] = TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
         h = ctx.lib.mia_s3tok_load(ctx.h, C.byref(c), views, len(weights))
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())

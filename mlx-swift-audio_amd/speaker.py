@@ -8,28 +8,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .whisper import _TensorView
+from ._abi import TensorView
 
 EMBEDDING_DIM = 192
-
-
-def _declare(lib):
-    if getattr(lib, "_campplus_declared", False):
-        return
-    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-    lib.mia_campplus_load.restype = vp
-    lib.mia_campplus_load.argtypes = [vp, C.POINTER(_TensorView), i32]
-    lib.mia_campplus_free.restype = None
-    lib.mia_campplus_free.argtypes = [vp]
-    lib.mia_kaldi_fbank_frames.restype = i64
-    lib.mia_kaldi_fbank_frames.argtypes = [i64]
-    lib.mia_campplus_fbank.restype = i32
-    lib.mia_campplus_fbank.argtypes = [vp, vp, i64, i32, vp, i32]
-    lib.mia_campplus_forward.restype = i32
-    lib.mia_campplus_forward.argtypes = [vp, vp, i32, vp, i32]
-    lib.mia_campplus_embed.restype = i32
-    lib.mia_campplus_embed.argtypes = [vp, vp, i64, vp, i32]
-    lib._campplus_declared = True
 
 
 class CAMPlusSpeakerEncoder:
@@ -48,16 +29,15 @@ class CAMPlusSpeakerEncoder:
     def load(ctx: _lib.Context, weights: dict[str, np.ndarray]) -> "CAMPlusSpeakerEncoder":
         """weights: the checkpoint's campplus tensors; a "campplus." key prefix is stripped (sanitizeWeights, :93-104).  An empty
         dict gives the reference's unloaded encoder (zero embeddings, :109-116)."""
-        _declare(ctx.lib)
         weights = {(k[len("campplus."):] if k.startswith("campplus.") else k): v for k, v in weights.items()}
         if not weights:
             return CAMPlusSpeakerEncoder(ctx, None)
-        views = (_TensorView * len(weights))()
+        views = (TensorView * len(weights))()
         keep = []
         for i, (name, arr) in enumerate(weights.items()):
             a = np.ascontiguousarray(arr, np.float32)
             keep.append(a)
-            views[i] = _TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
+            views[i] = TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
         h = ctx.lib.mia_campplus_load(ctx.h, views, len(weights))
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())

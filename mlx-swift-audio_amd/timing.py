@@ -4,7 +4,6 @@ jump-time arithmetic here.  Splitting tokens into words needs the tokenizer's te
 callable: tokens + [eot] -> (words, token groups), WhisperTokenizer.swift) -- the text codec itself is outside the hot path."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
@@ -23,19 +22,9 @@ class WordTiming:
     probability: float
 
 
-def _declare(lib):
-    if getattr(lib, "_align_declared", False):
-        return
-    vp, i32 = C.c_void_p, C.c_int
-    lib.mia_whisper_align.restype = i32
-    lib.mia_whisper_align.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp]
-    lib._align_declared = True
-
-
 def align(model, token_seqs: list[list[int]], heads, num_frames: list[int], row_start: int, eot: int, want_matrix: bool = False):
     """Raw call: one token sequence per clip of the last encode().  Returns (token_probs [B, stride], paths [(text_idx, time_idx)], matrix | None)."""
     lib = model.ctx.lib
-    _declare(lib)
     B = len(token_seqs)
     stride = max(len(t) for t in token_seqs)
     toks = np.zeros((B, stride), np.int32)

@@ -16,61 +16,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
+from ._abi import DecodeOpts, TensorView, WhisperDims
 from . import audio as _audio
-
-
-class _Dims(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("n_mels", "n_audio_ctx", "n_audio_state", "n_audio_head", "n_audio_layer",
-                                         "n_vocab", "n_text_ctx", "n_text_state", "n_text_head", "n_text_layer")]
-
-
-class _TensorView(C.Structure):
-    _fields_ = [("name", C.c_char_p), ("dtype", C.c_int32), ("ndim", C.c_int32), ("shape", C.c_int64 * 4),
-                ("data", C.c_void_p)]
-
-
-class _DecodeOpts(C.Structure):
-    _fields_ = [("initial_tokens", C.c_void_p), ("n_initial", C.c_int32), ("per_clip_initial", C.c_int32),
-                ("sot_index", C.c_int32), ("suppress_ids", C.c_void_p), ("n_suppress", C.c_int32),
-                ("blank_ids", C.c_void_p), ("n_blank", C.c_int32),
-                ("eot", C.c_int32), ("no_speech", C.c_int32), ("no_timestamps", C.c_int32), ("timestamp_begin", C.c_int32),
-                ("timestamps", C.c_int32), ("max_tokens", C.c_int32), ("max_initial_timestamp_index", C.c_int32),
-                ("max_new_tokens", C.c_int32), ("temperature", C.c_float), ("uniforms", C.c_void_p),
-                ("n_initial_per_clip", C.c_void_p), ("sot_index_per_clip", C.c_void_p), ("clip_temperature", C.c_void_p),
-                ("clip_active", C.c_void_p)]
-
-
-def _declare(lib):
-    if getattr(lib, "_whisper_declared", False):
-        return
-    vp, i32 = C.c_void_p, C.c_int
-    lib.mia_whisper_load.restype = vp
-    lib.mia_whisper_load.argtypes = [vp, C.POINTER(_Dims), C.POINTER(_TensorView), i32, i32]
-    lib.mia_whisper_free.restype = None
-    lib.mia_whisper_free.argtypes = [vp]
-    lib.mia_whisper_encode.restype = i32
-    lib.mia_whisper_encode.argtypes = [vp, vp, i32, i32]
-    lib.mia_whisper_get_audio_features.restype = i32
-    lib.mia_whisper_get_audio_features.argtypes = [vp, vp, i32, i32]
-    lib.mia_whisper_decode_greedy.restype = i32
-    lib.mia_whisper_decode_greedy.argtypes = [vp, C.POINTER(_DecodeOpts), vp, vp, vp, vp, i32]
-    lib.mia_whisper_detect_language.restype = i32
-    lib.mia_whisper_detect_language.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
-    lib.mia_whisper_encode_windows.restype = i32
-    lib.mia_whisper_encode_windows.argtypes = [vp, vp, vp, i32, C.c_int64, i32]
-    lib.mia_whisper_transcribe_windows.restype = i32
-    lib.mia_whisper_transcribe_windows.argtypes = [vp, vp, vp, i32, C.c_int64, C.POINTER(_DecodeOpts), vp, vp, vp, vp, i32]
-    lib.mia_whisper_audio_create.restype = vp
-    lib.mia_whisper_audio_create.argtypes = [vp, vp, vp, i32, C.c_int64, i32]
-    lib.mia_whisper_audio_free.restype = None
-    lib.mia_whisper_audio_free.argtypes = [vp]
-    lib.mia_whisper_audio_frames.restype = C.c_int64
-    lib.mia_whisper_audio_frames.argtypes = [vp]
-    lib.mia_whisper_audio_read.restype = i32
-    lib.mia_whisper_audio_read.argtypes = [vp, i32, C.c_int64, C.c_int64, vp]
-    lib.mia_whisper_encode_audio_windows.restype = i32
-    lib.mia_whisper_encode_audio_windows.argtypes = [vp, vp, vp, vp, vp, i32]
-    lib._whisper_declared = True
 
 
 @dataclass
@@ -149,9 +96,8 @@ class WhisperModel:
     @staticmethod
     def load(ctx: _lib.Context, dims, weights: dict[str, np.ndarray], dtype: int = _lib.BF16) -> "WhisperModel":
         """dims: any object with the ModelDimensions fields; weights: name -> fp32/fp16 array with the reference key schema."""
-        _declare(ctx.lib)
-        cd = _Dims(*[int(getattr(dims, f[0])) for f in _Dims._fields_])
-        views = (_TensorView * len(weights))()
+        cd = WhisperDims(*[int(getattr(dims, f[0])) for f in WhisperDims._fields_])
+        views = (TensorView * len(weights))()
         keep = []
         for i, (name, arr) in enumerate(weights.items()):
             if arr.dtype == np.float16:
@@ -160,7 +106,7 @@ class WhisperModel:
                 a, dt = np.ascontiguousarray(arr, np.float32), _lib.F32
             keep.append(a)
             shp = (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim)))
-            views[i] = _TensorView(name.encode(), dt, a.ndim, shp, a.ctypes.data)
+            views[i] = TensorView(name.encode(), dt, a.ndim, shp, a.ctypes.data)
         h = ctx.lib.mia_whisper_load(ctx.h, C.byref(cd), views, len(weights), dtype)
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
@@ -174,23 +120,17 @@ class WhisperModel:
     def set_gemm_variant(self, variant: int) -> None:
         """Test hook: force the encoder GEMM tile variant (0/1: 128^2, 2: 256^2 two-buffer, 3: auto, 4: 256^2 8-phase)."""
         lib = self.ctx.lib
-        lib.mia_whisper_set_gemm_variant.restype = C.c_int
-        lib.mia_whisper_set_gemm_variant.argtypes = [C.c_void_p, C.c_int]
         self.ctx.check(lib.mia_whisper_set_gemm_variant(self.h, int(variant)))
 
     def set_debug(self, flags: int) -> None:
         """Test hook (mia_whisper_set_debug): bit 0 = no hipGraph, bit 1 = one-workgroup head, bit 2 = split reduce + LayerNorm chain (no carried LayerNorm)."""
         lib = self.ctx.lib
-        lib.mia_whisper_set_debug.restype = C.c_int
-        lib.mia_whisper_set_debug.argtypes = [C.c_void_p, C.c_int]
         self.ctx.check(lib.mia_whisper_set_debug(self.h, int(flags)))
 
     def set_weight_sharing(self, concurrent_readers: int) -> None:
         """mia_whisper_set_weight_sharing: > 1 when clones of these weights decode concurrently on other streams (the step then loads
         its weights cacheable); 1 restores the lone-loop (non-temporal) form.  Results are bit-identical."""
         lib = self.ctx.lib
-        lib.mia_whisper_set_weight_sharing.restype = C.c_int
-        lib.mia_whisper_set_weight_sharing.argtypes = [C.c_void_p, C.c_int]
         self.ctx.check(lib.mia_whisper_set_weight_sharing(self.h, int(concurrent_readers)))
 
     def attach_quantized(self, tensors: dict[str, np.ndarray], bits: int | None = None, group_size: int = 64) -> None:
@@ -200,8 +140,6 @@ class WhisperModel:
         from the packed width when not given, as checkpoint.expand_checkpoint does.  The handle must have been loaded from the
         de-quantised tensors of the same checkpoint."""
         lib = self.ctx.lib
-        lib.mia_whisper_attach_quantized.restype = C.c_int
-        lib.mia_whisper_attach_quantized.argtypes = [C.c_void_p, C.POINTER(_TensorView), C.c_int, C.c_int, C.c_int]
         packed = {}
         for name, arr in tensors.items():
             base = name.rsplit(".", 1)[0]
@@ -212,7 +150,7 @@ class WhisperModel:
                 if name.endswith(".weight"):
                     bits = (32 * arr.shape[-1]) // (packed[name[:-7] + ".scales"].shape[-1] * group_size)
                     break
-        views = (_TensorView * max(len(packed), 1))()
+        views = (TensorView * max(len(packed), 1))()
         keep = []
         for i, (name, arr) in enumerate(packed.items()):
             a = np.ascontiguousarray(arr)
@@ -228,38 +166,30 @@ class WhisperModel:
                 raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, f"attach_quantized: '{name}' must be uint32 codes or f16 / bf16 / f32 scales / biases (got {a.dtype})")
             keep.append(a)
             shp = (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim)))
-            views[i] = _TensorView(name.encode(), dt, a.ndim, shp, a.ctypes.data)
+            views[i] = TensorView(name.encode(), dt, a.ndim, shp, a.ctypes.data)
         self.ctx.check(lib.mia_whisper_attach_quantized(self.h, views, len(packed), int(group_size), int(bits or 0)))
 
     def use_packed(self, on: bool) -> None:
         """mia_whisper_use_packed: the decode step (decode, align, detect_language) reads the attached packed weights (True) or the 16-bit
         copy (False, the default).  A clone inherits the switch of the handle it is made from."""
         lib = self.ctx.lib
-        lib.mia_whisper_use_packed.restype = C.c_int
-        lib.mia_whisper_use_packed.argtypes = [C.c_void_p, C.c_int]
         self.ctx.check(lib.mia_whisper_use_packed(self.h, 1 if on else 0))
 
     def set_encode_stream(self, hip_stream: int | None) -> None:
         """mia_whisper_set_encode_stream: run the encoder half of every window on another HIP stream (raw pointer, e.g.
         torch.cuda.Stream(...).cuda_stream); None restores the single-stream form."""
         lib = self.ctx.lib
-        lib.mia_whisper_set_encode_stream.restype = C.c_int
-        lib.mia_whisper_set_encode_stream.argtypes = [C.c_void_p, C.c_void_p]
         self.ctx.check(lib.mia_whisper_set_encode_stream(self.h, hip_stream))
 
     def trace_logits(self, clips: list[int]) -> None:
         """Test hook (mia_whisper_trace_logits): keep the raw step logits of these batch rows; [] switches the trace off."""
         lib = self.ctx.lib
-        lib.mia_whisper_trace_logits.restype = C.c_int
-        lib.mia_whisper_trace_logits.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         a = np.asarray(clips, np.int32)
         self.ctx.check(lib.mia_whisper_trace_logits(self.h, a.ctypes.data if a.size else None, int(a.size)))
 
     def read_logit_trace(self, slot: int, first_pos: int, n_pos: int) -> np.ndarray:
         """Rows [first_pos, first_pos + n_pos) of trace slot `slot`: float32 [n_pos, n_vocab]."""
         lib = self.ctx.lib
-        lib.mia_whisper_read_logit_trace.restype = C.c_int
-        lib.mia_whisper_read_logit_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         out = np.empty((n_pos, self.dims.n_vocab), np.float32)
         self.ctx.check(lib.mia_whisper_read_logit_trace(self.h, slot, first_pos, n_pos, out.ctypes.data))
         return out
@@ -267,8 +197,6 @@ class WhisperModel:
     def clone(self, ctx: "_lib.Context") -> "WhisperModel":
         """A second handle on the same weights with its own batch state, bound to `ctx` (another stream of the same device)."""
         lib = ctx.lib
-        lib.mia_whisper_clone.restype = C.c_void_p
-        lib.mia_whisper_clone.argtypes = [C.c_void_p, C.c_void_p]
         h = lib.mia_whisper_clone(self.h, ctx.h)
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, lib.mia_last_error(ctx.h).decode())
@@ -345,10 +273,10 @@ class WhisperModel:
         sup = np.asarray(o.suppress_ids, np.int32)
         blank = np.asarray(o.blank_ids, np.int32)
         keep = (init, sup, blank)
-        co = _DecodeOpts(init.ctypes.data, int(init.shape[-1]), per_clip, sot_index,
-                         sup.ctypes.data if sup.size else None, int(sup.size), blank.ctypes.data if blank.size else None, int(blank.size),
-                         st.eot, st.no_speech, st.no_timestamps, st.timestamp_begin, 1 if o.timestamps else 0, o.max_tokens,
-                         o.max_initial_timestamp_index, o.max_new_tokens, float(o.temperature), None, None, None, None, None)
+        co = DecodeOpts(init.ctypes.data, int(init.shape[-1]), per_clip, sot_index,
+                        sup.ctypes.data if sup.size else None, int(sup.size), blank.ctypes.data if blank.size else None, int(blank.size),
+                        st.eot, st.no_speech, st.no_timestamps, st.timestamp_begin, 1 if o.timestamps else 0, o.max_tokens,
+                        o.max_initial_timestamp_index, o.max_new_tokens, float(o.temperature), None, None, None, None, None)
         return co, keep
 
     def decode_greedy(self, o: DecodingOptions, initial: np.ndarray | None = None) -> list[DecodingResult]:
@@ -383,11 +311,11 @@ class WhisperModel:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, f"uniforms must be [{B},{o.max_tokens}]")
         sup = np.asarray(o.suppress_ids, np.int32)
         blank = np.asarray(o.blank_ids, np.int32)
-        co = _DecodeOpts(init.ctypes.data, n_max, 1, int(sot[0]), sup.ctypes.data if sup.size else None, int(sup.size),
-                         blank.ctypes.data if blank.size else None, int(blank.size), st.eot, st.no_speech, st.no_timestamps, st.timestamp_begin,
-                         1 if o.timestamps else 0, o.max_tokens, o.max_initial_timestamp_index, o.max_new_tokens, 0.0,
-                         None if uni is None else uni.ctypes.data, n_init.ctypes.data, sot.ctypes.data, temps.ctypes.data,
-                         None if act is None else act.ctypes.data)
+        co = DecodeOpts(init.ctypes.data, n_max, 1, int(sot[0]), sup.ctypes.data if sup.size else None, int(sup.size),
+                        blank.ctypes.data if blank.size else None, int(blank.size), st.eot, st.no_speech, st.no_timestamps, st.timestamp_begin,
+                        1 if o.timestamps else 0, o.max_tokens, o.max_initial_timestamp_index, o.max_new_tokens, 0.0,
+                        None if uni is None else uni.ctypes.data, n_init.ctypes.data, sot.ctypes.data, temps.ctypes.data,
+                        None if act is None else act.ctypes.data)
         tokens = np.zeros((B, o.max_tokens), np.int32)
         n = np.zeros(B, np.int32)
         avg = np.zeros(B, np.float32)

@@ -35,5 +35,4 @@ def test_no_cpu_fallback_without_gpu():
     assert e.value.code == m._lib.ERR_DEVICE
     lib = m._lib.load()
     assert lib.mia_create(0) in (None, 0)
-    lib.mia_last_error.restype = ctypes.c_char_p
     assert lib.mia_last_error(None) == b"null ctx"

@@ -99,7 +99,6 @@ def test_attention_h128_ragged_stack_equals_single_calls(ctx, kind):
 def test_attention_h128_rejects_bad_arguments(ctx):
     import mlx_swift_audio_amd as m
     from mlx_swift_audio_amd import ops
-    ops._declare(ctx.lib)
     x = np.zeros((4, 3 * 128), np.uint16)
     with pytest.raises(m.MiaError):          # row stride not a multiple of 8 elements
         ctx.check(ctx.lib.mia_op_attention_h128(ctx.h, x.ctypes.data, 380, x.ctypes.data, 380, x.ctypes.data, 380, x.ctypes.data, 128, 1, 4, 1,

@@ -61,7 +61,6 @@ def test_read_wav_rejects_garbage(tmp_path):
 
 
 def _table(lib, fr, to):
-    lib.mia_resample_sinc_table.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L, taps = C.c_int(0), C.c_int(0)
     assert lib.mia_resample_sinc_table(fr, to, None, 0, C.byref(L), C.byref(taps)) == 0
     t = np.zeros((L.value, taps.value), np.float32)

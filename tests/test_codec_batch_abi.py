@@ -7,7 +7,6 @@ def _lib():
     import mlx_swift_audio_amd as m
     from mlx_swift_audio_amd import codec as HC
     lib = m._lib.load()
-    HC._declare(lib)
     return m, lib
 
 

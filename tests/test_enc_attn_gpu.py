@@ -104,7 +104,6 @@ def test_attention_h64_rejects_bad_arguments(ctx):
     """refused by the host-side checks, before anything is copied or launched"""
     import mlx_swift_audio_amd as m
     from mlx_swift_audio_amd import ops
-    ops._declare_enc(ctx.lib)
     T, H, D = 8, 1, 64
     qk, vt, out = np.zeros((T, 2 * D + 8), np.uint16), np.zeros((H, 64, 128), np.uint16), np.zeros((T, D + 4), np.uint16)
 

@@ -84,8 +84,6 @@ def test_abi_shard_and_unpack_match_python_rule():
     import mlx_swift_audio_amd as m
     from mlx_swift_audio_amd import parallel as P
     lib = m._lib.load()
-    lib.mia_dp_shard_range.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.mia_dp_unpack_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L = 7
     for n in (0, 1, 5, 32, 256, 257):
         for w in (1, 2, 3, 8):

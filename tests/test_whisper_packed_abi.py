@@ -26,10 +26,6 @@ def test_symbols_exported_with_the_stated_signatures():
     for name in ("mia_whisper_attach_quantized", "mia_whisper_use_packed", "mia_quant_repack"):
         assert hasattr(lib, name), name
     # a null handle is reported, not dereferenced
-    lib.mia_whisper_attach_quantized.restype = C.c_int
-    lib.mia_whisper_attach_quantized.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
-    lib.mia_whisper_use_packed.restype = C.c_int
-    lib.mia_whisper_use_packed.argtypes = [C.c_void_p, C.c_int]
     assert lib.mia_whisper_attach_quantized(None, None, 0, 64, 4) == m._lib.ERR_MODEL_NOT_LOADED
     assert lib.mia_whisper_use_packed(None, 1) == m._lib.ERR_MODEL_NOT_LOADED
     # the Python surface
@@ -42,8 +38,6 @@ def test_symbols_exported_with_the_stated_signatures():
 def _repack(codes, scales, biases, bits, scale_dt, compute_dt):
     import mlx_swift_audio_amd as m
     lib = m._lib.load()
-    lib.mia_quant_repack.restype = C.c_int
-    lib.mia_quant_repack.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     N, K = codes.shape[0], codes.shape[1] * (32 // bits)
     tiles, nblk, planes = (N + 15) // 16, K // 128, bits // 4
     wf = np.zeros((tiles, nblk, planes, 64, 4), np.uint32)

@@ -1,5 +1,4 @@
 """fp32 attention timing sweep through mia_op_attention_f32: fixed cost vs per-key-tile cost; checks against torch."""
-import ctypes as C
 import os
 import sys
 
@@ -13,8 +12,6 @@ st = torch.cuda.Stream()
 torch.cuda.set_stream(st)
 ctx = M.Context(stream=st.cuda_stream)
 lib = ctx.lib
-lib.mia_op_attention_f32.restype = C.c_int
-lib.mia_op_attention_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_float]
 for (B, T, H) in ((2, 128, 8), (2, 256, 8), (2, 525, 8), (2, 1050, 8), (2, 2100, 8), (8, 1050, 8)):
     D = H * 64
     qkv = torch.randn(B * T, 3 * D, device="cuda")

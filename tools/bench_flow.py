@@ -40,8 +40,6 @@ print(f"flow inference: {e0.elapsed_time(e1) / reps:.2f} ms")
 import ctypes as C  # noqa: E402
 
 lib = ctx.lib
-lib.mia_flow_inference_batch.restype = C.c_int
-lib.mia_flow_inference_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_void_p, C.c_int]
 for U in ((int(sys.argv[2]),) if len(sys.argv) > 2 else (2, 4, 8, 16)):
     arr = lambda v: (C.c_void_p * U)(*([v] * U))
     mels = [torch.empty(80, Tm - 2 * n_prompt, device="cuda") for _ in range(U)]

@@ -1,5 +1,4 @@
 """fp32 tap-GEMM timing sweep through mia_op_conv1d_f32 (device buffers): separates fixed launch cost from per-K-tile cost."""
-import ctypes as C
 import os
 import sys
 
@@ -13,8 +12,6 @@ st = torch.cuda.Stream()
 torch.cuda.set_stream(st)
 ctx = M.Context(stream=st.cuda_stream)
 lib = ctx.lib
-lib.mia_op_conv1d_f32.restype = C.c_int
-lib.mia_op_conv1d_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int] * 8
 
 
 def bench(Mr, N, K, taps=1, reps=50):

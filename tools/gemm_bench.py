@@ -14,7 +14,6 @@ from mlx_swift_audio_amd import ops
 stream = torch.cuda.Stream()
 torch.cuda.set_stream(stream)
 ctx = m.Context(0, stream=stream.cuda_stream)
-ops._declare(ctx.lib)
 shapes = [(48000, 3840, 1280), (48000, 1280, 1280), (48000, 5120, 1280), (48000, 1280, 5120)]
 variants = [int(v) for v in (sys.argv[1:] or ["0", "1"])]
 for (M, N, K) in shapes:
