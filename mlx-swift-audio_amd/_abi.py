@@ -11,6 +11,9 @@ Type rule: `int` / `int32_t` -> c_int, `int64_t` -> c_int64, `float` -> c_float,
 `void` -> None.  Pointers to data and opaque handles are c_void_p, as arguments and as return values (a NumPy `.ctypes.data`, a
 tensor's `data_ptr()`, `byref(...)` and None all pass); a pointer to one of the structs below is POINTER(ThatStruct) or c_void_p.
 
+`tensor_views` builds the `mia_tensor_view` array of every load and attach call, and `dtype_tag` is the one rule for the dtype a NumPy
+array is handed over as.
+
 Adding an entry point:
   1. declare it in include/mia.h (and a struct it takes as a `typedef struct { ... } mia_x;`);
   2. add its line to PROTOTYPES (and the struct's class to this file and to STRUCTS);
@@ -54,6 +57,43 @@ class WhisperDims(C.Structure):
 
 class TensorView(C.Structure):
     _fields_ = [("name", cs), ("dtype", i32), ("ndim", i32), ("shape", i64 * 4), ("data", vp)]
+
+
+F32, F16, BF16, U32 = 0, 1, 2, 3          # mia_dtype
+
+
+def dtype_tag(a):
+    """The mia_dtype a NumPy array is handed over as, or None when it has none: float32 -> F32, float16 -> F16, uint32 -> U32 (packed
+    quantisation codes), uint16 -> BF16.  NumPy has no bfloat16, so a uint16 array IS a bf16 payload here: tagged `.st_dtype == "BF16"`
+    (checkpoint.read_safetensors) or untagged; only a uint16 array tagged as something else (a "U16" tensor of a file) has no tag."""
+    import numpy as np
+    if a.dtype == np.uint16:
+        return BF16 if getattr(a, "st_dtype", "BF16") == "BF16" else None
+    return {np.dtype(np.float32): F32, np.dtype(np.float16): F16, np.dtype(np.uint32): U32}.get(a.dtype)
+
+
+def tensor_views(tensors, kinds=(F32,), refuse=None):
+    """name -> array dict to the `mia_tensor_view` array every load / attach call takes: (views, count, keep_alive).
+
+    An array whose dtype_tag is in `kinds` is passed as it is (made contiguous).  Any other is converted to contiguous float32 -- the
+    dense loads; the fp32-only models pass kinds=(F32,) and so force float32 -- or, with `refuse` (a format of {name} and {dtype}),
+    is an INVALID_ARGUMENT MiaError with that text -- the packed tensors of an attach.  Shapes are padded with zeros to four entries.
+    `keep_alive` holds the arrays the views point into: keep it until the call has returned."""
+    import numpy as np
+    from . import _lib
+    views = (TensorView * max(len(tensors), 1))()
+    keep = []
+    for i, (name, arr) in enumerate(tensors.items()):
+        tag = dtype_tag(arr)
+        if tag in kinds:
+            a = np.ascontiguousarray(arr)
+        elif refuse is None:
+            a, tag = np.ascontiguousarray(arr, np.float32), F32
+        else:
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, refuse.format(name=name, dtype=arr.dtype))
+        keep.append(a)
+        views[i] = TensorView(name.encode(), tag, a.ndim, (i64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
+    return views, len(tensors), keep
 
 
 class DecodeOpts(C.Structure):

@@ -10,7 +10,7 @@ import struct
 
 import numpy as np
 
-from . import _lib
+from . import _abi, _lib
 
 _DT = {"F32": (np.float32, 4), "F16": (np.float16, 2), "BF16": (np.uint16, 2), "I32": (np.int32, 4), "U32": (np.uint32, 4), "I64": (np.int64, 8),
        "U8": (np.uint8, 1), "I8": (np.int8, 1), "U16": (np.uint16, 2), "I16": (np.int16, 2), "F64": (np.float64, 8), "BOOL": (np.bool_, 1)}
@@ -68,13 +68,9 @@ def load_model_dimensions(config_path: str):
 
 
 def _mia_dtype(a: np.ndarray) -> int:
-    tag = getattr(a, "st_dtype", None)
-    if tag == "BF16":
-        return _lib.BF16
-    if a.dtype == np.float16:
-        return _lib.F16
-    if a.dtype == np.float32:
-        return _lib.F32
+    tag = _abi.dtype_tag(a)
+    if tag in (_lib.F32, _lib.F16, _lib.BF16):
+        return tag
     raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, f"scales / biases must be f32, f16 or bf16 (got {a.dtype})")
 
 

@@ -8,21 +8,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import DacConfig, DacEncoderConfig, SnacConfig, TensorView
+from ._abi import DacConfig, DacEncoderConfig, SnacConfig, tensor_views
 
 
 MAX_BATCH = 64          # utterances per mia_*_decode_batch call
-
-
-def _views(weights):
-    views = (TensorView * len(weights))()
-    keep = []
-    for i, (name, arr) in enumerate(weights.items()):
-        a = np.ascontiguousarray(arr, np.float32)
-        keep.append(a)
-        shp = (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim)))
-        views[i] = TensorView(name.encode(), _lib.F32, a.ndim, shp, a.ctypes.data)
-    return views, keep
 
 
 class _Codec:
@@ -57,8 +46,8 @@ class SNACDecoder(_Codec):
     def load(ctx: _lib.Context, cfg, weights: dict[str, np.ndarray]) -> "SNACDecoder":
         c = SnacConfig(cfg.latent_dim, cfg.decoder_dim, len(cfg.decoder_rates), (C.c_int32 * 8)(*cfg.decoder_rates), len(cfg.vq_strides),
                        (C.c_int32 * 4)(*cfg.vq_strides), cfg.codebook_size, cfg.codebook_dim, 1 if cfg.noise else 0, 1 if cfg.depthwise else 0)
-        views, keep = _views(weights)
-        h = ctx.lib.mia_snac_load(ctx.h, C.byref(c), views, len(weights))
+        views, n, keep = tensor_views(weights)
+        h = ctx.lib.mia_snac_load(ctx.h, C.byref(c), views, n)
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
         return SNACDecoder(ctx, h, cfg)
@@ -103,14 +92,14 @@ class DACCodec(_Codec):
     def load(ctx: _lib.Context, cfg, weights: dict[str, np.ndarray]) -> "DACCodec":
         c = DacConfig(cfg.latent_dim, cfg.decoder_dim, len(cfg.decoder_rates), (C.c_int32 * 8)(*cfg.decoder_rates), cfg.n_codebooks,
                       cfg.codebook_size, cfg.codebook_dim)
-        views, keep = _views(weights)
-        h = ctx.lib.mia_dac_load(ctx.h, C.byref(c), views, len(weights))
+        views, n, keep = tensor_views(weights)
+        h = ctx.lib.mia_dac_load(ctx.h, C.byref(c), views, n)
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
         codec = DACCodec(ctx, h, cfg)
         if "encoder.block.layers.0.weight_v" in weights:            # checkpoints carry the encoder; decode-only callers may drop it
             e = DacEncoderConfig(cfg.encoder_dim, len(cfg.encoder_rates), (C.c_int32 * 8)(*cfg.encoder_rates))
-            ctx.check(ctx.lib.mia_dac_load_encoder(h, C.byref(e), views, len(weights)))
+            ctx.check(ctx.lib.mia_dac_load_encoder(h, C.byref(e), views, n))
         return codec
 
     def encode(self, audio: np.ndarray, n_quantizers: int | None = None) -> np.ndarray:

@@ -3,7 +3,6 @@
 // packed weights of the step (mia_lm_attach_quantized: host repack into the layout skinny_quant.hip reads).
 #include <algorithm>
 #include <cmath>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -13,51 +12,24 @@
 
 namespace {
 
-struct LmLoader {
-  mia_lm* m;
-  std::map<std::string, const mia_tensor_view*> by_name;
-  std::string err;
-  const mia_tensor_view* find(const std::string& n, bool req = true) {
-    auto it = by_name.find(n);
-    if (it == by_name.end()) { if (req && err.empty()) err = "missing tensor '" + n + "'"; return nullptr; }
-    return it->second;
+// the LM's tensors on top of the shared loader: what is fused (q|k|v stacked, gate / up interleaved) and the carried RMSNorm gains
+struct LmLoader : TensorLoader {
+  int dtype = MIA_BF16;
+  // a norm gain [D]: the plain copy, the pre-scaled one for the fused chain's producers and 1 / that scale (skinny.h, mia_carry_gain)
+  void norm(const std::string& n, int D, float*& plain, float*& scaled, float& rs) {
+    std::vector<float> g;
+    if (read(n, g, {D})) { plain = up(g); scaled = mia_carry_gain(*this, g, dtype, plain, &rs); }
   }
-  static float h2f(uint16_t h) { _Float16 x; memcpy(&x, &h, 2); return (float)x; }
-  bool to_f32(const std::string& n, std::vector<float>& out, int64_t rows, int64_t cols, bool req = true) {
-    const mia_tensor_view* t = find(n, req);
-    if (!t) return false;
-    const bool ok = cols > 0 ? (t->ndim == 2 && t->shape[0] == rows && t->shape[1] == cols) : (t->ndim == 1 && t->shape[0] == rows);
-    if (!ok) { if (err.empty()) err = "tensor '" + n + "' has an unexpected shape"; return false; }
-    const int64_t numel = rows * (cols > 0 ? cols : 1);
-    out.resize(numel);
-    if (t->dtype == MIA_F32) memcpy(out.data(), t->data, numel * 4);
-    else if (t->dtype == MIA_F16) { const uint16_t* p = (const uint16_t*)t->data; for (int64_t i = 0; i < numel; ++i) out[i] = h2f(p[i]); }
-    else { const uint16_t* p = (const uint16_t*)t->data; for (int64_t i = 0; i < numel; ++i) { uint32_t u = (uint32_t)p[i] << 16; memcpy(&out[i], &u, 4); } }
+  // tensors `<p><part><suffix>` of the given row counts stacked along the rows; cols == 0: vectors (the biases)
+  bool stacked(const std::string& p, std::initializer_list<std::pair<const char*, int>> parts, const char* suffix, int cols, std::vector<float>& out) {
+    std::vector<float> t;
+    out.clear();
+    for (const auto& part : parts) {
+      const std::string n = p + part.first + suffix;
+      if (!(cols ? read(n, t, {part.second, cols}) : read(n, t, {part.second}))) return false;
+      out.insert(out.end(), t.begin(), t.end());
+    }
     return true;
-  }
-  void* dev(size_t bytes) {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes + 64) != hipSuccess) { if (err.empty()) err = "hipMalloc failed"; return nullptr; }
-    m->allocs.push_back(p);
-    return p;
-  }
-  float* up32(const std::vector<float>& v) { float* d = (float*)dev(v.size() * 4); if (d) (void)hipMemcpy(d, v.data(), v.size() * 4, hipMemcpyHostToDevice); return d; }
-  // the gain of a carried RMSNorm times its pre-scale (skinny.h, mia_carry_prescale); *rs = 1 / scale.  `plain` when the scale is 1.
-  float* carried(const std::vector<float>& g, float* rs, float* plain) {
-    const float p = mia_carry_prescale(g.data(), (int)g.size(), m->dtype);
-    *rs = 1.f / p;
-    if (p == 1.f) return plain;
-    std::vector<float> v(g);
-    for (float& x : v) x *= p;
-    return up32(v);
-  }
-  void* up16(const std::vector<float>& v) {
-    std::vector<uint16_t> q(v.size());
-    if (m->dtype == MIA_F16) for (size_t i = 0; i < v.size(); ++i) { _Float16 hh = (_Float16)v[i]; memcpy(&q[i], &hh, 2); }
-    else for (size_t i = 0; i < v.size(); ++i) { uint32_t u; memcpy(&u, &v[i], 4); u += 0x7fffu + ((u >> 16) & 1); q[i] = (uint16_t)(u >> 16); }
-    void* d = dev(q.size() * 2);
-    if (d) (void)hipMemcpy(d, q.data(), q.size() * 2, hipMemcpyHostToDevice);
-    return d;
   }
 };
 
@@ -120,24 +92,24 @@ extern "C" mia_lm* mia_lm_load(mia_ctx* ctx, const mia_lm_config* cfg, const mia
     return fail(nullptr, "unsupported dimensions (hidden <= 4096 and % 32, inter % 32, max_ctx <= 8192)");
   if (hipSetDevice(ctx->device) != hipSuccess) return fail(nullptr, "hipSetDevice failed");
   mia_lm* m = new mia_lm(); m->ctx = ctx; m->cfg = c; m->dtype = dtype;
-  LmLoader L; L.m = m;
-  for (int i = 0; i < n_tensors; ++i) if (tensors[i].name && tensors[i].data) L.by_name[tensors[i].name] = &tensors[i];
+  LmLoader L; L.allocs = &m->allocs; L.dtype = dtype;
+  L.index(tensors, n_tensors);
   const int D = c.hidden, dh = c.head_dim, Nq = c.n_heads * dh, Nk = c.n_kv_heads * dh;
-  std::vector<float> t, t2, t3;
-  if (L.to_f32("model.embed_tokens.weight", t, c.vocab, D)) m->embed = L.up16(t);
+  std::vector<float> t, t2;
+  if (L.read("model.embed_tokens.weight", t, {c.vocab, D})) m->embed = L.up16(t, dtype);
   if (c.tie_embeddings) m->lm_head = m->embed;
-  else if (L.find("lm_head.weight", false) && L.to_f32("lm_head.weight", t, c.vocab, D)) m->lm_head = L.up16(t);
-  if (L.to_f32("model.norm.weight", t, D, 0)) { m->final_norm = L.up32(t); m->final_norm_c = L.carried(t, &m->final_rs, m->final_norm); }
-  if (const mia_tensor_view* hv = L.find("llm_decoder.weight", false)) {      // Qwen2LM: separate output head + speech embedding
+  else if (L.has("lm_head.weight") && L.read("lm_head.weight", t, {c.vocab, D})) m->lm_head = L.up16(t, dtype);
+  L.norm("model.norm.weight", D, m->final_norm, m->final_norm_c, m->final_rs);
+  if (const mia_tensor_view* hv = L.find("llm_decoder.weight")) {      // Qwen2LM: separate output head + speech embedding
     if (hv->ndim == 2 && hv->shape[1] == D) {
       m->head_vocab = (int)hv->shape[0];
-      if (L.to_f32("llm_decoder.weight", t, m->head_vocab, D)) m->lm_head = L.up16(t);
-      if (L.find("llm_decoder.bias", false) && L.to_f32("llm_decoder.bias", t, m->head_vocab, 0)) m->head_bias = L.up32(t);
-    } else L.err = "llm_decoder.weight has an unexpected shape";
+      if (L.read("llm_decoder.weight", t, {m->head_vocab, D})) m->lm_head = L.up16(t, dtype);
+      if (L.has("llm_decoder.bias") && L.read("llm_decoder.bias", t, {m->head_vocab})) m->head_bias = L.up(t);
+    } else L.fail(MIA_ERR_INVALID_ARGUMENT, "llm_decoder.weight has an unexpected shape");
   }
-  if (const mia_tensor_view* gv = L.find("speech_embedding.weight", false)) {
-    if (gv->ndim == 2 && gv->shape[1] == D) { m->gen_rows = (int)gv->shape[0]; if (L.to_f32("speech_embedding.weight", t, m->gen_rows, D)) m->gen_embed = L.up16(t); }
-    else L.err = "speech_embedding.weight has an unexpected shape";
+  if (const mia_tensor_view* gv = L.find("speech_embedding.weight")) {
+    if (gv->ndim == 2 && gv->shape[1] == D) { m->gen_rows = (int)gv->shape[0]; if (L.read("speech_embedding.weight", t, {m->gen_rows, D})) m->gen_embed = L.up16(t, dtype); }
+    else L.fail(MIA_ERR_INVALID_ARGUMENT, "speech_embedding.weight has an unexpected shape");
   }
   {  // rotary inverse frequencies: plain RoPE(base) or Llama3RoPE (Llama3RoPE.swift:41-65: period-like `freqs`, MLX divides positions by them)
     std::vector<float> inv(dh / 2);
@@ -155,7 +127,7 @@ extern "C" mia_lm* mia_lm_load(mia_ctx* ctx, const mia_lm_config* cfg, const mia
       }
       inv[i] = 1.0f / freq;
     }
-    m->inv_freq = L.up32(inv);
+    m->inv_freq = L.up(inv);
   }
   m->layers.resize(c.n_layers);
   // Qwen3's per-head q / k RMSNorm (STT/FunASR/Layers/Qwen3Model.swift:32-35,57-59) is switched by tensor presence, like the CosyVoice2
@@ -166,50 +138,35 @@ extern "C" mia_lm* mia_lm_load(mia_ctx* ctx, const mia_lm_config* cfg, const mia
     LmLayer& ly = m->layers[l];
     {
       const std::string qn = p + ".self_attn.q_norm.weight", kn = p + ".self_attn.k_norm.weight";
-      const bool has_q = L.find(qn, false) != nullptr, has_k = L.find(kn, false) != nullptr;
-      if (has_q != has_k) L.err = "missing tensor '" + (has_q ? kn : qn) + "' (q_norm and k_norm come as a pair)";
-      else if (l > 0 && has_q != !qkn.empty()) L.err = "tensor '" + qn + "' is " + (has_q ? "present" : "missing") + ": q_norm / k_norm must be in every layer or in none";
-      else if (has_q && L.to_f32(qn, t, dh, 0) && L.to_f32(kn, t2, dh, 0)) { qkn.insert(qkn.end(), t.begin(), t.end()); qkn.insert(qkn.end(), t2.begin(), t2.end()); }
+      const bool has_q = L.has(qn), has_k = L.has(kn);
+      if (has_q != has_k) L.fail(MIA_ERR_INVALID_ARGUMENT, "missing tensor '" + (has_q ? kn : qn) + "' (q_norm and k_norm come as a pair)");
+      else if (l > 0 && has_q != !qkn.empty())
+        L.fail(MIA_ERR_INVALID_ARGUMENT, "tensor '" + qn + "' is " + (has_q ? "present" : "missing") + ": q_norm / k_norm must be in every layer or in none");
+      else if (has_q && L.read(qn, t, {dh}) && L.read(kn, t2, {dh})) { qkn.insert(qkn.end(), t.begin(), t.end()); qkn.insert(qkn.end(), t2.begin(), t2.end()); }
     }
-    if (L.to_f32(p + ".input_layernorm.weight", t, D, 0)) { ly.in_norm = L.up32(t); ly.in_norm_c = L.carried(t, &ly.in_rs, ly.in_norm); }
-    if (L.to_f32(p + ".post_attention_layernorm.weight", t, D, 0)) { ly.post_norm = L.up32(t); ly.post_norm_c = L.carried(t, &ly.post_rs, ly.post_norm); }
-    std::vector<float> qkv((size_t)(Nq + 2 * Nk) * D);
-    if (L.to_f32(p + ".self_attn.q_proj.weight", t, Nq, D) && L.to_f32(p + ".self_attn.k_proj.weight", t2, Nk, D) && L.to_f32(p + ".self_attn.v_proj.weight", t3, Nk, D)) {
-      memcpy(qkv.data(), t.data(), t.size() * 4); memcpy(qkv.data() + t.size(), t2.data(), t2.size() * 4); memcpy(qkv.data() + t.size() + t2.size(), t3.data(), t3.size() * 4);
-      ly.wqkv = L.up16(qkv);
-    }
-    if (c.qkv_bias) {
-      std::vector<float> b((size_t)Nq + 2 * Nk);
-      if (L.to_f32(p + ".self_attn.q_proj.bias", t, Nq, 0) && L.to_f32(p + ".self_attn.k_proj.bias", t2, Nk, 0) && L.to_f32(p + ".self_attn.v_proj.bias", t3, Nk, 0)) {
-        memcpy(b.data(), t.data(), t.size() * 4); memcpy(b.data() + Nq, t2.data(), t2.size() * 4); memcpy(b.data() + Nq + Nk, t3.data(), t3.size() * 4);
-        ly.bqkv = L.up32(b);
-      }
-    }
-    if (L.to_f32(p + ".self_attn.o_proj.weight", t, D, Nq)) ly.wo = L.up16(t);
-    if (L.to_f32(p + ".mlp.gate_proj.weight", t, c.inter, D) && L.to_f32(p + ".mlp.up_proj.weight", t2, c.inter, D)) {
+    L.norm(p + ".input_layernorm.weight", D, ly.in_norm, ly.in_norm_c, ly.in_rs);
+    L.norm(p + ".post_attention_layernorm.weight", D, ly.post_norm, ly.post_norm_c, ly.post_rs);
+    const std::initializer_list<std::pair<const char*, int>> qkv = {{"q_proj", Nq}, {"k_proj", Nk}, {"v_proj", Nk}};
+    if (L.stacked(p + ".self_attn.", qkv, ".weight", D, t)) ly.wqkv = L.up16(t, dtype);
+    if (c.qkv_bias && L.stacked(p + ".self_attn.", qkv, ".bias", 0, t)) ly.bqkv = L.up(t);
+    if (L.read(p + ".self_attn.o_proj.weight", t, {D, Nq})) ly.wo = L.up16(t, dtype);
+    if (L.read(p + ".mlp.gate_proj.weight", t, {c.inter, D}) && L.read(p + ".mlp.up_proj.weight", t2, {c.inter, D})) {
       std::vector<float> gu((size_t)2 * c.inter * D);
       for (int r = 0; r < c.inter; ++r) { memcpy(&gu[(size_t)(2 * r) * D], &t[(size_t)r * D], (size_t)D * 4); memcpy(&gu[(size_t)(2 * r + 1) * D], &t2[(size_t)r * D], (size_t)D * 4); }
-      ly.wgu = L.up16(gu);
+      ly.wgu = L.up16(gu, dtype);
     }
-    if (L.to_f32(p + ".mlp.down_proj.weight", t, D, c.inter)) ly.wdown = L.up16(t);
+    if (L.read(p + ".mlp.down_proj.weight", t, {D, c.inter})) ly.wdown = L.up16(t, dtype);
   }
-  if (L.err.empty() && !qkn.empty()) m->qk_norm = L.up32(qkn);
+  if (L.err.empty() && !qkn.empty()) m->qk_norm = L.up(qkn);
   if (!L.err.empty()) return fail(m, L.err);
   {  // fragment-order copies for the decode step (one device repack per matrix)
     bool ok = true;
-    auto frag = [&](const void* src, int N, int K) -> void* {
-      if (!ok || !src || K % 32 != 0) return nullptr;
-      void* dst = nullptr;
-      if (hipMalloc(&dst, (size_t)((N + 15) / 16) * 16 * K * 2) != hipSuccess) { ok = false; return nullptr; }
-      m->allocs.push_back(dst);
-      if (dec_launch_repack_wfrag(src, dst, N, K, ctx->stream) != 0) ok = false;
-      return dst;
-    };
+    auto frag = [&](const void* src, int N, int K, void** dst) { ok = ok && dec_wfrag_copy(src, N, K, m->allocs, ctx->stream, dst); };
     for (LmLayer& ly : m->layers) {
-      ly.wqkv_f = frag(ly.wqkv, Nq + 2 * Nk, D); ly.wo_f = frag(ly.wo, D, Nq);
-      ly.wgu_f = frag(ly.wgu, 2 * c.inter, D); ly.wdown_f = frag(ly.wdown, D, c.inter);
+      frag(ly.wqkv, Nq + 2 * Nk, D, &ly.wqkv_f); frag(ly.wo, D, Nq, &ly.wo_f);
+      frag(ly.wgu, 2 * c.inter, D, &ly.wgu_f); frag(ly.wdown, D, c.inter, &ly.wdown_f);
     }
-    m->lm_head_f = frag(m->lm_head, m->head_vocab > 0 ? m->head_vocab : c.vocab, D);
+    frag(m->lm_head, m->head_vocab > 0 ? m->head_vocab : c.vocab, D, &m->lm_head_f);
     if (!ok) return fail(m, "fragment-order repack of the step weights failed");
   }
   m->S_qkv = pick_split(D, 4); m->S_o = pick_split(Nq, 4); m->S_down = pick_split(c.inter, 8);
@@ -219,30 +176,12 @@ extern "C" mia_lm* mia_lm_load(mia_ctx* ctx, const mia_lm_config* cfg, const mia
 }
 
 // ---- MLX-affine 4-bit weights for the decode step (OrpheusWeightLoader.swift:28-60: the reference's default checkpoints are q4, group 64) ----
-namespace {
-
-// rows[i] = (tensor index, row): the fused matrix's row i.  Builds the fragment-ordered arrays (quant_repack.h; layout and arithmetic:
-// skinny_gemm_qi) and uploads them.  bits 4 | 8; mag = the 16-bit float the codes are OR-ed into (128 for bf16, 1024 for f16 compute).
-bool q_repack(LmLoader& L, const std::vector<Q4Src>& src, const std::vector<std::pair<int, int>>& rows, int K, int bits, int sdt, float mag, Q4W& out) {
-  std::vector<uint32_t> wf;
-  std::vector<float> st;
-  q_repack_host(src, rows, K, bits, sdt, mag, wf, st);
-  out.wfrag = (uint32_t*)L.dev(wf.size() * 4);
-  out.stfrag = (float*)L.dev(st.size() * 4);
-  if (!out.wfrag || !out.stfrag) { if (L.err.empty()) L.err = "hipMalloc failed for the packed weights"; return false; }
-  if (hipMemcpy(out.wfrag, wf.data(), wf.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(out.stfrag, st.data(), st.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-    if (L.err.empty()) L.err = "upload of the packed weights failed";
-    return false;
-  }
-  return true;
-}
-
-}  // namespace
-
 // tensors: for every Linear of the step, `<name>.weight` (MIA_U32 packed codes [N][K * bits / 32]), `<name>.scales`, `<name>.biases`
 // ([N][K/64], both MIA_F16 or both MIA_BF16), names as in the checkpoint (model.layers.L.self_attn.{q,k,v,o}_proj, mlp.{gate,up,down}_proj,
 // model.embed_tokens / lm_head).  The handle must already hold the de-quantised 16-bit weights (mia_lm_load on the expanded
-// checkpoint): the batched prompt pass keeps using them, the per-token step switches to the packed form.
+// checkpoint): the batched prompt pass keeps using them, the per-token step switches to the packed form.  Nothing of the handle changes
+// unless every matrix was repacked and uploaded.  A bad argument or tensor list is MIA_ERR_INVALID_ARGUMENT; a refused hipMalloc
+// MIA_ERR_OUT_OF_MEMORY, a failed upload MIA_ERR_DEVICE.
 extern "C" int mia_lm_attach_quantized(mia_lm* m, const mia_tensor_view* tensors, int n_tensors, int group_size, int bits) {
   if (!m) return MIA_ERR_MODEL_NOT_LOADED;
   mia_ctx* ctx = m->ctx;
@@ -252,55 +191,42 @@ extern "C" int mia_lm_attach_quantized(mia_lm* m, const mia_tensor_view* tensors
   const int D = c.hidden, dh = c.head_dim, Nq = c.n_heads * dh, Nk = c.n_kv_heads * dh;
   MIA_CHECK_ARG(ctx, D % 128 == 0 && Nq % 128 == 0 && c.inter % 128 == 0, "lm_attach_quantized: hidden, n_heads*head_dim and inter must be multiples of 128");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
-  LmLoader L; L.m = m;
-  for (int i = 0; i < n_tensors; ++i) if (tensors[i].name && tensors[i].data) L.by_name[tensors[i].name] = &tensors[i];
-  int sdt = 0;
+  std::vector<void*> fresh;                      // joins m->allocs only when everything is in place
+  TensorLoader L; L.allocs = &fresh;
+  L.index(tensors, n_tensors);
+  int sdt = -1;
   const float mag = m->dtype == MIA_F16 ? 1024.0f : 128.0f;
-  auto get = [&](const std::string& p, int N, int K, Q4Src& q) -> bool {
-    const mia_tensor_view* w = L.find(p + ".weight"); const mia_tensor_view* s = L.find(p + ".scales"); const mia_tensor_view* b = L.find(p + ".biases");
-    if (!w || !s || !b) return false;
-    const bool ok = w->dtype == MIA_U32 && w->ndim == 2 && w->shape[0] == N && w->shape[1] == (int64_t)K * bits / 32 && s->ndim == 2 && s->shape[0] == N && s->shape[1] == K / 64 &&
-                    b->ndim == 2 && b->shape[0] == N && b->shape[1] == K / 64 && s->dtype == b->dtype && (s->dtype == MIA_F16 || s->dtype == MIA_BF16);
-    if (!ok) { if (L.err.empty()) L.err = "'" + p + "' is not a " + std::to_string(bits) + "-bit group-64 Linear of the expected shape (scales / biases must be f16 or bf16)"; return false; }
-    if (sdt == 0) sdt = s->dtype;
-    if (sdt != s->dtype) { if (L.err.empty()) L.err = "mixed scale dtypes"; return false; }
-    q = Q4Src{(const uint32_t*)w->data, s->data, b->data};
-    return true;
+  // parts (name, rows) fused as the dense loader fuses them: stacked along N, or their rows interleaved (gate / up, like wgu)
+  auto pack = [&](const std::string& p, std::initializer_list<std::pair<const char*, int>> parts, int K, bool interleave, Q4W& out) -> bool {
+    std::vector<Q4Src> src(parts.size());
+    std::vector<std::pair<int, int>> rows;
+    int i = 0;
+    for (const auto& part : parts) {
+      if (!q_find_linear(L, p + part.first, part.second, K, bits, false, &sdt, src[i])) return false;
+      if (!interleave) for (int n = 0; n < part.second; ++n) rows.push_back({i, n});
+      ++i;
+    }
+    if (interleave) for (int n = 0; n < parts.begin()->second; ++n) for (int j = 0; j < i; ++j) rows.push_back({j, n});
+    return q_upload(L, src, rows, K, bits, sdt, mag, &out.wfrag, &out.stfrag);
   };
-  auto seq = [](int tensor, int n, std::vector<std::pair<int, int>>& rows) { for (int i = 0; i < n; ++i) rows.push_back({tensor, i}); };
-  for (int l = 0; l < c.n_layers && L.err.empty(); ++l) {
+  bool ok = true;
+  for (int l = 0; l < c.n_layers && ok; ++l) {
     const std::string p = "model.layers." + std::to_string(l);
     LmLayer& ly = m->layers[l];
-    std::vector<Q4Src> src(3);
-    std::vector<std::pair<int, int>> rows;
-    if (get(p + ".self_attn.q_proj", Nq, D, src[0]) && get(p + ".self_attn.k_proj", Nk, D, src[1]) && get(p + ".self_attn.v_proj", Nk, D, src[2])) {
-      seq(0, Nq, rows); seq(1, Nk, rows); seq(2, Nk, rows);
-      if (!q_repack(L, src, rows, D, bits, sdt, mag, ly.q_qkv)) break;
-    }
-    src.assign(1, Q4Src{}); rows.clear();
-    if (get(p + ".self_attn.o_proj", D, Nq, src[0])) { seq(0, D, rows); if (!q_repack(L, src, rows, Nq, bits, sdt, mag, ly.q_o)) break; }
-    src.assign(2, Q4Src{}); rows.clear();
-    if (get(p + ".mlp.gate_proj", c.inter, D, src[0]) && get(p + ".mlp.up_proj", c.inter, D, src[1])) {
-      for (int i = 0; i < c.inter; ++i) { rows.push_back({0, i}); rows.push_back({1, i}); }      // gate / up rows interleaved like wgu
-      if (!q_repack(L, src, rows, D, bits, sdt, mag, ly.q_gu)) break;
-    }
-    src.assign(1, Q4Src{}); rows.clear();
-    if (get(p + ".mlp.down_proj", D, c.inter, src[0])) { seq(0, D, rows); if (!q_repack(L, src, rows, c.inter, bits, sdt, mag, ly.q_down)) break; }
+    ok = pack(p + ".self_attn.", {{"q_proj", Nq}, {"k_proj", Nk}, {"v_proj", Nk}}, D, false, ly.q_qkv) && pack(p + ".self_attn.", {{"o_proj", D}}, Nq, false, ly.q_o) &&
+         pack(p + ".mlp.", {{"gate_proj", c.inter}, {"up_proj", c.inter}}, D, true, ly.q_gu) && pack(p + ".mlp.", {{"down_proj", D}}, c.inter, false, ly.q_down);
   }
-  if (L.err.empty() && m->head_vocab == 0) {     // the tied / plain LM head (the CosyVoice2 speech head stays 16-bit: it is not quantised there)
-    std::vector<Q4Src> src(1);
-    std::vector<std::pair<int, int>> rows;
-    const std::string hp = c.tie_embeddings ? "model.embed_tokens" : "lm_head";
-    if (L.find(hp + ".scales", false)) { if (get(hp, c.vocab, D, src[0])) { seq(0, c.vocab, rows); q_repack(L, src, rows, D, bits, sdt, mag, m->q_head); } }
-  }
-  if (!L.err.empty()) {
-    // a partly packed handle must not run: drop every packed pointer (the buffers stay with the handle's allocation list until mia_lm_free)
+  // the tied / plain LM head, when the checkpoint packs it (the CosyVoice2 speech head stays 16-bit: it is not quantised there)
+  const char* hp = c.tie_embeddings ? "model.embed_tokens" : "lm_head";
+  if (ok && m->head_vocab == 0 && L.has(std::string(hp) + ".scales")) ok = pack("", {{hp, c.vocab}}, D, false, m->q_head);
+  if (ok && hipDeviceSynchronize() != hipSuccess) ok = L.fail(MIA_ERR_DEVICE, "device error during upload");
+  if (!ok) {      // a partly packed handle must not run: drop every packed pointer and the attach's buffers; the handle is as before
     for (LmLayer& ly : m->layers) { ly.q_qkv = Q4W{}; ly.q_o = Q4W{}; ly.q_gu = Q4W{}; ly.q_down = Q4W{}; }
     m->q_head = Q4W{};
-    const bool oom = L.err.find("hipMalloc") != std::string::npos;
-    return mia_fail(ctx, oom ? MIA_ERR_OUT_OF_MEMORY : MIA_ERR_INVALID_ARGUMENT, "lm_attach_quantized: %s", L.err.c_str());
+    for (void* p : fresh) (void)hipFree(p);
+    return mia_fail(ctx, L.code, "lm_attach_quantized: %s", L.err.c_str());
   }
-  MIA_HIP(ctx, hipDeviceSynchronize());
+  m->allocs.insert(m->allocs.end(), fresh.begin(), fresh.end());
   // the packed kernel splits K in 128-input blocks: re-pick the cross-workgroup splits on that granule (the 16-bit step uses the same
   // splits from here on)
   auto split128 = [](int K, int want) { for (int sp = want; sp > 1; --sp) if (K % (128 * sp) == 0) return sp; return 1; };

@@ -1,4 +1,4 @@
-// quant_repack.hip -- host repack of packed MLX-affine Linears into fragment order (quant_repack.h); no device code.
+// quant_repack.hip -- host repack of packed MLX-affine Linears into fragment order, their lookup and upload (quant_repack.h); no device code.
 #include "quant_repack.h"
 
 #include <string.h>
@@ -12,8 +12,7 @@ namespace {
 float q_to_f32(const void* p, size_t i, int sdt) {
   if (sdt == MIA_F32) return ((const float*)p)[i];
   const uint16_t v = ((const uint16_t*)p)[i];
-  if (sdt == MIA_F16) { _Float16 h; memcpy(&h, &v, 2); return (float)h; }
-  const uint32_t u = (uint32_t)v << 16; float f; memcpy(&f, &u, 4); return f;
+  return sdt == MIA_F16 ? f16_to_f32(v) : bf16_to_f32(v);
 }
 
 }  // namespace
@@ -52,6 +51,36 @@ void q_repack_host(const std::vector<Q4Src>& src, const std::vector<std::pair<in
         }
       }
     }
+}
+
+bool q_find_linear(TensorLoader& L, const std::string& p, int N, int K, int bits, bool f32_scales, int* sdt, Q4Src& q) {
+  const mia_tensor_view* t[3];
+  const char* suffix[3] = {".weight", ".scales", ".biases"};
+  for (int i = 0; i < 3; ++i)
+    if (!(t[i] = L.find(p + suffix[i]))) return L.fail(MIA_ERR_INVALID_ARGUMENT, "missing tensor '" + p + suffix[i] + "'");
+  const mia_tensor_view *w = t[0], *s = t[1], *b = t[2];
+  const bool ok = w->dtype == MIA_U32 && w->ndim == 2 && w->shape[0] == N && w->shape[1] == (int64_t)K * bits / 32 && s->ndim == 2 && s->shape[0] == N &&
+                  s->shape[1] == K / 64 && b->ndim == 2 && b->shape[0] == N && b->shape[1] == K / 64 && s->dtype == b->dtype &&
+                  (s->dtype == MIA_F16 || s->dtype == MIA_BF16 || (f32_scales && s->dtype == MIA_F32));
+  if (!ok)
+    return L.fail(MIA_ERR_INVALID_ARGUMENT, "'" + p + "' is not a " + std::to_string(bits) + "-bit group-64 Linear of the expected shape (scales / biases" +
+                                                (f32_scales ? ": f16, bf16 or f32)" : " must be f16 or bf16)"));
+  if (*sdt < 0) *sdt = s->dtype;
+  if (*sdt != s->dtype) return L.fail(MIA_ERR_INVALID_ARGUMENT, "mixed scale dtypes");
+  q = Q4Src{(const uint32_t*)w->data, s->data, b->data};
+  return true;
+}
+
+bool q_upload(TensorLoader& L, const std::vector<Q4Src>& src, const std::vector<std::pair<int, int>>& rows, int K, int bits, int sdt, float mag,
+              uint32_t** wfrag, float** stfrag) {
+  std::vector<uint32_t> wf;
+  std::vector<float> st;
+  q_repack_host(src, rows, K, bits, sdt, mag, wf, st);
+  *wfrag = (uint32_t*)L.alloc(wf.size() * 4);
+  *stfrag = L.up(st);
+  if (!*wfrag || !*stfrag) return false;
+  if (hipMemcpy(*wfrag, wf.data(), wf.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return L.fail(MIA_ERR_DEVICE, "upload of the packed weights failed");
+  return L.err.empty();
 }
 
 // Test hook (include/mia.h): the repack alone, host memory in and out -- needs no device.

@@ -57,25 +57,8 @@ struct mia_sensevoice {
 
 namespace {
 
-inline uint16_t host_bf16(float f) {
-  uint32_t u; memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1);
-  return (uint16_t)(u >> 16);
-}
-inline uint16_t host_f16(float f) { const _Float16 h = (_Float16)f; uint16_t r; memcpy(&r, &h, 2); return r; }   // RNE
-
 struct SvLoader : TensorLoader {
   int dtype = MIA_BF16;
-  void* up16(const std::vector<float>& v) {
-    std::vector<uint16_t> q(v.size());
-    for (size_t i = 0; i < v.size(); ++i) q[i] = dtype == MIA_F16 ? host_f16(v[i]) : host_bf16(v[i]);
-    void* p = nullptr;
-    if (hipMalloc(&p, q.size() * 2 + 64) != hipSuccess) { if (err.empty()) err = "hipMalloc failed"; return nullptr; }
-    allocs->push_back(p);
-    if (hipMemcpy(p, q.data(), q.size() * 2, hipMemcpyHostToDevice) != hipSuccess && err.empty()) err = "hipMemcpy failed";
-    return p;
-  }
   // Linear [N][K] + bias [N]; the weight's K is zero-padded to a multiple of 64
   bool linear(const std::string& n, SvLinear& l, int N, int K) {
     std::vector<float> w, b;
@@ -86,7 +69,7 @@ struct SvLoader : TensorLoader {
       for (int r = 0; r < N; ++r) memcpy(&wp[(size_t)r * Kp], &w[(size_t)r * K], (size_t)K * 4);
       w.swap(wp);
     }
-    l.w = up16(w); l.b = up(b); l.N = N; l.K = Kp;
+    l.w = up16(w, dtype); l.b = up(b); l.N = N; l.K = Kp;
     return l.w && l.b;
   }
   // three Linears [D][D] stacked into one [3 D][D] (the adaptor's linear_q / linear_k / linear_v)
@@ -96,7 +79,7 @@ struct SvLoader : TensorLoader {
       if (!f32(p + "." + n + ".weight", wi, {D, D}) || !f32(p + "." + n + ".bias", bi, {D})) return false;
       w.insert(w.end(), wi.begin(), wi.end()); b.insert(b.end(), bi.begin(), bi.end());
     }
-    l.w = up16(w); l.b = up(b); l.N = 3 * D; l.K = D;
+    l.w = up16(w, dtype); l.b = up(b); l.N = 3 * D; l.K = D;
     return l.w && l.b;
   }
   bool norm(const std::string& n, SvNorm& ln, int D) {
@@ -108,10 +91,10 @@ struct SvLoader : TensorLoader {
   // fsmn_block.weight: [D][1][K] (the checkpoint's torch Conv1d) or [D][K][1] (after FunASRModel.sanitize) -> [K][D]
   bool fsmn(const std::string& n, float*& out, int D, int K) {
     const mia_tensor_view* t = find(n);
-    if (!t) { if (err.empty()) err = "missing tensor '" + n + "'"; return false; }
+    if (!t) return fail(MIA_ERR_INVALID_ARGUMENT, "missing tensor '" + n + "'");
     const bool shape_ok = t->dtype == MIA_F32 && t->ndim == 3 && t->shape[0] == D &&
                           ((t->shape[1] == 1 && t->shape[2] == K) || (t->shape[1] == K && t->shape[2] == 1));
-    if (!shape_ok) { if (err.empty()) err = "tensor '" + n + "' must be float32 [D][1][K] or [D][K][1]"; return false; }
+    if (!shape_ok) return fail(MIA_ERR_INVALID_ARGUMENT, "tensor '" + n + "' must be float32 [D][1][K] or [D][K][1]");
     const float* src = (const float*)t->data;        // both layouts are [D][K] in memory
     std::vector<float> w((size_t)K * D);
     for (int d = 0; d < D; ++d)
@@ -325,8 +308,7 @@ extern "C" mia_sensevoice* mia_sensevoice_load(mia_ctx* ctx, const mia_sensevoic
          L.norm(p + ".norm2", b.norm2, LL) && L.linear(p + ".feed_forward.w_1", b.w1, LL / 4, LL) && L.linear(p + ".feed_forward.w_2", b.w2, LL, LL / 4);
   }
   if (!ok || !L.err.empty()) {
-    mia_fail(ctx, L.err.find("hipMalloc") != std::string::npos ? MIA_ERR_OUT_OF_MEMORY : MIA_ERR_INVALID_ARGUMENT, "sensevoice_load: %s",
-             L.err.empty() ? "load failed" : L.err.c_str());
+    mia_fail(ctx, L.err.empty() ? MIA_ERR_INVALID_ARGUMENT : L.code, "sensevoice_load: %s", L.err.empty() ? "load failed" : L.err.c_str());
     mia_sensevoice_free(sv);
     return nullptr;
   }

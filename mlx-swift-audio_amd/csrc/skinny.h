@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/mia.h"
+#include "tensor_loader.h"
 
 enum { SK_OUT16 = 0, SK_OUTF32 = 1, SK_PARTIAL = 2, SK_QKV = 3, SK_SWIGLU = 4, SK_RESID = 5 };
 
@@ -67,8 +68,22 @@ inline float mia_carry_prescale(const float* gain, int n, int dtype) {
   return ldexpf(1.f, -k);
 }
 
+// The gain of a carried norm as its producer stores with it: g x mia_carry_prescale, uploaded through L; *rs = 1 / that scale for the
+// consumer.  `plain` (the unscaled gain already on the device) when the scale is 1.
+inline float* mia_carry_gain(TensorLoader& L, const std::vector<float>& g, int dtype, float* plain, float* rs) {
+  const float p = mia_carry_prescale(g.data(), (int)g.size(), dtype);
+  *rs = 1.f / p;
+  if (p == 1.f) return plain;
+  std::vector<float> v(g);
+  for (float& x : v) x *= p;
+  return L.up(v);
+}
+
 // row-major [N][K] 16-bit -> weight fragment order (dst holds ceil(N/16)*16*K elements; rows past N are zero)
 int dec_launch_repack_wfrag(const void* src, void* dst, int N, int K, hipStream_t s);
+// The loaders' form: *dst = a fragment-order copy of src in a new buffer appended to `allocs` (one device repack per matrix).  A null src
+// (a matrix the model does not have) gives a null copy.  false: K % 32 != 0, a refused hipMalloc or a failed launch.
+bool dec_wfrag_copy(const void* src, int N, int K, std::vector<void*>& allocs, hipStream_t s, void** dst);
 // row-major activations (the LM step; skinny_rowmajor.hip), dtype = MIA_BF16 | MIA_F16; modes SK_OUTF32 / SK_PARTIAL / SK_SWIGLU / SK_RESID.
 // SK_SWIGLU: W rows interleaved gate/up, out[m][n/2] = silu(g)*u (16-bit)
 // Both launchers also refuse (-1) non-positive sizes and a W (16 bit: an A too) or packed code array of 4 GiB or more: the kernels address

@@ -33,6 +33,14 @@ int dec_launch_repack_wfrag(const void* src, void* dst, int N, int K, hipStream_
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+bool dec_wfrag_copy(const void* src, int N, int K, std::vector<void*>& allocs, hipStream_t s, void** dst) {
+  *dst = nullptr;
+  if (!src) return true;
+  if (K % 32 != 0 || hipMalloc(dst, (size_t)((N + 15) / 16) * 16 * K * 2) != hipSuccess) { *dst = nullptr; return false; }
+  allocs.push_back(*dst);
+  return dec_launch_repack_wfrag(src, *dst, N, K, s) == 0;
+}
+
 // c1[n] = sum_k W[n][k] gamma[k], c2[n] = sum_k W[n][k] beta[k]: one wave per row of a row-major 16-bit matrix (load time, once per Linear)
 template <typename T>
 __global__ __launch_bounds__(256) void dec_lnfold(const uint16_t* __restrict__ w, int N, int K, const float* __restrict__ gamma,

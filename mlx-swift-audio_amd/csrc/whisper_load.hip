@@ -8,137 +8,43 @@
 
 namespace {
 
-inline float half_to_float(uint16_t h) {
-  const uint32_t s = (h >> 15) & 1, e = (h >> 10) & 0x1f, m = h & 0x3ff;
-  uint32_t u;
-  if (e == 0) {
-    if (m == 0) u = s << 31;
-    else {
-      int sh = 0; uint32_t mm = m;
-      while (!(mm & 0x400)) { mm <<= 1; ++sh; }
-      u = (s << 31) | ((uint32_t)(127 - 15 - sh + 1) << 23) | ((mm & 0x3ff) << 13);
-    }
-  } else if (e == 31) u = (s << 31) | 0x7f800000u | (m << 13);
-  else u = (s << 31) | ((e - 15 + 127) << 23) | (m << 13);
-  float f; memcpy(&f, &u, 4); return f;
-}
-inline uint16_t float_to_bf16(float f) {
-  uint32_t u; memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1);
-  return (uint16_t)(u >> 16);
-}
-inline uint16_t float_to_half(float f) {
-  uint32_t x; memcpy(&x, &f, 4);
-  const uint32_t sign = (x >> 16) & 0x8000u;
-  x &= 0x7fffffffu;
-  if (x >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | (x > 0x7f800000u ? 0x200u : 0));
-  if (x >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                      // overflow -> inf (after rounding)
-  if (x < 0x38800000u) {                                                         // subnormal / zero
-    if (x < 0x33000000u) return (uint16_t)sign;
-    const int shift = 113 - (int)(x >> 23);
-    uint32_t m = (x & 0x7fffffu) | 0x800000u;
-    const uint32_t round_bit = 1u << (shift + 12);
-    uint32_t r = m >> (shift + 13);
-    const uint32_t rem = m & ((round_bit << 1) - 1);
-    if (rem > round_bit || (rem == round_bit && (r & 1))) ++r;
-    return (uint16_t)(sign | r);
-  }
-  uint32_t r = (x - 0x38000000u) >> 13;
-  const uint32_t rem = x & 0x1fffu;
-  if (rem > 0x1000u || (rem == 0x1000u && (r & 1))) ++r;
-  return (uint16_t)(sign | r);
-}
-
-struct Loader {
-  mia_whisper* w;
-  std::map<std::string, const mia_tensor_view*> by_name;
-  std::string err;
-
-  const mia_tensor_view* find(const std::string& n, bool required = true) {
-    auto it = by_name.find(n);
-    if (it == by_name.end()) {
-      if (required && err.empty()) err = "missing tensor '" + n + "'";
-      return nullptr;
-    }
-    return it->second;
-  }
-  static int64_t numel(const mia_tensor_view* t) {
-    int64_t n = 1;
-    for (int i = 0; i < t->ndim; ++i) n *= t->shape[i];
-    return n;
-  }
-  // read element i of a host tensor as fp32
-  static void to_f32(const mia_tensor_view* t, std::vector<float>& out) {
-    const int64_t n = numel(t);
-    out.resize(n);
-    if (t->dtype == MIA_F32) memcpy(out.data(), t->data, n * 4);
-    else if (t->dtype == MIA_F16) { const uint16_t* p = (const uint16_t*)t->data; for (int64_t i = 0; i < n; ++i) out[i] = half_to_float(p[i]); }
-    else { const uint16_t* p = (const uint16_t*)t->data; for (int64_t i = 0; i < n; ++i) { uint32_t u = (uint32_t)p[i] << 16; memcpy(&out[i], &u, 4); } }
-  }
-  void* dev_alloc(size_t bytes) {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) { if (err.empty()) err = "hipMalloc failed (weights)"; return nullptr; }
-    w->allocs.push_back(p);
-    return p;
-  }
-  float* upload_f32(const std::vector<float>& v) {
-    float* d = (float*)dev_alloc(v.size() * 4);
-    if (d && hipMemcpy(d, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess && err.empty()) err = "hipMemcpy failed";
-    return d;
-  }
-  void* upload_16(const std::vector<float>& v) {
-    std::vector<uint16_t> q(v.size());
-    if (w->dtype == MIA_F16) for (size_t i = 0; i < v.size(); ++i) q[i] = float_to_half(v[i]);
-    else for (size_t i = 0; i < v.size(); ++i) q[i] = float_to_bf16(v[i]);
-    void* d = dev_alloc(q.size() * 2);
-    if (d && hipMemcpy(d, q.data(), q.size() * 2, hipMemcpyHostToDevice) != hipSuccess && err.empty()) err = "hipMemcpy failed";
-    return d;
-  }
-  bool expect(const mia_tensor_view* t, std::initializer_list<int64_t> shp, const std::string& name) {
-    if (!t) return false;
-    bool ok = t->ndim == (int)shp.size();
-    int i = 0;
-    for (int64_t s : shp) { if (ok && t->shape[i] != s) ok = false; ++i; }
-    if (!ok && err.empty()) err = "tensor '" + name + "' has an unexpected shape";
-    return ok;
-  }
-  LNW ln(const std::string& p, int D) {
+// Whisper's tensors on top of the shared loader: LayerNorms, Linears stacked along N, the two convolutions
+struct Loader : TensorLoader {
+  int dtype = MIA_BF16;
+  // `gain` keeps the host copy of the gamma (the carried LayerNorms scale it again: mia_carry_gain)
+  LNW ln(const std::string& p, int D, std::vector<float>* gain = nullptr) {
     LNW o;
-    const mia_tensor_view* g = find(p + ".weight"); const mia_tensor_view* b = find(p + ".bias");
-    if (!expect(g, {D}, p + ".weight") || !expect(b, {D}, p + ".bias")) return o;
-    std::vector<float> v; to_f32(g, v); o.g = upload_f32(v); o.gc = o.g; to_f32(b, v); o.b = upload_f32(v);
+    std::vector<float> g, b;
+    if (!read(p + ".weight", g, {D}) || !read(p + ".bias", b, {D})) return o;
+    o.g = up(g); o.gc = o.g; o.b = up(b);
+    if (gain) gain->swap(g);
     return o;
   }
-  // one or several [N_i][K] matrices stacked along N; bias_flags[i] says whether part i has a bias
+  // one or several [N_i][K] matrices stacked along N; has_bias[i] says whether part i has a bias
   LinearW linear(const std::vector<std::string>& parts, const std::vector<bool>& has_bias, int N_each, int K) {
     LinearW o; o.N = N_each * (int)parts.size(); o.K = K;
-    std::vector<float> wv((size_t)o.N * K), bv((size_t)o.N, 0.f), tmp;
+    std::vector<float> wv, bv((size_t)o.N, 0.f), tmp;
     bool any_bias = false;
     for (size_t i = 0; i < parts.size(); ++i) {
-      const mia_tensor_view* t = find(parts[i] + ".weight");
-      if (!expect(t, {N_each, K}, parts[i] + ".weight")) return o;
-      to_f32(t, tmp); memcpy(&wv[i * (size_t)N_each * K], tmp.data(), tmp.size() * 4);
+      if (!read(parts[i] + ".weight", tmp, {N_each, K})) return o;
+      wv.insert(wv.end(), tmp.begin(), tmp.end());
       if (has_bias[i]) {
-        const mia_tensor_view* b = find(parts[i] + ".bias");
-        if (!expect(b, {N_each}, parts[i] + ".bias")) return o;
-        to_f32(b, tmp); memcpy(&bv[i * (size_t)N_each], tmp.data(), tmp.size() * 4); any_bias = true;
+        if (!read(parts[i] + ".bias", tmp, {N_each})) return o;
+        memcpy(&bv[i * (size_t)N_each], tmp.data(), tmp.size() * 4); any_bias = true;
       }
     }
-    o.w = upload_16(wv);
-    if (any_bias) o.b = upload_f32(bv);
+    o.w = up16(wv, dtype);
+    if (any_bias) o.b = up(bv);
     return o;
   }
   // Conv1d weight [Cout][3][Cin] -> [Cout][Kpad] (tap-major rows == the overlapping-window GEMM's K order)
   LinearW conv(const std::string& p, int Cout, int Cin, int Kpad) {
     LinearW o; o.N = Cout; o.K = Kpad;
-    const mia_tensor_view* t = find(p + ".weight"); const mia_tensor_view* b = find(p + ".bias");
-    if (!expect(t, {Cout, 3, Cin}, p + ".weight") || !expect(b, {Cout}, p + ".bias")) return o;
     std::vector<float> src, wv((size_t)Cout * Kpad, 0.f), bv;
-    to_f32(t, src);
+    if (!read(p + ".weight", src, {Cout, 3, Cin}) || !read(p + ".bias", bv, {Cout})) return o;
     for (int c = 0; c < Cout; ++c) memcpy(&wv[(size_t)c * Kpad], &src[(size_t)c * 3 * Cin], (size_t)3 * Cin * 4);
-    o.w = upload_16(wv);
-    to_f32(b, bv); o.b = upload_f32(bv);
+    o.w = up16(wv, dtype);
+    o.b = up(bv);
     return o;
   }
 };
@@ -165,19 +71,17 @@ extern "C" mia_whisper* mia_whisper_load(mia_ctx* ctx, const mia_whisper_dims* d
   mia_whisper* w = new mia_whisper();
   w->ctx = ctx; w->dims = d; w->dtype = compute_dtype;
   w->kpad_conv1 = (int)align_up((size_t)3 * d.n_mels, 64);
-  Loader L; L.w = w;
-  for (int i = 0; i < n_tensors; ++i) {
+  Loader L; L.allocs = &w->allocs; L.dtype = compute_dtype;
+  for (int i = 0; i < n_tensors; ++i)
     if (!tensors[i].name || !tensors[i].data) { mia_whisper_free(w); return fail("tensor view with null name/data"); }
-    L.by_name[tensors[i].name] = &tensors[i];
-  }
+  L.index(tensors, n_tensors);
   const int D = d.n_audio_state;
   w->conv1 = L.conv("encoder.conv1", D, d.n_mels, w->kpad_conv1);
   w->conv2 = L.conv("encoder.conv2", D, D, 3 * D);
   {
     std::vector<float> pos;
-    if (const mia_tensor_view* t = L.find("encoder.positional_embedding", false)) {
-      if (L.expect(t, {d.n_audio_ctx, D}, "encoder.positional_embedding")) Loader::to_f32(t, pos);
-    } else {  // sinusoids(length:channels:) AudioEncoder.swift:78-96, fp32 math
+    if (L.has("encoder.positional_embedding")) L.read("encoder.positional_embedding", pos, {d.n_audio_ctx, D});
+    else {  // sinusoids(length:channels:) AudioEncoder.swift:78-96, fp32 math
       pos.resize((size_t)d.n_audio_ctx * D);
       const float inc = logf(10000.0f) / (float)(D / 2 - 1);
       for (int p = 0; p < d.n_audio_ctx; ++p)
@@ -187,25 +91,25 @@ extern "C" mia_whisper* mia_whisper_load(mia_ctx* ctx, const mia_whisper_dims* d
           pos[(size_t)p * D + D / 2 + i] = cosf(st);
         }
     }
-    if (!pos.empty()) w->enc_pos = L.upload_f32(pos);
+    if (!pos.empty()) w->enc_pos = L.up(pos);
   }
   w->enc.resize(d.n_audio_layer);
+  std::vector<std::vector<float>> enc_mlp_g(d.n_audio_layer), cross_g(d.n_text_layer), mlp_g(d.n_text_layer);   // gammas of the carried LayerNorms
   for (int l = 0; l < d.n_audio_layer && L.err.empty(); ++l) {
     const std::string p = "encoder.blocks." + std::to_string(l);
     EncBlockW& b = w->enc[l];
     b.attn_ln = L.ln(p + ".attn_ln", D);
     b.qkv = L.linear({p + ".attn.query", p + ".attn.key", p + ".attn.value"}, {true, false, true}, D, D);
     b.out = L.linear({p + ".attn.out"}, {true}, D, D);
-    b.mlp_ln = L.ln(p + ".mlp_ln", D);
+    b.mlp_ln = L.ln(p + ".mlp_ln", D, &enc_mlp_g[l]);
     b.mlp1 = L.linear({p + ".mlp1"}, {true}, 4 * D, D);
     b.mlp2 = L.linear({p + ".mlp2"}, {true}, D, 4 * D);
   }
   w->ln_post = L.ln("encoder.ln_post", D);
-  if (const mia_tensor_view* t = L.find("decoder.token_embedding.weight")) {
-    if (L.expect(t, {d.n_vocab, D}, "decoder.token_embedding.weight")) { std::vector<float> v; Loader::to_f32(t, v); w->tok_emb = L.upload_16(v); }
-  }
-  if (const mia_tensor_view* t = L.find("decoder.positional_embedding")) {
-    if (L.expect(t, {d.n_text_ctx, D}, "decoder.positional_embedding")) { std::vector<float> v; Loader::to_f32(t, v); w->dec_pos = L.upload_f32(v); }
+  {
+    std::vector<float> v;
+    if (L.read("decoder.token_embedding.weight", v, {d.n_vocab, D})) w->tok_emb = L.up16(v, compute_dtype);
+    if (L.read("decoder.positional_embedding", v, {d.n_text_ctx, D})) w->dec_pos = L.up(v);
   }
   w->dec.resize(d.n_text_layer);
   for (int l = 0; l < d.n_text_layer && L.err.empty(); ++l) {
@@ -214,12 +118,12 @@ extern "C" mia_whisper* mia_whisper_load(mia_ctx* ctx, const mia_whisper_dims* d
     b.attn_ln = L.ln(p + ".attn_ln", D);
     b.qkv = L.linear({p + ".attn.query", p + ".attn.key", p + ".attn.value"}, {true, false, true}, D, D);
     b.out = L.linear({p + ".attn.out"}, {true}, D, D);
-    b.cross_ln = L.ln(p + ".cross_attn_ln", D);
+    b.cross_ln = L.ln(p + ".cross_attn_ln", D, &cross_g[l]);
     b.cq = L.linear({p + ".cross_attn.query"}, {true}, D, D);
     b.ck = L.linear({p + ".cross_attn.key"}, {false}, D, D);
     b.cv = L.linear({p + ".cross_attn.value"}, {true}, D, D);
     b.cout = L.linear({p + ".cross_attn.out"}, {true}, D, D);
-    b.mlp_ln = L.ln(p + ".mlp_ln", D);
+    b.mlp_ln = L.ln(p + ".mlp_ln", D, &mlp_g[l]);
     b.mlp1 = L.linear({p + ".mlp1"}, {true}, 4 * D, D);
     b.mlp2 = L.linear({p + ".mlp2"}, {true}, D, 4 * D);
   }
@@ -227,31 +131,13 @@ extern "C" mia_whisper* mia_whisper_load(mia_ctx* ctx, const mia_whisper_dims* d
   if (!L.err.empty()) { mia_whisper_free(w); return fail(L.err); }
   {  // the decode step reads its weights in MFMA-fragment order (skinny.h): one repack per matrix, on the device
     bool ok = true;
-    auto frag = [&](const void* src, int N, int K) -> void* {
-      if (!ok || !src) return nullptr;
-      void* dst = nullptr;
-      const size_t bytes = (size_t)((N + 15) / 16) * 16 * K * 2;
-      if (K % 32 != 0 || hipMalloc(&dst, bytes) != hipSuccess) { ok = false; return nullptr; }
-      w->allocs.push_back(dst);
-      if (dec_launch_repack_wfrag(src, dst, N, K, ctx->stream) != 0) ok = false;
-      return dst;
-    };
     for (DecBlockW& b : w->dec)
-      for (LinearW* lw : {&b.qkv, &b.out, &b.cq, &b.cout, &b.mlp1, &b.mlp2}) lw->wf = frag(lw->w, lw->N, lw->K);
-    w->tok_emb_f = frag(w->tok_emb, d.n_vocab, D);
+      for (LinearW* lw : {&b.qkv, &b.out, &b.cq, &b.cout, &b.mlp1, &b.mlp2}) ok = ok && dec_wfrag_copy(lw->w, lw->N, lw->K, w->allocs, ctx->stream, &lw->wf);
+    ok = ok && dec_wfrag_copy(w->tok_emb, d.n_vocab, D, w->allocs, ctx->stream, &w->tok_emb_f);
     if (!ok) { mia_whisper_free(w); return fail("fragment-order repack of the decoder weights failed"); }
     // LayerNorm fold constants of every decoder Linear that consumes a LayerNorm (whisper.h LinearW::c1 / c2; skinny.h)
     // carried LayerNorms (decoder: cross_attn_ln, mlp_ln; encoder: mlp_ln) get the pre-scaled gain of skinny.h (mia_carry_prescale)
-    auto carried = [&](LNW& ln, LinearW& consumer) {
-      if (!ok || !ln.g) return;
-      std::vector<float> g((size_t)D);
-      if (hipMemcpy(g.data(), ln.g, (size_t)D * 4, hipMemcpyDeviceToHost) != hipSuccess) { ok = false; return; }
-      const float p = mia_carry_prescale(g.data(), D, w->dtype);
-      if (p == 1.f) return;
-      for (float& v : g) v *= p;
-      ln.gc = L.upload_f32(g);
-      consumer.ln_rs = 1.f / p;
-    };
+    auto carried = [&](LNW& ln, const std::vector<float>& g, LinearW& consumer) { ln.gc = mia_carry_gain(L, g, w->dtype, ln.g, &consumer.ln_rs); };
     auto fold = [&](const void* w16, int N, const LNW& ln, float** c1, float** c2, const float* bias = nullptr) {
       if (!ok || !w16) return;
       void* p1 = nullptr; void* p2 = nullptr;
@@ -262,9 +148,10 @@ extern "C" mia_whisper* mia_whisper_load(mia_ctx* ctx, const mia_whisper_dims* d
       *c1 = (float*)p1; *c2 = (float*)p2;
       if (dec_launch_lnfold(w16, N, D, ln.gc, ln.b, *c1, *c2, w->dtype, ctx->stream, bias) != 0) ok = false;
     };
-    for (DecBlockW& b : w->dec) {
-      carried(b.cross_ln, b.cq);
-      carried(b.mlp_ln, b.mlp1);
+    for (int l = 0; l < d.n_text_layer; ++l) {
+      DecBlockW& b = w->dec[l];
+      carried(b.cross_ln, cross_g[l], b.cq);
+      carried(b.mlp_ln, mlp_g[l], b.mlp1);
       fold(b.qkv.w, b.qkv.N, b.attn_ln, &b.qkv.c1, &b.qkv.c2);
       fold(b.cq.w, b.cq.N, b.cross_ln, &b.cq.c1, &b.cq.c2);
       fold(b.mlp1.w, b.mlp1.N, b.mlp_ln, &b.mlp1.c1, &b.mlp1.c2);
@@ -272,8 +159,8 @@ extern "C" mia_whisper* mia_whisper_load(mia_ctx* ctx, const mia_whisper_dims* d
     fold(w->tok_emb, d.n_vocab, w->dec_ln, &w->emb_c1, &w->emb_c2);
     // encoder: the Linear behind mlp_ln takes its LayerNorm through the GEMM (gemm.h "LayerNorm carried across two GEMMs"); c2 includes the bias
     if (d.n_audio_state == D)
-      for (EncBlockW& b : w->enc) { carried(b.mlp_ln, b.mlp1); fold(b.mlp1.w, b.mlp1.N, b.mlp_ln, &b.mlp1.c1, &b.mlp1.c2, b.mlp1.b); }
-    if (!ok) { mia_whisper_free(w); return fail("LayerNorm fold of the decoder weights failed"); }
+      for (int l = 0; l < d.n_audio_layer; ++l) { EncBlockW& b = w->enc[l]; carried(b.mlp_ln, enc_mlp_g[l], b.mlp1); fold(b.mlp1.w, b.mlp1.N, b.mlp_ln, &b.mlp1.c1, &b.mlp1.c2, b.mlp1.b); }
+    if (!ok || !L.err.empty()) { mia_whisper_free(w); return fail("LayerNorm fold of the decoder weights failed"); }
   }
   if (hipDeviceSynchronize() != hipSuccess) { mia_whisper_free(w); return fail("device error during upload"); }
   return w;
@@ -333,54 +220,21 @@ extern "C" int mia_whisper_attach_quantized(mia_whisper* w, const mia_tensor_vie
   const int D = w->dims.n_text_state, V = w->dims.n_vocab;
   MIA_CHECK_ARG(ctx, D % 128 == 0, "whisper_attach_quantized: n_text_state must be a multiple of 128 (the packed kernels take 128-input blocks)");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
-  std::map<std::string, const mia_tensor_view*> by_name;
-  for (int i = 0; i < n_tensors; ++i) if (tensors[i].name && tensors[i].data) by_name[tensors[i].name] = &tensors[i];
-  std::string err;
-  int sdt = -1;
-  auto get = [&](const std::string& p, int N, int K, Q4Src& q) -> bool {
-    const mia_tensor_view* t[3];
-    const char* suffix[3] = {".weight", ".scales", ".biases"};
-    for (int i = 0; i < 3; ++i) {
-      auto it = by_name.find(p + suffix[i]);
-      if (it == by_name.end()) { if (err.empty()) err = "missing tensor '" + p + suffix[i] + "'"; return false; }
-      t[i] = it->second;
-    }
-    const mia_tensor_view *wt = t[0], *s = t[1], *b = t[2];
-    const bool ok = wt->dtype == MIA_U32 && wt->ndim == 2 && wt->shape[0] == N && wt->shape[1] == (int64_t)K * bits / 32 && s->ndim == 2 && s->shape[0] == N &&
-                    s->shape[1] == K / 64 && b->ndim == 2 && b->shape[0] == N && b->shape[1] == K / 64 && s->dtype == b->dtype &&
-                    (s->dtype == MIA_F16 || s->dtype == MIA_BF16 || s->dtype == MIA_F32);
-    if (!ok) { if (err.empty()) err = "'" + p + "' is not a " + std::to_string(bits) + "-bit group-64 Linear of the expected shape (scales / biases: f16, bf16 or f32)"; return false; }
-    if (sdt < 0) sdt = s->dtype;
-    if (sdt != s->dtype) { if (err.empty()) err = "mixed scale dtypes"; return false; }
-    q = Q4Src{(const uint32_t*)wt->data, s->data, b->data};
-    return true;
-  };
-  const float mag = w->dtype == MIA_F16 ? 1024.0f : 128.0f;
   std::vector<void*> fresh;                      // joins w->allocs only when everything is in place
-  int code = MIA_ERR_INVALID_ARGUMENT;           // what a failure is reported as: a bad tensor list, unless the device refused
+  TensorLoader T; T.allocs = &fresh;
+  T.index(tensors, n_tensors);
+  int sdt = -1;
+  const float mag = w->dtype == MIA_F16 ? 1024.0f : 128.0f;
   struct QPair { uint32_t* qw = nullptr; float* qst = nullptr; };
   // parts stacked along N as the dense loader stacks them (Loader::linear)
   auto pack = [&](const std::vector<std::string>& parts, int N_each, int K, QPair& out) -> bool {
     std::vector<Q4Src> src(parts.size());
     std::vector<std::pair<int, int>> rows;
     for (size_t i = 0; i < parts.size(); ++i) {
-      if (!get(parts[i], N_each, K, src[i])) return false;
+      if (!q_find_linear(T, parts[i], N_each, K, bits, true, &sdt, src[i])) return false;
       for (int n = 0; n < N_each; ++n) rows.push_back({(int)i, n});
     }
-    std::vector<uint32_t> wf;
-    std::vector<float> st;
-    q_repack_host(src, rows, K, bits, sdt, mag, wf, st);
-    void* dw = nullptr; void* ds = nullptr;
-    if (hipMalloc(&dw, wf.size() * 4) != hipSuccess) { code = MIA_ERR_OUT_OF_MEMORY; err = "hipMalloc failed for the packed weights"; return false; }
-    fresh.push_back(dw);
-    if (hipMalloc(&ds, st.size() * 4) != hipSuccess) { code = MIA_ERR_OUT_OF_MEMORY; err = "hipMalloc failed for the packed weights"; return false; }
-    fresh.push_back(ds);
-    if (hipMemcpy(dw, wf.data(), wf.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(ds, st.data(), st.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-      code = MIA_ERR_DEVICE; err = "upload of the packed weights failed";
-      return false;
-    }
-    out.qw = (uint32_t*)dw; out.qst = (float*)ds;
-    return true;
+    return q_upload(T, src, rows, K, bits, sdt, mag, &out.qw, &out.qst);
   };
   const int L = (int)w->dec.size();
   std::vector<QPair> qp((size_t)L * 6);
@@ -394,10 +248,10 @@ extern "C" int mia_whisper_attach_quantized(mia_whisper* w, const mia_tensor_vie
          pack({p + ".mlp1"}, 4 * D, D, q[4]) && pack({p + ".mlp2"}, D, 4 * D, q[5]);
   }
   ok = ok && pack({"decoder.token_embedding"}, V, D, emb);
-  if (ok && hipDeviceSynchronize() != hipSuccess) { ok = false; code = MIA_ERR_DEVICE; err = "device error during upload"; }
+  if (ok && hipDeviceSynchronize() != hipSuccess) ok = T.fail(MIA_ERR_DEVICE, "device error during upload");
   if (!ok) {
     for (void* p : fresh) (void)hipFree(p);
-    return mia_fail(ctx, code, "whisper_attach_quantized: %s", err.c_str());
+    return mia_fail(ctx, T.code, "whisper_attach_quantized: %s", T.err.c_str());
   }
   for (int l = 0; l < L; ++l) {
     DecBlockW& b = w->dec[l];

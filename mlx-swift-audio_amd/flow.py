@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import FlowConfig, TensorView
+from ._abi import FlowConfig, tensor_views
 
 
 class FlowModule:
@@ -20,13 +20,8 @@ class FlowModule:
         c = FlowConfig(cfg.input_size, cfg.output_size, cfg.spk_embed_dim, cfg.vocab_size, cfg.pre_lookahead_len, cfg.n_timesteps,
                        cfg.enc_heads, cfg.enc_linear_units, cfg.enc_blocks, cfg.enc_up_blocks, cfg.upsample_stride,
                        cfg.dec_in_channels, cfg.dec_channels, cfg.dec_heads, cfg.dec_n_blocks, cfg.dec_mid_blocks, cfg.cfg_rate)
-        views = (TensorView * len(weights))()
-        keep = []
-        for i, (name, arr) in enumerate(weights.items()):
-            a = np.ascontiguousarray(arr, np.float32)
-            keep.append(a)
-            views[i] = TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
-        h = ctx.lib.mia_flow_load(ctx.h, C.byref(c), views, len(weights))
+        views, n, keep = tensor_views(weights)
+        h = ctx.lib.mia_flow_load(ctx.h, C.byref(c), views, n)
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
         return FlowModule(ctx, h, cfg)

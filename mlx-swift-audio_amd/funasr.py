@@ -83,13 +83,8 @@ class SenseVoiceEncoder:
         """weights: float32 arrays under the reference's Module keys (audio_encoder.*, audio_adaptor.*); a quantised checkpoint goes through
         checkpoint.expand_checkpoint first."""
         c = _abi.SensevoiceConfig(*[getattr(cfg, f.name) for f in fields(SenseVoiceConfig)])
-        views = (_abi.TensorView * max(len(weights), 1))()
-        keep = []
-        for i, (name, arr) in enumerate(weights.items()):
-            a = np.ascontiguousarray(arr, np.float32)
-            keep.append(a)
-            views[i] = _abi.TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
-        h = ctx.lib.mia_sensevoice_load(ctx.h, C.byref(c), views, len(weights), dtype)
+        views, n, keep = _abi.tensor_views(weights)
+        h = ctx.lib.mia_sensevoice_load(ctx.h, C.byref(c), views, n, dtype)
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
         return SenseVoiceEncoder(ctx, h, cfg, dtype)

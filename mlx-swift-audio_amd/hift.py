@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import HiftConfig, TensorView
+from ._abi import HiftConfig, tensor_views
 
 
 def _pad4(v):
@@ -30,13 +30,8 @@ class HiFTGenerator:
                        _pad4(cfg.up_kernels), len(cfg.res_kernels), _pad4(cfg.res_kernels), _pad4(cfg.src_res_kernels),
                        len(cfg.dilations), _pad4(cfg.dilations), cfg.nsf_alpha, cfg.nsf_sigma, cfg.voiced_threshold, cfg.lrelu_slope,
                        cfg.audio_limit)
-        views = (TensorView * len(weights))()
-        keep = []
-        for i, (name, arr) in enumerate(weights.items()):
-            a = np.ascontiguousarray(arr, np.float32)
-            keep.append(a)
-            views[i] = TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
-        h = ctx.lib.mia_hift_load(ctx.h, C.byref(c), views, len(weights))
+        views, n, keep = tensor_views(weights)
+        h = ctx.lib.mia_hift_load(ctx.h, C.byref(c), views, n)
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
         return HiFTGenerator(ctx, h, cfg)

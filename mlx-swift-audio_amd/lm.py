@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import LmConfig, LmSampler, RasParams, TensorView
+from ._abi import LmConfig, LmSampler, RasParams, tensor_views
 
 END_TOKEN = 128258                    # OrpheusTTS.swift:75-85
 CODE_OFFSET = 128266
@@ -26,17 +26,8 @@ class CausalLM:
         c = LmConfig(cfg.vocab, cfg.hidden, cfg.inter, cfg.n_layers, cfg.n_heads, cfg.n_kv_heads, cfg.head_dim, cfg.max_ctx, cfg.rms_eps,
                      cfg.rope_theta, 1 if cfg.rope_llama3 else 0, cfg.rope_factor, cfg.rope_low, cfg.rope_high, cfg.rope_old_ctx,
                      1 if cfg.qkv_bias else 0, 1 if cfg.tie_embeddings else 0)
-        views = (TensorView * len(weights))()
-        keep = []
-        for i, (name, arr) in enumerate(weights.items()):
-            if arr.dtype == np.float16:
-                a, dt = np.ascontiguousarray(arr), _lib.F16
-            else:
-                a, dt = np.ascontiguousarray(arr, np.float32), _lib.F32
-            keep.append(a)
-            shp = (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim)))
-            views[i] = TensorView(name.encode(), dt, a.ndim, shp, a.ctypes.data)
-        h = ctx.lib.mia_lm_load(ctx.h, C.byref(c), views, len(weights), dtype)
+        views, n, keep = tensor_views(weights, (_lib.F32, _lib.F16, _lib.BF16))
+        h = ctx.lib.mia_lm_load(ctx.h, C.byref(c), views, n, dtype)
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
         return CausalLM(ctx, h, cfg)
@@ -46,22 +37,8 @@ class CausalLM:
         `<name>.scales` / `<name>.biases` float16 (or uint16 arrays tagged .st_dtype == "BF16", as checkpoint.read_safetensors returns
         bf16 payloads).  The handle must have been loaded from the de-quantised tensors of the same checkpoint."""
         lib = self.ctx.lib
-        views = (TensorView * len(packed))()
-        keep = []
-        for i, (name, arr) in enumerate(packed.items()):
-            a = np.ascontiguousarray(arr)
-            if a.dtype == np.uint32:
-                dt = _lib.U32
-            elif a.dtype == np.float16:
-                dt = _lib.F16
-            elif a.dtype == np.uint16 and getattr(arr, "st_dtype", "BF16") == "BF16":
-                dt = _lib.BF16
-            else:
-                raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, f"attach_q4: '{name}' must be uint32 codes or 16-bit scales / biases (got {a.dtype})")
-            keep.append(a)
-            shp = (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim)))
-            views[i] = TensorView(name.encode(), dt, a.ndim, shp, a.ctypes.data)
-        self.ctx.check(lib.mia_lm_attach_quantized(self.h, views, len(packed), group_size, bits))
+        views, n, keep = tensor_views(packed, (_lib.U32, _lib.F16, _lib.BF16), "attach_q4: '{name}' must be uint32 codes or 16-bit scales / biases (got {dtype})")
+        self.ctx.check(lib.mia_lm_attach_quantized(self.h, views, n, group_size, bits))
 
     def set_debug(self, flags: int) -> None:
         """Test hook (mia_lm_set_debug): bit 0 = no hipGraph, bit 1 = prompts token by token (no batched prompt pass)."""

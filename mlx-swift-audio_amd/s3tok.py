@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._abi import S3Config, TensorView
+from ._abi import S3Config, tensor_views
 
 
 def merge_tokenized_segments(segments, overlap=4, token_rate=25):
@@ -30,13 +30,8 @@ class S3Tokenizer:
     @staticmethod
     def load(ctx: _lib.Context, cfg, weights: dict[str, np.ndarray]) -> "S3Tokenizer":
         c = S3Config(cfg.n_mels, cfg.n_audio_state, cfg.n_audio_head, cfg.n_audio_layer)
-        views = (TensorView * len(weights))()
-        keep = []
-        for i, (name, arr) in enumerate(weights.items()):
-            a = np.ascontiguousarray(arr, np.float32)
-            keep.append(a)
-            views[i] = TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
-        h = ctx.lib.mia_s3tok_load(ctx.h, C.byref(c), views, len(weights))
+        views, n, keep = tensor_views(weights)
+        h = ctx.lib.mia_s3tok_load(ctx.h, C.byref(c), views, n)
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
         return S3Tokenizer(ctx, h, cfg)

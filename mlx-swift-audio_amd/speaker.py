@@ -3,12 +3,10 @@ HIP layer: `__call__(audio16k) -> [1, 192]` (zeros when no weights are loaded, a
 underlying CAMPPlus forward on precomputed features (Codec/S3Gen/CAMPPlus.swift:755-785)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
-from ._abi import TensorView
+from ._abi import tensor_views
 
 EMBEDDING_DIM = 192
 
@@ -32,13 +30,8 @@ class CAMPlusSpeakerEncoder:
         weights = {(k[len("campplus."):] if k.startswith("campplus.") else k): v for k, v in weights.items()}
         if not weights:
             return CAMPlusSpeakerEncoder(ctx, None)
-        views = (TensorView * len(weights))()
-        keep = []
-        for i, (name, arr) in enumerate(weights.items()):
-            a = np.ascontiguousarray(arr, np.float32)
-            keep.append(a)
-            views[i] = TensorView(name.encode(), _lib.F32, a.ndim, (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim))), a.ctypes.data)
-        h = ctx.lib.mia_campplus_load(ctx.h, views, len(weights))
+        views, n, keep = tensor_views(weights)
+        h = ctx.lib.mia_campplus_load(ctx.h, views, n)
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
         return CAMPlusSpeakerEncoder(ctx, h)

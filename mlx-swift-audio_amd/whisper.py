@@ -16,7 +16,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._abi import DecodeOpts, TensorView, WhisperDims
+from ._abi import DecodeOpts, WhisperDims, tensor_views
 from . import audio as _audio
 
 
@@ -95,19 +95,11 @@ class WhisperModel:
 
     @staticmethod
     def load(ctx: _lib.Context, dims, weights: dict[str, np.ndarray], dtype: int = _lib.BF16) -> "WhisperModel":
-        """dims: any object with the ModelDimensions fields; weights: name -> fp32/fp16 array with the reference key schema."""
+        """dims: any object with the ModelDimensions fields; weights: name -> array with the reference key schema: float32, float16 or bf16 payloads (uint16, _abi.dtype_tag) as
+        they are, anything else converted to float32."""
         cd = WhisperDims(*[int(getattr(dims, f[0])) for f in WhisperDims._fields_])
-        views = (TensorView * len(weights))()
-        keep = []
-        for i, (name, arr) in enumerate(weights.items()):
-            if arr.dtype == np.float16:
-                a, dt = np.ascontiguousarray(arr), _lib.F16
-            else:
-                a, dt = np.ascontiguousarray(arr, np.float32), _lib.F32
-            keep.append(a)
-            shp = (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim)))
-            views[i] = TensorView(name.encode(), dt, a.ndim, shp, a.ctypes.data)
-        h = ctx.lib.mia_whisper_load(ctx.h, C.byref(cd), views, len(weights), dtype)
+        views, n, keep = tensor_views(weights, (_lib.F32, _lib.F16, _lib.BF16))
+        h = ctx.lib.mia_whisper_load(ctx.h, C.byref(cd), views, n, dtype)
         if not h:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
         return WhisperModel(ctx, h, dims, dtype)
@@ -150,24 +142,9 @@ class WhisperModel:
                 if name.endswith(".weight"):
                     bits = (32 * arr.shape[-1]) // (packed[name[:-7] + ".scales"].shape[-1] * group_size)
                     break
-        views = (TensorView * max(len(packed), 1))()
-        keep = []
-        for i, (name, arr) in enumerate(packed.items()):
-            a = np.ascontiguousarray(arr)
-            if a.dtype == np.uint32:
-                dt = _lib.U32
-            elif a.dtype == np.float16:
-                dt = _lib.F16
-            elif a.dtype == np.float32:
-                dt = _lib.F32
-            elif a.dtype == np.uint16 and getattr(arr, "st_dtype", "BF16") == "BF16":
-                dt = _lib.BF16
-            else:
-                raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, f"attach_quantized: '{name}' must be uint32 codes or f16 / bf16 / f32 scales / biases (got {a.dtype})")
-            keep.append(a)
-            shp = (C.c_int64 * 4)(*(list(a.shape) + [0] * (4 - a.ndim)))
-            views[i] = TensorView(name.encode(), dt, a.ndim, shp, a.ctypes.data)
-        self.ctx.check(lib.mia_whisper_attach_quantized(self.h, views, len(packed), int(group_size), int(bits or 0)))
+        views, n, keep = tensor_views(packed, (_lib.U32, _lib.F16, _lib.BF16, _lib.F32),
+                                      "attach_quantized: '{name}' must be uint32 codes or f16 / bf16 / f32 scales / biases (got {dtype})")
+        self.ctx.check(lib.mia_whisper_attach_quantized(self.h, views, n, int(group_size), int(bits or 0)))
 
     def use_packed(self, on: bool) -> None:
         """mia_whisper_use_packed: the decode step (decode, align, detect_language) reads the attached packed weights (True) or the 16-bit
