@@ -12,7 +12,8 @@
  *     Models/STTError.swift:6-46); mia_last_error(ctx) returns a human readable string.
  *   - caller owns all input/output buffers.  `mem` says where they live: MIA_MEM_HOST (plain host
  *     pointers, the library copies) or MIA_MEM_DEVICE (HBM pointers valid on the ctx device; no copy,
- *     no synchronisation -- work is merely enqueued on the ctx stream).
+ *     no synchronisation -- work is merely enqueued on the ctx stream).  A MIA_MEM_HOST call returns, with
+ *     success or with an error, only when no copy that touches the caller's buffers is still pending.
  *   - there is NO CPU fallback: without a gfx950 device every compute entry point fails with
  *     MIA_ERR_DEVICE.
  */

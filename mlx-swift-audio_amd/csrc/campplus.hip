@@ -403,25 +403,20 @@ extern "C" int64_t mia_kaldi_fbank_frames(int64_t n_samples) { return fbank_fram
 extern "C" int mia_campplus_fbank(mia_campplus* m, const float* pcm, int64_t n_samples, int mean_norm, float* fbank, int mem) {
   if (!m) return MIA_ERR_MODEL_NOT_LOADED;
   mia_ctx* ctx = m->ctx;
-  MIA_CHECK_ARG(ctx, pcm && fbank && (mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE), "campplus_fbank: bad argument");
+  MIA_CHECK_ARG(ctx, pcm && fbank && HostIo::valid(mem), "campplus_fbank: bad argument");
   MIA_CHECK_ARG(ctx, n_samples >= FB_WIN && n_samples <= (int64_t)16000 * 600, "campplus_fbank: n_samples must be in [%d, 10 min]", FB_WIN);
   const int F = (int)fbank_frames_of(n_samples);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  auto al = [](size_t n) { return (n + 63) / 64 * 64; };
-  const size_t n_in = mem == MIA_MEM_HOST ? (size_t)n_samples : 0, n_fr = (size_t)F * FB_K, n_sp = (size_t)F * 2 * FB_NBP, n_fb = (size_t)F * FB_NMEL;
-  float* ws = (float*)mia_workspace(ctx, (al(n_in) + al(n_fr) + al(n_sp) + al(n_fb)) * 4);
+  HostIo io(ctx, mem);
+  const size_t in_bytes = (size_t)n_samples * 4, fb_bytes = (size_t)F * FB_NMEL * 4;
+  Carve cv;
+  const size_t o_in = cv.add(io.staged(in_bytes)), o_fr = cv.add((size_t)F * FB_K * 4), o_sp = cv.add((size_t)F * 2 * FB_NBP * 4), o_fb = cv.add(io.staged(fb_bytes));
+  char* ws = (char*)mia_workspace(ctx, cv.bytes);
   if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-  float* d_in = ws; float* frames = d_in + al(n_in); float* spec = frames + al(n_fr); float* d_fb = spec + al(n_sp);
-  const float* x = pcm;
-  if (mem == MIA_MEM_HOST) { MIA_HIP(ctx, hipMemcpyAsync(d_in, pcm, (size_t)n_samples * 4, hipMemcpyHostToDevice, s)); x = d_in; }
-  float* dst = mem == MIA_MEM_DEVICE ? fbank : d_fb;
-  if (int rc = run_fbank(m, x, n_samples, F, frames, spec, dst, mean_norm != 0)) return rc;
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(fbank, d_fb, n_fb * 4, hipMemcpyDeviceToHost, s));
-    MIA_HIP(ctx, hipStreamSynchronize(s));
-  }
-  return MIA_OK;
+  const float* x = io.in(pcm, ws + o_in, in_bytes);
+  float* dst = io.out(fbank, ws + o_fb, fb_bytes);
+  if (int rc = run_fbank(m, x, n_samples, F, (float*)(ws + o_fr), (float*)(ws + o_sp), dst, mean_norm != 0)) return rc;
+  return io.finish();
 }
 
 namespace {
@@ -508,46 +503,38 @@ int run_encoder(mia_campplus* m, const float* fb, int T, float* ws, float* emb) 
 extern "C" int mia_campplus_forward(mia_campplus* m, const float* feats, int n_frames, float* emb, int mem) {
   if (!m) return MIA_ERR_MODEL_NOT_LOADED;
   mia_ctx* ctx = m->ctx;
-  MIA_CHECK_ARG(ctx, feats && emb && (mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE), "campplus_forward: bad argument");
+  MIA_CHECK_ARG(ctx, feats && emb && HostIo::valid(mem), "campplus_forward: bad argument");
   MIA_CHECK_ARG(ctx, n_frames >= 1 && n_frames <= 60000, "campplus_forward: n_frames must be in [1, 60000]");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  auto al = [](size_t n) { return (n + 63) / 64 * 64; };
-  const size_t n_in = mem == MIA_MEM_HOST ? al((size_t)n_frames * FB_NMEL) : 0;
-  float* ws = (float*)mia_workspace(ctx, (n_in + al(MIA_CAMPPLUS_DIM) + encoder_ws_floats(n_frames)) * 4);
+  HostIo io(ctx, mem);
+  const size_t in_bytes = (size_t)n_frames * FB_NMEL * 4, emb_bytes = MIA_CAMPPLUS_DIM * 4;
+  Carve cv;
+  const size_t o_in = cv.add(io.staged(in_bytes)), o_emb = cv.add(io.staged(emb_bytes)), o_enc = cv.add(encoder_ws_floats(n_frames) * 4);
+  char* ws = (char*)mia_workspace(ctx, cv.bytes);
   if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-  float* d_in = ws; float* d_emb = d_in + n_in; float* enc = d_emb + al(MIA_CAMPPLUS_DIM);
-  const float* x = feats;
-  if (mem == MIA_MEM_HOST) { MIA_HIP(ctx, hipMemcpyAsync(d_in, feats, (size_t)n_frames * FB_NMEL * 4, hipMemcpyHostToDevice, s)); x = d_in; }
-  if (int rc = run_encoder(m, x, n_frames, enc, mem == MIA_MEM_DEVICE ? emb : d_emb)) return rc;
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(emb, d_emb, MIA_CAMPPLUS_DIM * 4, hipMemcpyDeviceToHost, s));
-    MIA_HIP(ctx, hipStreamSynchronize(s));
-  }
-  return MIA_OK;
+  const float* x = io.in(feats, ws + o_in, in_bytes);
+  if (int rc = run_encoder(m, x, n_frames, (float*)(ws + o_enc), io.out(emb, ws + o_emb, emb_bytes))) return rc;
+  return io.finish();
 }
 
 // CAMPPlus.inference (CAMPPlus.swift:788-818) for one clip: pcm 16 kHz [n_samples] -> emb [192]
 extern "C" int mia_campplus_embed(mia_campplus* m, const float* pcm, int64_t n_samples, float* emb, int mem) {
   if (!m) return MIA_ERR_MODEL_NOT_LOADED;
   mia_ctx* ctx = m->ctx;
-  MIA_CHECK_ARG(ctx, pcm && emb && (mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE), "campplus_embed: bad argument");
+  MIA_CHECK_ARG(ctx, pcm && emb && HostIo::valid(mem), "campplus_embed: bad argument");
   MIA_CHECK_ARG(ctx, n_samples >= FB_WIN && n_samples <= (int64_t)16000 * 600, "campplus_embed: n_samples must be in [%d, 10 min]", FB_WIN);
   const int F = (int)fbank_frames_of(n_samples);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  auto al = [](size_t n) { return (n + 63) / 64 * 64; };
-  const size_t n_in = mem == MIA_MEM_HOST ? al((size_t)n_samples) : 0, n_fr = al((size_t)F * FB_K), n_sp = al((size_t)F * 2 * FB_NBP), n_fb = al((size_t)F * FB_NMEL);
-  float* ws = (float*)mia_workspace(ctx, (n_in + n_fr + n_sp + n_fb + al(MIA_CAMPPLUS_DIM) + encoder_ws_floats(F)) * 4);
+  HostIo io(ctx, mem);
+  const size_t in_bytes = (size_t)n_samples * 4, emb_bytes = MIA_CAMPPLUS_DIM * 4;
+  Carve cv;
+  const size_t o_in = cv.add(io.staged(in_bytes)), o_fr = cv.add((size_t)F * FB_K * 4), o_sp = cv.add((size_t)F * 2 * FB_NBP * 4), o_fb = cv.add((size_t)F * FB_NMEL * 4);
+  const size_t o_emb = cv.add(io.staged(emb_bytes)), o_enc = cv.add(encoder_ws_floats(F) * 4);
+  char* ws = (char*)mia_workspace(ctx, cv.bytes);
   if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-  float* d_in = ws; float* frames = d_in + n_in; float* spec = frames + n_fr; float* fb = spec + n_sp; float* d_emb = fb + n_fb; float* enc = d_emb + al(MIA_CAMPPLUS_DIM);
-  const float* x = pcm;
-  if (mem == MIA_MEM_HOST) { MIA_HIP(ctx, hipMemcpyAsync(d_in, pcm, (size_t)n_samples * 4, hipMemcpyHostToDevice, s)); x = d_in; }
-  if (int rc = run_fbank(m, x, n_samples, F, frames, spec, fb, true)) return rc;
-  if (int rc = run_encoder(m, fb, F, enc, mem == MIA_MEM_DEVICE ? emb : d_emb)) return rc;
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(emb, d_emb, MIA_CAMPPLUS_DIM * 4, hipMemcpyDeviceToHost, s));
-    MIA_HIP(ctx, hipStreamSynchronize(s));
-  }
-  return MIA_OK;
+  float* fb = (float*)(ws + o_fb);
+  const float* x = io.in(pcm, ws + o_in, in_bytes);
+  if (int rc = run_fbank(m, x, n_samples, F, (float*)(ws + o_fr), (float*)(ws + o_sp), fb, true)) return rc;
+  if (int rc = run_encoder(m, fb, F, (float*)(ws + o_enc), io.out(emb, ws + o_emb, emb_bytes))) return rc;
+  return io.finish();
 }

@@ -78,7 +78,7 @@ int codec_run(mia_codec* c, Cursor& k, size_t begin, size_t end, const float* d_
 }
 
 // shared tail: codes already on the device, latent length T0 with geometry gm
-static int decode_common(mia_codec* c, const EmbedArgs& ea, int64_t T0, const Geometry& gm, const float* noise, int64_t n_noise_given, float* pcm, int64_t* n_out, int mem) {
+static int decode_common(mia_codec* c, const EmbedArgs& ea, int64_t T0, const Geometry& gm, const float* noise, int64_t n_noise_given, float* pcm, int64_t* n_out, HostIo& io) {
   mia_ctx* ctx = c->ctx;
   int rc = codec_scratch(c, gm.max_floats);
   if (rc != MIA_OK) return rc;
@@ -86,24 +86,16 @@ static int decode_common(mia_codec* c, const EmbedArgs& ea, int64_t T0, const Ge
   const float* d_noise = nullptr;
   if (noise && gm.noise_total > 0) {
     MIA_CHECK_ARG(ctx, n_noise_given == gm.noise_total, "codec: noise must hold %lld values (got %lld)", (long long)gm.noise_total, (long long)n_noise_given);
-    if (mem == MIA_MEM_DEVICE) d_noise = noise;
-    else {
-      if ((rc = mia_grow(ctx, c->d_noise, c->noise_cap, (size_t)gm.noise_total, "codec: hipMalloc failed")) != MIA_OK) return rc;
-      MIA_HIP(ctx, hipMemcpyAsync(c->d_noise, noise, (size_t)gm.noise_total * 4, hipMemcpyHostToDevice, ctx->stream));
-      d_noise = c->d_noise;
-    }
+    if (io.host() && (rc = mia_grow(ctx, c->d_noise, c->noise_cap, (size_t)gm.noise_total, "codec: hipMalloc failed")) != MIA_OK) return rc;
+    d_noise = io.in(noise, c->d_noise, (size_t)gm.noise_total * 4);
   }
   if (codec_embed_launch(ea, c->buf[0], (int)T0, c->latent, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "codec: embed launch failed");
-  float* dst = mem == MIA_MEM_DEVICE ? pcm : c->d_pcm;
+  float* dst = io.out(pcm, c->d_pcm, (size_t)gm.T_final * 4);
   Cursor k{c->buf[0], c->buf[1], c->buf[2], T0, c->latent};
   rc = codec_run(c, k, 0, c->ops.size(), d_noise, dst);
   if (rc != MIA_OK) return rc;
   if (n_out) *n_out = gm.T_final;
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(pcm, c->d_pcm, (size_t)gm.T_final * 4, hipMemcpyDeviceToHost, ctx->stream));
-    MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MIA_OK;
+  return io.finish();
 }
 
 extern "C" int mia_codec_set_stack_budget(mia_codec* c, int64_t bytes) {
@@ -126,7 +118,8 @@ extern "C" int mia_snac_decode(mia_codec* c, const int32_t* const* codes, const 
   mia_ctx* ctx = c->ctx;
   MIA_CHECK_ARG(ctx, c->kind == 0, "snac_decode: handle is not a SNAC model");
   MIA_CHECK_ARG(ctx, codes && n_codes && pcm && n_levels > 0, "snac_decode: null arguments");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "snac_decode: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "snac_decode: bad mem");
+  HostIo io(ctx, mem);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   // expanded length = max_i n_i * stride_i; a level whose expansion differs is skipped, as embedCodes does (SNACDecoder.swift:337-402)
   int64_t T0 = 0; size_t total = 0;
@@ -138,14 +131,14 @@ extern "C" int mia_snac_decode(mia_codec* c, const int32_t* const* codes, const 
   size_t off = 0;
   for (int i = 0; i < c->n_levels; ++i) {
     if (i >= n_levels || n_codes[i] <= 0 || (int64_t)n_codes[i] * c->vq_stride[i] != T0) continue;
-    for (int k = 0; k < n_codes[i] && mem == MIA_MEM_HOST; ++k)
+    for (int k = 0; k < n_codes[i] && io.host(); ++k)
       if (codes[i][k] < 0 || codes[i][k] >= c->cb_size) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "snac_decode: code %d out of range at level %d", codes[i][k], i);
-    MIA_HIP(ctx, hipMemcpyAsync(c->d_codes + off, codes[i], (size_t)n_codes[i] * 4, mem == MIA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    io.check(hipMemcpyAsync(c->d_codes + off, codes[i], (size_t)n_codes[i] * 4, io.from_caller(), ctx->stream));
     ea.codes[i] = c->d_codes + off; off += n_codes[i];
   }
   const Geometry gm = codec_geometry(c, T0);
   MIA_CHECK_ARG(ctx, pcm_capacity >= gm.T_final, "snac_decode: pcm buffer too small (%lld < %lld)", (long long)pcm_capacity, (long long)gm.T_final);
-  return decode_common(c, ea, T0, gm, noise, n_noise, pcm, n_samples, mem);
+  return decode_common(c, ea, T0, gm, noise, n_noise, pcm, n_samples, io);
 }
 
 extern "C" int mia_dac_decode(mia_codec* c, const int32_t* codes, int n_codebooks, int64_t T, float* pcm, int64_t pcm_capacity, int64_t* n_samples, int mem) {
@@ -153,18 +146,19 @@ extern "C" int mia_dac_decode(mia_codec* c, const int32_t* codes, int n_codebook
   mia_ctx* ctx = c->ctx;
   MIA_CHECK_ARG(ctx, c->kind == 1, "dac_decode: handle is not a DAC model");
   MIA_CHECK_ARG(ctx, codes && pcm && T > 0 && n_codebooks > 0 && n_codebooks <= c->n_levels, "dac_decode: bad arguments");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "dac_decode: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "dac_decode: bad mem");
+  HostIo io(ctx, mem);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   int rc = mia_grow(ctx, c->d_codes, c->codes_cap, (size_t)n_codebooks * T, "codec: hipMalloc failed");
   if (rc != MIA_OK) return rc;
-  if (mem == MIA_MEM_HOST)
+  if (io.host())
     for (int64_t k = 0; k < (int64_t)n_codebooks * T; ++k)
       if (codes[k] < 0 || codes[k] >= c->cb_size) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "dac_decode: code %d out of range", codes[k]);
-  MIA_HIP(ctx, hipMemcpyAsync(c->d_codes, codes, (size_t)n_codebooks * T * 4, mem == MIA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+  io.check(hipMemcpyAsync(c->d_codes, codes, (size_t)n_codebooks * T * 4, io.from_caller(), ctx->stream));
   const int ones[MIA_MAX_LEVELS] = {1, 1, 1, 1};
   EmbedArgs ea = codec_embed_args(c, n_codebooks, ones);
   for (int i = 0; i < n_codebooks; ++i) ea.codes[i] = c->d_codes + (size_t)i * T;
   const Geometry gm = codec_geometry(c, T);
   MIA_CHECK_ARG(ctx, pcm_capacity >= gm.T_final, "dac_decode: pcm buffer too small");
-  return decode_common(c, ea, T, gm, nullptr, 0, pcm, n_samples, mem);
+  return decode_common(c, ea, T, gm, nullptr, 0, pcm, n_samples, io);
 }

@@ -46,13 +46,14 @@ int upload_tables(mia_codec* c, const std::vector<BatchUtt>& ut, const Geometry&
   return MIA_OK;
 }
 
-// enqueue one stacked decode: every argument has been checked, nothing has touched the GPU yet
-int decode_batch_enqueue(mia_codec* c, std::vector<BatchUtt>& ut, const int strides[MIA_MAX_LEVELS], int n_levels, const int32_t* codes, size_t n_codes_total,
-                        const float* noise, float* pcm, const int64_t* pcm_off, int64_t* n_samples, int mem) {
+// shared tail of the two batch entries: every argument has been checked, nothing has touched the GPU yet.  Host memory: the caller's
+// codes / noise / pcm are behind asynchronous copies, and io keeps every return path, the failing ones included, from leaving one pending
+// (the tables' staging belongs to the handle and needs no such care).
+int decode_batch_common(mia_codec* c, std::vector<BatchUtt>& ut, const int strides[MIA_MAX_LEVELS], int n_levels, const int32_t* codes, size_t n_codes_total,
+                       const float* noise, float* pcm, const int64_t* pcm_off, int64_t* n_samples, HostIo& io) {
   mia_ctx* ctx = c->ctx;
-  hipStream_t s = ctx->stream;
   const int U = (int)ut.size();
-  const bool dev = mem == MIA_MEM_DEVICE;
+  const bool dev = !io.host();
   int64_t pcm_total = 0, noise_total = 0;
   const BatchUtt* longest = &ut[0];
   for (const BatchUtt& b : ut) { if (b.T0 > longest->T0) longest = &b; pcm_total += b.g.T_final; noise_total += b.g.noise_total; }
@@ -74,16 +75,12 @@ int decode_batch_enqueue(mia_codec* c, std::vector<BatchUtt>& ut, const int stri
   Stack st; st.U = U; st.slab = slab;
   if ((rc = upload_tables(c, ut, gmax, pcm_off, dev, st)) != MIA_OK) return rc;
   const int64_t* h_pcm_off = (const int64_t*)c->h_tab;
-  const int32_t* d_codes = codes; const float* d_noise = noise;
-  if (!dev) {                                              // (decode_batch_common synchronises before the caller gets its arrays back)
-    MIA_HIP(ctx, hipMemcpyAsync(c->d_codes, codes, n_codes_total * 4, hipMemcpyHostToDevice, s));
-    d_codes = c->d_codes;
-    if (noise) { MIA_HIP(ctx, hipMemcpyAsync(c->d_noise, noise, (size_t)noise_total * 4, hipMemcpyHostToDevice, s)); d_noise = c->d_noise; }
-  }
+  const int32_t* d_codes = io.in(codes, c->d_codes, n_codes_total * 4);
+  const float* d_noise = io.in(noise, c->d_noise, (size_t)noise_total * 4);
   EmbedArgs ea = codec_embed_args(c, n_levels, strides);
   ea.codes_base = d_codes; ea.seq_code_off = st.pcm_off + U;
   SeqArgs q0; q0.n = U; q0.len = st.len; q0.step = slab / c->latent;
-  if (codec_embed_launch(ea, c->buf[0], (int)Tmax, c->latent, s, q0)) return mia_fail(ctx, MIA_ERR_DEVICE, "codec: embed launch failed");
+  if (codec_embed_launch(ea, c->buf[0], (int)Tmax, c->latent, ctx->stream, q0)) return mia_fail(ctx, MIA_ERR_DEVICE, "codec: embed launch failed");
   // Stages run stacked while all the utterances' activations there (three buffers) fit the budget.  SNAC: 256 MiB, the Infinity Cache.
   // Its early stages have too few rows per utterance to fill the CUs, and stacking fills them; from the first stage that does not fit,
   // every utterance runs the rest of the program on its own slab, one after the other, with the single call's launches.  A late
@@ -113,24 +110,12 @@ int decode_batch_enqueue(mia_codec* c, std::vector<BatchUtt>& ut, const int stri
     }
   }
   if (n_samples) for (int u = 0; u < U; ++u) n_samples[u] = ut[u].g.T_final;
-  if (!dev) {
-    int64_t po = 0;
-    for (int u = 0; u < U; ++u) {
-      MIA_HIP(ctx, hipMemcpyAsync(pcm + pcm_off[u], c->d_pcm + po, (size_t)ut[u].g.T_final * 4, hipMemcpyDeviceToHost, s));
-      po += ut[u].g.T_final;
-    }
+  int64_t po = 0;
+  for (int u = 0; u < U && !dev; ++u) {                    // host: each utterance from the packed d_pcm to its place
+    io.out(pcm + pcm_off[u], c->d_pcm + po, (size_t)ut[u].g.T_final * 4);
+    po += ut[u].g.T_final;
   }
-  return MIA_OK;
-}
-
-// shared tail of the two batch entries.  Host memory: the caller's codes / noise / pcm are behind asynchronous copies, so the stream is
-// synchronised on EVERY return path, the failing ones included (the tables' staging belongs to the handle and needs no such care).
-int decode_batch_common(mia_codec* c, std::vector<BatchUtt>& ut, const int strides[MIA_MAX_LEVELS], int n_levels, const int32_t* codes, size_t n_codes_total,
-                        const float* noise, float* pcm, const int64_t* pcm_off, int64_t* n_samples, int mem) {
-  int rc = decode_batch_enqueue(c, ut, strides, n_levels, codes, n_codes_total, noise, pcm, pcm_off, n_samples, mem);
-  if (mem == MIA_MEM_HOST && hipStreamSynchronize(c->ctx->stream) != hipSuccess && rc == MIA_OK)
-    rc = mia_fail(c->ctx, MIA_ERR_DEVICE, "codec: device error in the stacked decode");
-  return rc;
+  return io.finish();
 }
 
 // the geometry of every utterance (one program walk each), and the checks both entries share; `what` prefixes the messages
@@ -159,7 +144,8 @@ extern "C" int mia_snac_decode_batch(mia_codec* c, int n_utt, const int32_t* cod
   MIA_CHECK_ARG(ctx, c->kind == 0, "snac_decode_batch: handle is not a SNAC model");
   MIA_CHECK_ARG(ctx, n_utt >= 1 && n_utt <= 64, "snac_decode_batch: n_utt must be 1..64 (got %d)", n_utt);
   MIA_CHECK_ARG(ctx, codes && n_codes && pcm && pcm_off && n_levels > 0, "snac_decode_batch: null arguments");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "snac_decode_batch: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "snac_decode_batch: bad mem");
+  HostIo io(ctx, mem);
   std::vector<BatchUtt> ut(n_utt);
   size_t off = 0;
   for (int u = 0; u < n_utt; ++u) {
@@ -170,7 +156,7 @@ extern "C" int mia_snac_decode_batch(mia_codec* c, int n_utt, const int32_t* cod
     for (int i = 0; i < n_levels; ++i) {
       if (n[i] <= 0) continue;
       if (i < c->n_levels && (int64_t)n[i] * c->vq_stride[i] == ut[u].T0) {
-        for (int k = 0; k < n[i] && mem == MIA_MEM_HOST; ++k)
+        for (int k = 0; k < n[i] && io.host(); ++k)
           MIA_CHECK_ARG(ctx, codes[off + k] >= 0 && codes[off + k] < c->cb_size, "snac_decode_batch: code %d out of range at level %d of utterance %d", codes[off + k], i, u);
         ut[u].code_off[i] = (int64_t)off;
       }
@@ -178,7 +164,7 @@ extern "C" int mia_snac_decode_batch(mia_codec* c, int n_utt, const int32_t* cod
     }
   }
   if (int rc = batch_lengths(c, ut, noise, n_noise, pcm_off, "snac_decode_batch")) return rc;
-  return decode_batch_common(c, ut, c->vq_stride, c->n_levels, codes, off, noise, pcm, pcm_off, n_samples, mem);
+  return decode_batch_common(c, ut, c->vq_stride, c->n_levels, codes, off, noise, pcm, pcm_off, n_samples, io);
 }
 
 extern "C" int mia_dac_decode_batch(mia_codec* c, int n_utt, const int32_t* codes, int n_codebooks, const int64_t* T, float* pcm,
@@ -188,7 +174,8 @@ extern "C" int mia_dac_decode_batch(mia_codec* c, int n_utt, const int32_t* code
   MIA_CHECK_ARG(ctx, c->kind == 1, "dac_decode_batch: handle is not a DAC model");
   MIA_CHECK_ARG(ctx, n_utt >= 1 && n_utt <= 64, "dac_decode_batch: n_utt must be 1..64 (got %d)", n_utt);
   MIA_CHECK_ARG(ctx, codes && T && pcm && pcm_off && n_codebooks > 0 && n_codebooks <= c->n_levels, "dac_decode_batch: bad arguments");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "dac_decode_batch: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "dac_decode_batch: bad mem");
+  HostIo io(ctx, mem);
   std::vector<BatchUtt> ut(n_utt);
   size_t off = 0;
   for (int u = 0; u < n_utt; ++u) {
@@ -196,11 +183,11 @@ extern "C" int mia_dac_decode_batch(mia_codec* c, int n_utt, const int32_t* code
     ut[u].T0 = T[u];
     for (int i = 0; i < n_codebooks; ++i) ut[u].code_off[i] = (int64_t)(off + (size_t)i * T[u]);
     const size_t n = (size_t)n_codebooks * T[u];
-    for (size_t k = 0; k < n && mem == MIA_MEM_HOST; ++k)
+    for (size_t k = 0; k < n && io.host(); ++k)
       MIA_CHECK_ARG(ctx, codes[off + k] >= 0 && codes[off + k] < c->cb_size, "dac_decode_batch: code %d out of range in utterance %d", codes[off + k], u);
     off += n;
   }
   if (int rc = batch_lengths(c, ut, nullptr, 0, pcm_off, "dac_decode_batch")) return rc;
   const int ones[MIA_MAX_LEVELS] = {1, 1, 1, 1};
-  return decode_batch_common(c, ut, ones, n_codebooks, codes, off, nullptr, pcm, pcm_off, n_samples, mem);
+  return decode_batch_common(c, ut, ones, n_codebooks, codes, off, nullptr, pcm, pcm_off, n_samples, io);
 }

@@ -28,7 +28,8 @@ extern "C" int mia_dac_encode(mia_codec* c, const float* pcm, int64_t n_samples,
   mia_ctx* ctx = c->ctx;
   MIA_CHECK_ARG(ctx, c->kind == 1 && c->has_encoder, "dac_encode: no encoder loaded (mia_dac_load_encoder)");
   MIA_CHECK_ARG(ctx, pcm && codes && n_samples > 0, "dac_encode: null pointer or empty audio");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "dac_encode: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "dac_encode: bad mem");
+  HostIo io(ctx, mem);
   const int nq = n_quantizers <= 0 ? c->n_levels : std::min(n_quantizers, c->n_levels);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
@@ -43,7 +44,7 @@ extern "C" int mia_dac_encode(mia_codec* c, const float* pcm, int64_t n_samples,
   if ((rc = mia_grow(ctx, c->d_ze, c->ze_cap, (size_t)Tc * (size_t)std::max(c->cb_dim, 1), "codec: hipMalloc failed")) != MIA_OK) return rc;
   if ((rc = mia_grow(ctx, c->d_codes, c->codes_cap, (size_t)nq * Tc, "codec: hipMalloc failed")) != MIA_OK) return rc;
   MIA_HIP(ctx, hipMemsetAsync(c->d_audio, 0, (size_t)T0 * 4, s));
-  MIA_HIP(ctx, hipMemcpyAsync(c->d_audio, pcm, (size_t)n_samples * 4, mem == MIA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  io.check(hipMemcpyAsync(c->d_audio, pcm, (size_t)n_samples * 4, io.from_caller(), s));
   float* x = c->buf[0]; float* h = c->buf[1]; float* y = c->buf[2];
   int64_t T = T0;
   if (codec_conv_in1_launch(c->d_audio, x, c->enc_in_w, c->enc_in_b, T, c->enc_dim, 7, 3, s)) return mia_fail(ctx, MIA_ERR_DEVICE, "dac_encode: input conv launch failed");
@@ -61,7 +62,6 @@ extern "C" int mia_dac_encode(mia_codec* c, const float* pcm, int64_t n_samples,
   }
   if (n_steps) *n_steps = T;
   // codes [nq][T] -> caller's [nq][codes_capacity] rows
-  MIA_HIP(ctx, hipMemcpy2DAsync(codes, (size_t)codes_capacity * 4, c->d_codes, (size_t)T * 4, (size_t)T * 4, nq, mem == MIA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-  if (mem == MIA_MEM_HOST) MIA_HIP(ctx, hipStreamSynchronize(s));
-  return MIA_OK;
+  io.check(hipMemcpy2DAsync(codes, (size_t)codes_capacity * 4, c->d_codes, (size_t)T * 4, (size_t)T * 4, nq, io.to_caller(), s));
+  return io.finish();
 }

@@ -50,7 +50,7 @@ struct mia_codec {
   void* h_tab = nullptr; void* d_tab = nullptr; size_t tab_cap = 0;
   hipEvent_t tab_ev = nullptr;
   // bytes of activations up to which a stage of the batch entries runs stacked (mia_codec_set_stack_budget).  SNAC: the Infinity Cache;
-  // DAC (mia_dac_load): no limit -- measured both ways, see decode_batch_enqueue
+  // DAC (mia_dac_load): no limit -- measured both ways, see decode_batch_common
   int64_t stack_budget_default = 256ll << 20, stack_budget = 256ll << 20;
   // ---- encoder side (mia_dac_load_encoder): conv_in1 -> [3 residual units, snake + strided conv] x n -> snake + conv3, then the RVQ stages
   bool has_encoder = false;

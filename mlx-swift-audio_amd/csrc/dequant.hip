@@ -55,29 +55,24 @@ extern "C" int mia_dequant_affine(mia_ctx* ctx, const uint32_t* wq, const void* 
   MIA_CHECK_ARG(ctx, group_size > 0 && group_size % (32 / bits) == 0 && cols % group_size == 0, "dequant_affine: cols must be a multiple of group_size");
   MIA_CHECK_ARG(ctx, (scale_dtype == MIA_F32 || scale_dtype == MIA_F16 || scale_dtype == MIA_BF16) &&
                          (out_dtype == MIA_F32 || out_dtype == MIA_F16 || out_dtype == MIA_BF16), "dequant_affine: bad dtype");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "dequant_affine: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "dequant_affine: bad mem");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
+  HostIo io(ctx, mem);
   const int64_t words = rows * cols * bits / 32, groups = rows * (cols / group_size);
   const size_t ssz = scale_dtype == MIA_F32 ? 4 : 2, osz = out_dtype == MIA_F32 ? 4 : 2;
-  const uint32_t* d_w = wq; const void* d_s = scales; const void* d_b = biases; void* d_o = out;
-  if (mem == MIA_MEM_HOST) {
-    auto al = [](size_t n) { return (n + 255) / 256 * 256; };
-    const size_t o_s = al((size_t)words * 4), o_b = o_s + al(groups * ssz), o_o = o_b + al(groups * ssz);
-    char* ws = (char*)mia_workspace(ctx, o_o + al((size_t)rows * cols * osz));
-    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-    MIA_HIP(ctx, hipMemcpyAsync(ws, wq, (size_t)words * 4, hipMemcpyHostToDevice, s));
-    MIA_HIP(ctx, hipMemcpyAsync(ws + o_s, scales, groups * ssz, hipMemcpyHostToDevice, s));
-    MIA_HIP(ctx, hipMemcpyAsync(ws + o_b, biases, groups * ssz, hipMemcpyHostToDevice, s));
-    d_w = (const uint32_t*)ws; d_s = ws + o_s; d_b = ws + o_b; d_o = ws + o_o;
-  }
+  const size_t w_bytes = (size_t)words * 4, s_bytes = groups * ssz, o_bytes = (size_t)rows * cols * osz;
+  Carve cv;
+  const size_t o_w = cv.add(io.staged(w_bytes)), o_s = cv.add(io.staged(s_bytes)), o_b = cv.add(io.staged(s_bytes)), o_o = cv.add(io.staged(o_bytes));
+  char* ws;
+  if (!cv.workspace(ctx, ws)) return MIA_ERR_OUT_OF_MEMORY;
+  const uint32_t* d_w = io.in(wq, ws + o_w, w_bytes);
+  const void* d_s = io.in(scales, ws + o_s, s_bytes);
+  const void* d_b = io.in(biases, ws + o_b, s_bytes);
+  void* d_o = io.out(out, ws + o_o, o_bytes);
   const unsigned grid = (unsigned)((words + 255) / 256);
   if (bits == 4) hipLaunchKernelGGL(dequant_affine_kernel<4>, dim3(grid), dim3(256), 0, s, d_w, d_s, d_b, rows, cols, group_size, scale_dtype, d_o, out_dtype);
   else hipLaunchKernelGGL(dequant_affine_kernel<8>, dim3(grid), dim3(256), 0, s, d_w, d_s, d_b, rows, cols, group_size, scale_dtype, d_o, out_dtype);
   MIA_HIP(ctx, hipGetLastError());
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(out, d_o, (size_t)rows * cols * osz, hipMemcpyDeviceToHost, s));
-    MIA_HIP(ctx, hipStreamSynchronize(s));
-  }
-  return MIA_OK;
+  return io.finish();
 }

@@ -477,25 +477,23 @@ static int flow_prepare(mia_flow* f, int Tt, int S, Bufs& b, int U = 1) {
   return mia_grow(f->ctx, f->d_ids, f->ids_cap, (size_t)U * Tt + 4 * (size_t)U, "flow: hipMalloc failed");
 }
 
-static int upload_tokens(mia_flow* f, int32_t* dst, const int32_t* prompt_token, int n_prompt, const int32_t* token, int n_token, int mem) {
-  const hipMemcpyKind kind = mem == MIA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  if (n_prompt) MIA_HIP(f->ctx, hipMemcpyAsync(dst, prompt_token, (size_t)n_prompt * 4, kind, f->ctx->stream));
-  MIA_HIP(f->ctx, hipMemcpyAsync(dst + n_prompt, token, (size_t)n_token * 4, kind, f->ctx->stream));
-  return MIA_OK;
+static void upload_tokens(mia_flow* f, int32_t* dst, const int32_t* prompt_token, int n_prompt, const int32_t* token, int n_token, HostIo& io) {
+  if (n_prompt) io.check(hipMemcpyAsync(dst, prompt_token, (size_t)n_prompt * 4, io.from_caller(), f->ctx->stream));
+  io.check(hipMemcpyAsync(dst + n_prompt, token, (size_t)n_token * 4, io.from_caller(), f->ctx->stream));
 }
 
 int mia_flow_encode(mia_flow* f, const int32_t* token, int n_token, float* mu, int mem) {
   if (!f) return MIA_ERR_MODEL_NOT_LOADED;
-  MIA_CHECK_ARG(f->ctx, token && mu && n_token > 0 && n_token <= 4096 && (mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE), "flow_encode: bad argument");
+  MIA_CHECK_ARG(f->ctx, token && mu && n_token > 0 && n_token <= 4096 && HostIo::valid(mem), "flow_encode: bad argument");
   MIA_HIP(f->ctx, hipSetDevice(f->ctx->device));
   Bufs b;
   if (int rc = flow_prepare(f, n_token, 1, b)) return rc;
-  if (int rc = upload_tokens(f, f->d_ids, nullptr, 0, token, n_token, mem)) return rc;
+  HostIo io(f->ctx, mem);
+  upload_tokens(f, f->d_ids, nullptr, 0, token, n_token, io);
   if (int rc = run_encoder(f, b, f->d_ids, n_token)) return rc;
   const size_t n = (size_t)n_token * f->cfg.upsample_stride * f->cfg.output_size;
-  MIA_HIP(f->ctx, hipMemcpyAsync(mu, b.mu, n * 4, mem == MIA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, f->ctx->stream));
-  if (mem == MIA_MEM_HOST) MIA_HIP(f->ctx, hipStreamSynchronize(f->ctx->stream));
-  return MIA_OK;
+  io.check(hipMemcpyAsync(mu, b.mu, n * 4, io.to_caller(), f->ctx->stream));
+  return io.finish();
 }
 
 // One utterance of a flow call (all pointers host or device per `mem`)
@@ -515,7 +513,7 @@ static int flow_inference_core(mia_flow* f, const FlowUtt* utt, int U, int n_tim
   if (!f) return MIA_ERR_MODEL_NOT_LOADED;
   mia_ctx* ctx = f->ctx;
   const mia_flow_config& c = f->cfg;
-  MIA_CHECK_ARG(ctx, utt && U >= 1 && U <= 64 && (mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE), "flow_inference: bad argument (1..64 utterances)");
+  MIA_CHECK_ARG(ctx, utt && U >= 1 && U <= 64 && HostIo::valid(mem), "flow_inference: bad argument (1..64 utterances)");
   const int S = n_timesteps > 0 ? n_timesteps : c.n_timesteps;
   const int st = c.upsample_stride, M = c.output_size, C = c.dec_channels, H = c.dec_heads;
   const int trim = finalize ? 0 : c.pre_lookahead_len * st;
@@ -542,18 +540,19 @@ static int flow_inference_core(mia_flow* f, const FlowUtt* utt, int U, int n_tim
   Bufs b;
   if (int rc = flow_prepare(f, Tt, S, b, U)) return rc;
   hipStream_t s = ctx->stream;
-  const hipMemcpyKind kind = mem == MIA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  HostIo io(ctx, mem);
   int32_t* d_len = f->d_ids + (size_t)U * Tt;
   if (U > 1) {
     MIA_HIP(ctx, hipMemsetAsync(f->d_ids, 0, (size_t)U * Tt * 4, s));     // padding ids: a valid table row
-    MIA_HIP(ctx, hipMemcpyAsync(d_len, lens.data(), lens.size() * 4, hipMemcpyHostToDevice, s));
+    io.table(lens.data(), d_len, lens.size() * 4);
   }
+  const hipMemcpyKind kind = io.from_caller();
   for (int u = 0; u < U; ++u) {
     const FlowUtt& q = utt[u];
-    if (int rc = upload_tokens(f, f->d_ids + (size_t)u * Tt, q.prompt_token, q.n_prompt, q.token, q.n_token, mem)) return rc;
-    MIA_HIP(ctx, hipMemcpyAsync(b.emb + (size_t)u * c.spk_embed_dim, q.embedding, (size_t)c.spk_embed_dim * 4, kind, s));
-    MIA_HIP(ctx, hipMemcpyAsync(b.z + (size_t)u * T * M, q.z, (size_t)Tu[u] * M * 4, kind, s));
-    if (q.prompt_feat_len) MIA_HIP(ctx, hipMemcpyAsync(b.pf + (size_t)u * T * M, q.prompt_feat, (size_t)q.prompt_feat_len * M * 4, kind, s));
+    upload_tokens(f, f->d_ids + (size_t)u * Tt, q.prompt_token, q.n_prompt, q.token, q.n_token, io);
+    io.check(hipMemcpyAsync(b.emb + (size_t)u * c.spk_embed_dim, q.embedding, (size_t)c.spk_embed_dim * 4, kind, s));
+    io.check(hipMemcpyAsync(b.z + (size_t)u * T * M, q.z, (size_t)Tu[u] * M * 4, kind, s));
+    if (q.prompt_feat_len) io.check(hipMemcpyAsync(b.pf + (size_t)u * T * M, q.prompt_feat, (size_t)q.prompt_feat_len * M * 4, kind, s));
   }
   const int32_t* len_tok = U > 1 ? d_len : nullptr;
   const int32_t* len_up = U > 1 ? d_len + U : nullptr;
@@ -589,8 +588,8 @@ static int flow_inference_core(mia_flow* f, const FlowUtt* utt, int U, int n_tim
       tsin[(size_t)k * IC + i] = sinf(arg);
       tsin[(size_t)k * IC + half + i] = cosf(arg);
     }
-  MIA_HIP(ctx, hipMemcpyAsync(b.tsin, tsin.data(), tsin.size() * 4, hipMemcpyHostToDevice, s));
-  MIA_HIP(ctx, hipStreamSynchronize(s));    // tsin / lens are stack-lifetime host buffers
+  io.table(tsin.data(), b.tsin, tsin.size() * 4);
+  if (int rc = io.finish()) return rc;      // tsin / lens are stack-lifetime host buffers: read before anything below can return
   Run r{f, s};
   r.gemm(f->t1, b.tsin, IC, S, b.te1, TE, 4);
   r.gemm(f->t2, b.te1, TE, S, b.te2, TE);
@@ -627,14 +626,12 @@ static int flow_inference_core(mia_flow* f, const FlowUtt* utt, int U, int n_tim
   for (int u = 0; u < U; ++u) {
     const int To = Tu[u] - utt[u].prompt_feat_len;
     if (utt[u].mel_frames) *utt[u].mel_frames = To;
-    float* dst = mem == MIA_MEM_DEVICE ? utt[u].mel : b.out + out_off;
+    float* dst = io.out(utt[u].mel, b.out + out_off, (size_t)To * M * 4);
     hipLaunchKernelGGL(flow_emit, dim3((unsigned)(((int64_t)To * M + 255) / 256)), dim3(256), 0, s, b.xs + (size_t)u * T * M, dst, Tu[u], M, utt[u].prompt_feat_len);
-    if (mem == MIA_MEM_HOST) MIA_HIP(ctx, hipMemcpyAsync(utt[u].mel, dst, (size_t)To * M * 4, hipMemcpyDeviceToHost, s));
     out_off += (size_t)To * M;
   }
   MIA_HIP(ctx, hipGetLastError());
-  if (mem == MIA_MEM_HOST) MIA_HIP(ctx, hipStreamSynchronize(s));
-  return MIA_OK;
+  return io.finish();
 }
 
 static int flow_inference_impl(mia_flow* f, const int32_t* token, int n_token, const int32_t* prompt_token, int n_prompt, const float* prompt_feat,

@@ -227,7 +227,8 @@ int funasr_features_device(mia_ctx* ctx, const float* pcm_dev, const int64_t* of
   float* d_stats = (float*)s; s += align_up((size_t)B * FEAT * 2 * 4, 256);
   float* d_mel = (float*)s;
   hipStream_t st = ctx->stream;
-  MIA_HIP(ctx, hipMemcpyAsync(d_clips, clips.data(), (size_t)B * sizeof(FaClip), hipMemcpyHostToDevice, st));
+  HostIo io = HostIo::device(ctx);             // clips[] lives on this call's stack: no return before its upload has been read
+  io.table(clips.data(), d_clips, (size_t)B * sizeof(FaClip));
   static std::once_flag lds_once;
   static hipError_t lds_rc = hipSuccess;
   std::call_once(lds_once, [] { lds_rc = hipFuncSetAttribute((const void*)fa_logmel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LOGMEL_LDS); });
@@ -242,8 +243,7 @@ int funasr_features_device(mia_ctx* ctx, const float* pcm_dev, const int64_t* of
   hipLaunchKernelGGL(fa_lfr_norm, dim3(gx, (unsigned)B), dim3(256), 0, st, d_mel, d_clips, d_stats, feats_dev, stride);
   mia_prof_end(ctx, rec);
   MIA_HIP(ctx, hipGetLastError());
-  MIA_HIP(ctx, hipStreamSynchronize(st));      // clips[] lives on this call's stack
-  return MIA_OK;
+  return io.finish();
 }
 
 extern "C" int64_t mia_sensevoice_feature_rows(const int64_t* offs, int B) {
@@ -260,28 +260,24 @@ extern "C" int64_t mia_sensevoice_feature_rows(const int64_t* offs, int B) {
 extern "C" int mia_sensevoice_features(mia_ctx* ctx, const float* pcm, const int64_t* offs, int B, float* feats_out, int32_t* t_lfr_out, int64_t stride, int mem) {
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
   MIA_CHECK_ARG(ctx, pcm && offs && feats_out && t_lfr_out && B > 0, "sensevoice_features: null pointer or B <= 0");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "sensevoice_features: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "sensevoice_features: bad mem");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   FunasrPlan plan;
   int rc = funasr_plan(ctx, offs, B, plan);
   if (rc != MIA_OK) return rc;
   const size_t sc = funasr_scratch_bytes(plan);
   const size_t pcm_bytes = (size_t)offs[B] * 4, out_bytes = (size_t)plan.rows * stride * 4;
-  char* ws = (char*)mia_workspace(ctx, sc + (mem == MIA_MEM_HOST ? align_up(pcm_bytes, 256) + align_up(out_bytes, 256) : 0));
+  HostIo io(ctx, mem);
+  Carve cv;
+  cv.add(sc);
+  const size_t o_pcm = cv.add(io.staged(pcm_bytes)), o_out = cv.add(io.staged(out_bytes));
+  char* ws = (char*)mia_workspace(ctx, cv.bytes);
   if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-  const float* d_pcm = pcm;
-  float* d_out = feats_out;
-  if (mem == MIA_MEM_HOST) {
-    d_pcm = (const float*)(ws + sc);
-    d_out = (float*)(ws + sc + align_up(pcm_bytes, 256));
-    MIA_HIP(ctx, hipMemcpyAsync((void*)d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (stride > FEAT) MIA_HIP(ctx, hipMemsetAsync(d_out, 0, out_bytes, ctx->stream));
-  }
+  const float* d_pcm = io.in(pcm, ws + o_pcm, pcm_bytes);
+  float* d_out = io.out(feats_out, ws + o_out, out_bytes);
+  if (io.host() && stride > FEAT) MIA_HIP(ctx, hipMemsetAsync(d_out, 0, out_bytes, ctx->stream));
   if ((rc = funasr_features_device(ctx, d_pcm, offs, plan, d_out, stride, ws)) != MIA_OK) return rc;
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(feats_out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
+  if ((rc = io.finish()) != MIA_OK) return rc;
   for (int b = 0; b < B; ++b) t_lfr_out[b] = plan.t_lfr[b];
   return MIA_OK;
 }
@@ -291,22 +287,22 @@ extern "C" int mia_sensevoice_features(mia_ctx* ctx, const float* pcm, const int
 extern "C" int mia_op_funasr_logmel(mia_ctx* ctx, const float* pcm, const int64_t* offs, int B, float* mel_out, int mem) {
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
   MIA_CHECK_ARG(ctx, pcm && offs && mel_out && B > 0, "op_funasr_logmel: null pointer or B <= 0");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "op_funasr_logmel: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "op_funasr_logmel: bad mem");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   FunasrPlan plan;
   int rc = funasr_plan(ctx, offs, B, plan);
   if (rc != MIA_OK) return rc;
   const size_t sc = funasr_scratch_bytes(plan), pcm_bytes = (size_t)offs[B] * 4, feat_bytes = (size_t)plan.rows * FEAT * 4;
-  char* ws = (char*)mia_workspace(ctx, sc + align_up(feat_bytes, 256) + (mem == MIA_MEM_HOST ? align_up(pcm_bytes, 256) : 0));
+  HostIo io(ctx, mem);
+  Carve cv;
+  cv.add(sc);
+  const size_t o_feat = cv.add(feat_bytes), o_pcm = cv.add(io.staged(pcm_bytes));
+  char* ws = (char*)mia_workspace(ctx, cv.bytes);
   if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-  const float* d_pcm = pcm;
-  if (mem == MIA_MEM_HOST) {
-    d_pcm = (const float*)(ws + sc + align_up(feat_bytes, 256));
-    MIA_HIP(ctx, hipMemcpyAsync((void*)d_pcm, pcm, pcm_bytes, hipMemcpyHostToDevice, ctx->stream));
-  }
-  if ((rc = funasr_features_device(ctx, d_pcm, offs, plan, (float*)(ws + sc), FEAT, ws)) != MIA_OK) return rc;
+  const float* d_pcm = io.in(pcm, ws + o_pcm, pcm_bytes);
+  if ((rc = funasr_features_device(ctx, d_pcm, offs, plan, (float*)(ws + o_feat), FEAT, ws)) != MIA_OK) return rc;
   const char* d_mel = ws + align_up((size_t)B * sizeof(FaClip), 256) + align_up((size_t)B * FEAT * 2 * 4, 256);
-  MIA_HIP(ctx, hipMemcpyAsync(mel_out, d_mel, (size_t)plan.frames * NMEL * 4, mem == MIA_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
-  MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MIA_OK;
+  io.check(hipMemcpyAsync(mel_out, d_mel, (size_t)plan.frames * NMEL * 4, io.to_caller(), ctx->stream));
+  MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));      // a test tap: it returns with the mel in place in either mode
+  return io.finish();
 }

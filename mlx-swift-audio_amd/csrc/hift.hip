@@ -365,20 +365,13 @@ int carve(mia_hift* h, const Plan& p, Scratch& sc) {
   return MIA_OK;
 }
 
-int download(mia_hift* h, float* dst, const float* src, size_t n) {
-  MIA_HIP(h->ctx, hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToHost, h->ctx->stream));
-  MIA_HIP(h->ctx, hipStreamSynchronize(h->ctx->stream));
-  return MIA_OK;
-}
-
 // mel of sequence u: [C][Tu] at mel + C * (sum of the T before it); packed to [u][p.T][Cp] (single call: u = 0, offset 0)
-int upload_mel(mia_hift* h, const Plan& p, Scratch& sc, const float* mel, bool dev) {
+int upload_mel(mia_hift* h, const Plan& p, Scratch& sc, const float* mel, HostIo& io) {
   hipStream_t s = h->ctx->stream;
   const int C = h->cfg.in_channels;
   int64_t tot = 0;
   for (int64_t t : p.Tu) tot += t;
-  if (dev) sc.mel_raw = const_cast<float*>(mel);
-  else MIA_HIP(h->ctx, hipMemcpyAsync(sc.mel_raw, mel, (size_t)C * tot * 4, hipMemcpyHostToDevice, s));
+  sc.mel_raw = const_cast<float*>(io.in(mel, sc.mel_raw, (size_t)C * tot * 4));
   if (p.U > 1) MIA_HIP(h->ctx, hipMemsetAsync(sc.melp, 0, (size_t)p.U * p.T * h->Cp_mel * 4, s));      // rows past an utterance's end
   int64_t off = 0;
   for (int u = 0; u < p.U; ++u) {
@@ -540,73 +533,63 @@ int mia_hift_upsample_factor(const mia_hift* h) { return h ? h->up : 0; }
 
 int mia_hift_f0(mia_hift* h, const float* mel, int T, float* f0, int mem) {
   if (int rc = check_T(h, T)) return rc;
-  MIA_CHECK_ARG(h->ctx, mel && f0 && (mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE), "hift_f0: bad argument");
+  MIA_CHECK_ARG(h->ctx, mel && f0 && HostIo::valid(mem), "hift_f0: bad argument");
   MIA_HIP(h->ctx, hipSetDevice(h->ctx->device));
   Plan p = make_plan(h, T); Scratch sc;
   if (int rc = carve(h, p, sc)) return rc;
-  const bool dev = mem == MIA_MEM_DEVICE;
-  if (dev) sc.f0 = f0;
-  if (int rc = upload_mel(h, p, sc, mel, dev)) return rc;
+  HostIo io(h->ctx, mem);
+  sc.f0 = io.out(f0, sc.f0, (size_t)T * 4);
+  if (int rc = upload_mel(h, p, sc, mel, io)) return rc;
   if (int rc = dev_f0(h, p, sc)) return rc;
-  return dev ? MIA_OK : download(h, f0, sc.f0, (size_t)T);
+  return io.finish();
 }
 
 int mia_hift_source(mia_hift* h, const float* f0, int T, const float* noise, float* source, int mem) {
   if (int rc = check_T(h, T)) return rc;
-  MIA_CHECK_ARG(h->ctx, f0 && source && (mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE), "hift_source: bad argument");
+  MIA_CHECK_ARG(h->ctx, f0 && source && HostIo::valid(mem), "hift_source: bad argument");
   MIA_HIP(h->ctx, hipSetDevice(h->ctx->device));
   Plan p = make_plan(h, T); Scratch sc;
   if (int rc = carve(h, p, sc)) return rc;
-  hipStream_t s = h->ctx->stream;
-  const bool dev = mem == MIA_MEM_DEVICE;
-  if (dev) { sc.f0 = const_cast<float*>(f0); sc.noise = const_cast<float*>(noise); sc.s = source; }
-  else {
-    MIA_HIP(h->ctx, hipMemcpyAsync(sc.f0, f0, (size_t)T * 4, hipMemcpyHostToDevice, s));
-    if (noise) MIA_HIP(h->ctx, hipMemcpyAsync(sc.noise, noise, (size_t)p.L * h->H * 4, hipMemcpyHostToDevice, s));
-  }
+  HostIo io(h->ctx, mem);
+  sc.f0 = const_cast<float*>(io.in(f0, sc.f0, (size_t)T * 4));
+  sc.noise = const_cast<float*>(io.in(noise, sc.noise, (size_t)p.L * h->H * 4));
+  sc.s = io.out(source, sc.s, (size_t)p.L * 4);
   if (int rc = dev_source(h, p, sc, noise != nullptr, 0)) return rc;
-  return dev ? MIA_OK : download(h, source, sc.s, (size_t)p.L);
+  return io.finish();
 }
 
 int mia_hift_decode(mia_hift* h, const float* mel, int T, const float* source, float* pcm, int mem) {
   if (int rc = check_T(h, T)) return rc;
-  MIA_CHECK_ARG(h->ctx, mel && source && pcm && (mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE), "hift_decode: bad argument");
+  MIA_CHECK_ARG(h->ctx, mel && source && pcm && HostIo::valid(mem), "hift_decode: bad argument");
   MIA_HIP(h->ctx, hipSetDevice(h->ctx->device));
   Plan p = make_plan(h, T); Scratch sc;
   if (int rc = carve(h, p, sc)) return rc;
-  hipStream_t s = h->ctx->stream;
-  const bool dev = mem == MIA_MEM_DEVICE;
-  if (int rc = upload_mel(h, p, sc, mel, dev)) return rc;
-  if (dev) { sc.s = const_cast<float*>(source); sc.pcm = pcm; }
-  else MIA_HIP(h->ctx, hipMemcpyAsync(sc.s, source, (size_t)p.L * 4, hipMemcpyHostToDevice, s));
+  HostIo io(h->ctx, mem);
+  if (int rc = upload_mel(h, p, sc, mel, io)) return rc;
+  sc.s = const_cast<float*>(io.in(source, sc.s, (size_t)p.L * 4));
+  sc.pcm = io.out(pcm, sc.pcm, (size_t)p.L * 4);
   if (int rc = dev_decode(h, p, sc)) return rc;
-  return dev ? MIA_OK : download(h, pcm, sc.pcm, (size_t)p.L);
+  return io.finish();
 }
 
 int mia_hift_vocode(mia_hift* h, const float* mel, int T, const float* noise, const float* cache_source, int cache_len, float* pcm,
                     float* source_out, int mem) {
   if (int rc = check_T(h, T)) return rc;
-  MIA_CHECK_ARG(h->ctx, mel && pcm && (mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE), "hift_vocode: bad argument");
+  MIA_CHECK_ARG(h->ctx, mel && pcm && HostIo::valid(mem), "hift_vocode: bad argument");
   MIA_HIP(h->ctx, hipSetDevice(h->ctx->device));
   Plan p = make_plan(h, T); Scratch sc;
   MIA_CHECK_ARG(h->ctx, cache_len >= 0 && cache_len <= p.L && (cache_len == 0 || cache_source), "hift_vocode: bad cache_source");
   if (int rc = carve(h, p, sc)) return rc;
-  hipStream_t s = h->ctx->stream;
-  const bool dev = mem == MIA_MEM_DEVICE;
-  if (int rc = upload_mel(h, p, sc, mel, dev)) return rc;
-  if (dev) {
-    sc.noise = const_cast<float*>(noise); sc.cache = const_cast<float*>(cache_source); sc.pcm = pcm;
-    if (source_out) sc.s = source_out;
-  } else {
-    if (noise) MIA_HIP(h->ctx, hipMemcpyAsync(sc.noise, noise, (size_t)p.L * h->H * 4, hipMemcpyHostToDevice, s));
-    if (cache_len) MIA_HIP(h->ctx, hipMemcpyAsync(sc.cache, cache_source, (size_t)cache_len * 4, hipMemcpyHostToDevice, s));
-  }
+  HostIo io(h->ctx, mem);
+  if (int rc = upload_mel(h, p, sc, mel, io)) return rc;
+  sc.noise = const_cast<float*>(io.in(noise, sc.noise, (size_t)p.L * h->H * 4));
+  sc.cache = const_cast<float*>(io.in(cache_source, sc.cache, (size_t)cache_len * 4));
+  if (source_out) sc.s = io.out(source_out, sc.s, (size_t)p.L * 4);
+  sc.pcm = io.out(pcm, sc.pcm, (size_t)p.L * 4);
   if (int rc = dev_f0(h, p, sc)) return rc;
   if (int rc = dev_source(h, p, sc, noise != nullptr, cache_len)) return rc;
   if (int rc = dev_decode(h, p, sc)) return rc;
-  if (dev) return MIA_OK;
-  if (source_out) MIA_HIP(h->ctx, hipMemcpyAsync(source_out, sc.s, (size_t)p.L * 4, hipMemcpyDeviceToHost, s));
-  return download(h, pcm, sc.pcm, (size_t)p.L);
+  return io.finish();
 }
 
 // U utterances in one pass: every convolution of the f0 predictor and of the decoder runs once over the stacked sequences (grid.z =
@@ -617,7 +600,7 @@ int mia_hift_vocode(mia_hift* h, const float* mel, int T, const float* noise, co
 // with the single-utterance call.
 int mia_hift_vocode_batch(mia_hift* h, const float* mels, const int32_t* T, int n, const float* noise, float* pcm, int mem) {
   if (!h) return MIA_ERR_INVALID_ARGUMENT;
-  MIA_CHECK_ARG(h->ctx, mels && T && pcm && n >= 1 && n <= 64 && (mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE), "hift_vocode_batch: bad argument (1 <= n <= 64)");
+  MIA_CHECK_ARG(h->ctx, mels && T && pcm && n >= 1 && n <= 64 && HostIo::valid(mem), "hift_vocode_batch: bad argument (1 <= n <= 64)");
   int Tm = 0;
   for (int u = 0; u < n; ++u) { if (int rc = check_T(h, T[u])) return rc; Tm = std::max(Tm, T[u]); }
   MIA_HIP(h->ctx, hipSetDevice(h->ctx->device));
@@ -627,32 +610,28 @@ int mia_hift_vocode_batch(mia_hift* h, const float* mels, const int32_t* T, int 
   int64_t Ltot = 0;
   for (int u = 0; u < n; ++u) { const int64_t L = (int64_t)T[u] * h->up; p.Tu.push_back(T[u]); p.Lu.push_back(L); p.Fu.push_back(L / 4 + 1); Ltot += L; }
   if (int rc = carve(h, p, sc)) return rc;
-  const bool dev = mem == MIA_MEM_DEVICE;
   std::vector<int32_t> lens((size_t)(2 + h->cfg.n_ups) * n);
   for (int u = 0; u < n; ++u) {
     lens[u] = T[u]; lens[(size_t)n + u] = (int32_t)p.Fu[u];
     for (int i = 0; i < h->cfg.n_ups; ++i) lens[(size_t)(2 + i) * n + u] = (int32_t)rows_after(h, T[u], i);
   }
+  HostIo io(h->ctx, mem);         // declared after `lens`: no return path leaves the table's upload pending, in either mode
+  io.table(lens.data(), sc.lens, lens.size() * 4);
   if (n > 1) {
-    MIA_HIP(h->ctx, hipMemcpyAsync(sc.lens, lens.data(), lens.size() * 4, hipMemcpyHostToDevice, s));
     p.len_T = sc.lens; p.len_F = sc.lens + n;
     for (int i = 0; i < h->cfg.n_ups; ++i) p.len_rows[i] = sc.lens + (size_t)(2 + i) * n;
   }
-  if (int rc = upload_mel(h, p, sc, mels, dev)) return rc;
-  if (noise) {
-    if (dev) sc.noise = const_cast<float*>(noise);
-    else MIA_HIP(h->ctx, hipMemcpyAsync(sc.noise, noise, (size_t)Ltot * h->H * 4, hipMemcpyHostToDevice, s));
-  }
+  if (int rc = upload_mel(h, p, sc, mels, io)) return rc;
+  sc.noise = const_cast<float*>(io.in(noise, sc.noise, (size_t)Ltot * h->H * 4));
   if (int rc = dev_f0(h, p, sc)) return rc;
   if (int rc = dev_source(h, p, sc, noise != nullptr, 0)) return rc;
   if (int rc = dev_decode(h, p, sc)) return rc;
   int64_t off = 0;
   for (int u = 0; u < n; ++u) {
-    MIA_HIP(h->ctx, hipMemcpyAsync(pcm + off, sc.pcm + (int64_t)u * p.L, (size_t)p.Lu[u] * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    io.check(hipMemcpyAsync(pcm + off, sc.pcm + (int64_t)u * p.L, (size_t)p.Lu[u] * 4, io.to_caller(), s));
     off += p.Lu[u];
   }
-  MIA_HIP(h->ctx, hipStreamSynchronize(s));       // (also keeps `lens` alive until its upload has been read)
-  return MIA_OK;
+  return io.finish();
 }
 
 }  // extern "C"

@@ -363,7 +363,8 @@ int mia_logmel_device(mia_ctx* ctx, const float* pcm_dev, const int64_t* offs_ho
   s += align_up((size_t)B * sizeof(int), 256);
   float* d_tmp = (float*)s;
 
-  MIA_HIP(ctx, hipMemcpyAsync(d_clips, clips.data(), (size_t)B * sizeof(ClipInfo), hipMemcpyHostToDevice, ctx->stream));
+  HostIo io = HostIo::device(ctx);      // clips[] lives on the host stack of this call: no return before its upload has consumed it
+  io.table(clips.data(), d_clips, (size_t)B * sizeof(ClipInfo));
   double alg_bytes = 0.0;   // algorithmic traffic: audio read once + output written once
   for (int b = 0; b < B; ++b) alg_bytes += (double)clips[b].len * 4.0 + (double)n_out * n_mels * mia_dtype_size(out_dtype);
   const int prof_rec = mia_prof_begin(ctx, MIA_PROF_LOGMEL, alg_bytes);
@@ -417,9 +418,7 @@ int mia_logmel_device(mia_ctx* ctx, const float* pcm_dev, const int64_t* offs_ho
   }
   mia_prof_end(ctx, prof_rec);
   MIA_HIP(ctx, hipGetLastError());
-  // clips[] lives on the host stack of this call: the async H2D copy above must have consumed it.
-  MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MIA_OK;
+  return io.finish();
 }
 
 static int logmel_public(mia_ctx* ctx, const float* pcm, const int64_t* offs, int B, int n_mels, int64_t pad_right,
@@ -427,7 +426,7 @@ static int logmel_public(mia_ctx* ctx, const float* pcm, const int64_t* offs, in
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
   MIA_CHECK_ARG(ctx, pcm && offs && mel, "logmel: null pointer argument");
   MIA_CHECK_ARG(ctx, B > 0 && n_out > 0, "logmel: B and n_frames_out must be > 0");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "logmel: bad mem space %d", mem);
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "logmel: bad mem space %d", mem);
   MIA_CHECK_ARG(ctx, out_dtype == MIA_F32 || out_dtype == MIA_F16 || out_dtype == MIA_BF16, "logmel: bad out_dtype %d", out_dtype);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   const int64_t total_samples = offs[B] - offs[0];
@@ -435,29 +434,20 @@ static int logmel_public(mia_ctx* ctx, const float* pcm, const int64_t* offs, in
   const size_t sc = mia_logmel_scratch_bytes(B, n_out, n_mels);
   const size_t out_bytes = (size_t)B * n_out * n_mels * mia_dtype_size(out_dtype);
   const size_t pcm_bytes = (size_t)(offs[B]) * sizeof(float);
-  size_t need = sc;
-  if (mem == MIA_MEM_HOST) need += align_up(pcm_bytes, 256) + align_up(out_bytes, 256);
-  char* ws = (char*)mia_workspace(ctx, need);
+  HostIo io(ctx, mem);
+  Carve cv;
+  cv.add(sc);
+  const size_t o_pcm = cv.add(io.staged(pcm_bytes)), o_out = cv.add(io.staged(out_bytes));
+  char* ws = (char*)mia_workspace(ctx, cv.bytes);
   if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-  const float* d_pcm = pcm;
-  void* d_out = mel;
-  if (mem == MIA_MEM_HOST) {
-    float* p = (float*)(ws + sc);
-    d_out = ws + sc + align_up(pcm_bytes, 256);
-    MIA_HIP(ctx, hipMemcpyAsync(p, pcm, pcm_bytes, hipMemcpyHostToDevice, ctx->stream));
-    d_pcm = p;
-  }
+  const float* d_pcm = io.in(pcm, ws + o_pcm, pcm_bytes);
+  void* d_out = io.out(mel, ws + o_out, out_bytes);
   int64_t clip_stride, row_stride, col_stride;
   if (channel_major) { clip_stride = n_out * n_mels; row_stride = 1; col_stride = n_out; }
   else { clip_stride = n_out * n_mels; row_stride = n_mels; col_stride = 1; }
   int rc = mia_logmel_device(ctx, d_pcm, offs, B, n_mels, window_kind, pad_right, n_out, d_out, out_dtype, channel_major,
                              clip_stride, row_stride, col_stride, 0, ws);
-  if (rc != MIA_OK) return rc;
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(mel, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MIA_OK;
+  return rc != MIA_OK ? rc : io.finish();
 }
 
 extern "C" int mia_logmel_whisper(mia_ctx* ctx, const float* pcm, const int64_t* offs, int B, int n_mels, int64_t pad_right,

@@ -119,7 +119,7 @@ extern "C" int64_t mia_mel_s3gen_frames(int64_t n_samples) {
 
 extern "C" int mia_mel_s3gen(mia_ctx* ctx, const float* pcm, int64_t n_samples, float* mel, int mem) {
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
-  MIA_CHECK_ARG(ctx, pcm && mel && (mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE), "mel_s3gen: bad argument");
+  MIA_CHECK_ARG(ctx, pcm && mel && HostIo::valid(mem), "mel_s3gen: bad argument");
   MIA_CHECK_ARG(ctx, n_samples > PAD && n_samples <= (int64_t)24000 * 600, "mel_s3gen: n_samples must be in (%d, 10 min]", PAD);
   const int64_t F = mia_mel_s3gen_frames(n_samples);
   MIA_CHECK_ARG(ctx, F > 0, "mel_s3gen: input too short for one frame");
@@ -129,28 +129,24 @@ extern "C" int mia_mel_s3gen(mia_ctx* ctx, const float* pcm, int64_t n_samples, 
   hipStream_t s = ctx->stream;
   const int64_t Tp = n_samples + 2 * PAD;
   const int64_t rows = (Tp + 31) / 32 + 1;
-  const size_t n_in = mem == MIA_MEM_HOST ? (size_t)n_samples : 0;
+  HostIo io(ctx, mem);
   const size_t n_xp = (size_t)rows * 32, n_spec = (size_t)F * 2 * tb->nbp, n_out = (size_t)F * NMEL;
-  auto al = [](size_t n) { return (n + 63) / 64 * 64; };
-  float* ws = (float*)mia_workspace(ctx, (al(n_in) + al(n_xp) + al(n_spec) + al(n_out)) * 4);
+  Carve cv;
+  const size_t o_in = cv.add(io.staged((size_t)n_samples * 4)), o_xp = cv.add(n_xp * 4), o_spec = cv.add(n_spec * 4), o_out = cv.add(io.staged(n_out * 4));
+  char* ws = (char*)mia_workspace(ctx, cv.bytes);
   if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-  float* d_in = ws; float* xp = d_in + al(n_in); float* spec = xp + al(n_xp); float* d_out = spec + al(n_spec);
-  const float* x = pcm;
-  if (mem == MIA_MEM_HOST) { MIA_HIP(ctx, hipMemcpyAsync(d_in, pcm, (size_t)n_samples * 4, hipMemcpyHostToDevice, s)); x = d_in; }
+  float* xp = (float*)(ws + o_xp); float* spec = (float*)(ws + o_spec);
+  const float* x = io.in(pcm, ws + o_in, (size_t)n_samples * 4);
   hipLaunchKernelGGL(mel24_reflect_pad, dim3((unsigned)((n_xp + 255) / 256)), dim3(256), 0, s, x, xp, n_samples, (int64_t)n_xp);
   ConvGemmArgs g;
   g.X = xp; g.ldx = 32; g.T_in = (int)rows; g.W = tb->dft; g.Y = spec; g.ldy = 2 * tb->nbp; g.T_out = (int)F;
   g.M = (int)F; g.N = 2 * tb->nbp; g.Cin = 32; g.taps = NFFT / 32; g.x_row_mul = HOP / 32;
   if (const char* e = codec_conv_gemm_check(g)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "mel_s3gen: %s", e);
   if (codec_conv_gemm_launch(g, 1, s)) return mia_fail(ctx, MIA_ERR_DEVICE, "mel_s3gen: GEMM launch failed");
-  float* dst = mem == MIA_MEM_DEVICE ? mel : d_out;
+  float* dst = io.out(mel, ws + o_out, n_out * 4);
   hipLaunchKernelGGL(mel24_finish, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, spec, tb->fb_w, tb->fb_meta, dst, (int)F, tb->nbp);
   MIA_HIP(ctx, hipGetLastError());
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(mel, d_out, n_out * 4, hipMemcpyDeviceToHost, s));
-    MIA_HIP(ctx, hipStreamSynchronize(s));
-  }
-  return MIA_OK;
+  return io.finish();
 }
 
 // ---- linear-interpolation resampler of the CosyVoice2 prompt path ---------------------------------------------------------------------------
@@ -178,25 +174,20 @@ extern "C" int64_t mia_resample_linear_len(int64_t n_samples, float scale) {
 
 extern "C" int mia_resample_linear(mia_ctx* ctx, const float* x, int64_t n_samples, float scale, float* out, int mem) {
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
-  MIA_CHECK_ARG(ctx, x && out && n_samples > 0 && n_samples < ((int64_t)1 << 24) && scale > 0.f && (mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE),
+  MIA_CHECK_ARG(ctx, x && out && n_samples > 0 && n_samples < ((int64_t)1 << 24) && scale > 0.f && HostIo::valid(mem),
                 "resample_linear: bad argument (n_samples must stay below 2^24: the reference indexes in float32)");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   const int64_t newT = mia_resample_linear_len(n_samples, scale);
   hipStream_t s = ctx->stream;
-  const float* d_x = x; float* d_o = out;
-  if (mem == MIA_MEM_HOST) {
-    auto al = [](size_t n) { return (n + 63) / 64 * 64; };
-    float* ws = (float*)mia_workspace(ctx, (al(n_samples) + al(newT)) * 4);
-    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-    MIA_HIP(ctx, hipMemcpyAsync(ws, x, (size_t)n_samples * 4, hipMemcpyHostToDevice, s));
-    d_x = ws; d_o = ws + al(n_samples);
-  }
+  HostIo io(ctx, mem);
+  Carve cv;
+  const size_t o_x = cv.add(io.staged((size_t)n_samples * 4)), o_o = cv.add(io.staged((size_t)newT * 4));
+  char* ws;
+  if (!cv.workspace(ctx, ws)) return MIA_ERR_OUT_OF_MEMORY;
+  const float* d_x = io.in(x, ws + o_x, (size_t)n_samples * 4);
+  float* d_o = io.out(out, ws + o_o, (size_t)newT * 4);
   hipLaunchKernelGGL(resample_linear_kernel, dim3((unsigned)((newT + 255) / 256)), dim3(256), 0, s, d_x, d_o, n_samples, newT,
                      (float)n_samples / (float)newT, (float)n_samples - 1.001f);
   MIA_HIP(ctx, hipGetLastError());
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(out, d_o, (size_t)newT * 4, hipMemcpyDeviceToHost, s));
-    MIA_HIP(ctx, hipStreamSynchronize(s));
-  }
-  return MIA_OK;
+  return io.finish();
 }

@@ -99,3 +99,5 @@ inline size_t mia_dtype_size(int dt) { return dt == MIA_F32 ? 4 : 2; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 void mia_resampler_free(mia_ctx* ctx);   // resample.hip
+
+#include "host_io.h"   // HostIo, Carve: the staging rule of every entry point that takes `int mem`

@@ -8,32 +8,23 @@ extern "C" int mia_op_linear(mia_ctx* ctx, const void* x, int64_t lda, const voi
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
   MIA_CHECK_ARG(ctx, x && w && y, "op_linear: null pointer");
   MIA_CHECK_ARG(ctx, dtype == MIA_BF16 || dtype == MIA_F16, "op_linear: dtype must be MIA_BF16 or MIA_F16");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "op_linear: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "op_linear: bad mem");
   MIA_CHECK_ARG(ctx, M > 0 && N > 0 && K > 0 && lda >= K && ldy >= N && (!r || ldr >= N), "op_linear: bad shape");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
+  HostIo io(ctx, mem);
   GemmArgs g;
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldy; g.ldr = ldr; g.act = act; g.out_f32 = out_f32 ? 1 : 0; g.variant = variant;
   const size_t xb = (size_t)M * lda * 2, wb = (size_t)N * K * 2, yb = (size_t)M * ldy * (out_f32 ? 4 : 2);
   const size_t bb = bias ? (size_t)N * 4 : 0, rb = r ? (size_t)M * ldr * 4 : 0;
-  if (mem == MIA_MEM_DEVICE) {
-    g.A = x; g.W = w; g.C = y; g.bias = bias; g.R = r;
-  } else {
-    const size_t o_w = align_up(xb, 256), o_y = o_w + align_up(wb, 256), o_b = o_y + align_up(yb, 256), o_r = o_b + align_up(bb, 256);
-    char* ws = (char*)mia_workspace(ctx, o_r + align_up(rb, 256));
-    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-    MIA_HIP(ctx, hipMemcpyAsync(ws, x, xb, hipMemcpyHostToDevice, ctx->stream));
-    MIA_HIP(ctx, hipMemcpyAsync(ws + o_w, w, wb, hipMemcpyHostToDevice, ctx->stream));
-    if (bias) MIA_HIP(ctx, hipMemcpyAsync(ws + o_b, bias, bb, hipMemcpyHostToDevice, ctx->stream));
-    if (r) MIA_HIP(ctx, hipMemcpyAsync(ws + o_r, r, rb, hipMemcpyHostToDevice, ctx->stream));
-    g.A = ws; g.W = ws + o_w; g.C = ws + o_y; g.bias = bias ? (const float*)(ws + o_b) : nullptr; g.R = r ? (const float*)(ws + o_r) : nullptr;
-  }
+  Carve cv;
+  const size_t o_x = cv.add(io.staged(xb)), o_w = cv.add(io.staged(wb)), o_y = cv.add(io.staged(yb)), o_b = cv.add(io.staged(bb)), o_r = cv.add(io.staged(rb));
+  char* ws;
+  if (!cv.workspace(ctx, ws)) return MIA_ERR_OUT_OF_MEMORY;
+  g.A = io.in(x, ws + o_x, xb); g.W = io.in(w, ws + o_w, wb); g.bias = io.in(bias, ws + o_b, bb); g.R = io.in(r, ws + o_r, rb);
+  g.C = io.out(y, ws + o_y, yb);
   if (const char* e = mia_gemm_check(g)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
   if (mia_gemm_launch(g, dtype, ctx->stream) != 0) return mia_fail(ctx, MIA_ERR_DEVICE, "op_linear: launch failed");
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(y, g.C, yb, hipMemcpyDeviceToHost, ctx->stream));
-    MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MIA_OK;
+  return io.finish();
 }
 
 // mia_op_linear with the two special store layouts of gemm.hip (test hook): epi 1 = MIA_EPI_QKV_VT (q|k rows into y, V transposed per head
@@ -44,7 +35,8 @@ extern "C" int mia_op_linear_epi(mia_ctx* ctx, const void* x, int64_t lda, const
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
   MIA_CHECK_ARG(ctx, x && w && y && (vt || epi != MIA_EPI_QKV_VT), "op_linear_epi: null pointer");
   MIA_CHECK_ARG(ctx, dtype == MIA_BF16 || dtype == MIA_F16, "op_linear_epi: dtype must be MIA_BF16 or MIA_F16");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "op_linear_epi: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "op_linear_epi: bad mem");
+  HostIo io(ctx, mem);
   MIA_CHECK_ARG(ctx, epi == MIA_EPI_QKV_VT || epi == MIA_EPI_HEADMAJOR, "op_linear_epi: epi must be 1 (QKV_VT) or 2 (HEADMAJOR)");
   MIA_CHECK_ARG(ctx, variant >= 0 && variant <= 4, "op_linear_epi: variant must be 0 .. 4");
   MIA_CHECK_ARG(ctx, M > 0 && N > 0 && K > 0 && T > 0 && H > 0 && lda >= K, "op_linear_epi: bad shape");
@@ -53,9 +45,9 @@ extern "C" int mia_op_linear_epi(mia_ctx* ctx, const void* x, int64_t lda, const
   if (epi == MIA_EPI_QKV_VT) {
     MIA_CHECK_ARG(ctx, ldy >= D2, "op_linear_epi: ldy must cover the q|k row (2 * H * 64)");
     MIA_CHECK_ARG(ctx, Tpad >= T, "op_linear_epi: Tpad must be >= T");
-    MIA_CHECK_ARG(ctx, (((uintptr_t)y | (uintptr_t)vt) & 7) == 0 || mem == MIA_MEM_HOST, "op_linear_epi: y and vt must be 8-byte aligned");
+    MIA_CHECK_ARG(ctx, (((uintptr_t)y | (uintptr_t)vt) & 7) == 0 || io.host(), "op_linear_epi: y and vt must be 8-byte aligned");
   } else {
-    MIA_CHECK_ARG(ctx, ((uintptr_t)y & 7) == 0 || mem == MIA_MEM_HOST, "op_linear_epi: y must be 8-byte aligned");
+    MIA_CHECK_ARG(ctx, ((uintptr_t)y & 7) == 0 || io.host(), "op_linear_epi: y must be 8-byte aligned");
   }
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   GemmArgs g;
@@ -64,29 +56,18 @@ extern "C" int mia_op_linear_epi(mia_ctx* ctx, const void* x, int64_t lda, const
   const size_t xb = (size_t)M * lda * 2, wb = (size_t)N * K * 2, bb = bias ? (size_t)N * 4 : 0;
   const size_t yb = epi == MIA_EPI_QKV_VT ? (size_t)(((int64_t)M - 1) * ldy + D2) * 2 : (size_t)B * H * T * 64 * 2;
   const size_t vb = epi == MIA_EPI_QKV_VT ? (size_t)B * H * 64 * Tpad * 2 : 0;
-  if (mem == MIA_MEM_DEVICE) {
-    g.A = x; g.W = w; g.C = y; g.C2 = vt; g.bias = bias;
-  } else {
-    const size_t o_w = align_up(xb, 256), o_y = o_w + align_up(wb, 256), o_v = o_y + align_up(yb, 256), o_b = o_v + align_up(vb, 256);
-    char* ws = (char*)mia_workspace(ctx, o_b + align_up(bb, 256));
-    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-    g.A = ws; g.W = ws + o_w; g.C = ws + o_y; g.C2 = vb ? ws + o_v : nullptr; g.bias = bias ? (const float*)(ws + o_b) : nullptr;
-  }
+  Carve cv;
+  const size_t o_x = cv.add(io.staged(xb)), o_w = cv.add(io.staged(wb)), o_y = cv.add(io.staged(yb)), o_v = cv.add(io.staged(vb)), o_b = cv.add(io.staged(bb));
+  char* ws;
+  if (!cv.workspace(ctx, ws)) return MIA_ERR_OUT_OF_MEMORY;
+  auto place = [&](const void* p, size_t off) -> void* { return p && io.host() ? ws + off : const_cast<void*>(p); };    // where in / inout will put it
+  g.A = place(x, o_x); g.W = place(w, o_w); g.C = place(y, o_y); g.C2 = vb ? place(vt, o_v) : (io.host() ? nullptr : vt); g.bias = (const float*)place(bias, o_b);
   if (const char* e = mia_gemm_check(g)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);     // before anything is copied or launched
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync((void*)g.A, x, xb, hipMemcpyHostToDevice, ctx->stream));
-    MIA_HIP(ctx, hipMemcpyAsync((void*)g.W, w, wb, hipMemcpyHostToDevice, ctx->stream));
-    if (bias) MIA_HIP(ctx, hipMemcpyAsync((void*)g.bias, bias, bb, hipMemcpyHostToDevice, ctx->stream));
-    MIA_HIP(ctx, hipMemcpyAsync(g.C, y, yb, hipMemcpyHostToDevice, ctx->stream));                      // untouched bytes survive the round trip
-    if (vb) MIA_HIP(ctx, hipMemcpyAsync(g.C2, vt, vb, hipMemcpyHostToDevice, ctx->stream));
-  }
+  io.in(x, ws + o_x, xb); io.in(w, ws + o_w, wb); io.in(bias, ws + o_b, bb);
+  io.inout(y, ws + o_y, yb);                                                                          // untouched bytes survive the round trip
+  if (vb) io.inout(vt, ws + o_v, vb);
   if (mia_gemm_launch(g, dtype, ctx->stream) != 0) return mia_fail(ctx, MIA_ERR_DEVICE, "op_linear_epi: launch failed");
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(y, g.C, yb, hipMemcpyDeviceToHost, ctx->stream));
-    if (vb) MIA_HIP(ctx, hipMemcpyAsync(vt, g.C2, vb, hipMemcpyDeviceToHost, ctx->stream));
-    MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MIA_OK;
+  return io.finish();
 }
 
 // The Whisper encoder's attention (attention.hip) in its native layout (test hook): qk [B*T][ld_qk] with q of head h in columns h*64.. and k
@@ -97,37 +78,28 @@ static int op_attention_h64(mia_ctx* ctx, const void* qk, int64_t ld_qk, const v
                             int Tpad, int dtype, int variant, int mem) {
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
   MIA_CHECK_ARG(ctx, variant >= -1 && variant < MIA_ATT_NVARIANTS, "op_attention_h64: unknown kernel variant");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "op_attention_h64: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "op_attention_h64: bad mem");
+  HostIo io(ctx, mem);
   MIA_CHECK_ARG(ctx, qk && vt && out, "op_attention_h64: null pointer");
   MIA_CHECK_ARG(ctx, dtype == MIA_BF16 || dtype == MIA_F16, "op_attention_h64: dtype must be MIA_BF16 or MIA_F16");
   if (const char* e = mia_enc_attention_check(B, T, H, Tpad, ld_qk, ld_out)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
   const int64_t rows = (int64_t)B * T, D = (int64_t)H * 64;
   MIA_CHECK_ARG(ctx, rows < (1ll << 31) && (int64_t)B * H * ((T + 127) / 128) < (1ll << 31), "op_attention_h64: B * T must stay below 2^31");
   MIA_CHECK_ARG(ctx, ld_qk >= 2 * D && ld_out >= D, "op_attention_h64: row strides must cover the row (ld_qk >= 2 * H * 64, ld_out >= H * 64)");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || ((((uintptr_t)qk | (uintptr_t)vt) & 15) == 0 && ((uintptr_t)out & 7) == 0),
+  MIA_CHECK_ARG(ctx, io.host() || ((((uintptr_t)qk | (uintptr_t)vt) & 15) == 0 && ((uintptr_t)out & 7) == 0),
                 "op_attention_h64: qk and vt must be 16-byte aligned, out 8-byte aligned");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
-  const void* d_qk = qk; const void* d_vt = vt; void* d_out = out;
-  size_t ob = 0;
-  if (mem == MIA_MEM_HOST) {
-    const size_t qb = (size_t)((rows - 1) * ld_qk + 2 * D) * 2, vb = (size_t)B * H * 64 * Tpad * 2;
-    ob = (size_t)((rows - 1) * ld_out + D) * 2;
-    const size_t o_v = align_up(qb, 256), o_o = o_v + align_up(vb, 256);
-    char* ws = (char*)mia_workspace(ctx, o_o + align_up(ob, 256));
-    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-    MIA_HIP(ctx, hipMemcpyAsync(ws + o_o, out, ob, hipMemcpyHostToDevice, ctx->stream));      // unwritten elements keep the caller's bytes
-    MIA_HIP(ctx, hipMemcpyAsync(ws, qk, qb, hipMemcpyHostToDevice, ctx->stream));
-    MIA_HIP(ctx, hipMemcpyAsync(ws + o_v, vt, vb, hipMemcpyHostToDevice, ctx->stream));
-    d_qk = ws; d_vt = ws + o_v; d_out = ws + o_o;
-  }
+  const size_t qb = (size_t)((rows - 1) * ld_qk + 2 * D) * 2, vb = (size_t)B * H * 64 * Tpad * 2, ob = (size_t)((rows - 1) * ld_out + D) * 2;
+  Carve cv;
+  const size_t o_q = cv.add(io.staged(qb)), o_v = cv.add(io.staged(vb)), o_o = cv.add(io.staged(ob));
+  char* ws;
+  if (!cv.workspace(ctx, ws)) return MIA_ERR_OUT_OF_MEMORY;
+  void* d_out = io.inout(out, ws + o_o, ob);                                                  // unwritten elements keep the caller's bytes
+  const void* d_qk = io.in(qk, ws + o_q, qb); const void* d_vt = io.in(vt, ws + o_v, vb);
   if (variant < 0 ? mia_enc_attention_launch(d_qk, ld_qk, d_vt, d_out, ld_out, B, T, H, Tpad, dtype, ctx->stream)
                   : mia_enc_attention_launch_variant(d_qk, ld_qk, d_vt, d_out, ld_out, B, T, H, Tpad, dtype, variant, ctx->stream))
     return mia_fail(ctx, MIA_ERR_DEVICE, "op_attention_h64: launch failed");
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(out, d_out, ob, hipMemcpyDeviceToHost, ctx->stream));
-    MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MIA_OK;
+  return io.finish();
 }
 extern "C" int mia_op_attention_h64(mia_ctx* ctx, const void* qk, int64_t ld_qk, const void* vt, void* out, int64_t ld_out, int B, int T, int H,
                                     int Tpad, int dtype, int mem) {
@@ -258,71 +230,50 @@ extern "C" int mia_op_attention_f32(mia_ctx* ctx, const float* q, int64_t ldq, c
 extern "C" int mia_op_attention_h128(mia_ctx* ctx, const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out,
                                      int64_t ldo, int B, int T, int H, float scale, const int32_t* seq_len, int dtype, int mem) {
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "op_attention_h128: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "op_attention_h128: bad mem");
   MIA_CHECK_ARG(ctx, q && k && v && out && B > 0 && T > 0 && H > 0 && (int64_t)B * T < (1ll << 31), "op_attention_h128: bad argument");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   Attn128Args a;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.B = B; a.T = T; a.H = H; a.scale = scale; a.dtype = dtype;
   const int64_t rows = (int64_t)B * T, D = (int64_t)H * 128;
-  size_t ob = 0;
-  if (mem == MIA_MEM_DEVICE) {
-    a.q = q; a.k = k; a.v = v; a.out = out; a.seq_len = seq_len;
-  } else {
-    MIA_CHECK_ARG(ctx, ldq >= D && ldk >= D && ldv >= D && ldo >= D, "op_attention_h128: row strides must be >= H * 128");
-    const size_t qb = (size_t)((rows - 1) * ldq + D) * 2, kb = (size_t)((rows - 1) * ldk + D) * 2, vb = (size_t)((rows - 1) * ldv + D) * 2;
-    ob = (size_t)((rows - 1) * ldo + D) * 2;
-    const size_t o_k = align_up(qb, 256), o_v = o_k + align_up(kb, 256), o_o = o_v + align_up(vb, 256), o_s = o_o + align_up(ob, 256);
-    char* ws = (char*)mia_workspace(ctx, o_s + align_up((size_t)B * 4, 256));
-    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-    MIA_HIP(ctx, hipMemcpyAsync(ws, q, qb, hipMemcpyHostToDevice, ctx->stream));
-    MIA_HIP(ctx, hipMemcpyAsync(ws + o_k, k, kb, hipMemcpyHostToDevice, ctx->stream));
-    MIA_HIP(ctx, hipMemcpyAsync(ws + o_v, v, vb, hipMemcpyHostToDevice, ctx->stream));
-    MIA_HIP(ctx, hipMemcpyAsync(ws + o_o, out, ob, hipMemcpyHostToDevice, ctx->stream));      // rows beyond seq_len keep the caller's bytes
-    if (seq_len) MIA_HIP(ctx, hipMemcpyAsync(ws + o_s, seq_len, (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
-    a.q = ws; a.k = ws + o_k; a.v = ws + o_v; a.out = ws + o_o; a.seq_len = seq_len ? (const int32_t*)(ws + o_s) : nullptr;
-  }
+  HostIo io(ctx, mem);
+  MIA_CHECK_ARG(ctx, !io.host() || (ldq >= D && ldk >= D && ldv >= D && ldo >= D), "op_attention_h128: row strides must be >= H * 128");
+  const size_t qb = (size_t)((rows - 1) * ldq + D) * 2, kb = (size_t)((rows - 1) * ldk + D) * 2, vb = (size_t)((rows - 1) * ldv + D) * 2;
+  const size_t ob = (size_t)((rows - 1) * ldo + D) * 2, sb = (size_t)B * 4;
+  Carve cv;
+  const size_t o_q = cv.add(io.staged(qb)), o_k = cv.add(io.staged(kb)), o_v = cv.add(io.staged(vb)), o_o = cv.add(io.staged(ob)), o_s = cv.add(io.staged(sb));
+  char* ws;
+  if (!cv.workspace(ctx, ws)) return MIA_ERR_OUT_OF_MEMORY;
+  a.q = io.in(q, ws + o_q, qb); a.k = io.in(k, ws + o_k, kb); a.v = io.in(v, ws + o_v, vb);
+  a.out = io.inout(out, ws + o_o, ob);                                                        // rows beyond seq_len keep the caller's bytes
+  a.seq_len = io.in(seq_len, ws + o_s, sb);
   if (const char* e = mia_attn128_check(a)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
   if (mia_attn128_launch(a, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_attention_h128: launch failed");
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(out, a.out, ob, hipMemcpyDeviceToHost, ctx->stream));
-    MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MIA_OK;
+  return io.finish();
 }
 
 // The SANM memory (fsmn.hip): x[t][c] += v[t][c] + sum_k w[k][c] v[t + k - left][c] per sequence of a [B][T] stack.
 extern "C" int mia_op_fsmn_add(mia_ctx* ctx, float* x, int64_t ldx, const void* v, int64_t ldv, const float* w, int B, int T, int D, int K, int left,
                                const int32_t* seq_len, int dtype, int mem) {
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "op_fsmn_add: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "op_fsmn_add: bad mem");
   MIA_CHECK_ARG(ctx, x && v && w && B > 0 && T > 0 && D > 0 && K > 0 && (int64_t)B * T < (1ll << 31), "op_fsmn_add: bad argument");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   FsmnArgs a;
   a.ldx = ldx; a.ldv = ldv; a.B = B; a.T = T; a.D = D; a.K = K; a.left = left; a.dtype = dtype;
   const int64_t rows = (int64_t)B * T;
-  size_t xb = 0;
-  if (mem == MIA_MEM_DEVICE) {
-    a.x = x; a.v = v; a.w = w; a.seq_len = seq_len;
-  } else {
-    MIA_CHECK_ARG(ctx, ldx >= D && ldv >= D, "op_fsmn_add: row strides must be >= D");
-    xb = (size_t)((rows - 1) * ldx + D) * 4;
-    const size_t vb = (size_t)((rows - 1) * ldv + D) * 2, wb = (size_t)K * D * 4;
-    const size_t o_v = align_up(xb, 256), o_w = o_v + align_up(vb, 256), o_s = o_w + align_up(wb, 256);
-    char* ws = (char*)mia_workspace(ctx, o_s + align_up((size_t)B * 4, 256));
-    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-    MIA_HIP(ctx, hipMemcpyAsync(ws, x, xb, hipMemcpyHostToDevice, ctx->stream));
-    MIA_HIP(ctx, hipMemcpyAsync(ws + o_v, v, vb, hipMemcpyHostToDevice, ctx->stream));
-    MIA_HIP(ctx, hipMemcpyAsync(ws + o_w, w, wb, hipMemcpyHostToDevice, ctx->stream));
-    if (seq_len) MIA_HIP(ctx, hipMemcpyAsync(ws + o_s, seq_len, (size_t)B * 4, hipMemcpyHostToDevice, ctx->stream));
-    a.x = (float*)ws; a.v = ws + o_v; a.w = (const float*)(ws + o_w); a.seq_len = seq_len ? (const int32_t*)(ws + o_s) : nullptr;
-  }
+  HostIo io(ctx, mem);
+  MIA_CHECK_ARG(ctx, !io.host() || (ldx >= D && ldv >= D), "op_fsmn_add: row strides must be >= D");
+  const size_t xb = (size_t)((rows - 1) * ldx + D) * 4, vb = (size_t)((rows - 1) * ldv + D) * 2, wb = (size_t)K * D * 4, sb = (size_t)B * 4;
+  Carve cv;
+  const size_t o_x = cv.add(io.staged(xb)), o_v = cv.add(io.staged(vb)), o_w = cv.add(io.staged(wb)), o_s = cv.add(io.staged(sb));
+  char* ws;
+  if (!cv.workspace(ctx, ws)) return MIA_ERR_OUT_OF_MEMORY;
+  a.x = io.inout(x, ws + o_x, xb);
+  a.v = io.in(v, ws + o_v, vb); a.w = io.in(w, ws + o_w, wb); a.seq_len = io.in(seq_len, ws + o_s, sb);
   if (const char* e = mia_fsmn_check(a)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
   if (mia_fsmn_launch(a, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_fsmn_add: launch failed");
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(x, a.x, xb, hipMemcpyDeviceToHost, ctx->stream));
-    MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MIA_OK;
+  return io.finish();
 }
 
 // The LM's single-token GQA attention over a cache it fills itself, without a model around it: K / V rows [Hkv][T][dh] (16 bit, taken
@@ -330,6 +281,67 @@ extern "C" int mia_op_fsmn_add(mia_ctx* ctx, float* x, int64_t ldx, const void* 
 // TransformerBlock.swift:182-201) -- with all rotation angles zero, which leaves a 16-bit value unchanged; then the non-fused attention
 // kernel of that cache mode runs q [Hq][dh] at position T - 1 over keys [0, T).  out fp32 [Hq][dh].  Host pointers.
 #include "lm.h"
+namespace {
+
+float widen16(uint16_t x, int dtype) {
+  if (dtype == MIA_F16) { _Float16 h; memcpy(&h, &x, 2); return (float)h; }
+  const uint32_t u = (uint32_t)x << 16; float f; memcpy(&f, &u, 4); return f;
+}
+
+// What mia_op_kvq_attention and mia_op_lm_prompt_attention share: the q|k|v rows a prompt pass would hand the cache writer, row t =
+// [q (last n rows only) | K[.][t] | V[.][t]], their row map, the workspace [part | map | freq | q | att | extra] with freq .. att (and the
+// first `zeroed` bytes of extra) cleared, and a bare handle holding what the launch sites read of one.  Declare it before the call's HostIo:
+// its vectors are uploaded through io.table and must outlive it.
+struct LmOpRows {
+  std::vector<float> part;
+  std::vector<int2> rowmap;
+  int Nq = 0, N = 0;
+  float* d_part = nullptr; int2* d_map = nullptr; uint16_t* d_q = nullptr; uint16_t* d_att = nullptr; char* extra = nullptr;
+  mia_lm sh;
+
+  void build(const void* q, const void* k, const void* v, int Hq, int Hkv, int T, int n, int dh, int dtype) {
+    const int Nk = Hkv * dh;
+    Nq = Hq * dh; N = Nq + 2 * Nk;
+    part.assign((size_t)T * N, 0.f);
+    rowmap.resize(T);
+    const uint16_t* q16 = (const uint16_t*)q; const uint16_t* k16 = (const uint16_t*)k; const uint16_t* v16 = (const uint16_t*)v;
+    for (int r = 0; r < n; ++r)
+      for (int i = 0; i < Nq; ++i) part[(size_t)(T - n + r) * N + i] = widen16(q16[(size_t)r * Nq + i], dtype);
+    for (int t = 0; t < T; ++t) {
+      rowmap[t] = make_int2(0, t);
+      for (int h = 0; h < Hkv; ++h)
+        for (int d = 0; d < dh; ++d) {
+          part[(size_t)t * N + Nq + h * dh + d] = widen16(k16[((size_t)h * T + t) * dh + d], dtype);
+          part[(size_t)t * N + Nq + Nk + h * dh + d] = widen16(v16[((size_t)h * T + t) * dh + d], dtype);
+        }
+    }
+  }
+  int stage(mia_ctx* ctx, HostIo& io, int Hq, int Hkv, int T, int n, int dh, int dtype, size_t extra_bytes, size_t zeroed) {
+    Carve cv;
+    const size_t o_part = cv.add(part.size() * 4), o_map = cv.add((size_t)T * sizeof(int2)), o_freq = cv.add((size_t)dh / 2 * 4),
+                 o_q = cv.add((size_t)T * Nq * 2), o_att = cv.add((size_t)n * Nq * 2), o_extra = cv.add(extra_bytes);
+    char* ws = (char*)mia_workspace(ctx, cv.bytes);
+    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
+    d_q = (uint16_t*)(ws + o_q); d_att = (uint16_t*)(ws + o_att); extra = ws + o_extra;
+    d_part = const_cast<float*>(io.table(part.data(), ws + o_part, part.size() * 4));
+    d_map = const_cast<int2*>(io.table(rowmap.data(), ws + o_map, (size_t)T * sizeof(int2)));
+    MIA_HIP(ctx, hipMemsetAsync(ws + o_freq, 0, o_extra - o_freq + zeroed, ctx->stream));
+    sh.ctx = ctx; sh.dtype = dtype; sh.B_cap = 1; sh.inv_freq = (float*)(ws + o_freq);
+    sh.cfg.n_layers = 1; sh.cfg.n_heads = Hq; sh.cfg.n_kv_heads = Hkv; sh.cfg.head_dim = dh; sh.cfg.max_ctx = T;
+    return MIA_OK;
+  }
+  // the attention rows [n][Nq] back as fp32
+  int read(HostIo& io, float* out, int n, int dtype) {
+    std::vector<uint16_t> att((size_t)n * Nq);
+    io.fetch(att.data(), d_att, att.size() * 2);
+    if (int rc = io.finish()) return rc;
+    for (size_t i = 0; i < att.size(); ++i) out[i] = widen16(att[i], dtype);
+    return MIA_OK;
+  }
+};
+
+}  // namespace
+
 extern "C" int mia_op_kvq_attention(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int dh, int bits, int dtype) {
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
   MIA_CHECK_ARG(ctx, q && k && v && out, "op_kvq_attention: null pointer");
@@ -338,58 +350,21 @@ extern "C" int mia_op_kvq_attention(mia_ctx* ctx, const void* q, const void* k, 
   int code = MIA_OK;
   if (const char* e = lm_kvq_check(bits, 64, dh, &code)) return mia_fail(ctx, code, "op_kvq_attention: %s (bits %d, head_dim %d)", e, bits, dh);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
-  const int Nq = Hq * dh, Nk = Hkv * dh, N = Nq + 2 * Nk;
-  auto widen = [&](uint16_t x) -> float {
-    if (dtype == MIA_F16) { _Float16 h; memcpy(&h, &x, 2); return (float)h; }
-    const uint32_t u = (uint32_t)x << 16; float f; memcpy(&f, &u, 4); return f;
-  };
-  // the q|k|v rows a prompt pass would hand the cache writer: row t = [q (last row only) | K[.][t] | V[.][t]]
-  std::vector<float> part((size_t)T * N, 0.f);
-  std::vector<int2> rowmap(T);
-  const uint16_t* q16 = (const uint16_t*)q; const uint16_t* k16 = (const uint16_t*)k; const uint16_t* v16 = (const uint16_t*)v;
-  for (int i = 0; i < Nq; ++i) part[(size_t)(T - 1) * N + i] = widen(q16[i]);
-  for (int t = 0; t < T; ++t) {
-    rowmap[t] = make_int2(0, t);
-    for (int h = 0; h < Hkv; ++h)
-      for (int d = 0; d < dh; ++d) {
-        part[(size_t)t * N + Nq + h * dh + d] = widen(k16[((size_t)h * T + t) * dh + d]);
-        part[(size_t)t * N + Nq + Nk + h * dh + d] = widen(v16[((size_t)h * T + t) * dh + d]);
-      }
-  }
+  LmOpRows f;
+  f.build(q, k, v, Hq, Hkv, T, 1, dh, dtype);
+  HostIo io = HostIo::device(ctx);
   const size_t rows = (size_t)Hkv * T;
-  const size_t b_part = align_up(part.size() * 4, 256), b_map = align_up((size_t)T * sizeof(int2), 256), b_freq = align_up((size_t)dh / 2 * 4, 256),
-               b_q = align_up((size_t)T * Nq * 2, 256), b_att = align_up((size_t)Nq * 2, 256), b_st = align_up(sizeof(LmState), 256),
-               b_codes = align_up(bits ? rows * dh * bits / 8 : rows * dh * 2, 256), b_pairs = align_up(rows * (dh / 64) * 4, 256);
-  char* ws = (char*)mia_workspace(ctx, b_part + b_map + b_freq + b_q + b_att + b_st + 2 * b_codes + 2 * b_pairs);
-  if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-  hipStream_t s = ctx->stream;
-  char* p = ws;
-  float* d_part = (float*)p; p += b_part;
-  int2* d_map = (int2*)p; p += b_map;
-  float* d_freq = (float*)p; p += b_freq;
-  uint16_t* d_q = (uint16_t*)p; p += b_q;
-  uint16_t* d_att = (uint16_t*)p; p += b_att;
-  LmState* d_st = (LmState*)p; p += b_st;
-  char* d_kc = p; p += b_codes;
-  char* d_vc = p; p += b_codes;
-  char* d_kp = p; p += b_pairs;
-  char* d_vp = p;
-  MIA_HIP(ctx, hipMemcpyAsync(d_part, part.data(), part.size() * 4, hipMemcpyHostToDevice, s));
-  MIA_HIP(ctx, hipMemcpyAsync(d_map, rowmap.data(), (size_t)T * sizeof(int2), hipMemcpyHostToDevice, s));
-  MIA_HIP(ctx, hipMemsetAsync(d_freq, 0, b_freq + b_q + b_att + b_st, s));
-  mia_lm sh;                      // a bare handle: what the two launch sites read of one
-  sh.ctx = ctx; sh.dtype = dtype; sh.kv_bits = bits; sh.B_cap = 1; sh.state = d_st; sh.inv_freq = d_freq;
-  sh.cfg.n_layers = 1; sh.cfg.n_heads = Hq; sh.cfg.n_kv_heads = Hkv; sh.cfg.head_dim = dh; sh.cfg.max_ctx = T;
+  const size_t b_st = align_up(sizeof(LmState), 256), b_codes = align_up(bits ? rows * dh * bits / 8 : rows * dh * 2, 256), b_pairs = align_up(rows * (dh / 64) * 4, 256);
+  if (int rc = f.stage(ctx, io, Hq, Hkv, T, 1, dh, dtype, b_st + 2 * b_codes + 2 * b_pairs, b_st)) return rc;
+  char* d_kc = f.extra + b_st; char* d_vc = d_kc + b_codes; char* d_kp = d_vc + b_codes; char* d_vp = d_kp + b_pairs;
+  mia_lm& sh = f.sh;
+  sh.kv_bits = bits; sh.state = (LmState*)f.extra;
   if (bits) { sh.kq_codes = (uint32_t*)d_kc; sh.vq_codes = (uint32_t*)d_vc; sh.kq_pairs = (uint32_t*)d_kp; sh.vq_pairs = (uint32_t*)d_vp; }
   else { sh.k_cache = d_kc; sh.v_cache = d_vc; }
-  lm_launch_rope_cache(&sh, 0, d_part, nullptr, d_q, d_map, T);
-  lm_launch_attention(&sh, false, 1, d_q + (size_t)(T - 1) * Nq, 0, d_att, d_map + (T - 1), nullptr, 0, nullptr);
+  lm_launch_rope_cache(&sh, 0, f.d_part, nullptr, f.d_q, f.d_map, T);
+  lm_launch_attention(&sh, false, 1, f.d_q + (size_t)(T - 1) * f.Nq, 0, f.d_att, f.d_map + (T - 1), nullptr, 0, nullptr);
   if (hipGetLastError() != hipSuccess) return mia_fail(ctx, MIA_ERR_DEVICE, "op_kvq_attention: launch failed");
-  std::vector<uint16_t> att(Nq);
-  MIA_HIP(ctx, hipMemcpyAsync(att.data(), d_att, (size_t)Nq * 2, hipMemcpyDeviceToHost, s));
-  MIA_HIP(ctx, hipStreamSynchronize(s));
-  for (int i = 0; i < Nq; ++i) out[i] = widen(att[i]);
-  return MIA_OK;
+  return f.read(io, out, 1, dtype);
 }
 
 // lm_prefill_attn.hip without a model around it: K / V rows [Hkv][T][dh] (16 bit, taken as already rotated) go through the prompt pass's
@@ -402,58 +377,21 @@ extern "C" int mia_op_lm_prompt_attention(mia_ctx* ctx, const void* q, const voi
   MIA_CHECK_ARG(ctx, Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq <= 1024 && n >= 1 && n <= T && T <= 8192, "op_lm_prompt_attention: bad shape (Hq %% Hkv == 0, 1 <= n <= T <= 8192)");
   if (dh != 64 && dh != 128) return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "op_lm_prompt_attention: head_dim %d (64 or 128)", dh);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
-  const int Nq = Hq * dh, Nk = Hkv * dh, N = Nq + 2 * Nk;
-  auto widen = [&](uint16_t x) -> float {
-    if (dtype == MIA_F16) { _Float16 h; memcpy(&h, &x, 2); return (float)h; }
-    const uint32_t u = (uint32_t)x << 16; float f; memcpy(&f, &u, 4); return f;
-  };
-  // the q|k|v rows a prompt pass would hand the cache writer: row t = [q (last n rows only) | K[.][t] | V[.][t]]
-  std::vector<float> part((size_t)T * N, 0.f);
-  std::vector<int2> rowmap(T);
-  const uint16_t* q16 = (const uint16_t*)q; const uint16_t* k16 = (const uint16_t*)k; const uint16_t* v16 = (const uint16_t*)v;
-  for (int r = 0; r < n; ++r)
-    for (int i = 0; i < Nq; ++i) part[(size_t)(T - n + r) * N + i] = widen(q16[(size_t)r * Nq + i]);
-  for (int t = 0; t < T; ++t) {
-    rowmap[t] = make_int2(0, t);
-    for (int h = 0; h < Hkv; ++h)
-      for (int d = 0; d < dh; ++d) {
-        part[(size_t)t * N + Nq + h * dh + d] = widen(k16[((size_t)h * T + t) * dh + d]);
-        part[(size_t)t * N + Nq + Nk + h * dh + d] = widen(v16[((size_t)h * T + t) * dh + d]);
-      }
-  }
+  LmOpRows f;
+  f.build(q, k, v, Hq, Hkv, T, n, dh, dtype);
   std::vector<int4> tiles;
-  lm_prefill_attn_tiles(rowmap.data() + (T - n), n, lm_prefill_attn_qtile(Hq, Hkv), tiles);     // rows 0 .. n - 1 of q / att below
-  const size_t b_part = align_up(part.size() * 4, 256), b_map = align_up((size_t)T * sizeof(int2), 256), b_freq = align_up((size_t)dh / 2 * 4, 256),
-               b_q = align_up((size_t)T * Nq * 2, 256), b_att = align_up((size_t)n * Nq * 2, 256), b_tiles = align_up(tiles.size() * sizeof(int4), 256),
-               b_cache = align_up((size_t)Hkv * T * dh * 2, 256);
-  char* ws = (char*)mia_workspace(ctx, b_part + b_map + b_freq + b_q + b_att + b_tiles + 2 * b_cache);
-  if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-  hipStream_t s = ctx->stream;
-  char* p = ws;
-  float* d_part = (float*)p; p += b_part;
-  int2* d_map = (int2*)p; p += b_map;
-  float* d_freq = (float*)p; p += b_freq;
-  uint16_t* d_q = (uint16_t*)p; p += b_q;
-  uint16_t* d_att = (uint16_t*)p; p += b_att;
-  int4* d_tiles = (int4*)p; p += b_tiles;
-  char* d_kc = p; p += b_cache;
-  char* d_vc = p;
-  MIA_HIP(ctx, hipMemcpyAsync(d_part, part.data(), part.size() * 4, hipMemcpyHostToDevice, s));
-  MIA_HIP(ctx, hipMemcpyAsync(d_map, rowmap.data(), (size_t)T * sizeof(int2), hipMemcpyHostToDevice, s));
-  MIA_HIP(ctx, hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice, s));
-  MIA_HIP(ctx, hipMemsetAsync(d_freq, 0, b_freq + b_q + b_att, s));
-  mia_lm sh;                      // a bare handle: what the cache writer reads of one
-  sh.ctx = ctx; sh.dtype = dtype; sh.B_cap = 1; sh.inv_freq = d_freq; sh.k_cache = d_kc; sh.v_cache = d_vc;
-  sh.cfg.n_layers = 1; sh.cfg.n_heads = Hq; sh.cfg.n_kv_heads = Hkv; sh.cfg.head_dim = dh; sh.cfg.max_ctx = T;
-  lm_launch_rope_cache(&sh, 0, d_part, nullptr, d_q, d_map, T);
+  lm_prefill_attn_tiles(f.rowmap.data() + (T - n), n, lm_prefill_attn_qtile(Hq, Hkv), tiles);     // rows 0 .. n - 1 of q / att below
+  HostIo io = HostIo::device(ctx);
+  const size_t b_tiles = align_up(tiles.size() * sizeof(int4), 256), b_cache = align_up((size_t)Hkv * T * dh * 2, 256);
+  if (int rc = f.stage(ctx, io, Hq, Hkv, T, n, dh, dtype, b_tiles + 2 * b_cache, 0)) return rc;
+  const int4* d_tiles = io.table(tiles.data(), f.extra, tiles.size() * sizeof(int4));
+  mia_lm& sh = f.sh;
+  sh.k_cache = f.extra + b_tiles; sh.v_cache = f.extra + b_tiles + b_cache;
+  lm_launch_rope_cache(&sh, 0, f.d_part, nullptr, f.d_q, f.d_map, T);
   LmPromptAttn a;
-  a.q = d_q + (size_t)(T - n) * Nq; a.kc = (const uint16_t*)d_kc; a.vc = (const uint16_t*)d_vc; a.out = d_att; a.tiles = d_tiles; a.n_tiles = (int)tiles.size();
+  a.q = f.d_q + (size_t)(T - n) * f.Nq; a.kc = (const uint16_t*)sh.k_cache; a.vc = (const uint16_t*)sh.v_cache; a.out = f.d_att; a.tiles = d_tiles; a.n_tiles = (int)tiles.size();
   a.Hq = Hq; a.Hkv = Hkv; a.dh = dh; a.max_ctx = T; a.seq_stride = (int64_t)Hkv * T * dh; a.dtype = dtype;
   if (const char* e = lm_prefill_attn_check(a)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
-  if (lm_prefill_attn_launch(a, s)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_lm_prompt_attention: launch failed");
-  std::vector<uint16_t> att((size_t)n * Nq);
-  MIA_HIP(ctx, hipMemcpyAsync(att.data(), d_att, att.size() * 2, hipMemcpyDeviceToHost, s));
-  MIA_HIP(ctx, hipStreamSynchronize(s));
-  for (size_t i = 0; i < att.size(); ++i) out[i] = widen(att[i]);
-  return MIA_OK;
+  if (lm_prefill_attn_launch(a, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_lm_prompt_attention: launch failed");
+  return f.read(io, out, n, dtype);
 }

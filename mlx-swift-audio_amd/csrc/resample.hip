@@ -88,7 +88,7 @@ extern "C" int mia_resample_sinc_table(int from_rate, int to_rate, float* table,
 extern "C" int mia_resample_sinc(mia_ctx* ctx, const float* x, int64_t n_samples, int from_rate, int to_rate, float* out, int64_t out_capacity,
                                  int64_t* n_out, int mem) {
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
-  MIA_CHECK_ARG(ctx, x && out && n_samples > 0 && from_rate > 0 && to_rate > 0 && (mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE), "resample_sinc: bad argument");
+  MIA_CHECK_ARG(ctx, x && out && n_samples > 0 && from_rate > 0 && to_rate > 0 && HostIo::valid(mem), "resample_sinc: bad argument");
   const int64_t N = mia_resample_sinc_len(n_samples, from_rate, to_rate);
   MIA_CHECK_ARG(ctx, N > 0 && out_capacity >= N, "resample_sinc: output buffer too small (%lld < %lld)", (long long)out_capacity, (long long)N);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
@@ -111,23 +111,18 @@ extern "C" int mia_resample_sinc(mia_ctx* ctx, const float* x, int64_t n_samples
     ctx->resampler->tables.push_back(SincTable{from_rate, to_rate, to_rate / g, from_rate / g, taps, (taps - 1) / 2, dev});
     tb = &ctx->resampler->tables.back();
   }
-  const float* d_x = x; float* d_o = out;
-  if (mem == MIA_MEM_HOST) {
-    auto al = [](size_t n) { return (n + 63) / 64 * 64; };
-    float* ws = (float*)mia_workspace(ctx, (al(n_samples) + al(N)) * 4);
-    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-    MIA_HIP(ctx, hipMemcpyAsync(ws, x, (size_t)n_samples * 4, hipMemcpyHostToDevice, s));
-    d_x = ws; d_o = ws + al(n_samples);
-  }
+  HostIo io(ctx, mem);
+  Carve cv;
+  const size_t o_x = cv.add(io.staged((size_t)n_samples * 4)), o_o = cv.add(io.staged((size_t)N * 4));
+  char* ws;
+  if (!cv.workspace(ctx, ws)) return MIA_ERR_OUT_OF_MEMORY;
+  const float* d_x = io.in(x, ws + o_x, (size_t)n_samples * 4);
+  float* d_o = io.out(out, ws + o_o, (size_t)N * 4);
   if (tb->L == 1 && tb->M == 1) MIA_HIP(ctx, hipMemcpyAsync(d_o, d_x, (size_t)N * 4, hipMemcpyDeviceToDevice, s));     // same rate: the reference returns its input
   else hipLaunchKernelGGL(resample_sinc_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, d_x, d_o, tb->dev, n_samples, N, tb->L, tb->M, tb->taps, tb->hw);
   MIA_HIP(ctx, hipGetLastError());
   if (n_out) *n_out = N;
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(out, d_o, (size_t)N * 4, hipMemcpyDeviceToHost, s));
-    MIA_HIP(ctx, hipStreamSynchronize(s));
-  }
-  return MIA_OK;
+  return io.finish();
 }
 
 void mia_resampler_free(mia_ctx* ctx) {

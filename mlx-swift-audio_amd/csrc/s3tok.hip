@@ -293,33 +293,27 @@ extern "C" int mia_s3tok_encode(mia_s3tok* m, const float* mel, const int32_t* m
   if (!m) return MIA_ERR_MODEL_NOT_LOADED;
   mia_ctx* ctx = m->ctx;
   MIA_CHECK_ARG(ctx, mel && mel_len && tokens && tok_len && B > 0 && T > 0, "s3tok_encode: null arguments");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "s3tok_encode: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "s3tok_encode: bad mem");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
+  HostIo io(ctx, mem);
   const int NM = m->cfg.n_mels;
-  const float* d_mel = mel;
-  if (mem == MIA_MEM_HOST) {
-    const size_t bytes = (size_t)B * NM * T * 4;
-    void* ws = mia_workspace(ctx, bytes);
-    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-    MIA_HIP(ctx, hipMemcpyAsync(ws, mel, bytes, hipMemcpyHostToDevice, ctx->stream));
-    d_mel = (const float*)ws;
-  }
+  const size_t mel_bytes = (size_t)B * NM * T * 4;
+  char* ws;
+  if (!Carve{io.staged(mel_bytes)}.workspace(ctx, ws)) return MIA_ERR_OUT_OF_MEMORY;
+  const float* d_mel = io.in(mel, ws, mel_bytes);
   if (int rc = mia_grow(ctx, m->d_ids, m->ids_cap, (size_t)tokens_stride, "s3tok: hipMalloc failed")) return rc;
   for (int b = 0; b < B; ++b) {
     const int L = mel_len[b];
     MIA_CHECK_ARG(ctx, L > 0 && L <= T, "s3tok_encode: mel_len[%d] = %d out of range", b, L);
     MIA_CHECK_ARG(ctx, L <= 3000, "s3tok_encode: clip %d has %d frames; windows above 30 s are split by the caller (S3Tokenizer.swift:497-650)", b, L);
     int n = 0;
-    int32_t* dst = mem == MIA_MEM_DEVICE ? tokens + (size_t)b * tokens_stride : m->d_ids;
+    int32_t* dst = io.out(tokens + (size_t)b * tokens_stride, m->d_ids, (size_t)tokens_stride * 4);
     MIA_CHECK_ARG(ctx, ((L - 1) / 2 + 1 - 1) / 2 + 1 <= tokens_stride, "s3tok_encode: tokens_stride too small");
     MIA_HIP(ctx, hipMemsetAsync(dst, 0, (size_t)tokens_stride * 4, ctx->stream));
     int rc = s3_encode_clip(m, d_mel + (size_t)b * NM * T, T, L, dst, &n);
     if (rc != MIA_OK) return rc;
     tok_len[b] = n;
-    if (mem == MIA_MEM_HOST) {
-      MIA_HIP(ctx, hipMemcpyAsync(tokens + (size_t)b * tokens_stride, m->d_ids, (size_t)tokens_stride * 4, hipMemcpyDeviceToHost, ctx->stream));
-      MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    if ((rc = io.finish()) != MIA_OK) return rc;           // host: d_ids holds one clip, so every clip is downloaded before the next
   }
   return MIA_OK;
 }

@@ -214,8 +214,8 @@ int sv_encode_device(mia_sensevoice* sv, const float* feats_dev, int64_t ld_feat
   if ((rc = mia_grow(ctx, sv->att, sv->att_cap, std::max(M * D, Ma * L), "sensevoice: out of memory")) != MIA_OK) return rc;
   if ((rc = mia_grow(ctx, sv->g, sv->g_cap, std::max(M * F, Ma * (size_t)FA), "sensevoice: out of memory")) != MIA_OK) return rc;
   if ((rc = mia_grow(ctx, sv->lens, sv->lens_cap, 2 * (size_t)B, "sensevoice: out of memory")) != MIA_OK) return rc;
-  MIA_HIP(ctx, hipMemcpyAsync(sv->lens, lens.data(), lens.size() * 4, hipMemcpyHostToDevice, s));
-  const int32_t* d_T = sv->lens;
+  HostIo io = HostIo::device(ctx);                     // lens[] lives on this call's stack: no return before its upload has been read
+  const int32_t* d_T = io.table(lens.data(), sv->lens, lens.size() * 4);
   const int32_t* d_N = sv->lens + B;
 
   // ---- encoder
@@ -271,8 +271,7 @@ int sv_encode_device(mia_sensevoice* sv, const float* feats_dev, int64_t ld_feat
   }
   hipLaunchKernelGGL(sv_unpad, dim3(grid_for((int64_t)N * L), (unsigned)B), dim3(256), 0, s, sv->x, d_N, emb_dev, N, L);
   MIA_HIP(ctx, hipGetLastError());
-  MIA_HIP(ctx, hipStreamSynchronize(s));               // lens[] lives on this call's stack
-  return MIA_OK;
+  return io.finish();
 }
 
 }  // namespace
@@ -330,9 +329,10 @@ extern "C" int mia_sensevoice_encode(mia_sensevoice* sv, const float* feats, con
   if (!sv) return MIA_ERR_MODEL_NOT_LOADED;
   mia_ctx* ctx = sv->ctx;
   MIA_CHECK_ARG(ctx, feats && t_lfr && emb_out && n_out && B > 0, "sensevoice_encode: null pointer or B <= 0");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "sensevoice_encode: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "sensevoice_encode: bad mem");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
-  if (mem == MIA_MEM_DEVICE) return sv_encode_device(sv, feats, sv->cfg.input_dim, t_lfr, B, enc_out, emb_out, n_out);
+  HostIo io(ctx, mem);
+  if (!io.host()) return sv_encode_device(sv, feats, sv->cfg.input_dim, t_lfr, B, enc_out, emb_out, n_out);
   const mia_sensevoice_config& c = sv->cfg;
   size_t rows = 0, rows_out = 0;
   for (int b = 0; b < B; ++b) {
@@ -342,20 +342,18 @@ extern "C" int mia_sensevoice_encode(mia_sensevoice* sv, const float* feats, con
   const size_t n_f = rows * c.input_dim, n_e = rows * c.encoder_dim, n_o = rows_out * c.llm_dim;
   int rc = mia_grow(ctx, sv->stage, sv->stage_cap, n_f + n_e + n_o, "sensevoice: out of memory");
   if (rc != MIA_OK) return rc;
-  float* d_f = sv->stage; float* d_e = d_f + n_f; float* d_o = d_e + n_e;
-  MIA_HIP(ctx, hipMemcpyAsync(d_f, feats, n_f * 4, hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = sv_encode_device(sv, d_f, c.input_dim, t_lfr, B, enc_out ? d_e : nullptr, d_o, n_out)) != MIA_OK) return rc;
-  if (enc_out) MIA_HIP(ctx, hipMemcpyAsync(enc_out, d_e, n_e * 4, hipMemcpyDeviceToHost, ctx->stream));
-  MIA_HIP(ctx, hipMemcpyAsync(emb_out, d_o, n_o * 4, hipMemcpyDeviceToHost, ctx->stream));
-  MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MIA_OK;
+  const float* d_f = io.in(feats, sv->stage, n_f * 4);
+  float* d_e = io.out(enc_out, sv->stage + n_f, n_e * 4);
+  float* d_o = io.out(emb_out, sv->stage + n_f + n_e, n_o * 4);
+  if ((rc = sv_encode_device(sv, d_f, c.input_dim, t_lfr, B, d_e, d_o, n_out)) != MIA_OK) return rc;
+  return io.finish();
 }
 
 extern "C" int mia_sensevoice_encode_audio(mia_sensevoice* sv, const float* pcm, const int64_t* offs, int B, float* emb_out, int32_t* n_out, int mem) {
   if (!sv) return MIA_ERR_MODEL_NOT_LOADED;
   mia_ctx* ctx = sv->ctx;
   MIA_CHECK_ARG(ctx, pcm && offs && emb_out && n_out && B > 0, "sensevoice_encode_audio: null pointer or B <= 0");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "sensevoice_encode_audio: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "sensevoice_encode_audio: bad mem");
   MIA_CHECK_ARG(ctx, sv->cfg.input_dim == funasr::NMEL * funasr::LFR_M, "sensevoice_encode_audio: the front end emits %d columns, input_dim is %d",
                 funasr::NMEL * funasr::LFR_M, sv->cfg.input_dim);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
@@ -367,19 +365,12 @@ extern "C" int mia_sensevoice_encode_audio(mia_sensevoice* sv, const float* pcm,
   for (int b = 0; b < B; ++b) rows_out += (size_t)((plan.t_lfr[b] - 1) / c.adaptor_k + 1);
   if ((rc = mia_grow(ctx, sv->feats, sv->feats_cap, (size_t)plan.rows * c.input_dim, "sensevoice: out of memory")) != MIA_OK) return rc;
   if ((rc = mia_grow(ctx, sv->fscratch, sv->fscratch_cap, funasr_scratch_bytes(plan), "sensevoice: out of memory")) != MIA_OK) return rc;
-  const float* d_pcm = pcm;
-  float* d_o = emb_out;
+  HostIo io(ctx, mem);
   const size_t n_p = (size_t)offs[B], n_o = rows_out * c.llm_dim;
-  if (mem == MIA_MEM_HOST) {
-    if ((rc = mia_grow(ctx, sv->stage, sv->stage_cap, n_p + n_o, "sensevoice: out of memory")) != MIA_OK) return rc;
-    MIA_HIP(ctx, hipMemcpyAsync(sv->stage, pcm, n_p * 4, hipMemcpyHostToDevice, ctx->stream));
-    d_pcm = sv->stage; d_o = sv->stage + n_p;
-  }
+  if ((rc = mia_grow(ctx, sv->stage, sv->stage_cap, io.staged(n_p + n_o), "sensevoice: out of memory")) != MIA_OK) return rc;
+  const float* d_pcm = io.in(pcm, sv->stage, n_p * 4);
+  float* d_o = io.out(emb_out, io.host() ? sv->stage + n_p : nullptr, n_o * 4);
   if ((rc = funasr_features_device(ctx, d_pcm, offs, plan, sv->feats, c.input_dim, sv->fscratch)) != MIA_OK) return rc;
   if ((rc = sv_encode_device(sv, sv->feats, c.input_dim, plan.t_lfr.data(), B, nullptr, d_o, n_out)) != MIA_OK) return rc;
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(emb_out, d_o, n_o * 4, hipMemcpyDeviceToHost, ctx->stream));
-    MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return MIA_OK;
+  return io.finish();
 }

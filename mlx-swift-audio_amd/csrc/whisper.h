@@ -192,7 +192,7 @@ int whisper_reserve(mia_whisper* w, int B);
 int whisper_encode_from_padded_mel(mia_whisper* w, int B);  // mel already in w->mel_pad
 // whisper_decode.hip
 int whisper_decode(mia_whisper* w, const mia_decode_opts* o, int32_t* tokens, int32_t* n_tokens, float* avg_logprob,
-                   float* no_speech_prob, int mem);
+                   float* no_speech_prob, HostIo& io);
 // logmel.hip
 size_t mia_logmel_scratch_bytes(int B, int64_t n_out, int n_mels);
 size_t mia_logmel_direct_scratch_bytes(int B, int64_t n_out);   // enough for a time-major, unit-column-stride output (no fp32 intermediate)

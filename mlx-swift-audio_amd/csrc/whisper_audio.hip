@@ -76,7 +76,7 @@ extern "C" mia_whisper_audio* mia_whisper_audio_create(mia_whisper* w, const flo
   auto fail = [&](int code, const char* msg) -> mia_whisper_audio* { mia_fail(ctx, code, "whisper_audio_create: %s", msg); return nullptr; };
   if (!pcm || !offs || n_clips <= 0) return fail(MIA_ERR_INVALID_ARGUMENT, "null input or n_clips <= 0");
   if (pad_right < 0) return fail(MIA_ERR_INVALID_ARGUMENT, "pad_right must be >= 0");
-  if (mem != MIA_MEM_HOST && mem != MIA_MEM_DEVICE) return fail(MIA_ERR_INVALID_ARGUMENT, "bad mem");
+  if (!HostIo::valid(mem)) return fail(MIA_ERR_INVALID_ARGUMENT, "bad mem");
   const int n_mels = w->dims.n_mels;
   if (n_mels % 8 != 0) return fail(MIA_ERR_UNSUPPORTED, "n_mels must be a multiple of 8 (16-byte rows)");
   int64_t F = 0;
@@ -89,7 +89,11 @@ extern "C" mia_whisper_audio* mia_whisper_audio_create(mia_whisper* w, const flo
   if (hipSetDevice(ctx->device) != hipSuccess) return fail(MIA_ERR_DEVICE, "hipSetDevice failed");
   const size_t sc = mia_logmel_direct_scratch_bytes(n_clips, F);
   const size_t pcm_bytes = (size_t)offs[n_clips] * sizeof(float);
-  char* ws = (char*)mia_workspace(ctx, sc + (mem == MIA_MEM_HOST ? align_up(pcm_bytes, 256) : 0));
+  HostIo io(ctx, mem);
+  Carve cv;
+  cv.add(sc);
+  const size_t o_pcm = cv.add(io.staged(pcm_bytes));
+  char* ws = (char*)mia_workspace(ctx, cv.bytes);
   if (!ws) return nullptr;
   mia_whisper_audio* a = new mia_whisper_audio();
   a->ctx = ctx; a->n_mels = n_mels; a->n_clips = n_clips; a->F = F;
@@ -97,16 +101,10 @@ extern "C" mia_whisper_audio* mia_whisper_audio_create(mia_whisper* w, const flo
     delete a;
     return fail(MIA_ERR_OUT_OF_MEMORY, "hipMalloc failed for the resident mel");
   }
-  const float* d_pcm = pcm;
-  if (mem == MIA_MEM_HOST) {
-    if (hipMemcpyAsync(ws + sc, pcm, pcm_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-      (void)hipFree(a->mel); delete a;
-      return fail(MIA_ERR_DEVICE, "upload of the audio failed");
-    }
-    d_pcm = (const float*)(ws + sc);
-  }
+  const float* d_pcm = io.in(pcm, ws + o_pcm, pcm_bytes);
   // fp32, dense time-major: the single-pass form of the front end; it returns with the stream drained, so any stream may read the mel
-  const int rc = mia_logmel_device(ctx, d_pcm, offs, n_clips, n_mels, 0, pad_right, F, a->mel, MIA_F32, false, F * n_mels, n_mels, 1, 0, ws);
+  int rc = mia_logmel_device(ctx, d_pcm, offs, n_clips, n_mels, 0, pad_right, F, a->mel, MIA_F32, false, F * n_mels, n_mels, 1, 0, ws);
+  if (rc == MIA_OK) rc = io.finish();
   if (rc != MIA_OK) { (void)hipFree(a->mel); delete a; return nullptr; }
   return a;
 }

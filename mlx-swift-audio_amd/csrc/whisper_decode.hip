@@ -142,7 +142,7 @@ int enqueue_step(mia_whisper* w, const DecodeParams& p, const AlignHook* hook = 
 }  // namespace
 
 int whisper_decode(mia_whisper* w, const mia_decode_opts* o, int32_t* tokens, int32_t* n_tokens, float* avg_logprob,
-                   float* no_speech_prob, int mem) {
+                   float* no_speech_prob, HostIo& io) {
   mia_ctx* ctx = w->ctx;
   const mia_whisper_dims& d = w->dims;
   MIA_CHECK_ARG(ctx, w->cur_B > 0, "decode: no audio features (call mia_whisper_encode first)");
@@ -154,7 +154,7 @@ int whisper_decode(mia_whisper* w, const mia_decode_opts* o, int32_t* tokens, in
                          o->timestamp_begin > 0 && o->timestamp_begin <= d.n_vocab && o->no_timestamps >= 0 && o->no_timestamps < d.n_vocab,
                 "decode: special token ids out of range");
   MIA_CHECK_ARG(ctx, o->n_suppress >= 0 && o->n_blank >= 0 && (o->n_suppress == 0 || o->suppress_ids) && (o->n_blank == 0 || o->blank_ids), "decode: bad suppress tables");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "decode: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(io.mem()), "decode: bad mem");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const int B = w->cur_B, C = d.n_text_ctx, V = d.n_vocab;
@@ -201,18 +201,17 @@ int whisper_decode(mia_whisper* w, const mia_decode_opts* o, int32_t* tokens, in
     for (int i = 0; i < o->n_suppress; ++i) { setbit(0, o->suppress_ids[i]); setbit(1, o->suppress_ids[i]); }
     for (int i = 0; i < o->n_blank; ++i) setbit(1, o->blank_ids[i]);
     setbit(1, o->eot);
-    MIA_HIP(ctx, hipMemcpyAsync(w->tokens, init.data(), init.size() * 4, hipMemcpyHostToDevice, s));
-    MIA_HIP(ctx, hipMemcpyAsync(w->suppress_bits, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, s));
-    MIA_HIP(ctx, hipMemcpyAsync(w->clip.n_init, n_init.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
-    MIA_HIP(ctx, hipMemcpyAsync(w->clip.sot_idx, sot_idx.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
-    MIA_HIP(ctx, hipMemcpyAsync(w->clip.temp, temp.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
-    MIA_HIP(ctx, hipMemcpyAsync(w->finished, fin.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+    io.table(init.data(), w->tokens, init.size() * 4);
+    io.table(bits.data(), w->suppress_bits, bits.size() * 4);
+    io.table(n_init.data(), w->clip.n_init, (size_t)B * 4);
+    io.table(sot_idx.data(), w->clip.sot_idx, (size_t)B * 4);
+    io.table(temp.data(), w->clip.temp, (size_t)B * 4);
+    io.table(fin.data(), w->finished, (size_t)B * 4);
     if (any_sampling) {
-      // uniforms arrive as [B][max_tokens]; the kernel indexes [B][n_ctx]
-      for (int b = 0; b < B; ++b)
-        MIA_HIP(ctx, hipMemcpyAsync(w->uniforms + (size_t)b * C, o->uniforms + (size_t)b * o->max_tokens, (size_t)o->max_tokens * 4, hipMemcpyHostToDevice, s));
+      // uniforms (the opts' host array in either mode) arrive as [B][max_tokens]; the kernel indexes [B][n_ctx]
+      for (int b = 0; b < B; ++b) io.table(o->uniforms + (size_t)b * o->max_tokens, w->uniforms + (size_t)b * C, (size_t)o->max_tokens * 4);
     }
-    MIA_HIP(ctx, hipStreamSynchronize(s));   // host vectors go out of scope
+    if (int rc = io.finish()) return rc;     // host vectors go out of scope
   }
   p.greedy = any_sampling ? 0 : 1;
   MIA_HIP(ctx, hipMemsetAsync(w->n_gen, 0, (size_t)B * 4, s));
@@ -264,8 +263,8 @@ int whisper_decode(mia_whisper* w, const mia_decode_opts* o, int32_t* tokens, in
     steps_run += n;
     // early exit: poll the finished flags every 16 steps once generation has started
     if (step > min_init && (step & 15) == 0 && step < total_steps) {
-      MIA_HIP(ctx, hipMemcpyAsync(fin.data(), w->finished, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-      MIA_HIP(ctx, hipStreamSynchronize(s));
+      io.fetch(fin.data(), w->finished, (size_t)B * 4);
+      if (int rc = io.finish()) return rc;
       bool all = true;
       for (int b = 0; b < B; ++b) all = all && fin[b];
       if (all) break;
@@ -274,13 +273,12 @@ int whisper_decode(mia_whisper* w, const mia_decode_opts* o, int32_t* tokens, in
   if (prof_rec >= 0) { ctx->prof[prof_rec].work = steps_run; mia_prof_end(ctx, prof_rec); }
   dec_launch_finalize(w, w->out_n, p, s);
   MIA_HIP(ctx, hipGetLastError());
-  const hipMemcpyKind kind = mem == MIA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (tokens) MIA_HIP(ctx, hipMemcpyAsync(tokens, w->out_tokens, (size_t)B * p.max_tokens * 4, kind, s));
-  if (n_tokens) MIA_HIP(ctx, hipMemcpyAsync(n_tokens, w->out_n, (size_t)B * 4, kind, s));
-  if (avg_logprob) MIA_HIP(ctx, hipMemcpyAsync(avg_logprob, w->out_avg, (size_t)B * 4, kind, s));
-  if (no_speech_prob) MIA_HIP(ctx, hipMemcpyAsync(no_speech_prob, w->no_speech, (size_t)B * 4, kind, s));
-  if (mem == MIA_MEM_HOST) MIA_HIP(ctx, hipStreamSynchronize(s));
-  return MIA_OK;
+  const hipMemcpyKind kind = io.to_caller();
+  if (tokens) io.check(hipMemcpyAsync(tokens, w->out_tokens, (size_t)B * p.max_tokens * 4, kind, s));
+  if (n_tokens) io.check(hipMemcpyAsync(n_tokens, w->out_n, (size_t)B * 4, kind, s));
+  if (avg_logprob) io.check(hipMemcpyAsync(avg_logprob, w->out_avg, (size_t)B * 4, kind, s));
+  if (no_speech_prob) io.check(hipMemcpyAsync(no_speech_prob, w->no_speech, (size_t)B * 4, kind, s));
+  return io.finish();
 }
 
 // ---- word-timestamp alignment -------------------------------------------------------------------------------
@@ -513,7 +511,8 @@ extern "C" int mia_whisper_read_logit_trace(mia_whisper* w, int slot, int first_
 extern "C" int mia_whisper_decode_greedy(mia_whisper* w, const mia_decode_opts* opts, int32_t* tokens, int32_t* n_tokens,
                                          float* avg_logprob, float* no_speech_prob, int mem) {
   if (!w) return MIA_ERR_MODEL_NOT_LOADED;
-  return whisper_decode(w, opts, tokens, n_tokens, avg_logprob, no_speech_prob, mem);
+  HostIo io(w->ctx, mem);
+  return whisper_decode(w, opts, tokens, n_tokens, avg_logprob, no_speech_prob, io);
 }
 
 // softmax / argmax over the language-token slice of the logits after one step on [sot]  (WhisperModel.swift:223-260)
@@ -543,7 +542,8 @@ extern "C" int mia_whisper_detect_language(mia_whisper* w, int32_t sot, int32_t 
   o.initial_tokens = &init; o.n_initial = 1; o.sot_index = 0;
   o.eot = sot > 0 ? sot - 1 : 0; o.no_speech = 0; o.no_timestamps = 0; o.timestamp_begin = d.n_vocab; o.timestamps = 0;
   o.max_tokens = 2; o.max_initial_timestamp_index = 50;
-  int rc = whisper_decode(w, &o, nullptr, nullptr, nullptr, nullptr, MIA_MEM_DEVICE);
+  HostIo io = HostIo::device(ctx);
+  int rc = whisper_decode(w, &o, nullptr, nullptr, nullptr, nullptr, io);
   if (rc != MIA_OK) return rc;
   const int B = w->cur_B;
   hipLaunchKernelGGL(lang_kernel, dim3(B), dim3(64), 0, ctx->stream, w->logits, d.n_vocab, sot + 1, n_languages, w->out_n, w->out_avg);
@@ -582,7 +582,7 @@ extern "C" int mia_whisper_encode_windows(mia_whisper* w, const float* pcm, cons
   if (!w) return MIA_ERR_MODEL_NOT_LOADED;
   mia_ctx* ctx = w->ctx;
   MIA_CHECK_ARG(ctx, pcm && offs && B > 0, "encode_windows: null input or B <= 0");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "encode_windows: bad mem");
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "encode_windows: bad mem");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   {  // a larger batch re-allocates the batch buffers: that synchronises the CONTEXT's stream, so it happens before the scope
     const int rc0 = whisper_reserve(w, B);
@@ -595,17 +595,18 @@ extern "C" int mia_whisper_encode_windows(mia_whisper* w, const float* pcm, cons
   const int64_t rows = 2 * (int64_t)d.n_audio_ctx;
   const size_t sc = mia_logmel_scratch_bytes(B, rows, d.n_mels);
   const size_t pcm_bytes = (size_t)offs[B] * sizeof(float);
-  char* ws = (char*)mia_workspace(ctx, sc + (mem == MIA_MEM_HOST ? align_up(pcm_bytes, 256) : 0));
+  HostIo io(ctx, mem);
+  Carve cv;
+  cv.add(sc);
+  const size_t o_pcm = cv.add(io.staged(pcm_bytes));
+  char* ws = (char*)mia_workspace(ctx, cv.bytes);
   if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-  const float* d_pcm = pcm;
-  if (mem == MIA_MEM_HOST) {
-    MIA_HIP(ctx, hipMemcpyAsync(ws + sc, pcm, pcm_bytes, hipMemcpyHostToDevice, ctx->stream));
-    d_pcm = (const float*)(ws + sc);
-  }
+  const float* d_pcm = io.in(pcm, ws + o_pcm, pcm_bytes);
   // log-mel straight into the zero-row-padded layout conv1 reads (row offset 1), in the compute dtype
   rc = mia_logmel_device(ctx, d_pcm, offs, B, d.n_mels, 0, pad_right, rows, w->mel_pad, w->dtype, false,
                          (rows + 2) * d.n_mels, d.n_mels, 1, 1, ws);
   if (rc != MIA_OK) return rc;
+  if ((rc = io.finish()) != MIA_OK) return rc;       // the log-mel returned with the stream drained: the encoder below is only enqueued
   return whisper_encode_from_padded_mel(w, B);
 }
 
@@ -614,5 +615,6 @@ extern "C" int mia_whisper_transcribe_windows(mia_whisper* w, const float* pcm, 
                                               float* no_speech_prob, int mem) {
   const int rc = mia_whisper_encode_windows(w, pcm, offs, B, pad_right, mem);
   if (rc != MIA_OK) return rc;
-  return whisper_decode(w, opts, tokens, n_tokens, avg_logprob, no_speech_prob, mem);
+  HostIo io(w->ctx, mem);
+  return whisper_decode(w, opts, tokens, n_tokens, avg_logprob, no_speech_prob, io);
 }

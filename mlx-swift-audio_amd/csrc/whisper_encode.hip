@@ -222,21 +222,19 @@ extern "C" int mia_whisper_encode(mia_whisper* w, const void* mel, int B, int me
   if (!w) return MIA_ERR_MODEL_NOT_LOADED;
   mia_ctx* ctx = w->ctx;
   MIA_CHECK_ARG(ctx, mel && B > 0, "whisper_encode: mel must be non-null and B > 0");
-  MIA_CHECK_ARG(ctx, mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE, "whisper_encode: bad mem %d", mem);
+  MIA_CHECK_ARG(ctx, HostIo::valid(mem), "whisper_encode: bad mem %d", mem);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   int rc = whisper_reserve(w, B);
   if (rc != MIA_OK) return rc;
   const int64_t rows = 2 * (int64_t)w->dims.n_audio_ctx;
   const size_t bytes = (size_t)B * rows * w->dims.n_mels * 2;
-  const uint16_t* src = (const uint16_t*)mel;
-  if (mem == MIA_MEM_HOST) {
-    void* ws = mia_workspace(ctx, bytes);
-    if (!ws) return MIA_ERR_OUT_OF_MEMORY;
-    MIA_HIP(ctx, hipMemcpyAsync(ws, mel, bytes, hipMemcpyHostToDevice, ctx->stream));
-    src = (const uint16_t*)ws;
-  }
+  HostIo io(ctx, mem);
+  char* ws;
+  if (!Carve{io.staged(bytes)}.workspace(ctx, ws)) return MIA_ERR_OUT_OF_MEMORY;
+  const uint16_t* src = io.in((const uint16_t*)mel, ws, bytes);
   hipLaunchKernelGGL(pad_mel_kernel, dim3(1024), dim3(256), 0, ctx->stream, src, (uint16_t*)w->mel_pad, rows, w->dims.n_mels, B);
-  return whisper_encode_from_padded_mel(w, B);
+  rc = whisper_encode_from_padded_mel(w, B);
+  return rc != MIA_OK ? rc : io.finish();
 }
 
 template <typename T>
@@ -251,20 +249,18 @@ extern "C" int mia_whisper_get_audio_features(mia_whisper* w, void* out, int dty
   MIA_CHECK_ARG(ctx, dtype == MIA_F32 || dtype == w->dtype, "get_audio_features: dtype must be MIA_F32 or the compute dtype");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   const int64_t n = (int64_t)w->cur_B * w->dims.n_audio_ctx * w->dims.n_audio_state;
-  const void* src = w->feat;
-  size_t bytes = (size_t)n * 2;
+  HostIo io(ctx, mem);
   if (dtype == MIA_F32) {
-    bytes = (size_t)n * 4;
-    float* dst = mem == MIA_MEM_DEVICE ? (float*)out : (float*)mia_workspace(ctx, bytes);
-    if (!dst) return MIA_ERR_OUT_OF_MEMORY;
+    const size_t bytes = (size_t)n * 4;
+    char* ws;
+    if (!Carve{io.staged(bytes)}.workspace(ctx, ws)) return MIA_ERR_OUT_OF_MEMORY;
+    float* dst = io.out((float*)out, ws, bytes);
     if (w->dtype == MIA_F16) hipLaunchKernelGGL(cvt16_to_f32<F16>, dim3(1024), dim3(256), 0, ctx->stream, (const uint16_t*)w->feat, dst, n);
     else hipLaunchKernelGGL(cvt16_to_f32<BF16>, dim3(1024), dim3(256), 0, ctx->stream, (const uint16_t*)w->feat, dst, n);
-    if (mem == MIA_MEM_DEVICE) return MIA_OK;
-    src = dst;
+  } else {
+    io.check(hipMemcpyAsync(out, w->feat, (size_t)n * 2, io.to_caller(), ctx->stream));
   }
-  MIA_HIP(ctx, hipMemcpyAsync(out, src, bytes, mem == MIA_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-  if (mem == MIA_MEM_HOST) MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return MIA_OK;
+  return io.finish();
 }
 
 // Test hook (tests/test_whisper_gpu.py): force the encoder GEMM tile variant so that every kernel is exercised at reduced sizes.

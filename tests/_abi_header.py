@@ -67,6 +67,12 @@ def parse(text: str):
     return functions, structs
 
 
+def mem_entry_points(text: str) -> list:
+    """Names of the functions whose last parameter is `int mem`, in header order."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    return [name for name, args in re.findall(r"\b(mia_\w+)\s*\(([^()]*)\)\s*;", text) if re.search(r"[\s,]int\s+mem\s*$", args)]
+
+
 def _ckind(t, structs) -> str:
     if t in CTYPES:
         return CTYPES[t]
