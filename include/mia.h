@@ -565,6 +565,41 @@ int64_t mia_dac_code_len(mia_codec* c, int64_t n_samples);
 int mia_dac_encode(mia_codec* c, const float* pcm, int64_t n_samples, int n_quantizers, int32_t* codes, int64_t codes_capacity,
                    int64_t* n_steps, int mem);
 
+/* ---- OuteTTS speaker-profile audio (TTS/OuteTTS/OuteTTSAudioProcessor.swift) ------------------------------------
+ * The sample arithmetic of createSpeakerFromTranscription (:363-453); the word / code slicing around it is host integer arithmetic
+ * (outetts.py).  Caller arrays are HOST pointers in every entry point of this section.
+ *   mia_speaker_audio_create: preprocessAudioForSpeaker (:289-336) of a host clip, kept in HBM as fp32 [n]: gain to target_loudness_db RMS
+ *     (measured over max(n, 0.4 s) samples, the reference's zero padding) and the peak limiter at peak_limit_db, folded into one factor
+ *     that multiplies once (the reference multiplies twice in fp32: one rounding apart).  target_loudness_db = NaN keeps the clip as
+ *     given (features of raw samples).  n <= 2^24 (11.6 min at 24 kHz).  NULL on
+ *     failure (mia_last_error of ctx).  Free it before ctx.
+ *   mia_speaker_audio_data: DEVICE pointer of the clip; feeds mia_dac_encode in device mode.  mia_speaker_audio_read: test hook.
+ *   mia_speaker_audio_features: extractAudioFeatures (:191-216) of S segments [start[s], start[s] + len[s]) of the clip.
+ *     feat int32 [S][3] = energy, spectral_centroid, pitch, each Int(round(v * 100)) in 0..100; raw (nullable) float32 [S][3] = RMS,
+ *     centroid in Hz, normalised pitch before that rounding.  len 0 or a non-finite sample -> (0, 0, 0).
+ *     Centroid (:219-277): real DFT of N = 2^ceil(log2 n) points, vDSP's packed bins (bin 0 = sqrt(DC^2 + Nyquist^2), no Nyquist bin).
+ *     Pitch (:15-161): the reference's forward + inverse vDSP round trip has no conjugate product, so its "autocorrelation" is
+ *     C (w x)[2j] for j < 200 and 0 above; that closed form is computed.  A segment of n <= 240 samples has no
+ *     frame and pitch 0 (the reference traps at n <= 80).  All sums run in double in a fixed order: a segment's result does not depend
+ *     on the other segments of the call.  The number of launches depends on the set of FFT sizes present, not on S:
+ *     statistics + pitch frames (if any segment has a frame) + one per size up to mia_op_rfft_block, two per larger size + finish;
+ *     mia_speaker_audio_launches returns the last call's count.
+ *   mia_op_rfft_pow2 (operator-level hook of the FFT): unscaled DFT of x [n] zero-padded to N, out float32 [N/2+1][2].
+ *     mia_op_rfft_block: the largest N one workgroup transforms in LDS; above it the transform is a four-step split.
+ * MIA_ERR_INVALID_ARGUMENT before anything is launched: null pointers, n <= 0, sample_rate <= 0, n > 2^24, a segment outside [0, len],
+ * S <= 0 (or > 65535), N not a power of two or outside 2..2^24, n > N. */
+typedef struct mia_speaker_audio mia_speaker_audio;
+mia_speaker_audio* mia_speaker_audio_create(mia_ctx* ctx, const float* pcm, int64_t n, int sample_rate, float target_loudness_db,
+                                            float peak_limit_db);
+void mia_speaker_audio_free(mia_speaker_audio* a);
+int64_t mia_speaker_audio_len(const mia_speaker_audio* a);
+const float* mia_speaker_audio_data(const mia_speaker_audio* a);
+int mia_speaker_audio_read(mia_speaker_audio* a, int64_t first, int64_t n, float* out);
+int mia_speaker_audio_features(mia_speaker_audio* a, const int64_t* start, const int64_t* len, int S, int32_t* feat, float* raw);
+int mia_speaker_audio_launches(const mia_speaker_audio* a);
+int64_t mia_op_rfft_block(void);
+int mia_op_rfft_pow2(mia_ctx* ctx, const float* x, int64_t n, int64_t N, float* out);
+
 /* ---- autoregressive LMs (Llama-3 / Qwen2 / Qwen3 blocks) ---------------------------------------- */
 /* OrpheusConfig (TTS/Orpheus/BuildingBlocks/TransformerBlock.swift:16-34) / Qwen2Config (TTS/CosyVoice2/LLM/Qwen2LM.swift:15-43).
  * Tensors use the Hugging Face key schema both ports load: model.embed_tokens.weight, model.layers.N.self_attn.{q,k,v,o}_proj.weight

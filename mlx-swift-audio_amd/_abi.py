@@ -272,6 +272,16 @@ PROTOTYPES = {
     "mia_dac_load_encoder": (i32, [vp, P(DacEncoderConfig), TV, i32]),
     "mia_dac_code_len": (i64, [vp, i64]),
     "mia_dac_encode": (i32, [vp, vp, i64, i32, vp, i64, vp, i32]),
+    # OuteTTS speaker-profile audio
+    "mia_speaker_audio_create": (vp, [vp, vp, i64, i32, f32, f32]),
+    "mia_speaker_audio_free": (None, [vp]),
+    "mia_speaker_audio_len": (i64, [vp]),
+    "mia_speaker_audio_data": (vp, [vp]),
+    "mia_speaker_audio_read": (i32, [vp, i64, i64, vp]),
+    "mia_speaker_audio_features": (i32, [vp, vp, vp, i32, vp, vp]),
+    "mia_speaker_audio_launches": (i32, [vp]),
+    "mia_op_rfft_block": (i64, []),
+    "mia_op_rfft_pow2": (i32, [vp, vp, i64, i64, vp]),
     # autoregressive LMs
     "mia_lm_load": (vp, [vp, P(LmConfig), TV, i32, i32]),
     "mia_lm_attach_quantized": (i32, [vp, TV, i32, i32, i32]),

@@ -104,6 +104,8 @@ class DACCodec(_Codec):
 
     def encode(self, audio: np.ndarray, n_quantizers: int | None = None) -> np.ndarray:
         """DACCodec.encode(_:nQuantizers:) for one mono sequence (DACModel.swift:284-296): float32 [samples] -> codes int32 [n_q, T]."""
+        if hasattr(audio, "device_ptr"):
+            return self._encode_resident(audio, n_quantizers)
         a = np.ascontiguousarray(audio, np.float32).reshape(-1)
         T = int(self.ctx.lib.mia_dac_code_len(self.h, a.size))
         nq = self.cfg.n_codebooks if not n_quantizers else min(n_quantizers, self.cfg.n_codebooks)
@@ -111,6 +113,20 @@ class DACCodec(_Codec):
         ns = C.c_int64(0)
         self.ctx.check(self.ctx.lib.mia_dac_encode(self.h, a.ctypes.data, a.size, nq, codes.ctypes.data, codes.shape[1], C.byref(ns), _lib.MEM_HOST))
         return codes[:, :ns.value]
+
+    def _encode_resident(self, audio, n_quantizers: int | None = None) -> np.ndarray:
+        """encode of an outetts.SpeakerAudio: the clip is read where it lies (device mode, no upload); the codes land in a torch
+        buffer on the same device and come back once."""
+        import torch
+        n = len(audio)
+        T = int(self.ctx.lib.mia_dac_code_len(self.h, n))
+        nq = self.cfg.n_codebooks if not n_quantizers else min(n_quantizers, self.cfg.n_codebooks)
+        codes = torch.zeros((nq, max(T, 1)), dtype=torch.int32, device=f"cuda:{self.ctx.device}")
+        torch.cuda.synchronize(self.ctx.device)               # the buffer's zero fill runs on torch's stream, the encode on the context's
+        ns = C.c_int64(0)
+        self.ctx.check(self.ctx.lib.mia_dac_encode(self.h, audio.device_ptr, n, nq, codes.data_ptr(), codes.shape[1], C.byref(ns), _lib.MEM_DEVICE))
+        self.ctx.synchronize()
+        return codes[:, :ns.value].cpu().numpy()
 
     def decode_from_codes(self, codes: np.ndarray) -> np.ndarray:
         """decodeFromCodes: codes int [B, n_codebooks, T] (or [n_codebooks, T]) -> float32 [B, samples] (or [samples]).  B > 1 goes

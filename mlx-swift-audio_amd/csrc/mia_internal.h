@@ -34,6 +34,7 @@ struct mia_ctx {
   std::vector<void*> table_allocs;   // other cached device tables (freed at destroy), e.g. the 24 kHz 80-mel front end
   void* s3gen_mel = nullptr;         // S3GenMelTables* (mel_s3gen.hip), lives in table_allocs' lifetime
   void* funasr_tables = nullptr;     // Fun-ASR front-end tables (funasr_frontend.hip), malloc'ed; device parts in table_allocs
+  void* speaker_tables = nullptr;    // FFT twiddles and the pitch window (speaker_features.hip), malloc'ed; device parts in table_allocs
   mia_resampler_cache* resampler = nullptr;   // per-ratio polyphase filters of mia_resample_sinc (resample.hip); device tables in table_allocs
   // optional HIP-event profiling of kernel classes (mia_profile_*): bench.py's roofline figures come from here
   bool prof_on = false;

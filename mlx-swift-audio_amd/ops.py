@@ -189,6 +189,19 @@ def lm_prompt_attention(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.n
     return out
 
 
+def rfft_block(ctx: _lib.Context) -> int:
+    """mia_op_rfft_block: the largest power-of-two transform one workgroup runs in LDS; larger ones take the four-step split."""
+    return int(ctx.lib.mia_op_rfft_block())
+
+
+def rfft_pow2(ctx: _lib.Context, x: np.ndarray, N: int) -> np.ndarray:
+    """mia_op_rfft_pow2: the unscaled DFT of x [n] zero-padded to N (a power of two), complex64 [N/2 + 1]."""
+    a = np.ascontiguousarray(x, np.float32).reshape(-1)
+    out = np.empty((max(int(N) // 2 + 1, 1), 2), np.float32)
+    ctx.check(ctx.lib.mia_op_rfft_pow2(ctx.h, a.ctypes.data, a.size, int(N), out.ctypes.data))
+    return out.view(np.complex64).reshape(-1)
+
+
 # ---- fp32 tap GEMM and fp32 attention (device pointers; the test hooks expose every launch argument) -------------------------------
 
 

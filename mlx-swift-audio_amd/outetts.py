@@ -1,11 +1,17 @@
 """Host-side mirror of the reference's OuteTTS engine (TTS/OuteTTS): speaker profile (OuteTTSTokens.swift:88-165), prompt processor
-(OuteTTSPromptProcessor.swift) and generateChunk (OuteTTS.swift:380-511), backed by the gfx950 HIP layer -- a Llama CausalLM (lm.py) for
-the token loop and the DAC codec (codec.py) for the waveform.  The tokenizer and the sentence splitter stay with the caller, as
-everywhere in this package; speaker profiles arrive as JSON (createSpeakerFromTranscription, OuteTTSAudioProcessor.swift:15-278, is CPU
-feature extraction that is not built here)."""
+(OuteTTSPromptProcessor.swift), generateChunk (OuteTTS.swift:380-511) and speaker-profile creation (OuteTTSAudioProcessor.swift:363-453,
+OuteTTSEngine.swift:233-327), backed by the gfx950 HIP layer -- a Llama CausalLM (lm.py) for the token loop, the DAC codec (codec.py)
+for the waveform and for the reference clip's codes, and speaker_features.hip for the loudness preprocessing and the three audio
+features (energy, spectral centroid, pitch) of the clip and of every word.  The tokenizer, the sentence splitter and the silence
+trimmer (AudioTrimmer.findSpeechBounds) stay with the caller, as everywhere in this package.  A profile is created from audio here
+(create_speaker_profile) or loaded from the reference's JSON (SpeakerProfile.load); SpeakerProfile.save writes that JSON.
+
+Rounding: the Swift's Int(x) truncates and its round() rounds half away from zero; Python's round() is half-to-even and is not used."""
 from __future__ import annotations
 
+import ctypes as C
 import json
+import math
 import re
 from dataclasses import dataclass, field
 
@@ -73,6 +79,21 @@ class SpeakerProfile:
     def load(path: str) -> "SpeakerProfile":
         with open(path, encoding="utf-8") as f:
             return SpeakerProfile.from_dict(json.load(f))
+
+    def to_dict(self) -> dict:
+        """The inverse of from_dict: the reference's JSON keys (OuteTTSTokens.swift:104-165); interface_version only when set."""
+        feat = lambda f: {"energy": int(f.energy), "spectral_centroid": int(f.spectral_centroid), "pitch": int(f.pitch)}
+        d = {"text": self.text,
+             "words": [{"word": w.word, "duration": float(w.duration), "c1": [int(c) for c in w.c1], "c2": [int(c) for c in w.c2],
+                        "features": feat(w.features)} for w in self.words],
+             "global_features": feat(self.global_features)}
+        if self.interface_version is not None:
+            d["interface_version"] = self.interface_version
+        return d
+
+    def save(self, path: str) -> None:
+        with open(path, "w", encoding="utf-8") as f:
+            json.dump(self.to_dict(), f, ensure_ascii=False)
 
 
 # CharacterSet.whitespaces: general category Zs and the tab; ICU's \\s: [\\t\\n\\f\\r\\p{Z}] (Zs, U+2028, U+2029)
@@ -229,6 +250,11 @@ class OuteTTS:
         if prompt_attention is not None:
             lm.set_prompt_attention(prompt_attention)
 
+    def get_speaker(self, reference_audio, reference_text: str, reference_words, processor: "OuteTTSAudioProcessor | None" = None) -> SpeakerProfile:
+        """getSpeaker (OuteTTS.swift): a profile from a 24 kHz clip, its text and its [(word, start, end)] list."""
+        p = processor or OuteTTSAudioProcessor(self.dac.ctx, self.dac)
+        return p.create_speaker_from_transcription(reference_audio, reference_text, reference_words)
+
     def _kw(self, temperature, top_p, max_tokens):
         return dict(temperature=temperature, top_p=top_p, rep_penalty=REPETITION_PENALTY, rep_window=REPETITION_CONTEXT_SIZE,
                     max_new_tokens=max_tokens, stop_ids=(self.eos_id,))
@@ -263,3 +289,181 @@ class OuteTTS:
         for i in range(0, len(codes), MAX_BATCH):
             pcms += self.dac.decode_batch(codes[i:i + MAX_BATCH])
         return list(zip(gens, pcms))
+
+
+# ---- speaker-profile creation (OuteTTSAudioProcessor.swift, OuteTTSEngine.swift:233-327) ----
+TOKENS_PER_SECOND, MAX_EXTENSION = 75.0, 20          # createSpeakerFromTranscription :395-396
+
+
+def _round_half_away(x: float) -> float:
+    """Swift's round(): half away from zero."""
+    return math.floor(x + 0.5) if x >= 0 else -math.floor(-x + 0.5)
+
+
+@dataclass
+class WordSlice:
+    """One word of slice_words: codes [c_start, c_end) and samples [a_start, a_end) (a_end == a_start: default features)."""
+    c_start: int
+    c_end: int
+    a_start: int
+    a_end: int
+    duration: float
+
+
+def slice_words(words, n_codes: int, n_samples: int, sample_rate: int) -> list[WordSlice]:
+    """The slicing rule of createSpeakerFromTranscription (:398-446) as integer arithmetic: words = [(word, start s, end s)].
+    Code bounds chain (each word starts where the previous one ended; the first start backs off MAX_EXTENSION codes and clamps to 0, the
+    last end extends by MAX_EXTENSION and clamps to n_codes; end < start gives an empty slice).  Audio bounds are Int(t * sr), used only
+    if start < end <= n_samples."""
+    out: list[WordSlice] = []
+    start = None
+    for i, (_, t0, t1) in enumerate(words):
+        if start is None:
+            start = max(0, int(t0 * TOKENS_PER_SECOND) - MAX_EXTENSION)
+        raw_end = min(n_codes, int(t1 * TOKENS_PER_SECOND) + MAX_EXTENSION) if i == len(words) - 1 else int(t1 * TOKENS_PER_SECOND)
+        end = max(start, raw_end)
+        c0, c1 = min(start, n_codes), max(min(start, n_codes), min(end, n_codes))     # c1[start ..< min(end, count)]; start > count traps there
+        a0, a1 = int(t0 * float(sample_rate)), int(t1 * float(sample_rate))
+        if not (a0 < a1 and a1 <= n_samples):
+            a0 = a1 = 0
+        out.append(WordSlice(c0, c1, a0, a1, _round_half_away((c1 - c0) / TOKENS_PER_SECOND * 100) / 100))
+        start = end
+    return out
+
+
+def adjust_words_after_trim(words, leading_trim_seconds: float, trimmed_duration: float):
+    """OuteTTSEngine.swift:282-297: shift by the leading trim, drop words that end before the trimmed audio starts or start after it
+    ends, clip the rest to [0, trimmed_duration]."""
+    out = []
+    for w, t0, t1 in words:
+        s, e = t0 - float(leading_trim_seconds), t1 - float(leading_trim_seconds)
+        if not e > 0 or not s < float(trimmed_duration):
+            continue
+        out.append((w, max(0.0, s), min(float(trimmed_duration), e)))
+    return out
+
+
+class SpeakerAudio:
+    """mia_speaker_audio: preprocessAudioForSpeaker (:289-336) of a clip, resident on the device.  features(segments) is
+    extractAudioFeatures (:191-216) of every (start, length) segment in one call."""
+
+    def __init__(self, ctx, pcm, sample_rate: int = 24000, target_loudness: float = -18.0, peak_limit: float = -1.0):
+        from . import _lib
+        a = np.ascontiguousarray(pcm, np.float32).reshape(-1)
+        self.ctx, self.sample_rate = ctx, int(sample_rate)
+        self.h = ctx.lib.mia_speaker_audio_create(ctx.h, a.ctypes.data, a.size, int(sample_rate), float(target_loudness), float(peak_limit))
+        if not self.h:
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
+        ctx.adopt(self)
+
+    def __len__(self) -> int:
+        return int(self.ctx.lib.mia_speaker_audio_len(self.h))
+
+    @property
+    def device_ptr(self) -> int:
+        return int(self.ctx.lib.mia_speaker_audio_data(self.h) or 0)
+
+    @property
+    def launches(self) -> int:
+        """Kernels launched by the last features call: it depends on the set of FFT sizes among the segments, not on their number."""
+        return int(self.ctx.lib.mia_speaker_audio_launches(self.h))
+
+    def read(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        n = len(self) - first if n is None else n
+        out = np.empty(max(n, 0), np.float32)
+        self.ctx.check(self.ctx.lib.mia_speaker_audio_read(self.h, int(first), int(n), out.ctypes.data))
+        return out
+
+    def _features(self, segments, want_raw: bool):
+        seg = np.ascontiguousarray(segments, np.int64).reshape(-1, 2)
+        start, length = np.ascontiguousarray(seg[:, 0]), np.ascontiguousarray(seg[:, 1])
+        feat = np.zeros((seg.shape[0], 3), np.int32)
+        raw = np.zeros((seg.shape[0], 3), np.float32) if want_raw else None
+        self.ctx.check(self.ctx.lib.mia_speaker_audio_features(self.h, start.ctypes.data, length.ctypes.data, seg.shape[0], feat.ctypes.data,
+                                                               None if raw is None else raw.ctypes.data))
+        return feat, raw
+
+    def features(self, segments) -> list[AudioFeatures]:
+        """segments: [(start sample, length)]; length 0 gives the default features."""
+        return [AudioFeatures(int(e), int(c), int(p)) for e, c, p in self._features(segments, False)[0]]
+
+    def raw_features(self, segments) -> np.ndarray:
+        """float32 [S][3] = RMS, centroid in Hz, normalised pitch: the values before min(., 1) and the x100 rounding."""
+        return self._features(segments, True)[1]
+
+    def close(self):
+        if self.h and getattr(self.ctx, "h", None):
+            self.ctx.lib.mia_speaker_audio_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class OuteTTSAudioProcessor:
+    """OuteTTSAudioProcessor (:341-453) over a DACCodec with its encoder loaded."""
+
+    def __init__(self, ctx, dac, sample_rate: int = 24000):
+        self.ctx, self.dac, self.sample_rate = ctx, dac, int(sample_rate)
+
+    def extract_audio_features(self, audio) -> AudioFeatures:
+        """extractAudioFeatures (:191-216) of samples taken as they are (target_loudness NaN: no gain); an empty array gives the defaults."""
+        a = np.ascontiguousarray(audio, np.float32).reshape(-1)
+        if a.size == 0:
+            return AudioFeatures()
+        sa = SpeakerAudio(self.ctx, a, self.sample_rate, target_loudness=float("nan"))
+        try:
+            return sa.features([(0, a.size)])[0]
+        finally:
+            sa.close()
+
+    def create_speaker_from_transcription(self, audio, text: str, words) -> SpeakerProfile:
+        """createSpeakerFromTranscription: one SpeakerAudio, one encode, ONE features call for the clip and all words."""
+        sa = SpeakerAudio(self.ctx, audio, self.sample_rate)
+        try:
+            codes = self.dac.encode(sa)
+            c1 = [int(v) for v in codes[0]] if codes.shape[0] > 0 else []
+            c2 = [int(v) for v in codes[1]] if codes.shape[0] > 1 else []
+            n = len(sa)
+            sl = slice_words(words, len(c1), n, self.sample_rate)
+            feats = sa.features([(0, n)] + [(w.a_start, w.a_end - w.a_start) for w in sl])
+        finally:
+            sa.close()
+        out = [WordData(w[0].strip(_TRIM), s.duration, c1[s.c_start:s.c_end], c2[s.c_start:min(s.c_end, len(c2))], f)
+               for w, s, f in zip(words, sl, feats[1:])]
+        return SpeakerProfile(normalize_text(text), out, feats[0])
+
+
+def create_speaker_profile(samples, sample_rate: int, stt, *, leading_trim_seconds: float = 0.0, transcribe_samples=None, processor=None,
+                           ctx=None, dac=None, target_rate: int = 24000, transcribe_sample_rate: int = 16000, **transcribe_kw) -> SpeakerProfile:
+    """createSpeakerProfile(from:) (OuteTTSEngine.swift:233-327) behind the file reader and the silence trimmer: `samples` is the trimmed
+    clip at `sample_rate`, `leading_trim_seconds` what AudioTrimmer cut from the front, `transcribe_samples` the untrimmed clip the
+    reference transcribes (default: `samples`), at the same rate.  stt: a WhisperSTT (transcribe(clips at transcribe_sample_rate,
+    word_timestamps=True)).  processor: an OuteTTSAudioProcessor, or ctx and dac to make one.  Rate conversions run on the device
+    (mia_resample_sinc) and only when the rates differ."""
+    from . import audio_io
+    if processor is None:
+        processor = OuteTTSAudioProcessor(ctx, dac, target_rate)
+    ctx = processor.ctx
+    samples = np.ascontiguousarray(samples, np.float32).reshape(-1)
+    full = samples if transcribe_samples is None else np.ascontiguousarray(transcribe_samples, np.float32).reshape(-1)
+    resample = lambda a, to: a if to == sample_rate else audio_io.resample(ctx, a, sample_rate, to)
+    result = stt.transcribe([resample(full, transcribe_sample_rate)], word_timestamps=True, **transcribe_kw)[0]
+    words = []
+    for seg in result.segments:                                   # transcribeAudio (:394-426): strip, drop empty words
+        for w in seg.words or []:
+            t = w.word.strip(_TRIM)
+            if t:
+                words.append((t, float(w.start), float(w.end)))
+    if not words:
+        raise ValueError("Could not transcribe audio - no words detected")
+    trimmed_duration = float(np.float32(samples.size) / np.float32(sample_rate))
+    words = adjust_words_after_trim(words, leading_trim_seconds, trimmed_duration)
+    if not words:
+        raise ValueError("No words remain after silence trimming")
+    audio = resample(samples, processor.sample_rate)
+    text = " ".join(w for w, _, _ in words).strip()
+    return processor.create_speaker_from_transcription(audio, text, words)

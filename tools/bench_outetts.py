@@ -13,6 +13,11 @@ Prints one JSON line:
   * ms per generated token (one sentence) and per step with 8 sentences side by side, with mode 1;
   * the DAC decode of --frames code frames, host inclusive.
 
+--speaker SECONDS WORDS measures speaker-profile creation instead (and nothing else): a synthetic clip of SECONDS at 24 kHz cut into
+WORDS equal words, on the dac_speech shape with random-init weights.  Per stage -- preprocess (SpeakerAudio), DAC encode of the resident
+clip, features of the clip and all words in one call -- the median of 5 host-inclusive runs after 2 warm-ups, the feature stage's kernel
+launch count, and the float64 numpy restatement of the feature stage (tests/_outetts_speaker_ref.py) timed once on this host for scale.
+
 --vocab: the reference reads the vocabulary size from the checkpoint's config.json; the default (128 256, Llama-3.2's) is an assumption."""
 import argparse
 import json
@@ -38,6 +43,57 @@ def spread(ms):
     return {"min": round(ms[0], 3), "median": round(ms[len(ms) // 2], 3), "max": round(ms[-1], 3)}
 
 
+def speaker(seconds: float, n_words: int, seed: int):
+    import _outetts_speaker_ref as SR
+    sr = 24000
+    n = int(seconds * sr)
+    rng = np.random.default_rng(seed)
+    t = np.arange(n) / sr
+    env = 0.5 * (1 + np.sin(2 * np.pi * 1.3 * t))
+    x = (0.3 * env * np.sin(2 * np.pi * (140 + 6 * np.sin(t)) * t) + 0.1 * env * np.sin(2 * np.pi * 1900 * t) + 0.02 * rng.standard_normal(n)).astype(np.float32)
+    edges = np.linspace(0.0, seconds, n_words + 1)
+    words = [("w%d" % i, float(edges[i]), float(edges[i + 1])) for i in range(n_words)]
+    ctx = m.Context(0)
+    dcfg = S.DAC_CONFIGS["dac_speech"]
+    dac = HC.DACCodec.load(ctx, dcfg, S.dac_weights(dcfg, 0))
+
+    def median_ms(f, keep=None):
+        ts = []
+        for i in range(7):                               # 2 warm-ups, then 5
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = f()
+            ctx.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+            if keep is not None:
+                keep(out)
+        return spread(ts[2:])
+
+    made = []
+    pre = median_ms(lambda: OT.SpeakerAudio(ctx, x, sr), made.append)
+    for sa in made[:-1]:
+        sa.close()
+    sa = made[-1]
+    enc = median_ms(lambda: dac.encode(sa))
+    codes = dac.encode(sa)
+    sl = OT.slice_words(words, codes.shape[1], n, sr)
+    segs = [(0, n)] + [(w.a_start, w.a_end - w.a_start) for w in sl]
+    feat = median_ms(lambda: sa.features(segs))
+    launches = sa.launches
+    whole = median_ms(lambda: OT.OuteTTSAudioProcessor(ctx, dac, sr).create_speaker_from_transcription(x, "bench", words))
+    p = sa.read()
+    t0 = time.perf_counter()
+    for s0, ln in segs:
+        SR.raw_features(p[s0:s0 + ln], sr)
+    ref_ms = (time.perf_counter() - t0) * 1e3
+    print(json.dumps({"speaker": {"seconds": seconds, "samples": n, "words": n_words, "codes": int(codes.shape[1]), "preprocess_ms": pre,
+                                  "dac_encode_ms": enc, "features_ms": feat, "feature_launches": launches,
+                                  "create_speaker_from_transcription_ms": whole, "features_numpy_float64_ms": round(ref_ms, 1)}}))
+    sa.close()
+    dac.close()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--vocab", type=int, default=128256, help="vocabulary size (an assumption: the checkpoint's config.json is not at hand)")
@@ -48,7 +104,10 @@ def main():
     ap.add_argument("--new-tokens", type=int, default=128)
     ap.add_argument("--frames", type=int, default=300, help="DAC code frames to decode (75 per second)")
     ap.add_argument("--lengths", type=int, nargs="*", default=[512, 4096])
+    ap.add_argument("--speaker", nargs=2, metavar=("SECONDS", "WORDS"), help="measure speaker-profile creation only")
     args = ap.parse_args()
+    if args.speaker:
+        return speaker(float(args.speaker[0]), int(args.speaker[1]), args.seed)
     reps = max(3, args.repeats)
     cfg = dataclasses.replace(S.LM_CONFIGS["llama-3.2-1b"], vocab=args.vocab)
     ctx = m.Context(0)
