@@ -600,6 +600,37 @@ int mia_speaker_audio_launches(const mia_speaker_audio* a);
 int64_t mia_op_rfft_block(void);
 int mia_op_rfft_pow2(mia_ctx* ctx, const float* x, int64_t n, int64_t N, float* out);
 
+/* ---- reference-clip trimming (Utils/AudioTrimmer.swift) ----------------------------------------------------------
+ * The sample arithmetic of AudioTrimmer: findSpeechBounds (:218-274), which trimSilence (:142-207) shares up to its fall-backs; called
+ * from TTS/CosyVoice2/CosyVoice2Engine.swift:420-424 and TTS/OuteTTS/OuteTTSEngine.swift:250-254.  The word logic of the same file
+ * (:285-567) is host code (trim.py).  Caller arrays are HOST pointers in every entry point of this section.
+ *   mia_clip_create: uploads a host clip once and keeps it in HBM as fp32 [n], unchanged.  n <= 2^26.  NULL on failure
+ *     (mia_last_error of ctx).  Free it before ctx.  mia_clip_data: DEVICE pointer of the clip.  mia_clip_read: test hook.
+ *   mia_clip_num_frames (host arithmetic): max(1, (n - frame) / hop + 1), the division truncating toward zero; 0 for a non-positive
+ *     argument.  Frame i covers [i hop, min(i hop + frame, n)): only the one frame of a clip shorter than `frame` is short, and samples
+ *     behind the last whole frame are in no frame.
+ *   mia_clip_speech_bounds: a frame qualifies when max(ms, 1e-20) >= max(ms_max, 1e-20) * 10^(-top_db / 10), ms its mean square: the
+ *     reference's 20 log10(max(rms, 1e-10)) >= max_dB - top_db in the energy domain, the ratio computed once on the host in double.
+ *     start = first qualifying frame * hop, end = min((last qualifying frame + 1) * hop, n); found = 0 when no frame qualifies
+ *     (top_db < 0 only) or start >= end.  Mean squares are summed in double in a fixed order (element j of a frame on lane j % 64, a
+ *     fixed shuffle tree): a frame's energy is the same bits wherever the frame sits.  Two launches whatever the clip length
+ *     (mia_clip_launches: the last bounds call's count, 0 after a refused one); energies stay in the ctx workspace, three integers
+ *     come back.  A frame with a non-finite energy (a NaN or Inf sample inside a frame) is MIA_ERR_INVALID_AUDIO: the reference's
+ *     max() over NaN depends on operand order and is not copied.
+ *   mia_clip_frame_energy (test hook): the mean squares of frames [first_frame, first_frame + n_frames) as doubles.
+ * MIA_ERR_INVALID_ARGUMENT before anything is launched: null pointers, n <= 0, n > 2^26, sample_rate <= 0, frame <= 0, hop <= 0,
+ * frame > 2^20, a non-finite top_db, a frame range outside the clip's frames.  More than 2^22 frames: MIA_ERR_UNSUPPORTED. */
+typedef struct mia_clip mia_clip;
+mia_clip* mia_clip_create(mia_ctx* ctx, const float* pcm, int64_t n, int sample_rate);
+void mia_clip_free(mia_clip* c);
+int64_t mia_clip_len(const mia_clip* c);
+const float* mia_clip_data(const mia_clip* c);
+int mia_clip_read(mia_clip* c, int64_t first, int64_t n, float* out);
+int mia_clip_speech_bounds(mia_clip* c, int64_t frame, int64_t hop, float top_db, int64_t* start, int64_t* end, int* found);
+int mia_clip_frame_energy(mia_clip* c, int64_t frame, int64_t hop, int64_t first_frame, int64_t n_frames, double* ms_out);
+int64_t mia_clip_num_frames(int64_t n, int64_t frame, int64_t hop);
+int mia_clip_launches(const mia_clip* c);
+
 /* ---- autoregressive LMs (Llama-3 / Qwen2 / Qwen3 blocks) ---------------------------------------- */
 /* OrpheusConfig (TTS/Orpheus/BuildingBlocks/TransformerBlock.swift:16-34) / Qwen2Config (TTS/CosyVoice2/LLM/Qwen2LM.swift:15-43).
  * Tensors use the Hugging Face key schema both ports load: model.embed_tokens.weight, model.layers.N.self_attn.{q,k,v,o}_proj.weight

@@ -282,6 +282,16 @@ PROTOTYPES = {
     "mia_speaker_audio_launches": (i32, [vp]),
     "mia_op_rfft_block": (i64, []),
     "mia_op_rfft_pow2": (i32, [vp, vp, i64, i64, vp]),
+    # reference-clip trimming
+    "mia_clip_create": (vp, [vp, vp, i64, i32]),
+    "mia_clip_free": (None, [vp]),
+    "mia_clip_len": (i64, [vp]),
+    "mia_clip_data": (vp, [vp]),
+    "mia_clip_read": (i32, [vp, i64, i64, vp]),
+    "mia_clip_speech_bounds": (i32, [vp, i64, i64, f32, vp, vp, vp]),
+    "mia_clip_frame_energy": (i32, [vp, i64, i64, i64, i64, vp]),
+    "mia_clip_num_frames": (i64, [i64, i64, i64]),
+    "mia_clip_launches": (i32, [vp]),
     # autoregressive LMs
     "mia_lm_load": (vp, [vp, P(LmConfig), TV, i32, i32]),
     "mia_lm_attach_quantized": (i32, [vp, TV, i32, i32, i32]),

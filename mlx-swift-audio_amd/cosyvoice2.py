@@ -1,7 +1,8 @@
 """Host-side mirror of CosyVoice2Model (TTS/CosyVoice2/CosyVoice2Model.swift:28-208) and of the tensor part of
 prepareConditionals (TTS/CosyVoice2/CosyVoice2TTS.swift:370-430): generateTokens -> tokensToMel -> melToAudio, every stage on
-the gfx950 HIP layer, including the CAM++ speaker embedding of the reference clip (speaker.py).  Text tokenisation stays with the
-caller (CPU text code), so text arrives as token ids.
+the gfx950 HIP layer, including the CAM++ speaker embedding of the reference clip (speaker.py); prepare_speaker
+(prepareSpeakerFromSamples, TTS/CosyVoice2/CosyVoice2Engine.swift:397-526) takes a raw clip through the trimmer (trim.py)
+first.  Text tokenisation stays with the caller (CPU text code), so text arrives as token ids.
 Every random draw of the reference is an explicit argument: `uniforms` (RAS sampler), `z` (CFM noise), `noise` (HiFT source)."""
 from __future__ import annotations
 
@@ -17,6 +18,16 @@ class CosyVoice2Conditionals:
     prompt_mel: np.ndarray               # float32 [2 m, 80] (time-major, as flow.inference consumes it)
     speaker_embedding: np.ndarray        # float32 [192]
     prompt_text: list[int]
+
+
+@dataclass
+class CosyVoice2Speaker:
+    """CosyVoice2Speaker (CosyVoice2Engine.swift:30-63) without its description string; the duration is sample_count / sample_rate."""
+    conditionals: CosyVoice2Conditionals
+    sample_rate: int
+    sample_count: int
+    transcription: str | None
+    clipped_at_word_boundary: bool
 
 
 class CosyVoice2Model:
@@ -44,6 +55,44 @@ class CosyVoice2Model:
             speaker_embedding = self.speaker_encoder(ref_wav_16k)[0]
         return CosyVoice2Conditionals(toks[:n].copy(), np.ascontiguousarray(mel80[:2 * n]), np.ascontiguousarray(speaker_embedding, np.float32),
                                       list(prompt_text))
+
+    # ---- prepareSpeakerFromSamples (CosyVoice2Engine.swift:397-526) -----------------------------------------------------------------------
+    def prepare_speaker(self, samples, sample_rate: int, transcription: str | None = None, stt=None, encode_text=None,
+                        speaker_embedding: np.ndarray | None = None, **transcribe_kw) -> CosyVoice2Speaker:
+        """A raw reference clip to a speaker: resample to 24 kHz (the engine's linear resampler), trim silence (AudioTrimmer, top_db 60),
+        and above 30 s clip at a word boundary when an `stt` (a WhisperSTT: the engine's autoTranscribe) gives word timestamps, else cut.
+        The transcription is the given one, the words that survive the clip, or -- with an stt and no clip at a word boundary -- the
+        transcription of the final audio.  encode_text(str) -> token ids turns it into the prompt text; without it the prompt is empty."""
+        from . import audio as A
+        from . import trim as T
+        target = 24000
+        wav = A.resample_audio(self.ctx, samples, sample_rate, target)
+        wav = T.trim_silence(self.ctx, wav, target, T.COSYVOICE2)
+        trimmed_duration = float(np.float32(wav.size) / np.float32(target))
+        max_duration = 30.0
+        max_samples = int(max_duration) * target
+        to16k = lambda a: A.resample_audio(self.ctx, a, target, 16000)      # transcribeWithTimestamps (:254-281): the linear resampler again
+        clipped = False
+        if wav.size > max_samples:
+            point = None
+            if stt is not None:
+                words = T.transcribed_words(stt.transcribe([to16k(wav)], word_timestamps=True, **transcribe_kw)[0])
+                if words:
+                    words = T.drop_unreliable_trailing_words(words, trimmed_duration, T.COSYVOICE2)
+                    point = T.find_word_boundary_clip_point(words, max_duration, target)
+            if point is not None:
+                wav = wav[:max(point[0], 0)]
+                transcription = "".join(w.word for w in point[1]).strip(" \t")     # .whitespaces: Whisper's words carry their leading space
+                clipped = True
+            else:
+                wav = wav[:max_samples]
+        if transcription is None and stt is not None and not clipped:             # after clipping: the text matches the final audio
+            transcription = stt.transcribe([to16k(wav)], **transcribe_kw)[0].text
+        if transcription is not None:
+            transcription = transcription.strip() or None
+        prompt = encode_text(transcription) if transcription is not None and encode_text is not None else ()
+        cond = self.prepare_conditionals(wav, speaker_embedding, prompt)
+        return CosyVoice2Speaker(cond, target, int(wav.size), transcription, clipped)
 
     # ---- the three stages (CosyVoice2Model.swift:53-133) ------------------------------------------------------------------------------
     def generate_tokens(self, text, prompt_text, prompt_speech_token, uniforms, sampling: int = 25, max_token_text_ratio: float = 20.0,

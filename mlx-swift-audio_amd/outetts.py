@@ -438,17 +438,30 @@ class OuteTTSAudioProcessor:
 
 
 def create_speaker_profile(samples, sample_rate: int, stt, *, leading_trim_seconds: float = 0.0, transcribe_samples=None, processor=None,
-                           ctx=None, dac=None, target_rate: int = 24000, transcribe_sample_rate: int = 16000, **transcribe_kw) -> SpeakerProfile:
-    """createSpeakerProfile(from:) (OuteTTSEngine.swift:233-327) behind the file reader and the silence trimmer: `samples` is the trimmed
-    clip at `sample_rate`, `leading_trim_seconds` what AudioTrimmer cut from the front, `transcribe_samples` the untrimmed clip the
-    reference transcribes (default: `samples`), at the same rate.  stt: a WhisperSTT (transcribe(clips at transcribe_sample_rate,
-    word_timestamps=True)).  processor: an OuteTTSAudioProcessor, or ctx and dac to make one.  Rate conversions run on the device
-    (mia_resample_sinc) and only when the rates differ."""
+                           ctx=None, dac=None, target_rate: int = 24000, transcribe_sample_rate: int = 16000, trim=None,
+                           **transcribe_kw) -> SpeakerProfile:
+    """createSpeakerProfile(from:) (OuteTTSEngine.swift:233-327) behind the file reader.  With `trim` (a trim.AudioTrimConfig; the engine
+    uses trim.DEFAULT) `samples` is the raw clip at `sample_rate`: its speech bounds are found on the device at the clip's own rate
+    (:250-266), the clip is sliced to them, the leading trim is Float(start) / Float(sampleRate), the untrimmed clip is transcribed, and
+    no bounds found means the whole clip with a trim of 0.  Without it `samples` is the already trimmed clip, `leading_trim_seconds`
+    what was cut from the front and `transcribe_samples` the untrimmed clip the reference transcribes (default: `samples`), at the same
+    rate; giving either of the two together with `trim` is a ValueError.  stt: a WhisperSTT (transcribe(clips at
+    transcribe_sample_rate, word_timestamps=True)).  processor: an OuteTTSAudioProcessor, or ctx and dac to make one.  Rate conversions
+    run on the device (mia_resample_sinc) and only when the rates differ."""
     from . import audio_io
+    if trim is not None and (leading_trim_seconds != 0.0 or transcribe_samples is not None):
+        raise ValueError("trim computes leading_trim_seconds and transcribe_samples itself: pass it alone")
     if processor is None:
         processor = OuteTTSAudioProcessor(ctx, dac, target_rate)
     ctx = processor.ctx
     samples = np.ascontiguousarray(samples, np.float32).reshape(-1)
+    if trim is not None:
+        from . import trim as T
+        transcribe_samples = samples
+        bounds = T.find_speech_bounds(ctx, samples, sample_rate, trim)
+        if bounds is not None:
+            samples = samples[bounds[0]:bounds[1]]
+            leading_trim_seconds = float(np.float32(bounds[0]) / np.float32(sample_rate))
     full = samples if transcribe_samples is None else np.ascontiguousarray(transcribe_samples, np.float32).reshape(-1)
     resample = lambda a, to: a if to == sample_rate else audio_io.resample(ctx, a, sample_rate, to)
     result = stt.transcribe([resample(full, transcribe_sample_rate)], word_timestamps=True, **transcribe_kw)[0]
