@@ -63,8 +63,9 @@ int mia_synchronize(mia_ctx* ctx);
 /* ---- profiling ------------------------------------------------------------------------------ */
 /* Optional HIP-event timing of kernel classes on the ctx stream (events bracket each launch of the class).
  * Classes: "logmel" (work = algorithmic bytes), "enc_gemm", "crosskv_gemm", "enc_attention" (work = FLOPs),
- * "enc_norm" (bytes), "decode" (work = decoder steps), "mel_gather" (bytes; mia_whisper_encode_audio_windows).  Reading synchronises
- * the stream. */
+ * "enc_norm" (bytes), "decode" (work = decoder steps), "mel_gather" (bytes; mia_whisper_encode_audio_windows), "decode_kept"
+ * (the same records as "decode", for the passes whose step kept the decoder layers' weights resident in the Infinity Cache; none when
+ * the layer weights exceed the cache budget and are streamed).  Reading synchronises the stream. */
 int mia_profile_enable(mia_ctx* ctx, int on);
 int mia_profile_reset(mia_ctx* ctx);
 int mia_profile_read(mia_ctx* ctx, const char* kernel_class, int64_t* launches, double* total_ms, double* total_work);
@@ -399,8 +400,11 @@ int mia_whisper_set_gemm_variant(mia_whisper* w, int variant);
  *   mia_whisper_set_debug: bit 0 = launch every step's kernels directly instead of replaying the captured hipGraph, bit 1 = the
  *     one-workgroup decode head at temperature 0 too (normally the split argmax head).  Results must not change.  Bit 2 = the step
  *     keeps every LayerNorm in its own reduce + LayerNorm kernel instead of carrying x * gamma across the attention output
- *     projections: the control chain of tests/test_norm_carry_gpu.py (same function, other 16-bit rounding points).  Other bits are
- *     MIA_ERR_INVALID_ARGUMENT.
+ *     projections: the control chain of tests/test_norm_carry_gpu.py (same function, other 16-bit rounding points).  Bit 4 (16) =
+ *     the step's cache policies as they were before the layer weights were kept resident: every weight load follows
+ *     mia_whisper_set_weight_sharing, self-attention's K/V load with the default policy (the control of
+ *     tests/test_decode_cache_policy_gpu.py and of A/B runs; results must not change).  Other bits, bit 3 (8) among them, are
+ *     MIA_ERR_INVALID_ARGUMENT.  A changed flag re-captures the step graph at the next decode.
  *   mia_whisper_trace_logits: from now on every decode step ALSO copies the raw fp32 logits (before the logit rules) of the listed
  *     batch rows into a trace [n_clips][n_text_ctx][n_vocab], filed under the position of the token the step consumed -- the copy is a
  *     node of the same captured step graph, so the trace is what the graph computed.  n_clips = 0 switches it off (<= 8 rows).
@@ -446,10 +450,13 @@ int mia_whisper_encode_windows(mia_whisper* w, const float* pcm, const int64_t* 
  * kernels of one batch are then dispatched ahead of the queued tiles of another batch's encoder instead of taking turns with them.
  * NULL restores the single-stream form.  The stream must belong to the context's device and outlive the handle's use of it. */
 int mia_whisper_set_encode_stream(mia_whisper* w, void* hip_stream);
-/* Throughput hint for handles that share one weight copy (mia_whisper_clone) and decode CONCURRENTLY on their own streams: with
- * concurrent_readers > 1 the decode step loads its weights with the default cache policy (the loops that read a matrix second and third
- * mostly hit the 256 MB Infinity Cache); with 1 (the default) it streams them non-temporal, which is faster for a lone loop.  Results
- * are bit-identical either way.  Call on every handle of the group; takes effect at the next decode. */
+/* Throughput hint for handles that share one weight copy (mia_whisper_clone) and decode CONCURRENTLY on their own streams.  The step
+ * chooses its cache policies from the model's byte counts alone (layer weights kept resident in the 256 MiB Infinity Cache when
+ * they fit beside a step's other cached bytes, everything read once per step non-temporal), for one reader and for several, so on a
+ * model that fits (large-v3-turbo, packed or not) this call selects nothing.  It still decides the weight loads of a model whose layer
+ * weights exceed that budget (large-v3) and of the earlier policies (mia_whisper_set_debug bit 4): default policy with
+ * concurrent_readers > 1, non-temporal with 1.  Results are bit-identical
+ * either way.  Call on every handle of the group; takes effect at the next decode. */
 int mia_whisper_set_weight_sharing(mia_whisper* w, int concurrent_readers);
 int mia_whisper_transcribe_windows(mia_whisper* w, const float* pcm, const int64_t* offs, int B, int64_t pad_right,
                                    const mia_decode_opts* opts, int32_t* tokens, int32_t* n_tokens, float* avg_logprob,

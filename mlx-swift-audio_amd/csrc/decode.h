@@ -14,7 +14,8 @@ int dec_launch_skinny_q(mia_whisper* w, const SkinnyArgs& a, const uint32_t* wfr
 int dec_launch_lnfold(const void* w16, int N, int K, const float* gamma, const float* beta, float* c1, float* c2, int dtype, hipStream_t s, const float* bias = nullptr);
 // qk_out (optional): pre-softmax scores of the heads with head_slot[h] >= 0 -> qk_out[b][slot][pos[b]][key] (word-timestamp alignment)
 int dec_launch_attention(mia_whisper* w, const void* q, const void* kc, const void* vc, void* out, int fixed_keys, int cap_keys,
-                         hipStream_t s, float* qk_out = nullptr, const int32_t* head_slot = nullptr, int n_slots = 0, int qk_ctx = 0);
+                         hipStream_t s, float* qk_out = nullptr, const int32_t* head_slot = nullptr, int n_slots = 0, int qk_ctx = 0,
+                         bool self_nt = false);     // self attention (fixed_keys == 0): load the cached K/V non-temporal (cross K/V always are)
 bool dec_head_is_split(const DecodeParams& p);
 // test hook: logits of the traced clips -> w->trace[slot][pos[clip]][0:V]
 int dec_launch_trace(mia_whisper* w, hipStream_t s);

@@ -659,7 +659,7 @@ int dec_launch_reduce_ln(mia_whisper* w, int S, const float* bias, const LNW& ln
 }
 
 int dec_launch_attention(mia_whisper* w, const void* q, const void* kc, const void* vc, void* out, int fixed_keys, int cap_keys,
-                         hipStream_t s, float* qk_out, const int32_t* head_slot, int n_slots, int qk_ctx) {
+                         hipStream_t s, float* qk_out, const int32_t* head_slot, int n_slots, int qk_ctx, bool self_nt) {
   if (cap_keys > DEC_MAX_KEYS) return -1;
   dim3 grid(w->dims.n_text_head, w->cur_B), block(256);
 #define ATT(T_, U_, NTL_)                                                                                                            \
@@ -667,8 +667,11 @@ int dec_launch_attention(mia_whisper* w, const void* q, const void* kc, const vo
                      (uint16_t*)out, w->clip.pos, fixed_keys, cap_keys, w->dims.n_text_head, 0.125f, qk_out, head_slot, n_slots, qk_ctx)
   // cross attention (fixed_keys = the 1500 encoder positions): bandwidth-bound streaming of 2 x 192 KB per (clip, head), non-temporal;
   // self attention: at most n_text_ctx cached keys, latency-bound.  (U = 8 was measured: 10 us per step SLOWER than U = 4.)
-  if (w->dtype == MIA_F16) { if (fixed_keys > 0) ATT(F16, 4, true); else ATT(F16, 4, false); }
-  else { if (fixed_keys > 0) ATT(BF16, 4, true); else ATT(BF16, 4, false); }
+  // (self K/V: each cached byte is read once per step, 0.66 MB x position; non-temporal when the step keeps its layer weights resident,
+  //  whisper_decode.hip: dec_cache_policy)
+  const bool nt = fixed_keys > 0 || self_nt;
+  if (w->dtype == MIA_F16) { if (nt) ATT(F16, 4, true); else ATT(F16, 4, false); }
+  else { if (nt) ATT(BF16, 4, true); else ATT(BF16, 4, false); }
 #undef ATT
   return 0;
 }

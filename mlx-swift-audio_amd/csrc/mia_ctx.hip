@@ -109,7 +109,7 @@ void mia_prof_end(mia_ctx* ctx, int rec) {
   (void)hipEventRecord(ctx->prof[rec].stop, ctx->stream);
 }
 
-static const char* kProfNames[MIA_PROF_NCLASSES] = {"logmel", "enc_gemm", "enc_attention", "enc_norm", "decode", "crosskv_gemm", "mel_gather", "fsmn"};
+static const char* kProfNames[MIA_PROF_NCLASSES] = {"logmel", "enc_gemm", "enc_attention", "enc_norm", "decode", "crosskv_gemm", "mel_gather", "fsmn", "decode_kept"};
 
 extern "C" int mia_profile_enable(mia_ctx* ctx, int on) {
   if (!ctx) return MIA_ERR_INVALID_ARGUMENT;

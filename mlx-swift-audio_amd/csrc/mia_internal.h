@@ -49,7 +49,9 @@ struct mia_ctx {
 };
 
 enum { MIA_PROF_LOGMEL = 0, MIA_PROF_ENC_GEMM = 1, MIA_PROF_ENC_ATTN = 2, MIA_PROF_ENC_NORM = 3, MIA_PROF_DECODE = 4,
-       MIA_PROF_CROSSKV_GEMM = 5, MIA_PROF_MEL_GATHER = 6, MIA_PROF_FSMN = 7, MIA_PROF_NCLASSES = 8 };
+       MIA_PROF_CROSSKV_GEMM = 5, MIA_PROF_MEL_GATHER = 6, MIA_PROF_FSMN = 7,
+       MIA_PROF_DECODE_KEPT = 8,      // the decode passes whose step kept the layer weights cache-resident (whisper_decode.hip: dec_cache_policy)
+       MIA_PROF_NCLASSES = 9 };
 
 // RAII-less helpers: if profiling is on, bracket the launches between begin/end with events on the ctx stream
 int mia_prof_begin(mia_ctx* ctx, int cls, double work);   // returns record index or -1

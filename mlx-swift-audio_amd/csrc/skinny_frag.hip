@@ -185,9 +185,12 @@ __global__ __launch_bounds__(64 * NW) void dec_skinny_fflat(SkinnyArgs a) {
   const uint16_t* ap = a.A + ((((int64_t)z * ksteps + ks0) * 2) * 64 + lane) * 8;
   const SkinnyPre<NT> pre = skinny_prefetch<MODE, NT>(a, blockIdx.x * (16 * NT), z * 32, lane);
   s16x8 fw[NSTEP][NT], fa0[NSTEP], fa1[NSTEP];
-  // Weights are read once per step: non-temporal, unless other decode loops stream the same copy at the same time (a.w_keep: then the
-  // second and third reader mostly hit the Infinity Cache; measured with 3 replicas: + 2.2 % audio-s/s, and - 3.6 % for a lone loop,
-  // whose 316 MB per step cycle through the 256 MB cache without a hit).  The cache policy is an instruction bit: two copies of the loop.
+  // Cache policy of the weight loads, per launch (a.w_keep; chosen in whisper_decode.hip: dec_cache_policy).  Measured first with ONE
+  // policy for every GEMM of the step: all 316 MB (layers + vocabulary matrix) cacheable cycle through the 256 MiB Infinity Cache
+  // without a hit (a lone loop - 3.6 %; three loops on one copy + 2.2 %, the second and third reader hitting).  Measured since with the
+  // policy split: the 183.5 MB of layer weights cacheable, the vocabulary matrix and all K/V non-temporal -- the layer weights then stay
+  // from step to step (fc1 8.1 -> 6.9 us, fc2 6.4 -> 5.4 us, the step 379 -> 368 us; non-temporal loads leave them in place).
+  // The cache policy is an instruction bit: two copies of the loop.
   // (`?:` or if / else between a plain and a non-temporal load of ONE pointer is hoisted by LLVM into a single plain load -- both
   //  forms then ran cacheable.  The policy is therefore the immediate `aux` operand of a buffer load, which cannot be merged: 0 = default,
   //  2 = nt.)

@@ -69,6 +69,10 @@ struct DecodeParams {  // immutable per graph (kernel argument, by value)
   int head_single;              // test hook (mia_whisper_set_debug bit 1): one-workgroup head even at temperature 0
   int split_ln;                 // test hook (mia_whisper_set_debug bit 2): no LayerNorm carried across the GEMMs (reduce + LayerNorm chain)
   int packed;                   // mia_whisper_use_packed: 0, or the bit width (4 | 8) of the packed weights the step's GEMMs read
+  // cache policy of the step's read-once-per-step streams (whisper_decode.hip: dec_cache_policy); 1 = default policy, 0 = non-temporal
+  int keep_layers;              // the weight loads of the layers' GEMMs
+  int keep_vocab;               // the weight loads of the vocabulary GEMM
+  int self_nt;                  // 1 = self-attention's cached K/V load non-temporal
 };
 
 struct mia_whisper {
@@ -160,7 +164,7 @@ struct mia_whisper {
   hipEvent_t ev_win = nullptr;
 
   // ---- test hooks (never set by the product path)
-  int debug_flags = 0;                // mia_whisper_set_debug: bit 0 = launch every step directly (no hipGraph), bit 1 = one-workgroup head, bit 2 = split LayerNorm chain
+  int debug_flags = 0;                // mia_whisper_set_debug: bit 0 = launch every step directly (no hipGraph), bit 1 = one-workgroup head, bit 2 = split LayerNorm chain, bit 4 = the cache policies before dec_cache_policy
   float* trace = nullptr;             // mia_whisper_trace_logits: fp32 [trace_n][n_text_ctx][V], row p = the logits computed at position p
   int32_t* trace_clips = nullptr;     // device int32 [trace_n]: batch rows traced
   int trace_n = 0;

@@ -56,6 +56,44 @@ __global__ __launch_bounds__(256) void align_token_prob(const float* __restrict_
   }
 }
 
+// Cache policy of what a step reads once (DecodeParams::keep_layers / keep_vocab / self_nt).  The layers' weights are the one large
+// stream that is the same from step to step; they are kept (default policy) while they, plus every default-policy byte of a step, fit
+// the Infinity Cache with room to spare, and everything else that is read once per step goes around it (non-temporal):
+//
+//   stream (large-v3-turbo, 32 clips, 16-bit)                  MB / step          policy
+//   layer weights (q|k|v, out, cross-q, cross-out, fc1, fc2)   183.5              keep if the budget below holds (else as before)
+//   vocabulary matrix                                          132.8              nt (kept where it fits the budget too: packed q4 / q8)
+//   cross K/V                                                  983                nt
+//   self K/V reads                                             0.66 x position    nt
+//   fp32 logits, written then read                             6.6 + 6.6          default
+//   fc2 partials, activations, statistics, constants, biases   < 10               default
+//
+// Budget: kept bytes + default-policy bytes per step <= 230 MB (of 256 MiB), per decode loop; the reader count of
+// mia_whisper_set_weight_sharing does not enter.  large-v3 (32 layers, 1.47 GB) fails it and runs with the earlier policies, as does
+// any model under debug bit 4 (mia_whisper_set_debug(16)): every weight load follows the sharing hint, self K/V default.
+constexpr double DEC_KEEP_BUDGET = 230e6;
+
+// returns true when the step keeps its layer weights resident
+bool dec_cache_policy(const mia_whisper* w, DecodeParams& p) {
+  const double D = p.D, B = w->cur_B, L = p.L, V = p.V;
+  // bytes per weight: 16-bit, or packed codes + one fp32 (scale, offset) pair per group of 64
+  const double bpw = p.packed ? p.packed / 8.0 + 8.0 / 64.0 : 2.0;
+  const double layers = L * 14.0 * D * D * bpw, vocab = V * D * bpw;
+  // default-policy bytes: the logits (fp32, written and read), the fc2 partials (fp32, up to 4 splits, written and read), and per layer
+  // and clip about 64 D bytes of 16-bit operands, the fp32 residual, the K/V cache rows written, statistics; biases and constants per layer
+  const double dflt = 8.0 * B * V + L * (32.0 * B * D + 64.0 * B * D + 40.0 * D);
+  if ((w->debug_flags & 16) || layers + dflt > DEC_KEEP_BUDGET) {
+    // the earlier policies: one for every weight load, from the sharing hint (a weight set that cannot stay is streamed by a lone
+    // loop and loaded cacheable by concurrent ones, whose second and third reader then mostly hit); self K/V with the default policy
+    p.keep_layers = p.keep_vocab = w->weight_sharing; p.self_nt = 0;
+    return false;
+  }
+  p.keep_layers = 1;
+  p.keep_vocab = layers + vocab + dflt <= DEC_KEEP_BUDGET ? 1 : 0;
+  p.self_nt = 1;
+  return true;
+}
+
 // enqueue one decoder step (consumes the token at st->pos, produces the token at st->pos + 1)
 int enqueue_step(mia_whisper* w, const DecodeParams& p, const AlignHook* hook = nullptr) {
   hipStream_t s = w->ctx->stream;
@@ -67,7 +105,7 @@ int enqueue_step(mia_whisper* w, const DecodeParams& p, const AlignHook* hook = 
                     float* stat_out = nullptr, const float* c1 = nullptr, const float* c2 = nullptr) {
     SkinnyArgs a{A, lda, (const uint16_t*)lw.wf, use_bias ? lw.b : nullptr, out, ldo, ck, cv, w->clip.pos, B, lw.N, lw.K, S, act, D, H, C};
     a.out_frag = out_frag;
-    a.w_keep = w->weight_sharing;
+    a.w_keep = mode == SK_OUTF32 ? p.keep_vocab : p.keep_layers;       // SK_OUTF32: the vocabulary GEMM alone (dec_cache_policy)
     if (stat_in) { a.ss_in = stat_in; a.ss_tiles = D / 16; a.ss_dim = D; a.eps = 1e-5f; a.c1 = c1 ? c1 : lw.c1; a.c2 = c2 ? c2 : lw.c2; a.rs_scale = lw.ln_rs; }
     if (mode == SK_RESID) { a.xres = w->dx; a.nw = next_ln->gc; a.ss_out = stat_out; }
     if (p.packed) return dec_launch_skinny_q(w, a, lw.qw, lw.qst, p.packed, mode, s);      // mia_whisper_use_packed (skinny_frag_quant.hip)
@@ -95,7 +133,7 @@ int enqueue_step(mia_whisper* w, const DecodeParams& p, const AlignHook* hook = 
     if (fused_ln) {
       // self attention (its input is always a normalised row: the embedding kernel's, or the previous layer's reduce + LayerNorm)
       if (skinny(dh, D, b.qkv, true, w->dq, D, 1, MIA_ACT_NONE, SK_QKV, sk, sv)) return -1;
-      if (dec_launch_attention(w, w->dq, sk, sv, w->da, 0, C, s)) return -1;
+      if (dec_launch_attention(w, w->dq, sk, sv, w->da, 0, C, s, nullptr, nullptr, 0, 0, p.self_nt != 0)) return -1;
       if (skinny((const uint16_t*)w->da, D, b.out, true, w->dh, D, 1, MIA_ACT_NONE, SK_RESID, nullptr, nullptr, 0, nullptr, &b.cross_ln, st_a)) return -1;
       // cross attention (K/V primed by the encode call)
       if (skinny(dh, D, b.cq, true, w->dq, D, 1, MIA_ACT_NONE, SK_OUT16, nullptr, nullptr, 0, st_a)) return -1;
@@ -112,7 +150,7 @@ int enqueue_step(mia_whisper* w, const DecodeParams& p, const AlignHook* hook = 
     }
     // self attention
     if (skinny(dh, D, b.qkv, true, w->dq, D, 1, MIA_ACT_NONE, SK_QKV, sk, sv)) return -1;
-    if (dec_launch_attention(w, w->dq, sk, sv, w->da, 0, C, s)) return -1;
+    if (dec_launch_attention(w, w->dq, sk, sv, w->da, 0, C, s, nullptr, nullptr, 0, 0, p.self_nt != 0)) return -1;
     if (skinny((const uint16_t*)w->da, D, b.out, false, w->partial, 0, S_d, MIA_ACT_NONE, SK_PARTIAL)) return -1;
     dec_launch_reduce_ln(w, S_d, b.out.b, b.cross_ln, s);
     // cross attention (K/V primed by the encode call)
@@ -166,6 +204,7 @@ int whisper_decode(mia_whisper* w, const mia_decode_opts* o, int32_t* tokens, in
   p.max_initial_ts = o->max_initial_timestamp_index; p.max_new_tokens = o->max_new_tokens;
   p.trace = w->trace ? 1 : 0; p.head_single = (w->debug_flags & 2) ? 1 : 0; p.split_ln = (w->debug_flags & 4) ? 1 : 0;
   p.packed = w->use_packed ? w->q_bits : 0;
+  const bool resident = dec_cache_policy(w, p);
   if (w->trace)
     for (int i = 0; i < w->trace_n; ++i) MIA_CHECK_ARG(ctx, w->trace_clip_ids[i] < w->cur_B, "decode: traced clip %d is not in this batch of %d", w->trace_clip_ids[i], w->cur_B);
 
@@ -252,6 +291,7 @@ int whisper_decode(mia_whisper* w, const mia_decode_opts* o, int32_t* tokens, in
 
   if (dec_head_is_split(p)) dec_launch_embed_ln(w, w->dec[0].attn_ln, s);   // position 0; later positions are embedded by the head
   int prof_rec = mia_prof_begin(ctx, MIA_PROF_DECODE, 0.0);
+  const int prof_kept = resident ? mia_prof_begin(ctx, MIA_PROF_DECODE_KEPT, 0.0) : -1;
   int steps_run = 0;
   const int min_init = *std::min_element(n_init.begin(), n_init.end());
   for (int step = 0; step < total_steps;) {
@@ -270,6 +310,7 @@ int whisper_decode(mia_whisper* w, const mia_decode_opts* o, int32_t* tokens, in
       if (all) break;
     }
   }
+  if (prof_kept >= 0) { ctx->prof[prof_kept].work = steps_run; mia_prof_end(ctx, prof_kept); }
   if (prof_rec >= 0) { ctx->prof[prof_rec].work = steps_run; mia_prof_end(ctx, prof_rec); }
   dec_launch_finalize(w, w->out_n, p, s);
   MIA_HIP(ctx, hipGetLastError());
@@ -436,6 +477,7 @@ extern "C" int mia_whisper_align(mia_whisper* w, const int32_t* tokens, int stri
 
   DecodeParams p{};
   p.B = B; p.V = d.n_vocab; p.D = d.n_text_state; p.H = H; p.L = L; p.n_ctx = C; p.packed = w->use_packed ? w->q_bits : 0;
+  dec_cache_policy(w, p);
   AlignHook hook; hook.qk = d_qk; hook.head_slot = d_slot; hook.n_slots = n_heads; hook.n_tok = d_ntok; hook.probs = d_probs; hook.eot = eot;
   // teacher-forced pass, one position per step (clips that have consumed their last token idle at it)
   for (int step = 0; step < max_tok; ++step)
@@ -467,7 +509,9 @@ extern "C" int mia_whisper_align(mia_whisper* w, const int32_t* tokens, int stri
 // ---- test hooks ---------------------------------------------------------------------------------------------------------------------
 extern "C" int mia_whisper_set_debug(mia_whisper* w, int flags) {
   if (!w) return MIA_ERR_MODEL_NOT_LOADED;
-  MIA_CHECK_ARG(w->ctx, flags >= 0 && flags <= 7, "set_debug: flags must be 0..7 (got %d)", flags);
+  // bits 0..2 and bit 4; bit 3 is not a hook and stays rejected.  Every flag reaches the step through DecodeParams (or skips the graph),
+  // so a change re-captures the step graph at the next decode.
+  MIA_CHECK_ARG(w->ctx, flags >= 0 && (flags & ~23) == 0, "set_debug: flags must be a combination of 1, 2, 4 and 16 (got %d)", flags);
   w->debug_flags = flags;
   return MIA_OK;
 }
@@ -567,10 +611,12 @@ extern "C" int mia_whisper_set_encode_stream(mia_whisper* w, void* hip_stream) {
   return MIA_OK;
 }
 
-// Several handles on one weight copy (mia_whisper_clone) decoding at the same time: the step's weight loads then use the default cache
-// policy, so that the loops that read a matrix second and third find it in the Infinity Cache; a lone decode loop streams its weights
-// non-temporal (316 MB per step cycle through a 256 MB cache without a hit and only evict what the chain needs).  Measured, large-v3-turbo,
-// 32 clips: three concurrent loops 4 715 -> 4 820 audio-s/s with sharing on; one loop 0.407 -> 0.423 ms per step with it on.
+// Several handles on one weight copy (mia_whisper_clone) decoding at the same time.  The hint once chose ONE policy for every weight
+// load of the step: default (cacheable) for shared copies, so that the loops that read a matrix second and third find it in the
+// Infinity Cache, non-temporal for a lone loop.  Measured then, large-v3-turbo, 32 clips: three concurrent loops 4 715 -> 4 820
+// audio-s/s with sharing on; one loop 0.407 -> 0.423 ms per step with it on (316 MB of layers + vocabulary matrix cycle through the
+// 256 MiB cache without a hit).  With the policies split per launch (dec_cache_policy) the 183.5 MB of layer weights do stay, for one
+// loop and for three, and the hint selects nothing on a model that fits; it still decides the weight loads of a model that does not fit, and under debug bit 4.
 extern "C" int mia_whisper_set_weight_sharing(mia_whisper* w, int concurrent_readers) {
   if (!w) return MIA_ERR_MODEL_NOT_LOADED;
   const int on = concurrent_readers > 1 ? 1 : 0;

@@ -264,8 +264,8 @@ extern "C" int mia_whisper_attach_quantized(mia_whisper* w, const mia_tensor_vie
   return MIA_OK;
 }
 
-// The step's GEMMs read the packed weights (1) or the 16-bit copy (0, the default).  Packed loads follow mia_whisper_set_weight_sharing
-// like the 16-bit ones.  Takes effect at the next decode (the step graph is re-captured: DecodeParams::packed).
+// The step's GEMMs read the packed weights (1) or the 16-bit copy (0, the default).  Packed loads take their cache policy from the same rule
+// as the 16-bit ones (whisper_decode.hip: dec_cache_policy; q4 and q8 of large-v3-turbo fit the budget whole and are kept).  Takes effect at the next decode (the step graph is re-captured: DecodeParams::packed).
 extern "C" int mia_whisper_use_packed(mia_whisper* w, int on) {
   if (!w) return MIA_ERR_MODEL_NOT_LOADED;
   MIA_CHECK_ARG(w->ctx, !on || w->q_bits != 0, "whisper_use_packed: no packed weights attached (mia_whisper_attach_quantized)");

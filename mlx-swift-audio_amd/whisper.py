@@ -115,13 +115,16 @@ class WhisperModel:
         self.ctx.check(lib.mia_whisper_set_gemm_variant(self.h, int(variant)))
 
     def set_debug(self, flags: int) -> None:
-        """Test hook (mia_whisper_set_debug): bit 0 = no hipGraph, bit 1 = one-workgroup head, bit 2 = split reduce + LayerNorm chain (no carried LayerNorm)."""
+        """Test hook (mia_whisper_set_debug): bit 0 = no hipGraph, bit 1 = one-workgroup head, bit 2 = split reduce + LayerNorm chain (no carried LayerNorm),
+        bit 4 (16) = the step's earlier cache policies (every weight load follows set_weight_sharing, self K/V default)."""
         lib = self.ctx.lib
         self.ctx.check(lib.mia_whisper_set_debug(self.h, int(flags)))
 
     def set_weight_sharing(self, concurrent_readers: int) -> None:
-        """mia_whisper_set_weight_sharing: > 1 when clones of these weights decode concurrently on other streams (the step then loads
-        its weights cacheable); 1 restores the lone-loop (non-temporal) form.  Results are bit-identical."""
+        """mia_whisper_set_weight_sharing: > 1 when clones of these weights decode concurrently on other streams ; 1 restores the
+        lone-loop form.  Selects nothing while the decoder layers' weights fit the Infinity Cache budget (the step keeps them resident
+        either way); otherwise, and under set_debug(16), the step loads its weights cacheable when > 1, non-temporal when 1.  Results
+        are bit-identical."""
         lib = self.ctx.lib
         self.ctx.check(lib.mia_whisper_set_weight_sharing(self.h, int(concurrent_readers)))
 
