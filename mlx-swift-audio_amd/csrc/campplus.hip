@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "codec.h"
+#include "frontend_tables.h"
 #include "mia_device.h"
 #include "mia_internal.h"
 #include "tensor_loader.h"
@@ -315,39 +316,16 @@ extern "C" mia_campplus* mia_campplus_load(mia_ctx* ctx, const mia_tensor_view* 
   Loader L; L.m = m; L.tl.allocs = &m->allocs; L.tl.index(tensors, n_tensors);
   // ---- front-end tables: Povey window, zero-padded 512-point DFT basis restricted to the 400 live samples, HTK triangles
   {
-    std::vector<float> win(FB_WIN);
-    for (int i = 0; i < FB_WIN; ++i) win[i] = powf(0.5f - 0.5f * cosf(2.0f * (float)M_PI * (float)i / (float)(FB_WIN - 1)), 0.85f);
+    std::vector<float> win, dft, dense, w;
+    std::vector<int> meta;
+    fe::povey_window(FB_WIN, win);
+    fe::dft_rows(FB_NFFT, FB_NBIN, FB_NBP, FB_WIN, FB_K, nullptr, dft);
+    fe::htk_bin_filters(FB_NMEL, FB_NBIN, 16000.0f, FB_NFFT, 20.0f, 8000.0f, dense);
+    fe::compact_filters(dense, FB_NMEL, FB_NBIN, w, meta);
     m->window = L.tl.up(win);
-    std::vector<float> dft((size_t)2 * FB_NBP * FB_K, 0.f);
-    for (int k = 0; k < FB_NBIN; ++k)
-      for (int n = 0; n < FB_WIN; ++n) {
-        const double ang = 2.0 * M_PI * (double)((k * n) % FB_NFFT) / (double)FB_NFFT;
-        dft[(size_t)k * FB_K + n] = (float)cos(ang);
-        dft[(size_t)(FB_NBP + k) * FB_K + n] = (float)-sin(ang);
-      }
     m->dft = L.tl.up(dft);
-    auto hz_to_mel = [](float hz) { return 2595.0f * log10f(1.0f + hz / 700.0f); };
-    auto mel_to_hz = [](float mel) { return 700.0f * (powf(10.0f, mel / 2595.0f) - 1.0f); };
-    const float mel_min = hz_to_mel(20.0f), mel_max = hz_to_mel(8000.0f);
-    std::vector<int> bins(FB_NMEL + 2);
-    for (int i = 0; i < FB_NMEL + 2; ++i) bins[i] = (int)roundf(mel_to_hz(mel_min + (float)i * (mel_max - mel_min) / (float)(FB_NMEL + 1)) * (float)FB_NFFT / 16000.0f);
-    std::vector<float> w; std::vector<int> meta(FB_NMEL * 3);
-    for (int q = 1; q <= FB_NMEL; ++q) {
-      const int lo = bins[q - 1], c = bins[q], hi = bins[q + 1];
-      std::vector<float> row(FB_NBIN, 0.f);
-      if (c != lo) for (int k = lo; k < c; ++k) if (k >= 0 && k < FB_NBIN) row[k] = (float)(k - lo) / (float)(c - lo);
-      if (hi != c) for (int k = c; k < hi; ++k) if (k >= 0 && k < FB_NBIN) row[k] = (float)(hi - k) / (float)(hi - c);
-      int first = -1, last = -2;
-      for (int k = 0; k < FB_NBIN; ++k) if (row[k] != 0.f) { if (first < 0) first = k; last = k; }
-      if (first < 0) { first = 0; last = -1; }
-      meta[(q - 1) * 3] = first; meta[(q - 1) * 3 + 1] = last - first + 1; meta[(q - 1) * 3 + 2] = (int)w.size();
-      for (int k = first; k <= last; ++k) w.push_back(row[k]);
-    }
-    if (w.empty()) w.push_back(0.f);
     m->fb_w = L.tl.up(w);
-    std::vector<float> metaf(meta.size());
-    memcpy(metaf.data(), meta.data(), meta.size() * 4);
-    m->fb_meta = (int*)L.tl.up(metaf);
+    m->fb_meta = (int*)L.tl.put(meta.data(), meta.size() * sizeof(int));
   }
   // ---- FCM
   L.conv2("head.conv1", "head.bn1", 1, 3, m->conv1);

@@ -17,7 +17,6 @@
 #include "sensevoice.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <mutex>
 
 namespace {
@@ -145,39 +144,20 @@ __global__ __launch_bounds__(256) void fa_lfr_norm(const float* __restrict__ mel
 
 struct FaTables { float* window; float* twiddle; float* fb_w; int* fb_meta; int fb_nnz; };
 
-// built once per context, freed with it (ctx->table_allocs)
-int fa_tables(mia_ctx* ctx, FaTables** out) {
-  if (ctx->funasr_tables) { *out = (FaTables*)ctx->funasr_tables; return MIA_OK; }
-  std::vector<float> win, dense, w;
-  std::vector<int> meta;
-  hamming_window(win);
-  mel_filters(dense);
-  compact_filters(dense, w, meta);
-  if ((int)w.size() > MAX_NNZ) return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "funasr front end: filterbank has %zu non-zeros (> %d)", w.size(), MAX_NNZ);
-  std::vector<float> tw((size_t)NFFT * 2 * NBP, 0.0f);
-  for (int k = 0; k < NFFT; ++k)
-    for (int j = 0; j < NFREQ; ++j) {
-      const int r = (int)(((int64_t)k * j) % NFFT);            // exact argument reduction
-      const double ang = 2.0 * M_PI * (double)r / (double)NFFT;
-      tw[((size_t)k * 2 + 0) * NBP + j] = (float)cos(ang);
-      tw[((size_t)k * 2 + 1) * NBP + j] = (float)sin(ang);
-    }
-  FaTables* t = (FaTables*)malloc(sizeof(FaTables));      // freed by mia_destroy
-  if (!t) return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "funasr front end: out of host memory");
-  t->fb_nnz = (int)w.size();
-  void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-  const size_t bytes[4] = {win.size() * 4, tw.size() * 4, w.size() * 4, meta.size() * 4};
-  const void* src[4] = {win.data(), tw.data(), w.data(), meta.data()};
-  for (int i = 0; i < 4; ++i) {
-    if (hipMalloc(&p[i], bytes[i]) != hipSuccess) { for (int j = 0; j < i; ++j) (void)hipFree(p[j]); free(t); return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "funasr front end: table allocation failed"); }
-    (void)hipMemcpyAsync(p[i], src[i], bytes[i], hipMemcpyHostToDevice, ctx->stream);
+int fa_tables(mia_ctx* ctx, FaTables& out) {
+  const mia_table_key key{MIA_TAB_FUNASR, 0, 0};
+  const mia_tables* t = mia_tables_find(ctx, key);
+  if (!t) {
+    std::vector<float> win, tw, dense, w;
+    std::vector<int> meta;
+    hamming_window(win);
+    fe::twiddle_400(NFREQ, NBP, tw);
+    mel_filters(dense);
+    fe::compact_filters(dense, NMEL, NFREQ, w, meta);
+    if ((int)w.size() > MAX_NNZ) return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "funasr front end: filterbank has %zu non-zeros (> %d)", w.size(), MAX_NNZ);
+    if (int rc = mia_tables_build(ctx, key, {win, tw, w, meta}, {(int)w.size()}, &t)) return rc;
   }
-  const hipError_t e = hipStreamSynchronize(ctx->stream);     // the host vectors die with this call
-  for (int i = 0; i < 4; ++i) ctx->table_allocs.push_back(p[i]);
-  t->window = (float*)p[0]; t->twiddle = (float*)p[1]; t->fb_w = (float*)p[2]; t->fb_meta = (int*)p[3];
-  ctx->funasr_tables = t;
-  *out = t;
-  MIA_HIP(ctx, e);
+  out = FaTables{(float*)t->dev[0], (float*)t->dev[1], (float*)t->dev[2], (int*)t->dev[3], t->meta[0]};
   return MIA_OK;
 }
 
@@ -209,8 +189,8 @@ size_t funasr_scratch_bytes(const FunasrPlan& plan) {
 // pcm_dev: the clips back to back (device); feats_dev fp32 [plan.rows][stride]; scratch: funasr_scratch_bytes(plan) bytes (device)
 int funasr_features_device(mia_ctx* ctx, const float* pcm_dev, const int64_t* offs, const FunasrPlan& plan, float* feats_dev, int64_t stride, void* scratch) {
   MIA_CHECK_ARG(ctx, stride >= FEAT, "sensevoice_features: stride must be >= %d", FEAT);
-  FaTables* tb = nullptr;
-  int rc = fa_tables(ctx, &tb);
+  FaTables tb;
+  int rc = fa_tables(ctx, tb);
   if (rc != MIA_OK) return rc;
   const int B = plan.B;
   std::vector<FaClip> clips(B);
@@ -236,8 +216,8 @@ int funasr_features_device(mia_ctx* ctx, const float* pcm_dev, const int64_t* of
   double bytes = (double)plan.rows * FEAT * 4.0;
   for (int b = 0; b < B; ++b) bytes += (double)clips[b].len * 4.0;
   const int rec = mia_prof_begin(ctx, MIA_PROF_LOGMEL, bytes);
-  hipLaunchKernelGGL(fa_logmel, dim3((unsigned)((plan.max_frames + FB - 1) / FB), (unsigned)B), dim3(256), LOGMEL_LDS, st, pcm_dev, d_clips, tb->window,
-                     tb->twiddle, tb->fb_w, tb->fb_meta, tb->fb_nnz, d_mel);
+  hipLaunchKernelGGL(fa_logmel, dim3((unsigned)((plan.max_frames + FB - 1) / FB), (unsigned)B), dim3(256), LOGMEL_LDS, st, pcm_dev, d_clips, tb.window,
+                     tb.twiddle, tb.fb_w, tb.fb_meta, tb.fb_nnz, d_mel);
   hipLaunchKernelGGL(fa_lfr_stats, dim3((FEAT + 63) / 64, (unsigned)B), dim3(256), 0, st, d_mel, d_clips, d_stats);
   const unsigned gx = (unsigned)std::min<int64_t>(((int64_t)max_lfr * FEAT + 255) / 256, 1024);
   hipLaunchKernelGGL(fa_lfr_norm, dim3(gx, (unsigned)B), dim3(256), 0, st, d_mel, d_clips, d_stats, feats_dev, stride);

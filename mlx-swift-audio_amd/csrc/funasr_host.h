@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/mia.h"
+#include "frontend_tables.h"      // the twiddles and the compact filter form, shared with the other front ends
 
 namespace funasr {
 
@@ -34,21 +35,6 @@ inline void mel_filters(std::vector<float>& dense) {
       dense[(size_t)m * NFREQ + k] = (float)w;
     }
   }
-}
-
-// dense rows -> the compact form the kernel stages: per filter (first bin, count, offset), weights of [first, first + count)
-inline void compact_filters(const std::vector<float>& dense, std::vector<float>& w, std::vector<int>& meta) {
-  w.clear();
-  meta.assign((size_t)NMEL * 3, 0);
-  for (int m = 0; m < NMEL; ++m) {
-    int lo = -1, hi = -1;
-    for (int k = 0; k < NFREQ; ++k)
-      if (dense[(size_t)m * NFREQ + k] != 0.0f) { if (lo < 0) lo = k; hi = k; }
-    if (lo < 0) { lo = 0; hi = -1; }
-    meta[m * 3 + 0] = lo; meta[m * 3 + 1] = hi - lo + 1; meta[m * 3 + 2] = (int)w.size();
-    for (int k = lo; k <= hi; ++k) w.push_back(dense[(size_t)m * NFREQ + k]);
-  }
-  if (w.empty()) w.push_back(0.0f);
 }
 
 inline int64_t n_frames(int64_t n_samples) { return 1 + n_samples / HOP; }                       // :262 after the 200 + 200 reflect pad

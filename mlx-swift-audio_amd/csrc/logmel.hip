@@ -20,6 +20,7 @@
 //   max(rnd((v+4)/4), rnd((c+4)/4)) == rnd((max(v, c)+4)/4), so logmel_clampfix rewrites -- in place, in the output type -- only the
 //   32-frame blocks whose smallest value lies below the clip's floor (pass 1 records each block's minimum) plus the rows past the audio.
 //   Traffic: audio once + output once (+ the few blocks that need the clamp) instead of + an fp32 mel tensor written and read back.
+#include "frontend_tables.h"
 #include "mia_device.h"
 #include "mia_internal.h"
 
@@ -228,85 +229,23 @@ __global__ __launch_bounds__(256) void logmel_pass2(const float* __restrict__ tm
   }
 }
 
-// ---- host-side table construction (fp32 scalar math, mirrors S3TokenizerUtils.swift:301-375) ------
-void build_mel_filters(int n_mels, std::vector<float>& dense) {
-  const float f_sp = 200.0f / 3.0f, min_log_hz = 1000.0f;
-  const float min_log_mel = min_log_hz / f_sp;
-  const float logstep = logf(6.4f) / 27.0f;
-  auto hz_to_mel = [&](float hz) { return hz >= min_log_hz ? min_log_mel + logf(hz / min_log_hz) / logstep : hz / f_sp; };
-  auto mel_to_hz = [&](float mel) { return mel >= min_log_mel ? min_log_hz * expf(logstep * (mel - min_log_mel)) : f_sp * mel; };
-  const float mel_min = hz_to_mel(0.0f), mel_max = hz_to_mel(8000.0f);
-  std::vector<float> pts(n_mels + 2);
-  for (int i = 0; i < n_mels + 2; ++i) pts[i] = mel_to_hz(mel_min + (float)i * (mel_max - mel_min) / (float)(n_mels + 1));
-  dense.assign((size_t)n_mels * NBIN, 0.0f);
-  for (int m = 0; m < n_mels; ++m) {
-    const float fl = pts[m], fc = pts[m + 1], fr = pts[m + 2];
-    const float enorm = 2.0f / (pts[m + 2] - pts[m]);
-    for (int k = 0; k < NBIN; ++k) {
-      const float freq = (float)k * 16000.0f / (float)NFFT;
-      float w = 0.0f;
-      if (freq >= fl && freq <= fc) w = (freq - fl) / (fc - fl);
-      else if (freq > fc && freq <= fr) w = (fr - freq) / (fr - fc);
-      dense[(size_t)m * NBIN + k] = w * enorm;
-    }
-  }
-}
+struct MelTables { const float* window; const float* twiddle; const float* fb_w; const int* fb_meta; int fb_nnz; };
 
 // window_kind 0: Whisper symmetric Hann (WhisperAudio.swift:32-44); 1: periodic Hann (S3TokenizerUtils.swift:117,213-221)
-int get_tables(mia_ctx* ctx, int n_mels, int window_kind, mia_ctx::MelTables** out) {
-  for (auto& t : ctx->mel_tables)
-    if (t.n_mels == n_mels && t.window_kind == window_kind) { *out = &t; return MIA_OK; }
-  mia_ctx::MelTables t;
-  t.n_mels = n_mels;
-  t.window_kind = window_kind;
-  std::vector<float> win(NFFT);
-  if (window_kind == 0) {
-    const float factor = 2.0f * (float)M_PI / (float)(NFFT - 1);
-    for (int n = 0; n < NFFT; ++n) win[n] = 0.5f * (1.0f - cosf((float)n * factor));
-  } else {
-    const int Lw = NFFT + 1;
-    const float factor = (float)M_PI / (float)(Lw - 1);
-    for (int n = 0; n < NFFT; ++n) win[n] = 0.5f + 0.5f * cosf((float)(1 - Lw + 2 * n) * factor);
+int get_tables(mia_ctx* ctx, int n_mels, int window_kind, MelTables& out) {
+  const mia_table_key key{MIA_TAB_LOGMEL, n_mels, window_kind};
+  const mia_tables* t = mia_tables_find(ctx, key);
+  if (!t) {
+    std::vector<float> win, tw, dense, w;
+    std::vector<int> meta;
+    if (window_kind == 0) fe::hann_symmetric(NFFT, win); else fe::hann_periodic(NFFT, win);
+    fe::twiddle_400(NBIN, NBP, tw);
+    fe::slaney_filters(n_mels, NBIN, 16000.0f, NFFT, 8000.0f, dense);
+    fe::compact_filters(dense, n_mels, NBIN, w, meta);
+    if ((int)w.size() > MAX_NNZ) return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "filterbank has %zu non-zeros (> %d)", w.size(), MAX_NNZ);
+    if (int rc = mia_tables_build(ctx, key, {win, tw, w, meta}, {(int)w.size()}, &t)) return rc;
   }
-  std::vector<float> tw((size_t)NFFT * 2 * NBP, 0.0f);
-  for (int k = 0; k < NFFT; ++k)
-    for (int j = 0; j < NBIN; ++j) {
-      const int r = (int)(((int64_t)k * j) % NFFT);            // exact argument reduction
-      const double ang = 2.0 * M_PI * (double)r / (double)NFFT;
-      tw[((size_t)k * 2 + 0) * NBP + j] = (float)cos(ang);
-      tw[((size_t)k * 2 + 1) * NBP + j] = (float)sin(ang);
-    }
-  std::vector<float> dense;
-  build_mel_filters(n_mels, dense);
-  std::vector<float> w;
-  std::vector<int> meta((size_t)n_mels * 3);
-  for (int m = 0; m < n_mels; ++m) {
-    int lo = -1, hi = -1;
-    for (int k = 0; k < NBIN; ++k)
-      if (dense[(size_t)m * NBIN + k] != 0.0f) { if (lo < 0) lo = k; hi = k; }
-    if (lo < 0) { lo = 0; hi = -1; }
-    meta[m * 3 + 0] = lo;
-    meta[m * 3 + 1] = hi - lo + 1;
-    meta[m * 3 + 2] = (int)w.size();
-    for (int k = lo; k <= hi; ++k) w.push_back(dense[(size_t)m * NBIN + k]);
-  }
-  if ((int)w.size() > MAX_NNZ) return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "filterbank has %zu non-zeros (> %d)", w.size(), MAX_NNZ);
-  if (w.empty()) w.push_back(0.0f);
-  t.fb_nnz = (int)w.size();
-  MIA_HIP(ctx, hipMalloc(&t.window, NFFT * sizeof(float)));
-  MIA_HIP(ctx, hipMalloc(&t.twiddle, tw.size() * sizeof(float)));
-  MIA_HIP(ctx, hipMalloc(&t.fb_w, w.size() * sizeof(float)));
-  MIA_HIP(ctx, hipMalloc(&t.fb_meta, meta.size() * sizeof(int)));
-  // uploads go through the context's OWN stream: a synchronous hipMemcpy runs on the legacy stream, which is illegal while another host
-  // thread captures a step graph on a blocking stream (bench.py's replicas; seen as "operation would make the legacy stream depend on a
-  // capturing blocking stream" in a 2-rank rehearsal)
-  MIA_HIP(ctx, hipMemcpyAsync(t.window, win.data(), NFFT * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  MIA_HIP(ctx, hipMemcpyAsync(t.twiddle, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  MIA_HIP(ctx, hipMemcpyAsync(t.fb_w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-  MIA_HIP(ctx, hipMemcpyAsync(t.fb_meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-  MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->mel_tables.push_back(t);
-  *out = &ctx->mel_tables.back();
+  out = MelTables{(const float*)t->dev[0], (const float*)t->dev[1], (const float*)t->dev[2], (const int*)t->dev[3], t->meta[0]};
   return MIA_OK;
 }
 
@@ -352,8 +291,8 @@ int mia_logmel_device(mia_ctx* ctx, const float* pcm_dev, const int64_t* offs_ho
     if (fc > ft) fc = ft;
     if (fc > max_content) max_content = fc;
   }
-  mia_ctx::MelTables* tb = nullptr;
-  int rc = get_tables(ctx, n_mels, window_kind, &tb);
+  MelTables tb;
+  int rc = get_tables(ctx, n_mels, window_kind, tb);
   if (rc != MIA_OK) return rc;
 
   char* s = (char*)scratch;
@@ -384,7 +323,7 @@ int mia_logmel_device(mia_ctx* ctx, const float* pcm_dev, const int64_t* offs_ho
   const bool direct = !channel_major && col_stride == 1;
 #define LAUNCH1(T, D)                                                                                                        \
   hipLaunchKernelGGL((logmel_pass1<T, D>), dim3(nblk1, (unsigned)B), dim3(256), PASS1_LDS, ctx->stream, pcm_dev, d_clips, pad_right, n_out, \
-                     n_mels, tb->window, tb->twiddle, tb->fb_w, tb->fb_meta, tb->fb_nnz, d_tmp, d_gmax, out_dev, clip_stride, row_stride, row_off)
+                     n_mels, tb.window, tb.twiddle, tb.fb_w, tb.fb_meta, tb.fb_nnz, d_tmp, d_gmax, out_dev, clip_stride, row_stride, row_off)
   if (max_content > 0) {
     if (!direct) LAUNCH1(float, false);
     else if (out_dtype == MIA_F32) LAUNCH1(float, true);

@@ -9,10 +9,10 @@
 // the bins the filterbank touches (k <= 640: 8 kHz), cosine rows then sine rows.  A small kernel takes magnitudes, applies the
 // sparse filterbank rows and the log.  This runs once per prompt (CosyVoice2TTS.swift:370-430), not per utterance.
 #include <cmath>
-#include <cstdlib>
 #include <vector>
 
 #include "codec.h"
+#include "frontend_tables.h"
 #include "mia_device.h"
 #include "mia_internal.h"
 
@@ -50,63 +50,20 @@ __global__ __launch_bounds__(256) void mel24_finish(const float* __restrict__ sp
   out[(int64_t)m * F + f] = logf(fmaxf(acc, 1e-5f));
 }
 
-int get_tables(mia_ctx* ctx, S3GenMelTables** out) {
-  if (ctx->s3gen_mel) { *out = (S3GenMelTables*)ctx->s3gen_mel; return MIA_OK; }
-  // filterbank: fp32 scalar math like the reference (S3TokenizerUtils.swift:301-375), fMin 0, fMax 8000
-  const float f_sp = 200.0f / 3.0f, min_log_hz = 1000.0f, min_log_mel = min_log_hz / f_sp, logstep = logf(6.4f) / 27.0f;
-  auto hz_to_mel = [&](float hz) { return hz >= min_log_hz ? min_log_mel + logf(hz / min_log_hz) / logstep : hz / f_sp; };
-  auto mel_to_hz = [&](float mel) { return mel >= min_log_mel ? min_log_hz * expf(logstep * (mel - min_log_mel)) : f_sp * mel; };
-  const float mel_min = hz_to_mel(0.0f), mel_max = hz_to_mel(8000.0f);
-  std::vector<float> pts(NMEL + 2);
-  for (int i = 0; i < NMEL + 2; ++i) pts[i] = mel_to_hz(mel_min + (float)i * (mel_max - mel_min) / (float)(NMEL + 1));
-  std::vector<float> w; std::vector<int> meta(NMEL * 3);
-  int kmax = 0;
-  for (int m = 0; m < NMEL; ++m) {
-    const float fl = pts[m], fc = pts[m + 1], fr = pts[m + 2], enorm = 2.0f / (pts[m + 2] - pts[m]);
-    int lo = -1, hi = -1; std::vector<float> row(NBIN, 0.f);
-    for (int k = 0; k < NBIN; ++k) {
-      const float freq = (float)k * (float)SR / (float)NFFT;
-      float v = 0.f;
-      if (freq >= fl && freq <= fc) v = (freq - fl) / (fc - fl);
-      else if (freq > fc && freq <= fr) v = (fr - freq) / (fr - fc);
-      row[k] = v * enorm;
-      if (row[k] != 0.f) { if (lo < 0) lo = k; hi = k; }
-    }
-    if (lo < 0) { lo = 0; hi = -1; }
-    meta[m * 3] = lo; meta[m * 3 + 1] = hi - lo + 1; meta[m * 3 + 2] = (int)w.size();
-    for (int k = lo; k <= hi; ++k) w.push_back(row[k]);
-    if (hi > kmax) kmax = hi;
+int get_tables(mia_ctx* ctx, S3GenMelTables& out) {
+  const mia_table_key key{MIA_TAB_S3GEN_MEL, 0, 0};
+  const mia_tables* t = mia_tables_find(ctx, key);
+  if (!t) {
+    std::vector<float> win, dense, w, dft;
+    std::vector<int> meta;
+    fe::slaney_filters(NMEL, NBIN, (float)SR, NFFT, 8000.0f, dense);      // fMin 0, fMax 8000
+    fe::compact_filters(dense, NMEL, NBIN, w, meta);
+    const int kmax = fe::last_live_bin(meta), nbp = (kmax + 1 + 31) / 32 * 32;
+    fe::hann_periodic(NFFT, win);                                          // hanningWindow(1921)[0..<1920]
+    fe::dft_rows(NFFT, kmax + 1, nbp, NFFT, NFFT, win.data(), dft);
+    if (int rc = mia_tables_build(ctx, key, {dft, w, meta}, {nbp, (int)w.size()}, &t)) return rc;
   }
-  const int nbp = (kmax + 1 + 31) / 32 * 32;
-  // Hann-windowed DFT basis rows: [2 nbp][1920]; window = hanningWindow(1921)[0..<1920] in fp32 (S3TokenizerUtils.swift:213-221)
-  std::vector<float> dft((size_t)2 * nbp * NFFT, 0.f);
-  const float factor = (float)M_PI / (float)NFFT;
-  for (int k = 0; k <= kmax; ++k)
-    for (int n = 0; n < NFFT; ++n) {
-      const float win = 0.5f + 0.5f * cosf((float)(1 - (NFFT + 1) + 2 * n) * factor);
-      const int r = (int)(((int64_t)k * n) % NFFT);
-      const double ang = 2.0 * M_PI * (double)r / (double)NFFT;
-      dft[(size_t)k * NFFT + n] = (float)(cos(ang) * (double)win);
-      dft[(size_t)(nbp + k) * NFFT + n] = (float)(-sin(ang) * (double)win);
-    }
-  S3GenMelTables* t = (S3GenMelTables*)calloc(1, sizeof(S3GenMelTables));
-  if (!t) return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "mel_s3gen: host allocation failed");
-  t->nbp = nbp; t->nnz = (int)w.size();
-  void* p[3] = {nullptr, nullptr, nullptr};
-  const size_t bytes[3] = {dft.size() * 4, w.size() * 4, meta.size() * 4};
-  const void* src[3] = {dft.data(), w.data(), meta.data()};
-  for (int i = 0; i < 3; ++i) {
-    if (hipMalloc(&p[i], bytes[i] + 64) != hipSuccess || hipMemcpyAsync(p[i], src[i], bytes[i], hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess) {     // the context's own stream, never the legacy stream (see logmel.hip)
-      for (int j = 0; j <= i; ++j) if (p[j]) (void)hipFree(p[j]);
-      free(t);
-      return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "mel_s3gen: table upload failed");
-    }
-  }
-  for (int i = 0; i < 3; ++i) ctx->table_allocs.push_back(p[i]);
-  t->dft = (float*)p[0]; t->fb_w = (float*)p[1]; t->fb_meta = (int*)p[2];
-  ctx->s3gen_mel = t;
-  *out = t;
+  out = S3GenMelTables{(float*)t->dev[0], (float*)t->dev[1], (int*)t->dev[2], t->meta[0], t->meta[1]};
   return MIA_OK;
 }
 
@@ -124,13 +81,13 @@ extern "C" int mia_mel_s3gen(mia_ctx* ctx, const float* pcm, int64_t n_samples, 
   const int64_t F = mia_mel_s3gen_frames(n_samples);
   MIA_CHECK_ARG(ctx, F > 0, "mel_s3gen: input too short for one frame");
   MIA_HIP(ctx, hipSetDevice(ctx->device));
-  S3GenMelTables* tb = nullptr;
-  if (int rc = get_tables(ctx, &tb)) return rc;
+  S3GenMelTables tb;
+  if (int rc = get_tables(ctx, tb)) return rc;
   hipStream_t s = ctx->stream;
   const int64_t Tp = n_samples + 2 * PAD;
   const int64_t rows = (Tp + 31) / 32 + 1;
   HostIo io(ctx, mem);
-  const size_t n_xp = (size_t)rows * 32, n_spec = (size_t)F * 2 * tb->nbp, n_out = (size_t)F * NMEL;
+  const size_t n_xp = (size_t)rows * 32, n_spec = (size_t)F * 2 * tb.nbp, n_out = (size_t)F * NMEL;
   Carve cv;
   const size_t o_in = cv.add(io.staged((size_t)n_samples * 4)), o_xp = cv.add(n_xp * 4), o_spec = cv.add(n_spec * 4), o_out = cv.add(io.staged(n_out * 4));
   char* ws = (char*)mia_workspace(ctx, cv.bytes);
@@ -139,12 +96,12 @@ extern "C" int mia_mel_s3gen(mia_ctx* ctx, const float* pcm, int64_t n_samples, 
   const float* x = io.in(pcm, ws + o_in, (size_t)n_samples * 4);
   hipLaunchKernelGGL(mel24_reflect_pad, dim3((unsigned)((n_xp + 255) / 256)), dim3(256), 0, s, x, xp, n_samples, (int64_t)n_xp);
   ConvGemmArgs g;
-  g.X = xp; g.ldx = 32; g.T_in = (int)rows; g.W = tb->dft; g.Y = spec; g.ldy = 2 * tb->nbp; g.T_out = (int)F;
-  g.M = (int)F; g.N = 2 * tb->nbp; g.Cin = 32; g.taps = NFFT / 32; g.x_row_mul = HOP / 32;
+  g.X = xp; g.ldx = 32; g.T_in = (int)rows; g.W = tb.dft; g.Y = spec; g.ldy = 2 * tb.nbp; g.T_out = (int)F;
+  g.M = (int)F; g.N = 2 * tb.nbp; g.Cin = 32; g.taps = NFFT / 32; g.x_row_mul = HOP / 32;
   if (const char* e = codec_conv_gemm_check(g)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "mel_s3gen: %s", e);
   if (codec_conv_gemm_launch(g, 1, s)) return mia_fail(ctx, MIA_ERR_DEVICE, "mel_s3gen: GEMM launch failed");
   float* dst = io.out(mel, ws + o_out, n_out * 4);
-  hipLaunchKernelGGL(mel24_finish, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, spec, tb->fb_w, tb->fb_meta, dst, (int)F, tb->nbp);
+  hipLaunchKernelGGL(mel24_finish, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, spec, tb.fb_w, tb.fb_meta, dst, (int)F, tb.nbp);
   MIA_HIP(ctx, hipGetLastError());
   return io.finish();
 }

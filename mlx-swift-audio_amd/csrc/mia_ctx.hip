@@ -1,5 +1,5 @@
 // mia_ctx.hip -- context lifecycle for the C ABI (include/mia.h).
-#include <cstdlib>
+#include <algorithm>
 #include "codec.h"
 #include "mia_internal.h"
 
@@ -43,17 +43,8 @@ extern "C" void mia_destroy(mia_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
   (void)mia_dp_shutdown(ctx);
-  for (auto& t : ctx->mel_tables) {
-    (void)hipFree(t.window);
-    (void)hipFree(t.twiddle);
-    (void)hipFree(t.fb_w);
-    (void)hipFree(t.fb_meta);
-  }
-  for (void* p : ctx->table_allocs) (void)hipFree(p);
-  if (ctx->s3gen_mel) free(ctx->s3gen_mel);
-  if (ctx->funasr_tables) free(ctx->funasr_tables);
-  if (ctx->speaker_tables) free(ctx->speaker_tables);
-  mia_resampler_free(ctx);
+  for (auto& t : ctx->tables)
+    for (void* p : t.dev) (void)hipFree(p);
   for (auto& r : ctx->prof) { (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); }
   for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
   if (ctx->ws) (void)hipFree(ctx->ws);
@@ -85,6 +76,39 @@ void* mia_workspace(mia_ctx* ctx, size_t bytes) {
   }
   ctx->ws_bytes = want;
   return ctx->ws;
+}
+
+// ---- the device-table cache ------------------------------------------------------------------
+const mia_tables* mia_tables_find(const mia_ctx* ctx, mia_table_key key) {
+  for (const mia_tables& t : ctx->tables)
+    if (t.key.owner == key.owner && t.key.a == key.a && t.key.b == key.b) return &t;
+  return nullptr;
+}
+
+int mia_tables_build(mia_ctx* ctx, mia_table_key key, std::initializer_list<mia_table_src> src, std::initializer_list<int> meta, const mia_tables** out) {
+  mia_tables t{};
+  t.key = key;
+  MIA_CHECK_ARG(ctx, src.size() <= 4 && meta.size() <= 4, "table cache: a set holds at most 4 tables and 4 ints");
+  std::copy(meta.begin(), meta.end(), t.meta);
+  auto drop = [&] { for (void* p : t.dev) (void)hipFree(p); };
+  int n = 0;
+  for (const mia_table_src& s : src) {
+    if (hipMalloc(&t.dev[n], s.bytes + 64) != hipSuccess) {
+      t.dev[n] = nullptr;
+      drop();
+      return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "table cache: hipMalloc(%zu) failed", s.bytes);
+    }
+    ++n;
+  }
+  // the uploads go on the context's stream as the caller has it (the encode stream inside EncStreamScope), never on the legacy stream:
+  // a copy there is illegal while another host thread captures a step graph on a blocking stream
+  HostIo io = HostIo::device(ctx);
+  n = 0;
+  for (const mia_table_src& s : src) io.table((const char*)s.host, t.dev[n++], s.bytes);
+  if (const int rc = io.finish()) { drop(); return rc; }      // the caller's host vectors are free to die from here
+  ctx->tables.push_back(t);
+  *out = &ctx->tables.back();
+  return MIA_OK;
 }
 
 // ---- profiling -------------------------------------------------------------------------------

@@ -5,12 +5,27 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <deque>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
 #include "../../include/mia.h"
 
-struct mia_resampler_cache;
+// One cache for the context's device tables ("One table cache"): a record per (owner, a, b) holds the device pointers of one
+// set, in the order they were given to mia_tables_build, and a few host ints of the owner's choosing.  Records never move, a failed
+// build registers nothing, and mia_destroy frees them all.
+enum { MIA_TAB_LOGMEL, MIA_TAB_S3GEN_MEL, MIA_TAB_FUNASR, MIA_TAB_SPEAKER, MIA_TAB_RESAMPLE };
+struct mia_table_key { int owner, a, b; };          // a, b: what tells an owner's sets apart (0 for a singleton)
+struct mia_table_src {
+  const void* host; size_t bytes;
+  template <class T> mia_table_src(const std::vector<T>& v) : host(v.data()), bytes(v.size() * sizeof(T)) {}
+};
+struct mia_tables {
+  mia_table_key key;
+  void* dev[4];
+  int meta[4];
+};
 
 struct mia_ctx {
   int device = 0;
@@ -20,22 +35,7 @@ struct mia_ctx {
   // grow-only scratch arena in HBM (never freed between calls: no hipMalloc on the hot path)
   void* ws = nullptr;
   size_t ws_bytes = 0;
-  // cached per-n_mels front-end tables (device)
-  struct MelTables {
-    int n_mels = 0;
-    int window_kind = -1;
-    float* window = nullptr;    // [400]
-    float* twiddle = nullptr;   // [400][2][224] cos|sin
-    float* fb_w = nullptr;      // compact non-zero filter weights
-    int* fb_meta = nullptr;     // [n_mels][3] = (first bin, count, offset into fb_w)
-    int fb_nnz = 0;
-  };
-  std::vector<MelTables> mel_tables;
-  std::vector<void*> table_allocs;   // other cached device tables (freed at destroy), e.g. the 24 kHz 80-mel front end
-  void* s3gen_mel = nullptr;         // S3GenMelTables* (mel_s3gen.hip), lives in table_allocs' lifetime
-  void* funasr_tables = nullptr;     // Fun-ASR front-end tables (funasr_frontend.hip), malloc'ed; device parts in table_allocs
-  void* speaker_tables = nullptr;    // FFT twiddles and the pitch window (speaker_features.hip), malloc'ed; device parts in table_allocs
-  mia_resampler_cache* resampler = nullptr;   // per-ratio polyphase filters of mia_resample_sinc (resample.hip); device tables in table_allocs
+  std::deque<mia_tables> tables;     // a deque: push_back leaves the records where they are
   // optional HIP-event profiling of kernel classes (mia_profile_*): bench.py's roofline figures come from here
   bool prof_on = false;
   struct ProfRec { int cls; hipEvent_t start, stop; double work; };
@@ -101,6 +101,10 @@ inline size_t mia_dtype_size(int dt) { return dt == MIA_F32 ? 4 : 2; }
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-void mia_resampler_free(mia_ctx* ctx);   // resample.hip
+// The set under `key`, or nullptr when it has not been built.
+const mia_tables* mia_tables_find(const mia_ctx* ctx, mia_table_key key);
+// Allocate one device buffer per source, upload them on ctx->stream as it is now, wait, and register the set (at most 4 sources and 4
+// meta ints).  On any failure every allocation of this call is freed, nothing is registered and the next call builds again.
+int mia_tables_build(mia_ctx* ctx, mia_table_key key, std::initializer_list<mia_table_src> src, std::initializer_list<int> meta, const mia_tables** out);
 
 #include "host_io.h"   // HostIo, Carve: the staging rule of every entry point that takes `int mem`

@@ -39,11 +39,9 @@ double bessel_i0(double x) {
   return sum;
 }
 
-struct SincTable { int from, to, L, M, taps, hw; float* dev; };
+struct SincTable { int L, M, taps, hw; const float* dev; };
 
 }  // namespace
-
-struct mia_resampler_cache { std::vector<SincTable> tables; };
 
 static const double kZeros = 16.0, kRolloff = 0.945, kBeta = 8.6;
 
@@ -93,24 +91,18 @@ extern "C" int mia_resample_sinc(mia_ctx* ctx, const float* x, int64_t n_samples
   MIA_CHECK_ARG(ctx, N > 0 && out_capacity >= N, "resample_sinc: output buffer too small (%lld < %lld)", (long long)out_capacity, (long long)N);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  if (!ctx->resampler) ctx->resampler = new mia_resampler_cache();
-  SincTable* tb = nullptr;
-  for (SincTable& t : ctx->resampler->tables) if (t.from == from_rate && t.to == to_rate) tb = &t;
-  if (!tb) {
+  const mia_table_key key{MIA_TAB_RESAMPLE, from_rate, to_rate};
+  const mia_tables* t = mia_tables_find(ctx, key);
+  if (!t) {
     int L = 0, taps = 0;
     mia_resample_sinc_table(from_rate, to_rate, nullptr, 0, &L, &taps);
     MIA_CHECK_ARG(ctx, (int64_t)L * taps <= (1 << 24), "resample_sinc: ratio %d/%d needs too many filter phases", to_rate, from_rate);
     std::vector<float> host((size_t)L * taps);
     mia_resample_sinc_table(from_rate, to_rate, host.data(), (int)host.size(), nullptr, nullptr);
-    float* dev = nullptr;
-    MIA_HIP(ctx, hipMalloc((void**)&dev, host.size() * 4));
-    ctx->table_allocs.push_back(dev);
-    MIA_HIP(ctx, hipMemcpyAsync(dev, host.data(), host.size() * 4, hipMemcpyHostToDevice, s));   // own stream, never the legacy stream (see logmel.hip)
-    MIA_HIP(ctx, hipStreamSynchronize(s));
     const int g = std::gcd(from_rate, to_rate);
-    ctx->resampler->tables.push_back(SincTable{from_rate, to_rate, to_rate / g, from_rate / g, taps, (taps - 1) / 2, dev});
-    tb = &ctx->resampler->tables.back();
+    if (int rc = mia_tables_build(ctx, key, {host}, {to_rate / g, from_rate / g, taps, (taps - 1) / 2}, &t)) return rc;
   }
+  const SincTable tb{t->meta[0], t->meta[1], t->meta[2], t->meta[3], (const float*)t->dev[0]};
   HostIo io(ctx, mem);
   Carve cv;
   const size_t o_x = cv.add(io.staged((size_t)n_samples * 4)), o_o = cv.add(io.staged((size_t)N * 4));
@@ -118,14 +110,9 @@ extern "C" int mia_resample_sinc(mia_ctx* ctx, const float* x, int64_t n_samples
   if (!cv.workspace(ctx, ws)) return MIA_ERR_OUT_OF_MEMORY;
   const float* d_x = io.in(x, ws + o_x, (size_t)n_samples * 4);
   float* d_o = io.out(out, ws + o_o, (size_t)N * 4);
-  if (tb->L == 1 && tb->M == 1) MIA_HIP(ctx, hipMemcpyAsync(d_o, d_x, (size_t)N * 4, hipMemcpyDeviceToDevice, s));     // same rate: the reference returns its input
-  else hipLaunchKernelGGL(resample_sinc_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, d_x, d_o, tb->dev, n_samples, N, tb->L, tb->M, tb->taps, tb->hw);
+  if (tb.L == 1 && tb.M == 1) MIA_HIP(ctx, hipMemcpyAsync(d_o, d_x, (size_t)N * 4, hipMemcpyDeviceToDevice, s));     // same rate: the reference returns its input
+  else hipLaunchKernelGGL(resample_sinc_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, d_x, d_o, tb.dev, n_samples, N, tb.L, tb.M, tb.taps, tb.hw);
   MIA_HIP(ctx, hipGetLastError());
   if (n_out) *n_out = N;
   return io.finish();
-}
-
-void mia_resampler_free(mia_ctx* ctx) {
-  delete ctx->resampler;
-  ctx->resampler = nullptr;
 }

@@ -326,39 +326,24 @@ __global__ __launch_bounds__(64) void seg_finish_kernel(const SegRec* __restrict
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-int speaker_tables(mia_ctx* ctx, SpeakerTables** out) {
-  if (ctx->speaker_tables) { *out = (SpeakerTables*)ctx->speaker_tables; return MIA_OK; }
-  std::vector<float2> t1(kFftBlock), t2((size_t)1 << kLoBits);
-  std::vector<float> hann(kFrame);
-  for (int k = 0; k < kFftBlock; ++k) {                  // k / 2^14 of a turn: the argument is exact
-    const double ang = 2.0 * M_PI * (double)k / (double)kFftBlock;
-    t1[k] = float2{(float)cos(ang), (float)-sin(ang)};
-  }
-  for (int b = 0; b < (1 << kLoBits); ++b) {             // exp(-i t) - 1 = -2 sin^2(t / 2) - i sin t
-    const double ang = 2.0 * M_PI * (double)b / (double)(1 << kFftMaxLog2), h = sin(0.5 * ang);
-    t2[b] = float2{(float)(-2.0 * h * h), (float)-sin(ang)};
-  }
-  for (int i = 0; i < kFrame; ++i) hann[i] = (float)(kHannNorm * (1.0 - cos(2.0 * M_PI * (double)i / (double)kFrame)));
-  SpeakerTables* t = (SpeakerTables*)malloc(sizeof(SpeakerTables));      // freed by mia_destroy
-  if (!t) return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "speaker features: out of host memory");
-  void* p[3] = {nullptr, nullptr, nullptr};
-  const size_t bytes[3] = {t1.size() * sizeof(float2), t2.size() * sizeof(float2), hann.size() * sizeof(float)};
-  const void* src[3] = {t1.data(), t2.data(), hann.data()};
-  HostIo io = HostIo::device(ctx);
-  for (int i = 0; i < 3; ++i) {
-    if (hipMalloc(&p[i], bytes[i]) != hipSuccess) {
-      for (int j = 0; j < i; ++j) (void)hipFree(p[j]);
-      free(t);
-      return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "speaker features: table allocation failed");
+int speaker_tables(mia_ctx* ctx, SpeakerTables& out) {
+  const mia_table_key key{MIA_TAB_SPEAKER, 0, 0};
+  const mia_tables* t = mia_tables_find(ctx, key);
+  if (!t) {
+    std::vector<float2> t1(kFftBlock), t2((size_t)1 << kLoBits);
+    std::vector<float> hann(kFrame);
+    for (int k = 0; k < kFftBlock; ++k) {                  // k / 2^14 of a turn: the argument is exact
+      const double ang = 2.0 * M_PI * (double)k / (double)kFftBlock;
+      t1[k] = float2{(float)cos(ang), (float)-sin(ang)};
     }
-    io.table((const char*)src[i], p[i], bytes[i]);
+    for (int b = 0; b < (1 << kLoBits); ++b) {             // exp(-i t) - 1 = -2 sin^2(t / 2) - i sin t
+      const double ang = 2.0 * M_PI * (double)b / (double)(1 << kFftMaxLog2), h = sin(0.5 * ang);
+      t2[b] = float2{(float)(-2.0 * h * h), (float)-sin(ang)};
+    }
+    for (int i = 0; i < kFrame; ++i) hann[i] = (float)(kHannNorm * (1.0 - cos(2.0 * M_PI * (double)i / (double)kFrame)));
+    if (int rc = mia_tables_build(ctx, key, {t1, t2, hann}, {}, &t)) return rc;
   }
-  const int rc = io.finish();                            // the host vectors die with this call
-  if (rc != MIA_OK) { for (int i = 0; i < 3; ++i) (void)hipFree(p[i]); free(t); return rc; }
-  for (int i = 0; i < 3; ++i) ctx->table_allocs.push_back(p[i]);
-  t->t1 = (float2*)p[0]; t->t2 = (float2*)p[1]; t->hann = (float*)p[2];
-  ctx->speaker_tables = t;
-  *out = t;
+  out = SpeakerTables{(float2*)t->dev[0], (float2*)t->dev[1], (float*)t->dev[2]};
   return MIA_OK;
 }
 
@@ -475,8 +460,8 @@ extern "C" int mia_speaker_audio_features(mia_speaker_audio* a, const int64_t* s
   const int lo = std::max(1, (int)((float)sr / kMaxFreq)), hi = std::min(kFrame, (int)((float)sr / kMinFreq));
   MIA_CHECK_ARG(ctx, lo + 64 <= hi, "speaker_audio_features: sample rate %d leaves no pitch search range", sr);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
-  SpeakerTables* tb;
-  int rc = speaker_tables(ctx, &tb);
+  SpeakerTables tb;
+  int rc = speaker_tables(ctx, tb);
   if (rc != MIA_OK) return rc;
   // segment records, and the segments of every FFT size class side by side
   std::vector<SegRec> recs((size_t)S);
@@ -524,11 +509,11 @@ extern "C" int mia_speaker_audio_features(mia_speaker_audio* a, const int64_t* s
   launch_stats(st, a->pcm, d_recs, d_stat, max_chunks, S);
   if (frames > 0) {
     ++launches;
-    PitchArgs p{a->pcm, d_recs, tb->hann, d_pitch, frames, S, sr, lo, hi};
+    PitchArgs p{a->pcm, d_recs, tb.hann, d_pitch, frames, S, sr, lo, hi};
     hipLaunchKernelGGL(pitch_frames_kernel, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, p);
   }
   FftArgs f{};
-  f.audio = a->pcm; f.recs = d_recs; f.z = (float2*)(ws + o_z); f.part = d_part; f.t1 = tb->t1; f.t2 = tb->t2;
+  f.audio = a->pcm; f.recs = d_recs; f.z = (float2*)(ws + o_z); f.part = d_part; f.t1 = tb.t1; f.t2 = tb.t2;
   for (int e = 1; e <= kFftMaxLog2; ++e) {
     if (!cls_count[e]) continue;
     f.ids = d_ids + cls_first[e];
@@ -551,8 +536,8 @@ extern "C" int mia_op_rfft_pow2(mia_ctx* ctx, const float* x, int64_t n, int64_t
   MIA_CHECK_ARG(ctx, N >= 2 && N <= ((int64_t)1 << kFftMaxLog2) && (N & (N - 1)) == 0, "op_rfft_pow2: N must be a power of two in [2, 2^24] (got %lld)", (long long)N);
   MIA_CHECK_ARG(ctx, n > 0 && n <= N, "op_rfft_pow2: n must be in [1, N] (got %lld)", (long long)n);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
-  SpeakerTables* tb;
-  int rc = speaker_tables(ctx, &tb);
+  SpeakerTables tb;
+  int rc = speaker_tables(ctx, tb);
   if (rc != MIA_OK) return rc;
   const int e = ceil_log2(N);
   SegRec rec{};
@@ -569,7 +554,7 @@ extern "C" int mia_op_rfft_pow2(mia_ctx* ctx, const float* x, int64_t n, int64_t
   f.recs = io.table(&rec, ws + o_rec, sizeof(SegRec));
   f.ids = io.table(&id0, ws + o_id, 4);
   f.audio = io.table(x, ws + o_x, (size_t)n * 4);
-  f.z = (float2*)(ws + o_z); f.spec = (float2*)(ws + o_spec); f.t1 = tb->t1; f.t2 = tb->t2;
+  f.z = (float2*)(ws + o_z); f.spec = (float2*)(ws + o_spec); f.t1 = tb.t1; f.t2 = tb.t2;
   int launches = 0;
   fft_class<true>(ctx->stream, f, e, 1, 1, launches);
   io.check(hipGetLastError());

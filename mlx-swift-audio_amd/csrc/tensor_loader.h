@@ -36,6 +36,12 @@ struct TensorLoader {
     allocs->push_back(p);
     return p;
   }
+  // bytes as they are (tables that are not floats), and the fp32 form of it
+  MIA_HIDDEN void* put(const void* host, size_t bytes) {
+    void* p = alloc(bytes);
+    if (p && hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) != hipSuccess) fail(MIA_ERR_DEVICE, "hipMemcpy failed");
+    return p;
+  }
   float* up(const std::vector<float>& v) { return (float*)put(v.data(), v.size() * 4); }
   // the values rounded to dtype (MIA_F16, else bf16)
   MIA_HIDDEN void* up16(const std::vector<float>& v, int dtype) {
@@ -60,10 +66,5 @@ struct TensorLoader {
     if (t->dtype == MIA_F16) for (int64_t k = 0; k < numel; ++k) out[k] = f16_to_f32(p[k]);
     else for (int64_t k = 0; k < numel; ++k) out[k] = bf16_to_f32(p[k]);
     return true;
-  }
-  MIA_HIDDEN void* put(const void* host, size_t bytes) {
-    void* p = alloc(bytes);
-    if (p && hipMemcpy(p, host, bytes, hipMemcpyHostToDevice) != hipSuccess) fail(MIA_ERR_DEVICE, "hipMemcpy failed");
-    return p;
   }
 };

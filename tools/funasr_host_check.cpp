@@ -22,7 +22,7 @@ int main() {
   for (int n = 0; n < NFFT / 2; ++n) CHECK(fabsf(win[n] - win[NFFT - 1 - n]) < 1e-6f);
   mel_filters(dense);
   CHECK(dense.size() == (size_t)NMEL * NFREQ);
-  compact_filters(dense, w, meta);
+  fe::compact_filters(dense, NMEL, NFREQ, w, meta);
   CHECK(meta.size() == (size_t)NMEL * 3 && w.size() <= 1024);
   size_t nnz = 0;
   printf("first:");
