@@ -754,7 +754,7 @@ int mia_lm_generate_ras_batch(mia_lm* lm, const float* prompt_embeds, const int3
  * index on an exact tie, as MLX.argMax), embeds it through model.embed_tokens and projects through the tied embedding or lm_head.weight.
  * A sequence ends when it draws one of stop_ids (n_stop in 1..4) -- that id is NOT written to out_tokens and not counted in n_out
  * (:151-155) -- or after max_new_tokens ids.  out_tokens holds max_new_tokens ids.  The sampler is a node of the captured step graph; no
- * uniforms are involved.  The reference's temperature > 0 branch (top-k 50, then top-p 0.95) is not built.  MIA_ERR_INVALID_ARGUMENT,
+ * uniforms are involved.  The reference's temperature > 0 branch is mia_lm_generate_topk below.  MIA_ERR_INVALID_ARGUMENT,
  * before anything is launched: a null pointer, n_prompt <= 0, n_prompt + max_new_tokens > max_ctx, n_stop outside 1..4, a stop id
  * outside the vocabulary, a handle with llm_decoder / speech_embedding tensors.  Host pointers. */
 int mia_lm_generate_greedy(mia_lm* lm, const float* prompt_embeds, int n_prompt, const int32_t* stop_ids, int n_stop,
@@ -765,6 +765,34 @@ int mia_lm_generate_greedy(mia_lm* lm, const float* prompt_embeds, int n_prompt,
  * same handle capacity.  Host pointers. */
 int mia_lm_generate_greedy_batch(mia_lm* lm, const float* prompt_embeds, const int32_t* prompt_offsets, int n_seq,
                                  const int32_t* stop_ids, int n_stop, int max_new_tokens, int32_t* out_tokens, int out_stride, int32_t* n_out);
+/* The same loop with sampleNextToken's temperature > 0 branch (STT/FunASR/FunASRModel.swift:165-198: top-k, 50 when topK == 0, then
+ * top-p inside the top-k set, then a categorical draw).  The reference leaves argPartition's ties, the order of the kept set when
+ * topP >= 1 and MLXRandom open; here they are fixed by explicit uniforms, lowest index on ties and an inverse CDF.  For a row x[0..V) of
+ * fp32 logits, temperature > 0, top_k >= 0, top_p > 0 and one uniform u in [0,1):
+ *   1. k = min(top_k > 0 ? top_k : 50, V); 1 <= k <= 1024, a larger k is MIA_ERR_UNSUPPORTED.
+ *   2. The kept set is the first k entries under "higher value first, then lower index" on the raw logits (-0 counts as +0); the selection
+ *      is exact, ties at the k-th value included.  A NaN ranks below every number; a row whose best entry is NaN gives id 0.
+ *   3. The kept entries are held in that order (the reference's argSort(-probs) order), also when top_p >= 1.
+ *   4. top_p < 1: p_j = softmax((x_j - x_max) / temperature) over the k kept entries in fp32 (a kept NaN has p = 0),
+ *      n = clamp(count(cumsum(p)_j < top_p) + 1, 1, k); otherwise n = k.
+ *   5. q_j = softmax over the first n kept entries, w_j = q_j + 1e-10 (categorical(log(probs + 1e-10))); the pick is the first j with
+ *      cumsum(w)_j > u * sum(w), or the last entry if rounding leaves none.  All sums run in a fixed order that depends on the row alone:
+ *      a row's pick is the same bits in any batch, any call, captured graph or direct launch.
+ *   6. Bookkeeping as mia_lm_generate_greedy (FunASRSTT.swift:132-156): a stop id ends the sequence and is neither emitted nor counted;
+ *      the loop also ends after max_new_tokens ids.  Each draw of a sequence takes the next value of uniforms (max_new_tokens of them).
+ * MIA_ERR_INVALID_ARGUMENT before anything is launched (the handle stays usable): what mia_lm_generate_greedy lists, a null uniforms
+ * pointer, temperature or top_p not finite or <= 0, top_k < 0.  Host pointers. */
+int mia_lm_generate_topk(mia_lm* lm, const float* prompt_embeds, int n_prompt, float temperature, int top_k, float top_p,
+                         const int32_t* stop_ids, int n_stop, int max_new_tokens, const float* uniforms, int32_t* out_tokens, int32_t* n_out);
+/* mia_lm_generate_topk for n_seq utterances side by side (see mia_lm_generate_greedy_batch): uniforms [n_seq][max_new_tokens]; utterance
+ * b's ids equal mia_lm_generate_topk(prompt b, uniforms row b) on the same handle capacity.  Host pointers. */
+int mia_lm_generate_topk_batch(mia_lm* lm, const float* prompt_embeds, const int32_t* prompt_offsets, int n_seq, float temperature,
+                               int top_k, float top_p, const int32_t* stop_ids, int n_stop, int max_new_tokens, const float* uniforms,
+                               int32_t* out_tokens, int out_stride, int32_t* n_out);
+/* One sampleNextToken call of that branch (steps 1-5) on caller-provided logits [V]: *out = the picked id; kept_ids (may be NULL; room
+ * for k ids) receives the n kept ids in kept order and *n_kept (may be NULL) their count.  Host pointers. */
+int mia_sample_top_k_top_p(mia_ctx* ctx, const float* logits, int V, float temperature, int top_k, float top_p, float uniform,
+                           int32_t* out, int32_t* kept_ids, int32_t* n_kept);
 /* One sampleNextToken call on caller-provided logits (host pointers). */
 int mia_sample_top_p(mia_ctx* ctx, const float* logits, int V, const int32_t* history, int n_hist, float rep_penalty,
                      float temperature, float top_p, float uniform, int32_t* out);

@@ -311,6 +311,9 @@ PROTOTYPES = {
     "mia_lm_generate_ras_batch": (i32, [vp, vp, vp, i32, P(RasParams), vp, i32, vp, i32, vp]),
     "mia_lm_generate_greedy": (i32, [vp, vp, i32, vp, i32, i32, vp, vp]),
     "mia_lm_generate_greedy_batch": (i32, [vp, vp, vp, i32, vp, i32, i32, vp, i32, vp]),
+    "mia_lm_generate_topk": (i32, [vp, vp, i32, f32, i32, f32, vp, i32, i32, vp, vp, vp]),
+    "mia_lm_generate_topk_batch": (i32, [vp, vp, vp, i32, f32, i32, f32, vp, i32, i32, vp, vp, i32, vp]),
+    "mia_sample_top_k_top_p": (i32, [vp, vp, i32, f32, i32, f32, f32, vp, vp, vp]),
     "mia_sample_top_p": (i32, [vp, vp, i32, vp, i32, f32, f32, f32, f32, vp]),
     # Fun-ASR audio half
     "mia_sensevoice_load": (vp, [vp, P(SensevoiceConfig), TV, i32, i32]),

@@ -70,6 +70,7 @@ struct mia_lm {
   int prompt_attn = 0;                  // mia_lm_set_prompt_attention: 0 = the row kernel (lm_attention), 1 = lm_prefill_attn.hip on the 16-bit cache
   mia_lm_sampler graph_sampler{};
   RasParams graph_ras{};
+  int graph_top_k = 0;                  // LM_STEP_TOPK: the effective k (temperature and top_p travel in graph_sampler)
   int S_qkv = 1, S_o = 1, S_down = 1;
   // batched prompt pass (lm_prefill_rows): row buffers for one chunk of PF_ROWS positions, allocated on first use
   char* pf_buf = nullptr;
@@ -80,8 +81,8 @@ struct mia_lm {
   std::vector<void*> state_allocs;
 };
 
-// what ends a decode step: nothing (the host reads the logits), the top-p sampler, the RAS sampler, the greedy argmax
-enum { LM_STEP_FORWARD = 0, LM_STEP_TOP_P = 1, LM_STEP_RAS = 2, LM_STEP_GREEDY = 3 };
+// what ends a decode step: nothing (the host reads the logits), the top-p sampler, the RAS sampler, the greedy argmax, the top-k / top-p sampler
+enum { LM_STEP_FORWARD = 0, LM_STEP_TOP_P = 1, LM_STEP_RAS = 2, LM_STEP_GREEDY = 3, LM_STEP_TOPK = 4 };
 
 // launch a kernel template's F16 or BF16 instance; expects `const bool f16` and `hipStream_t s` in scope
 #define LAUNCH_T(kern, grid, block, lds, ...) do { if (f16) hipLaunchKernelGGL((kern<F16>), grid, block, lds, s, __VA_ARGS__); else hipLaunchKernelGGL((kern<BF16>), grid, block, lds, s, __VA_ARGS__); } while (0)
@@ -100,6 +101,14 @@ void lm_sample_ras_launch(hipStream_t s, const float* logits, int V, int32_t* to
 // LmState::max_len.  ws: the top-p workspace (lm_sample_ws_bytes() per sequence)
 void lm_sample_greedy_launch(hipStream_t s, const float* logits, int V, int32_t* tokens, int32_t* out_tokens, LmState* st, void* ws, const mia_lm_sampler& sp,
                              int max_ctx, int B);
+// top-k / top-p sampler (Fun-ASR's temperature > 0 branch; the rule is stated at mia_lm_generate_topk in mia.h), six launches: a 4-level
+// radix select of the k-th largest logit over the vocabulary slices, a gather of the kept entries, one finishing workgroup per sequence
+// (sort, nucleus, draw, the greedy loop's bookkeeping).  sp: temperature, top_p and the stop ids; k: the effective k, 1 <= k <=
+// LM_TOPK_MAX_K (the caller clamps it to V).  Sequence b draws uniforms[b][LmState::u_cursor].  kept_ids / n_kept: null in the step; the
+// standalone op reads the kept set through them (one sequence).  ws: the top-p workspace
+constexpr int LM_TOPK_MAX_K = 1024;
+void lm_sample_topk_launch(hipStream_t s, const float* logits, int V, int32_t* tokens, int32_t* out_tokens, const float* uniforms, LmState* st, void* ws,
+                           const mia_lm_sampler& sp, int k, int max_ctx, int B, int32_t* kept_ids = nullptr, int32_t* n_kept = nullptr);
 
 // ---- lm.hip: the two launch sites that branch on the cache mode (layer l of the handle's caches; the op ABI calls them on a bare handle) ----
 // q|k|v rows of the prompt pass -> RoPE -> q rows + the layer's K/V rows at rowmap's (sequence, position)

@@ -411,8 +411,9 @@ int lm_launch_attention(mia_lm* m, bool fused, int rows, const void* q, int laye
 namespace {
 
 // (the samplers read each sequence's prompt length from its state: a captured and a directly launched step issue the same arguments)
-// mode: LM_STEP_* (what ends the step); sp: the top-p sampler's arguments, or the greedy one's stop ids; ras: the RAS sampler's
-int lm_enqueue_step(mia_lm* m, int mode, const mia_lm_sampler& sp, const RasParams* ras = nullptr, int nb = 1) {
+// mode: LM_STEP_* (what ends the step); sp: the top-p sampler's arguments, the greedy one's stop ids, or the top-k one's temperature, top_p
+// and stop ids with its effective k in top_k; ras: the RAS sampler's
+int lm_enqueue_step(mia_lm* m, int mode, const mia_lm_sampler& sp, const RasParams* ras = nullptr, int nb = 1, int top_k = 0) {
   hipStream_t s = m->ctx->stream;
   const mia_lm_config& c = m->cfg;
   const int D = c.hidden, dh = c.head_dim, Nq = c.n_heads * dh, Nk = c.n_kv_heads * dh, Nqkv = Nq + 2 * Nk;
@@ -466,6 +467,7 @@ int lm_enqueue_step(mia_lm* m, int mode, const mia_lm_sampler& sp, const RasPara
   if (mode == LM_STEP_RAS) lm_sample_ras_launch(s, m->logits, HV, m->tokens, m->out_tokens, m->uniforms, m->state, *ras, c.max_ctx, nb);
   else if (mode == LM_STEP_TOP_P) lm_sample_launch(s, m->logits, HV, m->tokens, m->hist, m->uniforms, m->state, m->smx, sp, -1, c.max_ctx, nb);
   else if (mode == LM_STEP_GREEDY) lm_sample_greedy_launch(s, m->logits, HV, m->tokens, m->out_tokens, m->state, m->smx, sp, c.max_ctx, nb);
+  else if (mode == LM_STEP_TOPK) lm_sample_topk_launch(s, m->logits, HV, m->tokens, m->out_tokens, m->uniforms, m->state, m->smx, sp, top_k, c.max_ctx, nb);
   else hipLaunchKernelGGL(lm_advance, dim3(nb), dim3(1), 0, s, m->state);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -570,23 +572,25 @@ int lm_prefill(mia_lm* m, int pos0, int P) {
   return lm_prefill_rows(m, rows, {pos0 + P});
 }
 
-int lm_graph(mia_lm* m, int mode, const mia_lm_sampler& sp, const RasParams* ras = nullptr, int nb = 1) {
+int lm_graph(mia_lm* m, int mode, const mia_lm_sampler& sp, const RasParams* ras = nullptr, int nb = 1, int top_k = 0) {
   mia_ctx* ctx = m->ctx;
   if (m->debug_flags & 1) return 1;                  // test hook (mia_lm_set_debug): launch every step directly
   mia_lm_sampler key{}; RasParams rkey{};
-  if (mode == LM_STEP_TOP_P || mode == LM_STEP_GREEDY) key = sp;
+  if (mode == LM_STEP_TOP_P || mode == LM_STEP_GREEDY || mode == LM_STEP_TOPK) key = sp;
   if (mode == LM_STEP_RAS) rkey = *ras;
-  if (m->graph && m->graph_mode == mode && m->graph_nb == nb && memcmp(&m->graph_sampler, &key, sizeof(key)) == 0 && memcmp(&m->graph_ras, &rkey, sizeof(rkey)) == 0) return 0;
+  const int kkey = mode == LM_STEP_TOPK ? top_k : 0;
+  if (m->graph && m->graph_mode == mode && m->graph_nb == nb && m->graph_top_k == kkey && memcmp(&m->graph_sampler, &key, sizeof(key)) == 0 &&
+      memcmp(&m->graph_ras, &rkey, sizeof(rkey)) == 0) return 0;
   if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; }
   hipGraph_t g = nullptr;
   MIA_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-  const int erc = lm_enqueue_step(m, mode, sp, ras, nb);
+  const int erc = lm_enqueue_step(m, mode, sp, ras, nb, top_k);
   hipError_t ce = hipStreamEndCapture(ctx->stream, &g);
   if (erc != 0 || ce != hipSuccess || !g) { if (g) (void)hipGraphDestroy(g); return mia_fail(ctx, MIA_ERR_DEVICE, "lm: step graph capture failed"); }
   hipError_t ie = hipGraphInstantiate(&m->graph, g, nullptr, nullptr, 0);
   (void)hipGraphDestroy(g);
   if (ie != hipSuccess) { m->graph = nullptr; return mia_fail(ctx, MIA_ERR_DEVICE, "lm: hipGraphInstantiate failed"); }
-  m->graph_sampler = key; m->graph_ras = rkey; m->graph_mode = mode; m->graph_nb = nb;
+  m->graph_sampler = key; m->graph_ras = rkey; m->graph_top_k = kkey; m->graph_mode = mode; m->graph_nb = nb;
   return 0;
 }
 
@@ -722,7 +726,8 @@ namespace {
 
 // One validated call of a generate entry point.  The samplers tie the two forms together: the top-p kernels count a prompt of ids
 // (LmState::n_prompt) and append the drawn ids to `tokens` (n_gen of them); the RAS kernel counts a prompt of embedding rows (n_embeds)
-// and emits to `out_tokens` (n_out ids), and so does the greedy kernel (embedding rows in, no uniforms).  A single-sequence call is
+// and emits to `out_tokens` (n_out ids), and so do the greedy kernel (embedding rows in, no uniforms) and the top-k kernels (embedding
+// rows AND uniforms, top_k > 0).  A single-sequence call is
 // n_seq = 1 with offsets {0, n_prompt}.
 struct LmGenCall {
   const char* name;                       // entry point, for error messages
@@ -733,6 +738,7 @@ struct LmGenCall {
   const float* embeds = nullptr;          // RAS / greedy: the prompts' embedding rows [.][hidden] ...
   const mia_ras_params* ras = nullptr;    // ... RAS: [n_seq] parameters (min_len / max_len per sequence, the rest equal)
   const float* uniforms = nullptr;        // sequence b draws from uniforms[b * u_stride + i], i < n_uniforms (staged up to max_ctx of them); greedy: none
+  int top_k = 0;                          // > 0: the top-k / top-p sampler on an embedding-row prompt, with this effective k and sp's temperature / top_p
   int u_stride = 0, n_uniforms = 0;
   int max_new = 0;                        // the most steps any sequence runs past its prompt
   // A prompt with at least this many positions before its last one goes through the batched prompt pass; a shorter one walks the step.
@@ -770,8 +776,8 @@ int lm_generate_run(mia_lm* m, const LmGenCall& g) {
   if (g.ras) r = RasParams{g.ras[0].top_p, g.ras[0].top_k, g.ras[0].win, g.ras[0].tau, g.ras[0].eos, 0, 0, nu};   // (the length bounds travel in the state: one graph serves every text length)
   else sp = *g.sp;
   const RasParams* rp = g.ras ? &r : nullptr;
-  const int mode = g.ras ? LM_STEP_RAS : g.embeds ? LM_STEP_GREEDY : LM_STEP_TOP_P;
-  const int gr = lm_graph(m, mode, sp, rp, B);
+  const int mode = g.ras ? LM_STEP_RAS : g.embeds ? (g.top_k > 0 ? LM_STEP_TOPK : LM_STEP_GREEDY) : LM_STEP_TOP_P;
+  const int gr = lm_graph(m, mode, sp, rp, B, g.top_k);
   if (gr < 0) return gr;
   // prompts: everything but a prompt's last position through the batched prompt pass (K/V only; the rows of all prompts share its
   // GEMMs), the last position takes the first step.  A prompt that does not take the pass walks the step instead -- its sampler idles
@@ -796,7 +802,7 @@ int lm_generate_run(mia_lm* m, const LmGenCall& g) {
   const int total = walk + g.max_new;
   for (int step = 0; step < total; ++step) {
     if (gr == 0) MIA_HIP(ctx, hipGraphLaunch(m->graph, s));
-    else if (lm_enqueue_step(m, mode, sp, rp, B)) return mia_fail(ctx, MIA_ERR_DEVICE, "%s: launch failed", g.name);
+    else if (lm_enqueue_step(m, mode, sp, rp, B, g.top_k)) return mia_fail(ctx, MIA_ERR_DEVICE, "%s: launch failed", g.name);
     if ((step & 15) == 15) {                               // after every 16th launched step: a finished sequence's further steps are no-ops
       if (const int rc = read_state()) return rc;
       bool all = true;
@@ -952,5 +958,58 @@ extern "C" int mia_lm_generate_greedy_batch(mia_lm* m, const float* prompt_embed
   }
   LmGenCall g{"lm_generate_greedy_batch", n_seq, prompt_offsets};
   g.embeds = prompt_embeds; g.sp = &sp; g.max_new = max_new_tokens; g.out = out_tokens; g.out_stride = out_stride; g.n_out = n_out;
+  return lm_generate_run(m, g);
+}
+
+// ---- the same loop with sampleNextToken's temperature > 0 branch (FunASRModel.swift:165-198; the rule is stated in mia.h) ----
+namespace {
+
+// the greedy checks plus the sampler's own; *k = the effective k
+int lm_topk_check(mia_lm* m, const char* name, float temperature, int top_k, float top_p, const int32_t* stop_ids, int n_stop, int max_new_tokens, mia_lm_sampler* sp,
+                  int* k) {
+  mia_ctx* ctx = m->ctx;
+  if (const int rc = lm_greedy_check(m, name, stop_ids, n_stop, max_new_tokens, sp)) return rc;
+  MIA_CHECK_ARG(ctx, std::isfinite(temperature) && temperature > 0.f, "%s: temperature must be finite and positive (0 is mia_lm_generate_greedy)", name);
+  MIA_CHECK_ARG(ctx, std::isfinite(top_p) && top_p > 0.f, "%s: top_p must be finite and positive", name);
+  MIA_CHECK_ARG(ctx, top_k >= 0, "%s: top_k must not be negative (0 = the reference's 50)", name);
+  *k = std::min(top_k > 0 ? top_k : 50, m->cfg.vocab);
+  if (*k > LM_TOPK_MAX_K) return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "%s: k %d exceeds %d", name, *k, LM_TOPK_MAX_K);
+  sp->temperature = temperature; sp->top_p = top_p;
+  return MIA_OK;
+}
+
+}  // namespace
+
+extern "C" int mia_lm_generate_topk(mia_lm* m, const float* prompt_embeds, int n_prompt, float temperature, int top_k, float top_p, const int32_t* stop_ids, int n_stop,
+                                    int max_new_tokens, const float* uniforms, int32_t* out_tokens, int32_t* n_out) {
+  if (!m) return MIA_ERR_MODEL_NOT_LOADED;
+  mia_ctx* ctx = m->ctx;
+  MIA_CHECK_ARG(ctx, prompt_embeds && stop_ids && uniforms && out_tokens && n_out, "lm_generate_topk: null arguments");
+  mia_lm_sampler sp; int k = 0;
+  if (const int rc = lm_topk_check(m, "lm_generate_topk", temperature, top_k, top_p, stop_ids, n_stop, max_new_tokens, &sp, &k)) return rc;
+  MIA_CHECK_ARG(ctx, n_prompt > 0 && n_prompt <= m->cfg.max_ctx - max_new_tokens, "lm_generate_topk: prompt %d + max_new_tokens %d exceeds max_ctx %d", n_prompt, max_new_tokens, m->cfg.max_ctx);
+  const int32_t offsets[2] = {0, n_prompt};
+  LmGenCall g{"lm_generate_topk", 1, offsets};
+  g.embeds = prompt_embeds; g.sp = &sp; g.top_k = k; g.uniforms = uniforms; g.n_uniforms = g.max_new = max_new_tokens; g.out = out_tokens; g.n_out = n_out;
+  return lm_generate_run(m, g);
+}
+
+extern "C" int mia_lm_generate_topk_batch(mia_lm* m, const float* prompt_embeds, const int32_t* prompt_offsets, int n_seq, float temperature, int top_k, float top_p,
+                                          const int32_t* stop_ids, int n_stop, int max_new_tokens, const float* uniforms, int32_t* out_tokens, int out_stride,
+                                          int32_t* n_out) {
+  if (!m) return MIA_ERR_MODEL_NOT_LOADED;
+  mia_ctx* ctx = m->ctx;
+  MIA_CHECK_ARG(ctx, prompt_embeds && prompt_offsets && stop_ids && uniforms && out_tokens && n_out, "lm_generate_topk_batch: null arguments");
+  MIA_CHECK_ARG(ctx, n_seq >= 1 && n_seq <= m->B_cap, "lm_generate_topk_batch: n_seq %d exceeds the batch set with mia_lm_set_batch (%d)", n_seq, m->B_cap);
+  mia_lm_sampler sp; int k = 0;
+  if (const int rc = lm_topk_check(m, "lm_generate_topk_batch", temperature, top_k, top_p, stop_ids, n_stop, max_new_tokens, &sp, &k)) return rc;
+  MIA_CHECK_ARG(ctx, out_stride >= max_new_tokens, "lm_generate_topk_batch: out_stride %d must hold max_new_tokens %d ids", out_stride, max_new_tokens);
+  for (int b = 0; b < n_seq; ++b) {
+    const int np_ = prompt_offsets[b + 1] - prompt_offsets[b];
+    MIA_CHECK_ARG(ctx, np_ > 0 && np_ <= m->cfg.max_ctx - max_new_tokens, "lm_generate_topk_batch: prompt %d: length %d + max_new_tokens exceeds max_ctx", b, np_);
+  }
+  LmGenCall g{"lm_generate_topk_batch", n_seq, prompt_offsets};
+  g.embeds = prompt_embeds; g.sp = &sp; g.top_k = k; g.uniforms = uniforms; g.u_stride = g.n_uniforms = g.max_new = max_new_tokens;
+  g.out = out_tokens; g.out_stride = out_stride; g.n_out = n_out;
   return lm_generate_run(m, g);
 }

@@ -145,11 +145,18 @@ class FunASRModel:
             return self.encoder.encode_audio(pcm)
         return self.encoder.encode_audio([pcm])[0]
 
-    def transcribe_tokens(self, pcm, input_ids, sos_id: int, eos_id: int, stop_ids, max_tokens: int = 512):
+    def transcribe_tokens(self, pcm, input_ids, sos_id: int, eos_id: int, stop_ids, max_tokens: int = 512,
+                          temperature: float = 0.0, top_p: float = 0.95, top_k: int = 0, uniforms=None):
         """One clip + its prompt ids -> token ids (FunASRDecoder.transcribe_tokens on the clip's audio rows).  A list of clips, with one
-        prompt per clip, is encoded in one stacked pass and decoded side by side (generate_greedy_batch; lm.set_batch(n) first)."""
+        prompt per clip, is encoded in one stacked pass and decoded side by side (generate_greedy_batch; lm.set_batch(n) first).
+        temperature > 0 samples (top-k, then top-p, FunASRModel.swift:165-198) with the caller's uniforms: [max_tokens] for one clip,
+        [n, max_tokens] for a list."""
+        if temperature != 0 and uniforms is None:
+            raise ValueError("temperature > 0 needs `uniforms`: the draw takes explicit uniforms")
         if not isinstance(pcm, (list, tuple)):
-            return self.decoder.transcribe_tokens(input_ids, self.encode_audio(pcm), sos_id, eos_id, stop_ids, max_tokens)
+            return self.decoder.transcribe_tokens(input_ids, self.encode_audio(pcm), sos_id, eos_id, stop_ids, max_tokens, temperature, top_p, top_k, uniforms)
         embs = self.encode_audio(list(pcm))
         prompts = [self.decoder.merge_embeddings(ids, e, sos_id, eos_id) for ids, e in zip(input_ids, embs)]
-        return self.decoder.lm.generate_greedy_batch(prompts, stop_ids, max_tokens)
+        if temperature == 0:
+            return self.decoder.lm.generate_greedy_batch(prompts, stop_ids, max_tokens)
+        return self.decoder.lm.generate_topk_batch(prompts, uniforms, stop_ids, max_tokens, temperature, top_p, top_k)

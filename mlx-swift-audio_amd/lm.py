@@ -211,6 +211,60 @@ CausalLM.generate_greedy = _generate_greedy
 CausalLM.generate_greedy_batch = _generate_greedy_batch
 
 
+def _generate_topk(self, prompt_embeds, uniforms, stop_ids, max_new_tokens: int, temperature: float, top_p: float = 0.95, top_k: int = 0) -> list[int]:
+    """mia_lm_generate_topk: generate_greedy's loop with sampleNextToken's temperature > 0 branch (top-k, 50 when top_k == 0, then top-p inside
+    the top-k set, then an inverse-CDF draw).  uniforms: at least max_new_tokens values in [0, 1), one per drawn id."""
+    lib = self.ctx.lib
+    x = np.ascontiguousarray(prompt_embeds, np.float32).reshape(-1, self.cfg.hidden)
+    stop = _stop_array(stop_ids)
+    u = np.ascontiguousarray(uniforms, np.float32).reshape(-1)
+    if u.size < max_new_tokens:
+        raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, "uniforms must hold max_new_tokens values")
+    out = np.zeros(max(int(max_new_tokens), 1), np.int32)
+    n = C.c_int32(0)
+    self.ctx.check(lib.mia_lm_generate_topk(self.h, x.ctypes.data, x.shape[0], float(temperature), int(top_k), float(top_p), stop.ctypes.data, stop.size,
+                                            int(max_new_tokens), u.ctypes.data, out.ctypes.data, C.byref(n)))
+    return out[:n.value].tolist()
+
+
+def _generate_topk_batch(self, prompt_embeds, uniforms, stop_ids, max_new_tokens: int, temperature: float, top_p: float = 0.95,
+                         top_k: int = 0) -> list[list[int]]:
+    """mia_lm_generate_topk_batch: one embedding-row prompt and one uniform row [max_new_tokens] per utterance, decoded side by side
+    (set_batch(n) first); utterance b's ids equal generate_topk(prompt_embeds[b], uniforms[b], ...) on the same handle capacity."""
+    lib = self.ctx.lib
+    n_seq = len(prompt_embeds)
+    xs = [np.ascontiguousarray(x, np.float32).reshape(-1, self.cfg.hidden) for x in prompt_embeds]
+    offs = np.zeros(n_seq + 1, np.int32)
+    np.cumsum([x.shape[0] for x in xs], out=offs[1:])
+    flat = np.ascontiguousarray(np.concatenate(xs, axis=0))
+    stop = _stop_array(stop_ids)
+    u = np.ascontiguousarray(uniforms, np.float32)
+    if u.ndim != 2 or u.shape[0] != n_seq or u.shape[1] < max_new_tokens:
+        raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, "uniforms must be [n_seq, >= max_new_tokens]")
+    u = np.ascontiguousarray(u[:, :max(int(max_new_tokens), 0)])
+    stride = max(int(max_new_tokens), 1)
+    out = np.zeros((n_seq, stride), np.int32)
+    n = np.zeros(n_seq, np.int32)
+    self.ctx.check(lib.mia_lm_generate_topk_batch(self.h, flat.ctypes.data, offs.ctypes.data, n_seq, float(temperature), int(top_k), float(top_p),
+                                                  stop.ctypes.data, stop.size, int(max_new_tokens), u.ctypes.data, out.ctypes.data, stride, n.ctypes.data))
+    return [out[b, :n[b]].tolist() for b in range(n_seq)]
+
+
+CausalLM.generate_topk = _generate_topk
+CausalLM.generate_topk_batch = _generate_topk_batch
+
+
+def sample_top_k_top_p(ctx: _lib.Context, logits: np.ndarray, uniform: float, temperature: float, top_p: float = 0.95, top_k: int = 0, want_kept: bool = False):
+    """FunASRModel.sampleNextToken with temperature > 0 (mia_sample_top_k_top_p) on one row of logits, with an explicit uniform for the draw:
+    the picked id, or (id, kept ids in kept order) with want_kept."""
+    lg = np.ascontiguousarray(logits, np.float32).reshape(-1)
+    out, nk = C.c_int32(0), C.c_int32(0)
+    kept = np.zeros(1024, np.int32)
+    ctx.check(ctx.lib.mia_sample_top_k_top_p(ctx.h, lg.ctypes.data, lg.size, float(temperature), int(top_k), float(top_p), float(uniform), C.byref(out),
+                                             kept.ctypes.data if want_kept else None, C.byref(nk)))
+    return (out.value, kept[:nk.value].tolist()) if want_kept else out.value
+
+
 def sample_next_token(ctx: _lib.Context, logits: np.ndarray, history, uniform: float, temperature=0.6, top_p=0.8, rep_penalty=1.3) -> int:
     """sampleNextToken(logits:history:temperature:topP:repetitionPenalty:) with an explicit uniform for the categorical draw."""
     lg = np.ascontiguousarray(logits, np.float32)
@@ -285,8 +339,16 @@ class FunASRDecoder:
         text = np.asarray(self.embed[np.asarray(list(input_ids), np.int64)], np.float32)
         return merge_embeddings(text, input_ids, audio_embeddings, sos_id, eos_id)
 
-    def transcribe_tokens(self, input_ids, audio_embeddings, sos_id: int, eos_id: int, stop_ids, max_tokens: int = 512) -> list[int]:
-        return self.lm.generate_greedy(self.merge_embeddings(input_ids, audio_embeddings, sos_id, eos_id), stop_ids, max_tokens)
+    def transcribe_tokens(self, input_ids, audio_embeddings, sos_id: int, eos_id: int, stop_ids, max_tokens: int = 512,
+                          temperature: float = 0.0, top_p: float = 0.95, top_k: int = 0, uniforms=None) -> list[int]:
+        """temperature == 0: the greedy loop (the reference's `if temperature == 0`).  temperature > 0: sampleNextToken's top-k / top-p
+        branch; the RNG stays with the caller, who passes max_tokens uniforms."""
+        x = self.merge_embeddings(input_ids, audio_embeddings, sos_id, eos_id)
+        if temperature == 0:
+            return self.lm.generate_greedy(x, stop_ids, max_tokens)
+        if uniforms is None:
+            raise ValueError("temperature > 0 needs `uniforms` (max_tokens values in [0, 1)): the draw takes explicit uniforms")
+        return self.lm.generate_topk(x, uniforms, stop_ids, max_tokens, temperature, top_p, top_k)
 
 
 class OrpheusTTS:

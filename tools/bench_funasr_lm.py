@@ -4,7 +4,10 @@
 line: prompt pass + first step, ms per generated token and its fraction of the HBM roofline (the bf16 weights are read once per step:
 tied embedding + 28 layers, as tools/bench_orpheus.py counts them), at batch 1 and with 8 and 32 utterances side by side.
 --no-qk-norm drops the q_norm / k_norm tensors from the checkpoint: same dims on the kernel instances without the norm (the A/B of
-what the norm costs)."""
+what the norm costs).
+--temperature T [--top-k K] [--top-p P] (T > 0) also times the sampled loop (sampleNextToken's second branch: top-k, top-p, draw) against
+the greedy loop in the same process, same prompts, at batch 1 and 8: the "sampled" entry holds ms per step of both and their difference,
+which is what the six sampler launches cost over the greedy sampler's two."""
 import json
 import os
 import sys
@@ -20,6 +23,18 @@ from mlx_swift_audio_amd import synthetic as S
 
 qk_norm = "--no-qk-norm" not in sys.argv
 args = [a for a in sys.argv[1:] if a != "--no-qk-norm"]
+
+
+def _flag(name, default, kind):
+    if name not in args:
+        return default
+    i = args.index(name)
+    value = kind(args[i + 1])
+    del args[i:i + 2]
+    return value
+
+
+temperature, top_k, top_p = _flag("--temperature", 0.0, float), _flag("--top-k", 0, int), _flag("--top-p", 0.95, float)
 n_new = int(args[0]) if args else 128
 cfg = S.LM_CONFIGS["qwen3-0.6b"]
 ctx = m.Context(0)
@@ -78,5 +93,31 @@ for batch in (8, 32):
     res["batch"].append({"utterances": batch, "generated_tokens": sum(len(o) for o in outs), "prompt_pass_plus_first_step_ms": round(b1 * 1e3, 2),
                          "ms_per_step": round(ms_step, 4), "ms_per_token": round(ms_step / batch, 4), "tokens_per_s": round(batch / (ms_step * 1e-3), 1),
                          "hbm_frac_of_8TBs": round(bytes_per_step / (ms_step * 1e-3) / 8e12, 4)})
+if temperature > 0:
+    # greedy against sampled, interleaved in one process on the same prompts; a run that draws the stop id early counts its own steps
+    def step_ms(call, n):
+        call(8)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call(1)
+        t1 = time.perf_counter()
+        outs = call(n)
+        t2 = time.perf_counter()
+        return ((t2 - t1) - (t1 - t0)) / max(max(len(o) for o in outs) - 1, 1) * 1e3
+
+    res["sampled"] = {"temperature": temperature, "top_k": top_k, "top_p": top_p, "batch": []}
+    for batch in (1, 8):
+        model.set_batch(batch)
+        xs = [prompt() for _ in range(batch)]
+        us = rng.random((batch, n_new)).astype(np.float32)
+        greedy = lambda n: model.generate_greedy_batch(xs, (STOP,), n)
+        sampled = lambda n: model.generate_topk_batch(xs, us, (STOP,), n, temperature, top_p, top_k)
+        g, s_ = [], []
+        for _ in range(3):
+            g.append(step_ms(greedy, n_new))
+            s_.append(step_ms(sampled, n_new))
+        res["sampled"]["batch"].append({"utterances": batch, "greedy_ms_per_step": round(min(g), 4), "sampled_ms_per_step": round(min(s_), 4),
+                                        "sampler_extra_us_per_step": round((min(s_) - min(g)) * 1e3, 1),
+                                        "greedy_runs": [round(v, 4) for v in g], "sampled_runs": [round(v, 4) for v in s_]})
 model.set_batch(1)
 print(json.dumps(res))
