@@ -572,6 +572,44 @@ int64_t mia_dac_code_len(mia_codec* c, int64_t n_samples);
 int mia_dac_encode(mia_codec* c, const float* pcm, int64_t n_samples, int n_quantizers, int32_t* codes, int64_t codes_capacity,
                    int64_t* n_steps, int mem);
 
+/* ---- Mimi codec decode (TTS/Marvis/Mimi/, fp32 like the reference) ------------------------------------------------
+ * mia_mimi_config (include/mia_mimi.h, included by the callers that fill one) carries the fields of MimiConfig / SeanetConfig /
+ * MimiTransformerConfig (Mimi.swift:17-103) the decoder uses.  upsample_stride =
+ * sample_rate / prod(ratios) / frame_rate (Mimi.swift:128-129).  Flags are 0 / 1: seanet_pad_constant = padMode == .constant,
+ * layer_norm = norm == "layer_norm", layer_scale = a LayerScale is present, rope = positionalEmbedding == "rope".
+ * Tensors: float32 under the names and layouts Mimi.sanitize produces (Mimi.swift:305-377; checkpoint.sanitize_mimi), decoder side only:
+ * quantizer.rvq_{first,rest}.{vq.layers.N.codebook.{embedding_sum,cluster_usage},output_proj.weight}, upsample.convtr.convtr.weight,
+ * decoder_transformer.transformer.layers.N.*, decoder.{init_conv1d,layers.N.upsample,layers.N.residuals.0.block.M,final_conv1d}.*.
+ * The loader refuses, each with its own message (MIA_ERR_INVALID_ARGUMENT): head_dim != 64, kv_repeat != 1, gating, a norm other than
+ * layer_norm, a non-causal / non-constant-padded / shortcut-convolution SEANet, more than one residual layer per stage, an upsample
+ * stride other than 2, and channel counts that are not multiples of 32 (the tap GEMM's rule). */
+typedef struct mia_mimi_config mia_mimi_config;        /* defined in include/mia_mimi.h */
+typedef struct mia_mimi mia_mimi;
+typedef struct mia_mimi_stream mia_mimi_stream;
+mia_mimi* mia_mimi_load(mia_ctx* ctx, const mia_mimi_config* cfg, const mia_tensor_view* tensors, int n_tensors);
+void mia_mimi_free(mia_mimi* m);
+/* samples per n_frames code frames: n_frames * upsample_stride * prod(ratios) (1920 per frame for mimi_202407) */
+int64_t mia_mimi_output_len(mia_mimi* m, int64_t n_frames);
+/* Replaces Mimi.decode (Mimi.swift:184-192; MarvisTTS.swift:534): codes int32 [n_q][T] -> pcm float32 [T * samples per frame].  The
+ * transformer runs full bidirectional attention over all 2 T positions at RoPE offset 0, as the reference's fresh cache with a nil mask
+ * does.  1 <= n_q <= nq: the sum runs over the codebooks given.
+ * `codes` is a HOST array in both entries; `pcm_mem` (a mia_mem) describes pcm alone.  Before anything is launched every id is checked:
+ * an id outside [0, bins), n_q outside [1, nq], a pcm_capacity below mia_mimi_output_len(T) and, in a stream, an n_q other than the
+ * stream's first call's are MIA_ERR_INVALID_ARGUMENT, and the handle / stream is unchanged.  T = 0 / n = 0 succeed with 0 samples. */
+int mia_mimi_decode(mia_mimi* m, const int32_t* codes, int n_q, int64_t T, float* pcm, int64_t pcm_capacity, int64_t* n_samples,
+                    int pcm_mem);
+/* Replaces MimiStreamingDecoder (Mimi.swift:213-239; MarvisTTS.swift:536).  A stream owns, on the device, what the reference's step
+ * carries: per transformer layer the last `context` positions of rotated keys and of values, the running position, and per
+ * convolution the input rows its next call needs.  Several streams may share a handle; calls on one context are serialised by the
+ * caller.  mia_mimi_stream_decode(n frames) equals n calls of decodeStep: the two positions of frame f attend to the keys at positions
+ * [max(0, 2 f - context), 2 f + 2).  It runs ONE pass over the n frames.  Streamed and whole-clip decodes are different functions of
+ * the same codes, as in the reference.  mia_mimi_stream_reset = MimiStreamingDecoder.reset().  Free a handle's streams before the handle. */
+mia_mimi_stream* mia_mimi_stream_create(mia_mimi* m);
+void mia_mimi_stream_free(mia_mimi_stream* s);
+int mia_mimi_stream_reset(mia_mimi_stream* s);
+int mia_mimi_stream_decode(mia_mimi_stream* s, const int32_t* codes, int n_q, int64_t n, float* pcm, int64_t pcm_capacity,
+                           int64_t* n_samples, int pcm_mem);
+
 /* ---- OuteTTS speaker-profile audio (TTS/OuteTTS/OuteTTSAudioProcessor.swift) ------------------------------------
  * The sample arithmetic of createSpeakerFromTranscription (:363-453); the word / code slicing around it is host integer arithmetic
  * (outetts.py).  Caller arrays are HOST pointers in every entry point of this section.

@@ -120,6 +120,17 @@ class DacEncoderConfig(C.Structure):
     _fields_ = [("encoder_dim", i32), ("n_rates", i32), ("encoder_rates", i32 * 8)]
 
 
+class MimiConfig(C.Structure):
+    """struct mia_mimi_config of include/mia_mimi.h (mia.h only declares the type, so it is not in STRUCTS)."""
+    _fields_ = [("sample_rate", i32), ("upsample_stride", i32), ("nq", i32), ("bins", i32), ("quantizer_dim", i32),
+                ("seanet_dimension", i32), ("seanet_nfilters", i32), ("seanet_n_ratios", i32), ("seanet_ratios", i32 * 8),
+                ("seanet_ksize", i32), ("seanet_residual_ksize", i32), ("seanet_last_ksize", i32), ("seanet_n_residual_layers", i32),
+                ("seanet_dilation_base", i32), ("seanet_compress", i32),
+                ("seanet_causal", i32), ("seanet_true_skip", i32), ("seanet_pad_constant", i32),
+                ("d_model", i32), ("n_heads", i32), ("n_layers", i32), ("dim_feedforward", i32), ("context", i32), ("kv_repeat", i32),
+                ("gating", i32), ("layer_norm", i32), ("layer_scale", i32), ("rope", i32), ("max_period", i32)]
+
+
 class LmConfig(C.Structure):
     _fields_ = [("vocab", i32), ("hidden", i32), ("inter", i32), ("n_layers", i32), ("n_heads", i32), ("n_kv_heads", i32),
                 ("head_dim", i32), ("max_ctx", i32),
@@ -272,6 +283,15 @@ PROTOTYPES = {
     "mia_dac_load_encoder": (i32, [vp, P(DacEncoderConfig), TV, i32]),
     "mia_dac_code_len": (i64, [vp, i64]),
     "mia_dac_encode": (i32, [vp, vp, i64, i32, vp, i64, vp, i32]),
+    # Mimi codec decode
+    "mia_mimi_load": (vp, [vp, vp, TV, i32]),
+    "mia_mimi_free": (None, [vp]),
+    "mia_mimi_output_len": (i64, [vp, i64]),
+    "mia_mimi_decode": (i32, [vp, vp, i32, i64, vp, i64, vp, i32]),
+    "mia_mimi_stream_create": (vp, [vp]),
+    "mia_mimi_stream_free": (None, [vp]),
+    "mia_mimi_stream_reset": (i32, [vp]),
+    "mia_mimi_stream_decode": (i32, [vp, vp, i32, i64, vp, i64, vp, i32]),
     # OuteTTS speaker-profile audio
     "mia_speaker_audio_create": (vp, [vp, vp, i64, i32, f32, f32]),
     "mia_speaker_audio_free": (None, [vp]),

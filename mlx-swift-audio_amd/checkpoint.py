@@ -146,3 +146,50 @@ def quantize_affine(w: np.ndarray, group_size: int = 64, bits: int = 4, scale_dt
     for j in range(per):
         packed |= q[:, :, j] << np.uint32(j * bits)
     return packed, scale, bias
+
+
+def sanitize_mimi_name(raw: str) -> str:
+    """Mimi.sanitize's renaming of one checkpoint key (TTS/Marvis/Mimi/Mimi.swift:308-354), replacement for replacement."""
+    k = ".".join(seg[1:] if seg.startswith("_") else seg for seg in raw.split("."))
+    if k.startswith("encoder.model."):
+        k = k.replace("encoder.model.", "encoder.")
+    if k.startswith("decoder.model."):
+        k = k.replace("decoder.model.", "decoder.")
+    if k.endswith(".in_proj_weight"):
+        k = k.replace(".in_proj_weight", ".in_proj.weight")
+    if k.endswith(".linear1.weight"):
+        k = k.replace(".linear1.weight", ".gating.linear1.weight")
+    if k.endswith(".linear2.weight"):
+        k = k.replace(".linear2.weight", ".gating.linear2.weight")
+    for layer, idx in enumerate((2, 5, 8, 11)):
+        k = k.replace(f"decoder.{idx}.", f"decoder.layers.{layer}.upsample.")
+        k = k.replace(f"decoder.{idx + 1}.", f"decoder.layers.{layer}.residuals.0.")
+    for layer, idx in enumerate((1, 4, 7, 10)):
+        k = k.replace(f"encoder.{idx}.", f"encoder.layers.{layer}.residuals.0.")
+        k = k.replace(f"encoder.{idx + 2}.", f"encoder.layers.{layer}.downsample.")
+    k = k.replace("decoder.0.", "decoder.init_conv1d.")
+    k = k.replace("decoder.14.", "decoder.final_conv1d.")
+    k = k.replace("encoder.0.", "encoder.init_conv1d.")
+    k = k.replace("encoder.14.", "encoder.final_conv1d.")
+    k = k.replace(".block.1.", ".block.0.")
+    k = k.replace(".block.3.", ".block.1.")
+    return k
+
+
+def sanitize_mimi(tensors):
+    """Mimi.sanitize (Mimi.swift:305-377): the checkpoint's own names -> the module key schema, and the axis swaps that take the
+    PyTorch layouts to the reference's ([out, in, k] -> [out, k, in] for `.conv.weight` / `.output_proj.weight` / `.input_proj.weight`,
+    [in, out, k] -> [out, k, in] for `.convtr.weight`).  A name -> array dict (the raw safetensors contents) gives the dict
+    MimiCodec.load takes; a list of names gives the list of renamed keys."""
+    if not isinstance(tensors, dict):
+        return [sanitize_mimi_name(n) for n in tensors]
+    out = {}
+    for raw, v in tensors.items():
+        k = sanitize_mimi_name(raw)
+        v = np.asarray(v)
+        if k.endswith((".conv.weight", ".output_proj.weight", ".input_proj.weight")) and v.ndim >= 2:
+            v = np.swapaxes(v, -1, -2)
+        if k.endswith(".convtr.weight") and v.ndim == 3:
+            v = np.transpose(v, (1, 2, 0))
+        out[k] = v
+    return out

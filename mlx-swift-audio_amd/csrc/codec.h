@@ -25,7 +25,8 @@ struct ConvGemmArgs {
   int M = 0, N = 0, Cin = 0, taps = 1, dil = 1, pad = 0;
   int tanh_out = 0;
   int x_row_mul = 1;                   // convolution stride: A(m, tap, c) = X[m*x_row_mul + tap*dil - pad][c]
-  int gelu = 0;                        // activation on acc + bias (before the residual): 1 = exact-erf GELU, 2 = ELU, 3 = abs, 4 = SiLU, 5 = leaky-ReLU(0.01), 6 = ReLU
+  int gelu = 0;                        // activation on acc + bias (before the residual): 1 = exact-erf GELU, 2 = ELU, 3 = abs, 4 = SiLU, 5 = leaky-ReLU(0.01), 6 = ReLU,
+                                       // 7 = tanh-form GELU (Mimi)
   int64_t ldw = 0;                     // row stride of W (0 = taps*Cin, i.e. dense)
   const int32_t* phase_len = nullptr;  // device [phases], optional (with x_phase_step): sequence z holds phase_len[z] <= T_in valid rows, rows at or
                                        // beyond it read as zero like rows past T_in (padded stacked sequences under a forward-looking window)
@@ -41,6 +42,10 @@ struct ConvGemmArgs {
   // noise term under stacked sequences (needs seq_len, T_out rows == T_in rows): sequence u's value for row r is
   // noise[noise_seq_off[u] + r]; its rows at or past seq_len[u] have no noise value and are not written
   const int32_t* noise_seq_off = nullptr;   // device [n_seq]
+  // ELU(alpha = 1) prologue on X instead of snake / leaky-ReLU (Mimi's SEANet).  elu_pre and gelu == 7 are served by a second set of
+  // instantiations of the kernel (template flag MIMI): the launches without them run the code they ran before the flag existed.
+  // (Not mirrored in mia_conv_gemm_desc: the operator-level hook has no Mimi case; tests/test_mimi_gpu.py covers it end to end.)
+  int elu_pre = 0;
 };
 
 constexpr int MIA_MAX_LEVELS = 4;

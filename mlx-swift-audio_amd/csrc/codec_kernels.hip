@@ -37,14 +37,28 @@ __device__ __forceinline__ float snake_p(float x, float a, float ra) {
   const float s = sin_cw(a * x);
   return x + ra * (s * s);
 }
-
+// ELU with alpha = 1 and the tanh-form GELU 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) of Mimi (Transformer.swift:91-97), on the
+// hardware exponential: libm's expm1f / tanhf took the 128 x 128 tile from 168 to 324 VGPRs.  exp(x) - 1 cancels near 0, so the ELU
+// switches to the Taylor series there (|x| < 0.25: the x^8 / 8! remainder is below 2e-9 of the value); elsewhere the difference keeps
+// the exponential's ~1e-7 absolute error.  tanh(u) = 1 - 2 / (1 + exp(2 u)) is exact at both saturated ends.
+__device__ __forceinline__ float elu1(float x) {
+  if (x > 0.f) return x;
+  if (x > -0.25f) return x * (1.0f + x * (0.5f + x * (1.0f / 6 + x * (1.0f / 24 + x * (1.0f / 120 + x * (1.0f / 720 + x * (1.0f / 5040)))))));
+  return __expf(x) - 1.0f;
+}
+__device__ __forceinline__ float gelu_tanh(float x) {
+  const float u = 0.7978845608028654f * (x + 0.044715f * (x * x * x));
+  return 0.5f * x * (2.0f - 2.0f / (1.0f + __expf(2.0f * u)));
+}
 
 // WM / WN = 32-row / 32-column MFMA tiles per wave (4 waves as 2 x 2): block tile (64 WM) x (64 WN).  <2,2> = 128 x 128 for large
 // problems, <2,1> = 128 x 64 for narrow outputs, <1,1> = 64 x 64 when 128-row tiles would leave most of the 256 CUs idle.
 // KC = 32-wide K chunks per pipeline stage: the next stage's global loads are issued before the MFMAs of the current one, so a stage
 // must hold more MFMA time than one HBM / L2 round trip -- with 64 x 64 tiles a 32-wide stage is only 0.4 us of MFMAs (measured:
 // 3.5x slower than the MFMA bound), hence KC = 4 there.  A chunk never straddles a tap (Cin % 32 == 0); chunks past K are zero.
-template <int WM, int WN, int KC>
+// MIMI = the instantiations that know the ELU prologue (g.elu_pre) and the tanh-form GELU (g.gelu == 7); with MIMI = false both are
+// compiled out and the kernel is the one every other model launches.
+template <int WM, int WN, int KC, bool MIMI = false>
 __global__ __launch_bounds__(256) void conv_gemm_f32(ConvGemmArgs g) {
   constexpr int GBM = 64 * WM;
   constexpr int GBN = 64 * WN;
@@ -151,7 +165,9 @@ __global__ __launch_bounds__(256) void conv_gemm_f32(ConvGemmArgs g) {
 #pragma unroll
       for (int i = 0; i < 2 * WM; ++i) {
         float4 v = ra[ch][i];
-        if (g.alpha) {
+        if (MIMI && g.elu_pre) {
+          v.x = elu1(v.x); v.y = elu1(v.y); v.z = elu1(v.z); v.w = elu1(v.w);
+        } else if (g.alpha) {
           v.x = snake_p(v.x, al[0], ral[0]); v.y = snake_p(v.y, al[1], ral[1]);
           v.z = snake_p(v.z, al[2], ral[2]); v.w = snake_p(v.w, al[3], ral[3]);
         } else if (g.lrelu_slope > 0.f) {
@@ -238,6 +254,7 @@ __global__ __launch_bounds__(256) void conv_gemm_f32(ConvGemmArgs g) {
         else if (g.gelu == 4) v = v / (1.0f + __expf(-v));
         else if (g.gelu == 5) v = v > 0.f ? v : 0.01f * v;
         else if (g.gelu == 6) v = fmaxf(v, 0.f);
+        else if (MIMI && g.gelu == 7) v = gelu_tanh(v);
         if (nz) v = Rb[yr * g.ldr + n] + nz[yr] * v;
         else if (Rb) v += Rb[yr * g.ldr + n];
         if (g.out_scale != 0.f) v *= g.out_scale;
@@ -457,6 +474,7 @@ const char* codec_conv_gemm_check(const ConvGemmArgs& g) {
   if (g.ldx % 4 || ((uintptr_t)g.X & 15) || ((uintptr_t)g.W & 15)) return "conv_gemm: X rows / W must be 16-byte aligned";
   if (g.ldw && (g.ldw % 4 || g.ldw < (int64_t)g.taps * g.Cin)) return "conv_gemm: W row stride must be a multiple of 4 floats and cover taps * Cin";
   if (g.noise && !g.R) return "conv_gemm: noise modulation needs the residual input";
+  if (g.elu_pre && (g.alpha || g.lrelu_slope > 0.f)) return "conv_gemm: one prologue at a time";
   if (g.n_seq < 1 || (g.n_seq > 1 && (g.x_seq_step < g.T_in || g.y_seq_step <= 0 || g.x_phase_step))) return "conv_gemm: bad stacked-sequence arguments";
   if ((g.n_seq > 1 && g.noise && !g.noise_seq_off) || (g.noise_seq_off && (!g.noise || !g.seq_len || g.y_row_mul != 1 || g.y_row_off || g.T_out != g.T_in)))
     return "conv_gemm: stacked noise needs noise_seq_off and seq_len on a row-for-row mapping";
@@ -494,11 +512,27 @@ static void account_conv_gemm(const ConvGemmArgs& g, int phases) {
   t_alg_bytes += b;
 }
 
+// The launches with the ELU prologue or the tanh-form GELU (Mimi): the same choice of tile as below on the MIMI instantiations, except
+// that there is no 128 x 128 tile among them -- the plain one sits at exactly 168 VGPRs, the last count that keeps three waves per SIMD,
+// and anything added to it is compiled to 324 -- so the 128 x 64 tile takes those launches.
+static int conv_gemm_launch_mimi(const ConvGemmArgs& g, int phases, int64_t big_blocks, hipStream_t s) {
+  if (big_blocks < 384) {
+    dim3 grid((g.M + 63) / 64, (g.N + 63) / 64, phases);
+    if ((int64_t)grid.x * grid.y * grid.z <= 320 && g.taps * g.Cin >= 256) hipLaunchKernelGGL((conv_gemm_f32<1, 1, 4, true>), grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL((conv_gemm_f32<1, 1, 1, true>), grid, dim3(256), 0, s, g);
+  } else {
+    dim3 grid((g.M + 127) / 128, (g.N + 63) / 64, phases);
+    hipLaunchKernelGGL((conv_gemm_f32<2, 1, 1, true>), grid, dim3(256), 0, s, g);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int codec_conv_gemm_launch(const ConvGemmArgs& g, int phases_per_seq, hipStream_t s) {
   account_conv_gemm(g, phases_per_seq);
   const int phases = phases_per_seq * (g.n_seq > 1 ? g.n_seq : 1);
   // 128-row tiles only when they still give every CU work; otherwise 64 x 64 tiles (4x the workgroups)
   const int64_t big_blocks = (int64_t)((g.M + 127) / 128) * ((g.N + 127) / 128) * phases;
+  if (g.elu_pre || g.gelu == 7) return conv_gemm_launch_mimi(g, phases, big_blocks, s);
   if (big_blocks < 384) {
     dim3 grid((g.M + 63) / 64, (g.N + 63) / 64, phases);
     // at most ~1 workgroup per CU: nothing else hides the global-load latency of a stage, so stages are 4 chunks deep

@@ -733,3 +733,72 @@ def sensevoice_weights(cfg, seed: int = 0, round_to: str | None = None) -> dict[
         ln(p + ".norm2", L)
         ffn(p + ".feed_forward", L, L // 4)
     return w
+
+
+# ---- Mimi codec (TTS/Marvis/Mimi) ---------------------------------------------------------------------------------------
+def _mimi_micro(context: int):
+    from .mimi import MimiConfig, MimiTransformerConfig, SeanetConfig
+    # d_model 128 = 2 heads x 64; SEANet channels 256 -> 128 -> 64, residual hidden 64 and 32; 2 * 3 * 2 = 12 samples per frame
+    return MimiConfig(sample_rate=24000.0, frame_rate=2000.0, seanet=SeanetConfig(dimension=128, nfilters=64, ratios=(3, 2)),
+                      transformer=MimiTransformerConfig(d_model=128, num_heads=2, num_layers=2, context=context, dim_feedforward=256),
+                      quantizer_nq=4, quantizer_bins=32, quantizer_dim=32)
+
+
+def _mimi_202407():
+    from .mimi import mimi_202407
+    return mimi_202407(32)
+
+
+MIMI_CONFIGS = {"mimi_micro": _mimi_micro(6), "mimi_micro_ctx250": _mimi_micro(250), "mimi_202407": _mimi_202407()}
+
+
+def mimi_weights(cfg, seed: int = 0) -> dict[str, np.ndarray]:
+    """Random-init Mimi decoder-side tensors under the names Mimi.sanitize produces (Mimi.swift:305-377), float32.  LayerScale is not
+    the identity, LayerNorm weight / bias are not 1 / 0, cluster_usage has entries below the 1e-5 floor, and the convolution gains
+    (LeCun x sqrt(2) after each ELU, so the activations neither die nor blow up through the stages) leave the waveform's peak at O(0.1 - 1)."""
+    w: dict[str, np.ndarray] = {}
+    rng = np.random.Generator(np.random.PCG64(seed + 4242))
+    s, t = cfg.seanet, cfg.transformer
+    D, dq = t.d_model, cfg.quantizer_dim
+
+    def normal(shape, scale):
+        return (scale * rng.standard_normal(shape)).astype(np.float32)
+
+    for i in range(cfg.quantizer_nq):
+        p = "quantizer.rvq_first.vq.layers.0.codebook." if i == 0 else f"quantizer.rvq_rest.vq.layers.{i - 1}.codebook."
+        usage = rng.uniform(0.5, 20.0, cfg.quantizer_bins).astype(np.float32)
+        usage[rng.choice(cfg.quantizer_bins, max(cfg.quantizer_bins // 16, 1), replace=False)] = np.float32(1e-7)      # below the floor
+        usage[0] = np.float32(0.0)
+        emb = normal((cfg.quantizer_bins, dq), 1.0 / (1.0 + 0.3 * i))
+        w[p + "embedding_sum"] = (emb * np.maximum(usage, np.float32(1e-5))[:, None]).astype(np.float32)
+        w[p + "cluster_usage"] = usage
+        w[p + "initialized"] = np.ones(1, np.float32)
+    w["quantizer.rvq_first.output_proj.weight"] = normal((D, 1, dq), 1.0 / math.sqrt(dq))
+    w["quantizer.rvq_rest.output_proj.weight"] = normal((D, 1, dq), 1.0 / math.sqrt(dq))
+    w["upsample.convtr.convtr.weight"] = normal((1, 2 * cfg.upsample_stride, D), 0.7)
+    for l in range(t.num_layers):
+        p = f"decoder_transformer.transformer.layers.{l}."
+        for nm in ("norm1", "norm2"):
+            w[p + nm + ".weight"] = (1.0 + 0.2 * rng.standard_normal(D)).astype(np.float32)
+            w[p + nm + ".bias"] = normal(D, 0.1)
+        w[p + "self_attn.in_proj.weight"] = normal((3 * D, D), 1.5 / math.sqrt(D))
+        w[p + "self_attn.out_proj.weight"] = normal((D, D), 1.0 / math.sqrt(D))
+        w[p + "gating.linear1.weight"] = normal((t.dim_feedforward, D), 1.0 / math.sqrt(D))
+        w[p + "gating.linear2.weight"] = normal((D, t.dim_feedforward), 1.0 / math.sqrt(t.dim_feedforward))
+        w[p + "layer_scale_1.scale"] = rng.uniform(0.2, 0.8, D).astype(np.float32)
+        w[p + "layer_scale_2.scale"] = rng.uniform(0.2, 0.8, D).astype(np.float32)
+
+    def conv(p, cout, k, cin, gain):
+        w[p + ".weight"] = normal((cout, k, cin), gain / math.sqrt(k * cin))
+        w[p + ".bias"] = normal(cout, 0.02)
+
+    c = s.nfilters << len(s.ratios)
+    conv("decoder.init_conv1d.conv.conv", c, s.ksize, s.dimension, 0.5)
+    for i, r in enumerate(s.ratios):
+        p = f"decoder.layers.{i}."
+        conv(p + "upsample.convtr.convtr", c // 2, 2 * r, c, 2.0)         # two of the 2 r taps reach an output
+        c //= 2
+        conv(p + "residuals.0.block.0.conv.conv", c // s.compress, s.residual_ksize, c, 1.4)
+        conv(p + "residuals.0.block.1.conv.conv", c, 1, c // s.compress, 1.4)
+    conv("decoder.final_conv1d.conv.conv", 1, s.last_ksize, c, 0.15)
+    return w
