@@ -835,6 +835,87 @@ int mia_sample_top_k_top_p(mia_ctx* ctx, const float* logits, int V, float tempe
 int mia_sample_top_p(mia_ctx* ctx, const float* logits, int V, const int32_t* history, int n_hist, float rep_penalty,
                      float temperature, float top_p, float uniform, int32_t* out);
 
+/* ---- Marvis TTS (CSM): backbone, depth decoder and frame sampler ----------------------------------------------- */
+/* MarvisModel.generateFrame (TTS/Marvis/Models/MarvisModel.swift:466-545) and the loop of MarvisTTS.decodePrompt
+ * (TTS/Marvis/MarvisTTS.swift:452-523) on device; the codes they produce are what mia_mimi_decode / mia_mimi_stream_decode take.
+ * mia_marvis_config (include/mia_marvis.h, included by the callers that fill one) carries MarvisConfig and the two Llama stacks'
+ * dimensions.  Tensors: 16-bit or float32 under the Module keys after the reference's stripModelPrefix + sanitize
+ * (MarvisTTS.swift:249-282; checkpoint.sanitize_marvis): backbone.layers.N.self_attn.{q,k,v,o}_proj.weight, .mlp.{gate,up,down}_proj.weight,
+ * .{input,post_attention}_layernorm.weight, backbone.norm.weight, the same under decoder., text_embeddings.weight [text_vocab][D],
+ * audio_embeddings.weight [n_codebooks * audio_vocab][D], projection.weight [d_dec][D], codebook0_head.weight [audio_vocab][D],
+ * audio_head [n_codebooks - 1][d_dec][audio_vocab] (applied as x @ W).  Weights are rounded to `dtype` (MIA_BF16 | MIA_F16); the residual
+ * stream is fp32 as in the LM step.  A missing or mis-shaped tensor fails the load with a message naming it.  *status (may be NULL)
+ * receives the code: MIA_ERR_UNSUPPORTED for attention_bias / mlp_bias and for audio_vocab > 8192 (the frame sampler holds a row in one
+ * workgroup), MIA_ERR_INVALID_ARGUMENT for everything else wrong with the call.  head_dim 64 | 128, n_codebooks 2..32.
+ *
+ * A row is n_codebooks + 1 ids and a 0/1 mask of the same width; its embedding is
+ *   sum_{c < K} mask[c] * audio_embeddings[c * audio_vocab + id[c]] + mask[K] * text_embeddings[id[K]]        (fp32, columns in that order).
+ * RoPE is interleaved in the reference (pairs (x[2i], x[2i+1]), MarvisLlamaBackbone.swift:129-164); the loader permutes the rows of every
+ * q_proj / k_proj head (new[i] = old[2i], new[i + dh/2] = old[2i+1]) and runs the LM step's split-half kernels: q.k is invariant under a
+ * permutation applied to both.  The frequencies are Llama3ScaledRoPE.applyScaling's (:102-127) in its own fp32 operation order.
+ * A frame: c0 = sample(codebook0_head(lastH)); the decoder starts on an empty cache at position 0, takes projection(lastH) and
+ * projection(audio_emb(0, c0)) at positions 0 and 1 (as two single-row steps: row 0 contributes only its K/V), then
+ * projection(audio_emb(i, c_i)) at position i + 1; the row at position i goes through audio_head[i - 1] and gives c_i;
+ * codebooks = min(n_codebooks, max_codebooks), and codebooks = 1 runs no decoder step.
+ *
+ * The sampler (mia_sample_top_p_ascending is one draw of it) restates MLXLMCommon's TopPSampler -- the reference uses
+ * TopPSampler(temperature: 0.9, topP: 0.8), MarvisTTS.swift:417 -- from that library's published source, which is not part of the reference
+ * tree: the rule is unpinned against it.  Explicit uniforms replace its random draw.  For a row x[0..V) of fp32 logits, V <= 8192,
+ * temperature > 0, 0 < top_p <= 1 and one uniform u in [0,1):
+ *   1. p = softmax(x / temperature) in fp32 with the maximum subtracted; a NaN logit has p = 0.  A row without a positive finite sum gives id 0.
+ *   2. The entries are ordered ascending by p, the lower index first on equal p; a NaN ranks below every number.
+ *   3. c_j = the inclusive ascending cumulative sum.
+ *   4. The kept entries are those from the first j with c_j > 1 - top_p (the subtraction in fp32) to the largest; if there is none, the
+ *      largest alone.
+ *   5. The pick is the first kept j whose cumulative sum over the kept entries, in that ascending order, exceeds u * (their sum); the
+ *      last kept entry if rounding leaves none.
+ *   6. Every sum runs in a fixed order that depends on the row alone: a pick is the same bits in a captured graph and in a direct launch.
+ *
+ * mia_marvis_frame = one generateFrame: appends T >= 1 rows (tokens, mask) [T][n_codebooks + 1] -- a fed-back frame narrower than the
+ * prompt rows is written with mask 0 in its unused columns, which is the same sum -- draws `codebooks` ids with uniforms[codebooks], and
+ * returns them in ids_out.  forced (may be NULL) [codebooks]: id i is replaced by forced[i] after its draw (teacher forcing).  logits_out
+ * (may be NULL) [codebooks][audio_vocab] receives every head's fp32 logits.  The call applies no stop rule of its own.
+ * mia_marvis_generate = decodePrompt: feeds the prompt [T][n_codebooks + 1], then draws up to max_frames frames, each fed back as
+ * [frame | 0] with mask [1 .. 1 | 0]; a frame whose ids are all 0 ends the sentence and is not emitted.  uniforms [max_frames][codebooks],
+ * frames_out [max_frames][codebooks], *n_frames = frames emitted.  T = 0 continues from the state the previous call left (the fed-back
+ * row is the last emitted frame; the codebook count must not change): N frames per call, then the next N, for streaming.  A sequence
+ * that has drawn the all-zero frame stays finished (0 frames) until mia_marvis_reset (= resetCaches).  The loop is one graph launch per
+ * frame and reads the finished flags every 16th frame; for a finished sequence every kernel of the frames launched behind its all-zero
+ * one is a no-op: nothing is drawn or emitted, no K/V row is written and no position advances.
+ * Sentence-level batching (MI355X-side addition; the reference runs its sentences one after another, each behind the same voice prompt,
+ * MarvisTTS.swift:421-445): mia_marvis_set_batch sizes the per-sequence state of the handle and of both stacks (K/V caches included) for up
+ * to max_batch <= 32 sequences and resets them; mia_marvis_generate_batch runs mia_marvis_generate's loop for n_seq prompts side by side --
+ * one read of the weights per step for all of them.  tokens / mask: the rows of all prompts back to back, prompt_offsets [n_seq + 1] (in
+ * rows); uniforms [n_seq][max_frames][codebooks]; frames_out [n_seq][max_frames][codebooks]; n_frames [n_seq].  Sequence b's frames equal
+ * mia_marvis_generate(prompt b, uniforms row b) on the same handle capacity (the capacity selects the step's kernel chain, as in
+ * mia_lm_set_batch).  Sequences finish at different frames; the call returns when all have, or after max_frames.  It starts from and leaves
+ * a reset handle (no continuation).  n_seq above the capacity, an empty prompt, or rows + max_frames > max_ctx for any prompt:
+ * MIA_ERR_INVALID_ARGUMENT.
+ * MIA_ERR_INVALID_ARGUMENT before anything is launched (the handle stays usable): null pointers, an id outside its table (text column
+ * against text_vocab, audio columns against audio_vocab), a mask value other than 0 / 1, max_codebooks < 1, rows in the cache + T +
+ * max_frames > max_ctx, a temperature that is not finite and positive, top_p outside (0, 1], T = 0 on a handle that has drawn no frame
+ * since its reset.  A MIA_ERR_DEVICE after the first launch of a call (a failed launch or copy) resets the handle: its message says so.
+ * Host pointers.
+ * mia_marvis_set_debug: bit 0 launches every frame's kernels directly (no hipGraph), bit 1 walks prompts row by row through the step (no
+ * batched prompt pass).  Ids are the same with bit 0; with bit 1 the logits agree up to fp32 summation order. */
+typedef struct mia_marvis_config mia_marvis_config;    /* defined in include/mia_marvis.h */
+typedef struct mia_marvis mia_marvis;
+mia_marvis* mia_marvis_load(mia_ctx* ctx, const mia_marvis_config* cfg, const mia_tensor_view* tensors, int n_tensors, int dtype, int32_t* status);
+void mia_marvis_free(mia_marvis* m);
+int mia_marvis_reset(mia_marvis* m);
+int mia_marvis_set_debug(mia_marvis* m, int flags);
+int mia_marvis_set_batch(mia_marvis* m, int max_batch);
+int mia_marvis_frame(mia_marvis* m, const int32_t* tokens, const int32_t* mask, int T, int max_codebooks, float temperature, float top_p,
+                     const float* uniforms, const int32_t* forced, int32_t* ids_out, float* logits_out);
+int mia_marvis_generate(mia_marvis* m, const int32_t* tokens, const int32_t* mask, int T, int max_codebooks, float temperature, float top_p,
+                        int max_frames, const float* uniforms, int32_t* frames_out, int32_t* n_frames);
+int mia_marvis_generate_batch(mia_marvis* m, const int32_t* tokens, const int32_t* mask, const int32_t* prompt_offsets, int n_seq, int max_codebooks,
+                              float temperature, float top_p, int max_frames, const float* uniforms, int32_t* frames_out, int32_t* n_frames);
+/* One draw of the rule above on caller-provided logits [V]: *out = the picked id; kept_ids (may be NULL; room for V ids) receives the
+ * kept ids in ascending order of p and *n_kept (may be NULL) their count.  V > 8192: MIA_ERR_UNSUPPORTED.  Host pointers. */
+int mia_sample_top_p_ascending(mia_ctx* ctx, const float* logits, int V, float temperature, float top_p, float uniform, int32_t* out,
+                               int32_t* kept_ids, int32_t* n_kept);
+
 /* ---- Fun-ASR audio half: fbank + LFR + CMVN front end, SenseVoice SANM encoder, audio adaptor ------------------ */
 /* FunASRModel.encodeAudio (STT/FunASR/FunASRModel.swift:41-58): waveform -> the audio rows mia_lm_generate_greedy's prompt takes.
  * SenseVoiceEncoderConfig + AudioAdaptorConfig (STT/FunASR/Config/FunASRConfig.swift:79-214).  Head dim is 128 in both stacks

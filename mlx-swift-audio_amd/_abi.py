@@ -131,6 +131,16 @@ class MimiConfig(C.Structure):
                 ("gating", i32), ("layer_norm", i32), ("layer_scale", i32), ("rope", i32), ("max_period", i32)]
 
 
+class MarvisConfig(C.Structure):
+    """struct mia_marvis_config of include/mia_marvis.h (mia.h only declares the type, so it is not in STRUCTS)."""
+    _fields_ = [("text_vocab", i32), ("audio_vocab", i32), ("n_codebooks", i32), ("max_ctx", i32),
+                ("bb_hidden", i32), ("bb_inter", i32), ("bb_layers", i32), ("bb_heads", i32), ("bb_kv_heads", i32), ("bb_head_dim", i32),
+                ("dec_hidden", i32), ("dec_inter", i32), ("dec_layers", i32), ("dec_heads", i32), ("dec_kv_heads", i32), ("dec_head_dim", i32),
+                ("bb_rms_eps", f32), ("dec_rms_eps", f32), ("bb_rope_theta", f32), ("dec_rope_theta", f32),
+                ("rope_llama3", i32), ("rope_factor", f32), ("rope_low", f32), ("rope_high", f32), ("rope_old_ctx", f32),
+                ("attention_bias", i32), ("mlp_bias", i32)]
+
+
 class LmConfig(C.Structure):
     _fields_ = [("vocab", i32), ("hidden", i32), ("inter", i32), ("n_layers", i32), ("n_heads", i32), ("n_kv_heads", i32),
                 ("head_dim", i32), ("max_ctx", i32),
@@ -335,6 +345,16 @@ PROTOTYPES = {
     "mia_lm_generate_topk_batch": (i32, [vp, vp, vp, i32, f32, i32, f32, vp, i32, i32, vp, vp, i32, vp]),
     "mia_sample_top_k_top_p": (i32, [vp, vp, i32, f32, i32, f32, f32, vp, vp, vp]),
     "mia_sample_top_p": (i32, [vp, vp, i32, vp, i32, f32, f32, f32, f32, vp]),
+    # Marvis TTS
+    "mia_marvis_load": (vp, [vp, vp, TV, i32, i32, vp]),
+    "mia_marvis_free": (None, [vp]),
+    "mia_marvis_reset": (i32, [vp]),
+    "mia_marvis_set_debug": (i32, [vp, i32]),
+    "mia_marvis_set_batch": (i32, [vp, i32]),
+    "mia_marvis_frame": (i32, [vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp]),
+    "mia_marvis_generate": (i32, [vp, vp, vp, i32, i32, f32, f32, i32, vp, vp, vp]),
+    "mia_marvis_generate_batch": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, i32, vp, vp, vp]),
+    "mia_sample_top_p_ascending": (i32, [vp, vp, i32, f32, f32, f32, vp, vp, vp]),
     # Fun-ASR audio half
     "mia_sensevoice_load": (vp, [vp, P(SensevoiceConfig), TV, i32, i32]),
     "mia_sensevoice_free": (None, [vp]),

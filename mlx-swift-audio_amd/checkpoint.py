@@ -193,3 +193,31 @@ def sanitize_mimi(tensors):
             v = np.transpose(v, (1, 2, 0))
         out[k] = v
     return out
+
+
+def sanitize_marvis_name(raw: str) -> str:
+    """stripModelPrefix + sanitize of one Marvis checkpoint key (TTS/Marvis/MarvisTTS.swift:237-282), replacement for replacement."""
+    k = raw[6:] if raw.startswith("model.") else raw
+    if "attn" in k and "self_attn" not in k:
+        k = k.replace("attn", "self_attn")
+        k = k.replace("output_proj", "o_proj")
+    if "mlp" in k:
+        k = k.replace("w1", "gate_proj")
+        k = k.replace("w2", "down_proj")
+        k = k.replace("w3", "up_proj")
+    if "sa_norm" in k or "mlp_norm" in k:
+        k = k.replace("sa_norm", "input_layernorm")
+        k = k.replace("scale", "weight")
+        k = k.replace("mlp_norm", "post_attention_layernorm")
+        k = k.replace("scale", "weight")
+    if "decoder.norm" in k or "backbone.norm" in k:
+        k = k.replace("scale", "weight")
+    return k
+
+
+def sanitize_marvis(tensors):
+    """A name -> array dict (the raw safetensors contents) gives the dict MarvisModel.load takes; a list of names gives the renamed keys.
+    No tensor changes its layout."""
+    if not isinstance(tensors, dict):
+        return [sanitize_marvis_name(n) for n in tensors]
+    return {sanitize_marvis_name(n): v for n, v in tensors.items()}

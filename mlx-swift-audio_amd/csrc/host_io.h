@@ -17,6 +17,7 @@ class HostIo {
  public:
   HostIo(mia_ctx* ctx, int mem) : ctx_(ctx), mem_(mem) {}
   static HostIo device(mia_ctx* ctx) { return HostIo(ctx, MIA_MEM_DEVICE); }     // internal calls on device pointers
+  static HostIo host(mia_ctx* ctx) { return HostIo(ctx, MIA_MEM_HOST); }         // entry points whose pointers are host memory by contract
   static bool valid(int mem) { return mem == MIA_MEM_HOST || mem == MIA_MEM_DEVICE; }
   HostIo(const HostIo&) = delete;
   ~HostIo() { if (pending_) (void)hipStreamSynchronize(ctx_->stream); }           // a return before finish(): it already carries its own error

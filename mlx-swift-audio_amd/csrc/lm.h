@@ -6,7 +6,9 @@
 
 #include "mia_internal.h"
 
-struct LmState { int pos; int n_hist; int finished; int n_gen; int n_embeds; int n_out; int u_cursor; int n_prompt; int min_len; int max_len; };   // min/max_len: RAS and greedy loops, per sequence
+struct LmState { int pos; int n_hist; int finished; int n_gen; int n_embeds; int n_out; int u_cursor; int n_prompt; int min_len; int max_len; int frozen; };   // min/max_len: RAS and greedy loops, per sequence
+// frozen (the Marvis frame sets it when a sequence has drawn its all-zero frame; 0 everywhere else): the step's kernels on the 16-bit cache
+// are no-ops for the sequence -- no embedding, no K/V row, no position advance -- so steps launched before the host reads the flag touch nothing of it
 
 struct RasParams { float top_p; int top_k; int win; float tau; int eos; int min_len; int max_len; int n_uniforms; };
 
@@ -115,6 +117,23 @@ void lm_sample_topk_launch(hipStream_t s, const float* logits, int V, int32_t* t
 void lm_launch_rope_cache(mia_lm* m, int layer, const float* qkv, const float* bias, void* q, const int2* rowmap, int M);
 // fused: rows = sequences (row b uses state b and the b-th cache of the layer); otherwise rows = (sequence, position) pairs of rowmap
 int lm_launch_attention(mia_lm* m, bool fused, int rows, const void* q, int layer, void* att, const int2* rowmap, const float* part, int S, const float* bias);
+
+// ---- lm.hip: the pieces of one decode step, shared by the LM step (lm_enqueue_step) and the Marvis frame (marvis.hip) ----
+// rows 0 .. nb-1 = sequences 0 .. nb-1 at their own LmState::pos: embedding (token id or the embedding row at that position) + first norm,
+// then every layer (q|k|v GEMM -> RoPE + cache row + attention -> o-proj -> gate|up -> down).  Leaves the residual stream in m->x and the
+// last layer's carried activation in m->h; positions are NOT advanced.  -1 when a launch is refused
+int lm_enqueue_layers(mia_lm* m, int nb);
+// out [nb][ldo] fp32 = final_norm(last hidden state) . W^T (+ bias), W [N][hidden] (Wf: its fragment-order copy or null; qw: packed copy or null)
+int lm_enqueue_linear_of_last(mia_lm* m, int nb, const void* W, const void* Wf, const float* bias, const Q4W* qw, float* out, int64_t ldo, int N);
+// pos += 1 for sequences 0 .. nb-1
+void lm_enqueue_advance(mia_lm* m, int nb);
+// whether the handle's step carries the RMSNorm across its GEMMs (capacity <= 4) or runs the split-K + reduce / norm chain
+bool lm_fused_norm(const mia_lm* m);
+// batched prompt pass.  rows: (sequence, position) pairs, every sequence's positions ascending; after the pass set_pos[b] (if >= 0) becomes
+// state b's position.  Only K/V rows are produced: the caller runs each prompt's last position through the step
+constexpr int LM_PREFILL_MIN_ROWS = 8;     // below this the step is as fast
+bool lm_prefill_supported(const mia_lm* m);
+int lm_prefill_rows(mia_lm* m, const std::vector<int2>& rows, const std::vector<int>& set_pos);
 
 // ---- lm_kvq.hip ----
 // one layer's packed cache (all sequences) and what its kernels need of the model

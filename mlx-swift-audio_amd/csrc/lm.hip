@@ -65,6 +65,7 @@ __global__ __launch_bounds__(256) void lm_embed_norm(const int32_t* __restrict__
   const int tid = threadIdx.x, nv = D >> 2;
   const int seq = rowmap ? rowmap[blockIdx.x].x : (int)blockIdx.x;         // prompt pass: row -> (sequence, position)
   st += seq; tokens += (int64_t)seq * max_ctx; embeds += (int64_t)seq * max_ctx * D;
+  if (!rowmap && st->frozen) return;                       // (the same for every thread of the workgroup)
   const int pos = rowmap ? rowmap[blockIdx.x].y : st->pos;
   x += (int64_t)blockIdx.x * D; h += (int64_t)blockIdx.x * D;
   const bool from_rows = pos < st->n_embeds;               // prompt given as embedding rows
@@ -196,6 +197,7 @@ __global__ __launch_bounds__(64 * ATT_NW) void lm_attention(const uint16_t* __re
   extern __shared__ float sc[];            // [max_ctx] scores, then red[ATT_NW][DH] + red2[2 * ATT_NW] (+ FUSED: q, k, v rows [3][DH])
   const int seq = FUSED ? (int)blockIdx.y : rowmap[blockIdx.y].x;          // FUSED: row = sequence; prompt pass: row -> (sequence, position)
   st += seq; kc += (int64_t)seq * seq_stride; vc += (int64_t)seq * seq_stride;
+  if (FUSED && st->frozen) return;                          // a frozen sequence's step writes no cache row (uniform over the workgroup)
   constexpr int LPK = DH / 8;              // lanes per key
   constexpr int KPW = 64 / LPK;            // keys per wave instruction
   float* red = sc + max_ctx;
@@ -339,7 +341,7 @@ __global__ __launch_bounds__(64 * ATT_NW) void lm_attention(const uint16_t* __re
 }
 
 // greedy / plain path: advance only (logits are read back by the host)
-__global__ void lm_advance(LmState* st) { st[blockIdx.x].pos += 1; }
+__global__ void lm_advance(LmState* st) { if (!st[blockIdx.x].frozen) st[blockIdx.x].pos += 1; }
 __global__ void lm_set_pos(LmState* st, int pos) { st->pos = pos; }
 
 // batched prompt pass: act[r][j] = silu(gu[r][2j]) * gu[r][2j+1] from the fp32 GEMM output (same expression as the SK_SWIGLU epilogue)
@@ -408,37 +410,40 @@ int lm_launch_attention(mia_lm* m, bool fused, int rows, const void* q, int laye
   return 0;
 }
 
-namespace {
+// one skinny GEMM of the step chain on nb rows of the handle (16-bit or packed weights; fragment order when the handle has the copy)
+static int lm_skinny(mia_lm* m, int nb, const void* A, int64_t lda, const void* W, const void* Wf, const float* bias, void* out, int64_t ldo, int N, int K, int S,
+                     int mode, const Q4W* qw = nullptr, const float* ss_in = nullptr, const float* nw = nullptr, float* ss_out = nullptr, float rs_scale = 1.f) {
+  const mia_lm_config& c = m->cfg;
+  SkinnyArgs a{(const uint16_t*)A, lda, (const uint16_t*)W, bias, out, ldo, nullptr, nullptr, nullptr, nb, N, K, S, MIA_ACT_NONE, 0, 0, 0};
+  if (ss_in) { a.ss_in = ss_in; a.ss_tiles = c.hidden / 16; a.ss_dim = c.hidden; a.eps = c.rms_eps; a.rs_scale = rs_scale; }
+  if (mode == SK_RESID) { a.xres = m->x; a.nw = nw; a.ss_out = ss_out; }
+  if (m->q4 && qw && qw->wfrag) return skinny_gemm_q_launch(a, qw->wfrag, qw->stfrag, m->q_bits, mode, m->dtype, m->ctx->stream, m->B_cap);      // the form follows the capacity (skinny.h)
+  if (Wf) { a.W = (const uint16_t*)Wf; a.w_frag = 1; }      // same K order and partition as the row-major form: identical results
+  return skinny_gemm_launch(a, mode, m->dtype, m->ctx->stream);
+}
 
-// (the samplers read each sequence's prompt length from its state: a captured and a directly launched step issue the same arguments)
-// mode: LM_STEP_* (what ends the step); sp: the top-p sampler's arguments, the greedy one's stop ids, or the top-k one's temperature, top_p
-// and stop ids with its effective k in top_k; ras: the RAS sampler's
-int lm_enqueue_step(mia_lm* m, int mode, const mia_lm_sampler& sp, const RasParams* ras = nullptr, int nb = 1, int top_k = 0) {
+bool lm_fused_norm(const mia_lm* m) { return (m->cfg.hidden % 16) == 0 && m->cfg.hidden <= 8192 && m->B_cap <= 4; }
+
+// nb sequences = nb rows of every skinny GEMM: the weights are still read once per step
+// RMSNorm rides on the GEMMs (skinny.h, SkinnyArgs): the two residual-writing projections (o, down) add into x, emit the next block's
+// activation x * norm weight (16 bit) and per-tile sums of squares; the GEMM that consumes it scales its accumulators by rstd.  Two
+// launches less per layer than "GEMM -> split-K partials -> reduce + norm kernel" (5.1 us each on Orpheus-3B, 56 per token).
+// Up to 4 sequences (the latency-critical case).  Wider batches keep the split-K + reduce / norm chain: without a cross-workgroup split the
+// residual-writing projections run on hidden / 16 workgroups only (32 sentences side by side, Orpheus-3B: 6 400 tokens/s fused, 9 500 split).
+// The choice follows the handle's CAPACITY (mia_lm_set_batch), not the rows of this call: within one capacity every call -- one sequence
+// or many -- runs the same chain, so a sequence's ids do not depend on which batch it sits in.
+int lm_enqueue_layers(mia_lm* m, int nb) {
   hipStream_t s = m->ctx->stream;
   const mia_lm_config& c = m->cfg;
   const int D = c.hidden, dh = c.head_dim, Nq = c.n_heads * dh, Nk = c.n_kv_heads * dh, Nqkv = Nq + 2 * Nk;
   const bool f16 = m->dtype == MIA_F16;
-  // nb sequences = nb rows of every skinny GEMM: the weights are still read once per step
-  // RMSNorm rides on the GEMMs (skinny.h, SkinnyArgs): the two residual-writing projections (o, down) add into x, emit the next block's
-  // activation x * norm weight (16 bit) and per-tile sums of squares; the GEMM that consumes it scales its accumulators by rstd.  Two
-  // launches less per layer than "GEMM -> split-K partials -> reduce + norm kernel" (5.1 us each on Orpheus-3B, 56 per token).
-  // Up to 4 sequences (the latency-critical case).  Wider batches keep the split-K + reduce / norm chain: without a cross-workgroup split the
-  // residual-writing projections run on hidden / 16 workgroups only (32 sentences side by side, Orpheus-3B: 6 400 tokens/s fused, 9 500 split).
-  // The choice follows the handle's CAPACITY (mia_lm_set_batch), not the rows of this call: within one capacity every call -- one sequence
-  // or many -- runs the same chain, so a sequence's ids do not depend on which batch it sits in.
-  const bool fused_norm = (D % 16) == 0 && D <= 8192 && m->B_cap <= 4;
+  const bool fused_norm = lm_fused_norm(m);
   const int ss_tiles = D / 16;
   float* ss_o = m->ss;                                   // written by o-proj, read by gate|up
   float* ss_d = m->ss + (size_t)ss_tiles * m->B_cap;     // written by down-proj, read by the next q|k|v (or the head)
-  struct Norm { const float* ss = nullptr; };            // consumer side: which partial sums (null = activation already normalised)
   auto skinny = [&](const void* A, int64_t lda, const void* W, const void* Wf, const float* bias, void* out, int64_t ldo, int N, int K, int S, int mode,
                     const Q4W* qw = nullptr, const float* ss_in = nullptr, const float* nw = nullptr, float* ss_out = nullptr, float rs_scale = 1.f) {
-    SkinnyArgs a{(const uint16_t*)A, lda, (const uint16_t*)W, bias, out, ldo, nullptr, nullptr, nullptr, nb, N, K, S, MIA_ACT_NONE, 0, 0, 0};
-    if (ss_in) { a.ss_in = ss_in; a.ss_tiles = ss_tiles; a.ss_dim = D; a.eps = c.rms_eps; a.rs_scale = rs_scale; }
-    if (mode == SK_RESID) { a.xres = m->x; a.nw = nw; a.ss_out = ss_out; }
-    if (m->q4 && qw && qw->wfrag) return skinny_gemm_q_launch(a, qw->wfrag, qw->stfrag, m->q_bits, mode, m->dtype, s, m->B_cap);      // the form follows the capacity (skinny.h)
-    if (Wf) { a.W = (const uint16_t*)Wf; a.w_frag = 1; }      // same K order and partition as the row-major form: identical results
-    return skinny_gemm_launch(a, mode, m->dtype, s);
+    return lm_skinny(m, nb, A, lda, W, Wf, bias, out, ldo, N, K, S, mode, qw, ss_in, nw, ss_out, rs_scale);
   };
   LAUNCH_T(lm_embed_norm, dim3(nb), dim3(256), 0, m->tokens, (const uint16_t*)m->embed, (const uint16_t*)m->gen_embed, m->embeds, m->layers[0].in_norm, m->x, (uint16_t*)m->h, m->state, D, c.rms_eps, (const int2*)nullptr, c.max_ctx, c.vocab, m->gen_rows);
   for (int l = 0; l < c.n_layers; ++l) {
@@ -462,15 +467,39 @@ int lm_enqueue_step(mia_lm* m, int mode, const mia_lm_sampler& sp, const RasPara
     if (skinny(m->act, c.inter, L.wdown, L.wdown_f, nullptr, m->partial, 0, D, c.inter, m->S_down, SK_PARTIAL, &L.q_down)) return -1;
     LAUNCH_T(lm_reduce_norm, dim3(nb), dim3(256), 0, m->partial, m->S_down, next_norm, m->x, (uint16_t*)m->h, D, c.rms_eps, nb);
   }
+  return 0;
+}
+
+// out [nb][ldo] (fp32) = final_norm(x) . W^T (+ bias): m->h is the last layer's carried activation (fused chain: still to be divided by its
+// rms, which the GEMM does from the down-projection's sums of squares) or the normalised row (split-K chain)
+int lm_enqueue_linear_of_last(mia_lm* m, int nb, const void* W, const void* Wf, const float* bias, const Q4W* qw, float* out, int64_t ldo, int N) {
+  const mia_lm_config& c = m->cfg;
+  const float* ss_d = m->ss + (size_t)(c.hidden / 16) * m->B_cap;
+  return lm_skinny(m, nb, m->h, c.hidden, W, Wf, bias, out, ldo, N, c.hidden, 1, SK_OUTF32, qw, lm_fused_norm(m) && c.n_layers > 0 ? ss_d : nullptr, nullptr, nullptr, m->final_rs);
+}
+
+void lm_enqueue_advance(mia_lm* m, int nb) { hipLaunchKernelGGL(lm_advance, dim3(nb), dim3(1), 0, m->ctx->stream, m->state); }
+
+namespace {
+
+// (the samplers read each sequence's prompt length from its state: a captured and a directly launched step issue the same arguments)
+// mode: LM_STEP_* (what ends the step); sp: the top-p sampler's arguments, the greedy one's stop ids, or the top-k one's temperature, top_p
+// and stop ids with its effective k in top_k; ras: the RAS sampler's
+int lm_enqueue_step(mia_lm* m, int mode, const mia_lm_sampler& sp, const RasParams* ras = nullptr, int nb = 1, int top_k = 0) {
+  hipStream_t s = m->ctx->stream;
+  const mia_lm_config& c = m->cfg;
+  if (lm_enqueue_layers(m, nb)) return -1;
   const int HV = m->head_vocab > 0 ? m->head_vocab : c.vocab;
-  if (skinny(m->h, D, m->lm_head, m->lm_head_f, m->head_bias, m->logits, HV, HV, D, 1, SK_OUTF32, &m->q_head, fused_norm && c.n_layers > 0 ? ss_d : nullptr, nullptr, nullptr, m->final_rs)) return -1;
+  if (lm_enqueue_linear_of_last(m, nb, m->lm_head, m->lm_head_f, m->head_bias, &m->q_head, m->logits, HV, HV)) return -1;
   if (mode == LM_STEP_RAS) lm_sample_ras_launch(s, m->logits, HV, m->tokens, m->out_tokens, m->uniforms, m->state, *ras, c.max_ctx, nb);
   else if (mode == LM_STEP_TOP_P) lm_sample_launch(s, m->logits, HV, m->tokens, m->hist, m->uniforms, m->state, m->smx, sp, -1, c.max_ctx, nb);
   else if (mode == LM_STEP_GREEDY) lm_sample_greedy_launch(s, m->logits, HV, m->tokens, m->out_tokens, m->state, m->smx, sp, c.max_ctx, nb);
   else if (mode == LM_STEP_TOPK) lm_sample_topk_launch(s, m->logits, HV, m->tokens, m->out_tokens, m->uniforms, m->state, m->smx, sp, top_k, c.max_ctx, nb);
-  else hipLaunchKernelGGL(lm_advance, dim3(nb), dim3(1), 0, s, m->state);
+  else lm_enqueue_advance(m, nb);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+}  // namespace
 
 // ---- batched prompt pass ---------------------------------------------------------------------------
 // Positions [pos0, pos0 + P) of the sequence (token ids already in m->tokens, or embedding rows in m->embeds) go through the
@@ -480,8 +509,8 @@ int lm_enqueue_step(mia_lm* m, int mode, const mia_lm_sampler& sp, const RasPara
 // fp32 residual stream, 16-bit RMSNorm output, fp32 q|k|v -> RoPE -> 16-bit, same attention kernel (row r sees keys [0, pos0+r]),
 // fp32 gate/up -> silu(g)*u -> 16-bit.  (The reference does the same thing: model(promptIds, cache) is one batched call,
 // OrpheusTTS.swift:262-279 / Qwen2LM.swift:353-361.)
-constexpr int PF_ROWS = 512;
-constexpr int PF_MIN_ROWS = 8;     // below this the step graph is as fast
+static constexpr int PF_ROWS = 512;
+static constexpr int PF_MIN_ROWS = LM_PREFILL_MIN_ROWS;
 
 bool lm_prefill_supported(const mia_lm* m) {
   const bool off = (m->debug_flags & 2) != 0;      // test hook (mia_lm_set_debug)
@@ -566,11 +595,13 @@ int lm_prefill_rows(mia_lm* m, const std::vector<int2>& rows, const std::vector<
 }
 
 // positions [pos0, pos0 + P) of sequence 0
-int lm_prefill(mia_lm* m, int pos0, int P) {
+static int lm_prefill(mia_lm* m, int pos0, int P) {
   std::vector<int2> rows(P);
   for (int i = 0; i < P; ++i) rows[i] = make_int2(0, pos0 + i);
   return lm_prefill_rows(m, rows, {pos0 + P});
 }
+
+namespace {
 
 int lm_graph(mia_lm* m, int mode, const mia_lm_sampler& sp, const RasParams* ras = nullptr, int nb = 1, int top_k = 0) {
   mia_ctx* ctx = m->ctx;

@@ -802,3 +802,56 @@ def mimi_weights(cfg, seed: int = 0) -> dict[str, np.ndarray]:
         conv(p + "residuals.0.block.1.conv.conv", c, 1, c // s.compress, 1.4)
     conv("decoder.final_conv1d.conv.conv", 1, s.last_ksize, c, 0.15)
     return w
+
+
+# ---- Marvis TTS ---------------------------------------------------------------------------------------------------
+def _marvis_configs():
+    from .marvis import MarvisConfig, MarvisStackConfig
+    bb = MarvisStackConfig(256, 512, 2, 4, 2, 64)
+    micro = dict(text_vocab=300, audio_vocab=67, n_codebooks=5, max_ctx=96)      # audio_vocab odd and no multiple of 16
+    return {
+        "marvis-micro": MarvisConfig(bb, MarvisStackConfig(128, 384, 2, 2, 1, 64), **micro),
+        # the llama-100M flavour's head width in the decoder
+        "marvis-micro128": MarvisConfig(bb, MarvisStackConfig(128, 384, 2, 1, 1, 128), **micro),
+        "marvis-csm-1b": MarvisConfig.from_flavors("llama-1B", "llama-100M"),
+    }
+
+
+MARVIS_CONFIGS = _marvis_configs()
+
+
+def marvis_weights(cfg, seed: int = 0, round_to: str | None = None, head_scale: float = 1.0) -> dict[str, np.ndarray]:
+    """Random-init Marvis checkpoint under the Module key schema (what checkpoint.sanitize_marvis produces).  N(0, 1/fan_in) matrices,
+    RMSNorm weights ~ 1; embeddings N(0, 1/D) x 3 in every row, id 0 included (the all-zero frame and text id 0 embed to something); the
+    heads N(0, 1/fan_in) x 3 x head_scale, so that the logits spread over a few units."""
+    w: dict[str, np.ndarray] = {}
+
+    def rnd(name, shape, std):
+        rng = np.random.Generator(np.random.PCG64(_key_seed(name, seed)))
+        w[name] = round_array(rng.standard_normal(shape, dtype=np.float32) * np.float32(std), round_to)
+
+    def vec(name, n):
+        rng = np.random.Generator(np.random.PCG64(_key_seed(name, seed)))
+        w[name] = (1.0 + 0.1 * rng.standard_normal(n)).astype(np.float32)
+
+    for prefix, s in (("backbone", cfg.backbone), ("decoder", cfg.decoder)):
+        D, dh = s.hidden, s.head_dim
+        for l in range(s.layers):
+            p = f"{prefix}.layers.{l}"
+            vec(p + ".input_layernorm.weight", D)
+            vec(p + ".post_attention_layernorm.weight", D)
+            rnd(p + ".self_attn.q_proj.weight", (s.heads * dh, D), 1.0 / math.sqrt(D))
+            rnd(p + ".self_attn.k_proj.weight", (s.kv_heads * dh, D), 1.0 / math.sqrt(D))
+            rnd(p + ".self_attn.v_proj.weight", (s.kv_heads * dh, D), 1.0 / math.sqrt(D))
+            rnd(p + ".self_attn.o_proj.weight", (D, s.heads * dh), 1.0 / math.sqrt(s.heads * dh))
+            rnd(p + ".mlp.gate_proj.weight", (s.inter, D), 1.0 / math.sqrt(D))
+            rnd(p + ".mlp.up_proj.weight", (s.inter, D), 1.0 / math.sqrt(D))
+            rnd(p + ".mlp.down_proj.weight", (D, s.inter), 1.0 / math.sqrt(s.inter))
+        vec(prefix + ".norm.weight", D)
+    D, Dd, V, K = cfg.backbone.hidden, cfg.decoder.hidden, cfg.audio_vocab, cfg.n_codebooks
+    rnd("text_embeddings.weight", (cfg.text_vocab, D), 3.0 / math.sqrt(D))
+    rnd("audio_embeddings.weight", (K * V, D), 3.0 / math.sqrt(D))
+    rnd("projection.weight", (Dd, D), 1.0 / math.sqrt(D))
+    rnd("codebook0_head.weight", (V, D), 3.0 * head_scale / math.sqrt(D))
+    rnd("audio_head", (K - 1, Dd, V), 3.0 * head_scale / math.sqrt(Dd))
+    return w
