@@ -609,6 +609,32 @@ void mia_mimi_stream_free(mia_mimi_stream* s);
 int mia_mimi_stream_reset(mia_mimi_stream* s);
 int mia_mimi_stream_decode(mia_mimi_stream* s, const int32_t* codes, int n_q, int64_t n, float* pcm, int64_t pcm_capacity,
                            int64_t* n_samples, int pcm_mem);
+/* Mimi encode (Mimi.encode, Mimi.swift:174-182; the codec call of MarvisTTS.tokenizeAudio, MarvisTTS.swift:318-348).  The encode side of
+ * a handle is OPTIONAL: it is loaded when the tensors carry encoder.{init_conv1d,layers.N.residuals.0.block.M,layers.N.downsample,
+ * final_conv1d}.conv.conv.*, encoder_transformer.transformer.layers.N.*, downsample.conv.conv.weight [D][2 stride][D] and
+ * quantizer.rvq_{first,rest}.input_proj.weight [dq][1][D].  With none of them the handle is the decode-only one and every entry below
+ * returns MIA_ERR_INVALID_ARGUMENT ("no encoder loaded"); with some but not all the load fails and names the missing tensor.  The encode
+ * side additionally needs quantizer_dim to be a multiple of 8, at most 504.
+ * Lengths: every strided stage maps L rows to ceil(L / r), so n_samples samples give P = the ceil chain over the SEANet ratios
+ * positions and mia_mimi_encode_frames = ceil(P / upsample_stride) code frames (one frame per 1920 samples, rounded up, for
+ * mimi_202407); 0 for a decode-only handle or n_samples < 1.
+ * mia_mimi_encode: pcm float32 [n_samples] at the codec's rate (host or device, `pcm_mem`) -> codes int32 [n_q][T], a HOST array of
+ * dense rows of T = *n_frames ids (codes_capacity, in frames, only has to cover T).  n_q in [1, nq] asks for the first n_q stages of the
+ * split residual quantiser (row 0 = rvq_first); their codes do not depend on the later stages.  Equal distances go to the lowest index.
+ * mia_mimi_encode_latent stops in front of the quantiser: the [T][d_model] rows it sees (`data_mem` describes pcm and latent alike;
+ * capacity in frames).  mia_mimi_quantize is the quantiser alone on caller latents (`latent_mem` describes `latent`; `codes` is a
+ * host array [n_q][T]).  As with pcm_mem above, the parameter names say what the memory kind covers.
+ * mia_mimi_quantize(mia_mimi_encode_latent(x)) == mia_mimi_encode(x) bit for bit.
+ * Refused with MIA_ERR_INVALID_ARGUMENT before anything is launched, the handle and its streams unchanged: a null pointer,
+ * n_samples < 1, n_q outside [1, nq], a capacity below mia_mimi_encode_frames(n_samples), T outside [1, 2^21], and a clip of more than
+ * 2^27 / seanet_nfilters samples (2^21 = 87 s at 24 kHz for mimi_202407: the three rotating SEANet buffers of n_samples x nfilters
+ * floats are 512 MiB each at that length).  Mimi.encodeStep (streaming encode) has no caller in the reference and is not built. */
+int64_t mia_mimi_encode_frames(mia_mimi* m, int64_t n_samples);
+int mia_mimi_encode(mia_mimi* m, const float* pcm, int64_t n_samples, int n_q, int32_t* codes, int64_t codes_capacity, int64_t* n_frames,
+                    int pcm_mem);
+int mia_mimi_encode_latent(mia_mimi* m, const float* pcm, int64_t n_samples, float* latent, int64_t capacity, int64_t* n_frames,
+                           int data_mem);
+int mia_mimi_quantize(mia_mimi* m, const float* latent, int64_t T, int n_q, int32_t* codes, int latent_mem);
 
 /* ---- OuteTTS speaker-profile audio (TTS/OuteTTS/OuteTTSAudioProcessor.swift) ------------------------------------
  * The sample arithmetic of createSpeakerFromTranscription (:363-453); the word / code slicing around it is host integer arithmetic

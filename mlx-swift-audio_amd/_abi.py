@@ -302,6 +302,10 @@ PROTOTYPES = {
     "mia_mimi_stream_free": (None, [vp]),
     "mia_mimi_stream_reset": (i32, [vp]),
     "mia_mimi_stream_decode": (i32, [vp, vp, i32, i64, vp, i64, vp, i32]),
+    "mia_mimi_encode_frames": (i64, [vp, i64]),
+    "mia_mimi_encode": (i32, [vp, vp, i64, i32, vp, i64, vp, i32]),
+    "mia_mimi_encode_latent": (i32, [vp, vp, i64, vp, i64, vp, i32]),
+    "mia_mimi_quantize": (i32, [vp, vp, i64, i32, vp, i32]),
     # OuteTTS speaker-profile audio
     "mia_speaker_audio_create": (vp, [vp, vp, i64, i32, f32, f32]),
     "mia_speaker_audio_free": (None, [vp]),

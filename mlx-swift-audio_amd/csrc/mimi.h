@@ -1,4 +1,5 @@
-// mimi.h -- launch interface of the Mimi decoder's own kernels (mimi_kernels.hip); the layer program and the C ABI are in mimi.hip.
+// mimi.h -- launch interface of Mimi's own kernels: the decoder's (mimi_kernels.hip; layer program and C ABI in mimi.hip) and the
+// encoder's (mimi_encode_kernels.hip; layer program and C ABI in mimi_encode.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,3 +18,29 @@ int mimi_window_attn_launch(const float* q, const float* K, const float* V, floa
                             int ctx, float scale, hipStream_t s);
 // out[t] = bias + sum_{k, c} w[k * C + c] * elu(x[t + k][c])      x: [K - 1 + T][C], the first K - 1 rows are the left context
 int mimi_conv_out1_launch(const float* x, const float* w, const float* bias, float* out, int64_t T, int C, int K, hipStream_t s);
+
+// ---- encode side (mimi_encode_kernels.hip)
+// edge padding of the latent downsample: y = [front copies of x[0] | the P rows of x | back copies of x[P - 1]], rows of D floats
+int mimi_edge_rows_launch(const float* x, float* y, int64_t P, int D, int front, int back, hipStream_t s);
+
+constexpr int MIMI_RVQ_TILE = 32;      // frames per workgroup of the chain stage
+constexpr int MIMI_RVQ_SLICE = 128;    // codebook entries per workgroup
+// One stage of one residual chain for the launch below.  r_in: the residual the PREVIOUS stage saw, [n_tiles * 32][ld_in] (rows at or
+// past T are never read).  If prev_pd is set, the stage's prologue first finishes the previous stage: it reduces that stage's partials
+// (prev_slices per frame, lexicographic on (distance, index)), writes the code to prev_codes[frame], and continues on
+// r = r_in - e_prev[code]; the workgroups of slice 0 also store r to r_out ([n_tiles * 32][dq]).  Without prev_pd, r = r_in.
+// Then every workgroup forms d[j] = c2[j] - r . e[j] over its slice of entries and writes its best (d, j) per frame to pd / pi
+// ([slices][n_tiles * 32]).
+struct MimiRvqChain {
+  const float* r_in = nullptr; int64_t ld_in = 0;
+  const float* e = nullptr; const float* c2 = nullptr;           // this stage's entries [bins][dq] and ||e||^2 / 2
+  float* pd = nullptr; int32_t* pi = nullptr;
+  const float* prev_pd = nullptr; const int32_t* prev_pi = nullptr; const float* e_prev = nullptr;
+  int32_t* prev_codes = nullptr; float* r_out = nullptr;
+};
+// grid = (frame tiles, slices of `a` + slices of `b`): chain b (optional, b.e == nullptr: absent) rides in the same launch
+int mimi_rvq_stage_launch(const MimiRvqChain& a, const MimiRvqChain& b, int64_t T, int bins, int dq, hipStream_t s);
+// the reduction of a chain's last stage: codes[frame] from its partials, for up to two chains (pd_b == nullptr: one)
+int mimi_rvq_finish_launch(const float* pd_a, const int32_t* pi_a, int32_t* codes_a, const float* pd_b, const int32_t* pi_b, int32_t* codes_b,
+                           int64_t T, int bins, hipStream_t s);
+static inline int mimi_rvq_slices(int bins) { return (bins + MIMI_RVQ_SLICE - 1) / MIMI_RVQ_SLICE; }

@@ -1,5 +1,6 @@
 // mimi.hip -- Mimi codec decode (TTS/Marvis/Mimi/): whole clips (Mimi.decode, Mimi.swift:184-192) and carried-state streaming
 // (MimiStreamingDecoder.decodeFrames, Mimi.swift:227-238), fp32 like the reference.  Loader, layer program, stream state, C ABI.
+// The handle's types and the loader helpers are in mimi_model.h, shared with the optional encode side (mimi_encode.hip).
 //
 // One layer program serves both entries.  Every convolution is causal, so a call's convolutions run ONCE over [carried context | new
 // rows]: a stride-1 convolution carries its last (k - 1) dil input rows, a transposed one (k = 2 stride) its last input row, which
@@ -17,95 +18,9 @@
 #include <algorithm>
 #include <cmath>
 
-#include "../../include/mia_mimi.h"
-#include "codec.h"
-#include "mimi.h"
-#include "ops.h"
-#include "tensor_loader.h"
+#include "mimi_model.h"
 
 namespace {
-
-constexpr int MIMI_MAX_RATIOS = 8;
-
-struct MConv { float* w = nullptr; float* b = nullptr; int N = 0, Cin = 0, taps = 0; };                    // causal, stride 1, dilation 1
-struct MConvT { float* w = nullptr; float* b = nullptr; int N = 0, Cin = 0, stride = 0; };                 // causal, kernel 2 * stride, phase weights
-struct MLayer { float *ln1g, *ln1b, *ln2g, *ln2b, *win, *wout, *w1, *w2; };
-struct SLayer { MConvT up; MConv c3, c1; };
-
-}  // namespace
-
-struct mia_mimi {
-  mia_ctx* ctx = nullptr;
-  mia_mimi_config cfg{};
-  std::vector<void*> allocs;
-  int D = 0, H = 0, L = 0, FF = 0, context = 0, us = 0, nq = 0, bins = 0, dq = 0, nr = 0;
-  int64_t spf = 0;                                    // samples per frame
-  float *cb = nullptr, *wfT = nullptr, *wrT = nullptr, *wup = nullptr;
-  double* inv_freq = nullptr;
-  std::vector<MLayer> layers;
-  MConv init, fin;
-  SLayer sl[MIMI_MAX_RATIOS];
-  // a stream's carried convolution rows, one block of floats: offsets of each convolution's rows
-  size_t st_z = 0, st_x = 0, st_up[MIMI_MAX_RATIOS] = {}, st_c3[MIMI_MAX_RATIOS] = {}, st_fin = 0, st_floats = 0;
-  int live_streams = 0;
-};
-
-struct mia_mimi_stream {
-  mia_mimi* m = nullptr;
-  float* conv_state = nullptr;
-  float* hist[2] = {nullptr, nullptr};
-  size_t cap[2] = {0, 0};                             // rows per (layer, k | v) of each buffer
-  int cur = 0;
-  int64_t fill = 0, pos = 0;
-  int n_q = -1;
-  bool broken = false;                                // a launch failed after the state had been touched: reset first
-};
-
-namespace {
-
-struct MLoader : TensorLoader {
-  bool conv(const std::string& p, int Cout, int K, int Cin, MConv& o) {
-    std::vector<float> w, b;
-    if (!f32(p + ".weight", w, {Cout, K, Cin}) || !f32(p + ".bias", b, {Cout})) return false;
-    o.w = up(w); o.b = up(b); o.N = Cout; o.Cin = Cin; o.taps = K;
-    return true;
-  }
-  // effective weight w[co][k][ci], k = 2 s: phase r holds [co][ x[t-1] tap: k = r + s | x[t] tap: k = r ][ci]
-  bool convt(const std::string& p, int Cout, int s, int Cin, MConvT& o) {
-    std::vector<float> w, b;
-    if (!f32(p + ".weight", w, {Cout, 2 * s, Cin}) || !f32(p + ".bias", b, {Cout})) return false;
-    std::vector<float> ph((size_t)s * Cout * 2 * Cin);
-    for (int r = 0; r < s; ++r)
-      for (int co = 0; co < Cout; ++co)
-        for (int ci = 0; ci < Cin; ++ci) {
-          ph[(((size_t)r * Cout + co) * 2 + 0) * Cin + ci] = w[((size_t)co * 2 * s + r + s) * Cin + ci];
-          ph[(((size_t)r * Cout + co) * 2 + 1) * Cin + ci] = w[((size_t)co * 2 * s + r) * Cin + ci];
-        }
-    o.w = up(ph); o.b = up(b); o.N = Cout; o.Cin = Cin; o.stride = s;
-    return true;
-  }
-  // Linear weight [N][K], rows optionally scaled by a LayerScale vector (folded: scale * (W x) == (scale W) x up to one rounding)
-  bool linear(const std::string& p, int N, int K, const std::string& scale, float*& o) {
-    std::vector<float> w, sc;
-    if (!f32(p + ".weight", w, {N, K})) return false;
-    if (!scale.empty()) {
-      if (!f32(scale, sc, {N})) return false;
-      for (int n = 0; n < N; ++n) for (int k = 0; k < K; ++k) w[(size_t)n * K + k] *= sc[n];
-    }
-    o = up(w);
-    return true;
-  }
-  bool vec(const std::string& p, int N, float*& o) { std::vector<float> v; if (!f32(p, v, {N})) return false; o = up(v); return true; }
-  // output_proj [D][1][dq] -> transposed [dq][D]
-  bool projT(const std::string& p, int D, int dq, float*& o) {
-    std::vector<float> w;
-    if (!f32(p, w, {D, 1, dq})) return false;
-    std::vector<float> t((size_t)dq * D);
-    for (int d = 0; d < D; ++d) for (int j = 0; j < dq; ++j) t[(size_t)j * D + d] = w[(size_t)d * dq + j];
-    o = up(t);
-    return true;
-  }
-};
 
 const char* config_error(const mia_mimi_config& g) {
   if (g.d_model <= 0 || g.n_heads <= 0 || g.d_model != g.n_heads * 64) return "head_dim must be 64";
@@ -146,7 +61,7 @@ struct Run {
 };
 
 // the program over n frames; d_codes: device [n_q][n]; d_pcm: device, n * spf samples.  ws: the carved workspace.
-struct Work { float *zp, *xb, *nb, *qkv, *qb, *ob, *ff, *kt, *vt, *sb[3]; };
+struct Work { float *zp, *xb, *sb[3]; MimiTfWork tf; };
 
 size_t seanet_buf_floats(const mia_mimi* m, int64_t P) {
   size_t mx = (size_t)(1 + P) * m->init.N;
@@ -175,39 +90,7 @@ int mimi_run(mia_mimi* m, mia_mimi_stream* st, const int32_t* d_codes, int n_q, 
   if (!r.ctx_out(w.zp, m->st_z, D, (size_t)n * D)) return dev_fail("state copy");
 
   // ---- transformer
-  const int64_t pos0 = st ? st->pos : 0;
-  auto gemm = [&](const float* X, int K, const float* W, int N, float* Y, const float* R, int act) {
-    ConvGemmArgs g;
-    g.X = X; g.ldx = K; g.T_in = (int)P; g.W = W; g.M = (int)P; g.N = N; g.Cin = K; g.taps = 1;
-    g.Y = Y; g.ldy = N; g.T_out = (int)P; g.R = R; g.ldr = N; g.gelu = act;
-    return codec_conv_gemm_run(ctx, g, 1, "mimi");
-  };
-  for (int l = 0; l < m->L; ++l) {
-    const MLayer& ly = m->layers[l];
-    if (mia_norm_launch(x, D, ly.ln1g, ly.ln1b, w.nb, D, (int)P, D, 1e-5f, false, MIA_F32, s)) return dev_fail("norm launch");
-    if (int rc = gemm(w.nb, D, ly.win, 3 * D, w.qkv, nullptr, 0)) return rc;
-    float *kn = w.kt, *vn = w.vt, *Kl = nullptr, *Vl = nullptr;
-    if (st) {
-      const size_t cap = st->cap[st->cur];
-      Kl = st->hist[st->cur] + ((size_t)l * 2 * cap) * D;
-      Vl = Kl + cap * D;
-      kn = Kl + (size_t)st->fill * D;
-      vn = Vl + (size_t)st->fill * D;
-    }
-    if (mimi_qkv_finish_launch(w.qkv, w.qb, kn, vn, P, D, pos0, m->inv_freq, s)) return dev_fail("qkv finish launch");
-    if (st) {
-      if (mimi_window_attn_launch(w.qb, Kl, Vl, w.ob, P, D, m->H, pos0, pos0 - st->fill, m->context, 0.125f, s)) return dev_fail("window attention launch");
-    } else {
-      AttnF32Args a;
-      a.q = w.qb; a.ldq = D; a.k = kn; a.ldk = D; a.v = vn; a.ldv = D; a.out = w.ob; a.ldo = D; a.B = 1; a.T = (int)P; a.H = m->H; a.scale = 0.125f;
-      if (const char* e = mia_attn_f32_check(a)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "mimi: %s", e);
-      if (mia_attn_f32_launch(a, s)) return dev_fail("attention launch");
-    }
-    if (int rc = gemm(w.ob, D, ly.wout, D, x, x, 0)) return rc;
-    if (mia_norm_launch(x, D, ly.ln2g, ly.ln2b, w.nb, D, (int)P, D, 1e-5f, false, MIA_F32, s)) return dev_fail("norm launch");
-    if (int rc = gemm(w.nb, D, ly.w1, m->FF, w.ff, nullptr, 7)) return rc;
-    if (int rc = gemm(w.ff, m->FF, ly.w2, D, x, x, 0)) return rc;
-  }
+  if (int rc = mimi_transformer_run(m, m->layers, st, x, P, w.tf)) return rc;
 
   // ---- SEANet decoder.  Buffers rotate: a = the stage's input, b = the transposed convolution's output (and the residual), c = hidden.
   auto conv = [&](const MConv& c, const float* X, int64_t T, float* Y, const float* R, int elu) {
@@ -303,7 +186,7 @@ int decode_call(mia_mimi* m, mia_mimi_stream* st, const int32_t* codes, int n_q,
   }
   Work w;
   auto f = [&](size_t off) { return (float*)(ws + off); };
-  w.zp = f(o_zp); w.xb = f(o_xb); w.nb = f(o_nb); w.qkv = f(o_qkv); w.qb = f(o_qb); w.ob = f(o_ob); w.ff = f(o_ff); w.kt = f(o_kt); w.vt = f(o_vt);
+  w.zp = f(o_zp); w.xb = f(o_xb); w.tf = MimiTfWork{f(o_nb), f(o_qkv), f(o_qb), f(o_ob), f(o_ff), f(o_kt), f(o_vt)};
   for (int i = 0; i < 3; ++i) w.sb[i] = f(o_sb[i]);
   const int32_t* d_codes = io.table(codes, ws + o_codes, (size_t)n_q * n * 4);       // codes are host arrays whatever `mem` says of pcm
   float* d_pcm = io.out(pcm, ws + o_pcm, (size_t)S * 4);
@@ -318,6 +201,47 @@ int decode_call(mia_mimi* m, mia_mimi_stream* st, const int32_t* codes, int n_q,
 }
 
 }  // namespace
+
+int mimi_transformer_run(mia_mimi* m, const std::vector<MLayer>& layers, mia_mimi_stream* st, float* x, int64_t P, const MimiTfWork& w) {
+  mia_ctx* ctx = m->ctx;
+  hipStream_t s = ctx->stream;
+  const int D = m->D;
+  auto dev_fail = [&](const char* what) { return mia_fail(ctx, MIA_ERR_DEVICE, "mimi: %s failed", what); };
+  const int64_t pos0 = st ? st->pos : 0;
+  auto gemm = [&](const float* X, int K, const float* W, int N, float* Y, const float* R, int act) {
+    ConvGemmArgs g;
+    g.X = X; g.ldx = K; g.T_in = (int)P; g.W = W; g.M = (int)P; g.N = N; g.Cin = K; g.taps = 1;
+    g.Y = Y; g.ldy = N; g.T_out = (int)P; g.R = R; g.ldr = N; g.gelu = act;
+    return codec_conv_gemm_run(ctx, g, 1, "mimi");
+  };
+  for (int l = 0; l < (int)layers.size(); ++l) {
+    const MLayer& ly = layers[l];
+    if (mia_norm_launch(x, D, ly.ln1g, ly.ln1b, w.nb, D, (int)P, D, 1e-5f, false, MIA_F32, s)) return dev_fail("norm launch");
+    if (int rc = gemm(w.nb, D, ly.win, 3 * D, w.qkv, nullptr, 0)) return rc;
+    float *kn = w.kt, *vn = w.vt, *Kl = nullptr, *Vl = nullptr;
+    if (st) {
+      const size_t cap = st->cap[st->cur];
+      Kl = st->hist[st->cur] + ((size_t)l * 2 * cap) * D;
+      Vl = Kl + cap * D;
+      kn = Kl + (size_t)st->fill * D;
+      vn = Vl + (size_t)st->fill * D;
+    }
+    if (mimi_qkv_finish_launch(w.qkv, w.qb, kn, vn, P, D, pos0, m->inv_freq, s)) return dev_fail("qkv finish launch");
+    if (st) {
+      if (mimi_window_attn_launch(w.qb, Kl, Vl, w.ob, P, D, m->H, pos0, pos0 - st->fill, m->context, 0.125f, s)) return dev_fail("window attention launch");
+    } else {
+      AttnF32Args a;
+      a.q = w.qb; a.ldq = D; a.k = kn; a.ldk = D; a.v = vn; a.ldv = D; a.out = w.ob; a.ldo = D; a.B = 1; a.T = (int)P; a.H = m->H; a.scale = 0.125f;
+      if (const char* e = mia_attn_f32_check(a)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "mimi: %s", e);
+      if (mia_attn_f32_launch(a, s)) return dev_fail("attention launch");
+    }
+    if (int rc = gemm(w.ob, D, ly.wout, D, x, x, 0)) return rc;
+    if (mia_norm_launch(x, D, ly.ln2g, ly.ln2b, w.nb, D, (int)P, D, 1e-5f, false, MIA_F32, s)) return dev_fail("norm launch");
+    if (int rc = gemm(w.nb, D, ly.w1, m->FF, w.ff, nullptr, 7)) return rc;
+    if (int rc = gemm(w.ff, m->FF, ly.w2, D, x, x, 0)) return rc;
+  }
+  return MIA_OK;
+}
 
 extern "C" {
 
@@ -355,16 +279,7 @@ mia_mimi* mia_mimi_load(mia_ctx* ctx, const mia_mimi_config* cfg, const mia_tens
     for (int i = 0; i < 32; ++i) fr[i] = g.rope ? std::pow((double)g.max_period, -(double)(2 * i) / 64.0) : 0.0;
     m->inv_freq = (double*)L.put(fr.data(), fr.size() * 8);
   }
-  m->layers.resize(m->L);
-  for (int l = 0; l < m->L && ok; ++l) {
-    const std::string p = "decoder_transformer.transformer.layers." + std::to_string(l) + ".";
-    MLayer& y = m->layers[l];
-    ok = L.vec(p + "norm1.weight", D, y.ln1g) && L.vec(p + "norm1.bias", D, y.ln1b) && L.vec(p + "norm2.weight", D, y.ln2g) && L.vec(p + "norm2.bias", D, y.ln2b) &&
-         L.linear(p + "self_attn.in_proj", 3 * D, D, "", y.win) &&
-         L.linear(p + "self_attn.out_proj", D, D, g.layer_scale ? p + "layer_scale_1.scale" : "", y.wout) &&
-         L.linear(p + "gating.linear1", m->FF, D, "", y.w1) &&
-         L.linear(p + "gating.linear2", D, m->FF, g.layer_scale ? p + "layer_scale_2.scale" : "", y.w2);
-  }
+  ok = ok && L.transformer("decoder_transformer", g, m->layers);
   // SEANet decoder (Seanet.swift:334-387)
   int C = g.seanet_nfilters << m->nr;
   size_t off = 0;
@@ -389,6 +304,7 @@ mia_mimi* mia_mimi_load(mia_ctx* ctx, const mia_mimi_config* cfg, const mia_tens
   }
   m->st_fin = off; off += (size_t)(g.seanet_last_ksize - 1) * C;
   m->st_floats = off;
+  ok = ok && mimi_encoder_load(m, L);
   if (!ok || !L.err.empty()) {
     mia_fail(ctx, L.err.empty() ? MIA_ERR_INVALID_ARGUMENT : L.code, "mimi_load: %s", L.err.empty() ? "failed" : L.err.c_str());
     mia_mimi_free(m);

@@ -1,8 +1,9 @@
 """Host-side mirror of the reference's Marvis TTS interface (TTS/Marvis/Models/MarvisModel.swift, TTS/Marvis/MarvisTTS.swift), backed by
 the gfx950 HIP layer: MarvisModel.generateFrame and the decodePrompt loop run on the device (csrc/marvis.hip); the codes go to the Mimi
-decoder of mimi.py.  Python builds rows and calls; no arithmetic of the model happens here.
+decoder of mimi.py, and a voice prompt's codes come from its encoder (tokenize_audio, MarvisTTS.reference_prompt).  Python builds rows
+and calls; no arithmetic of the model happens here.
 
-Out of scope: Mimi encode (the voice prompt's codes come from the caller), the text tokenizer and the sentence splitter."""
+Out of scope: the text tokenizer and the sentence splitter."""
 from __future__ import annotations
 
 import ctypes as C
@@ -117,8 +118,25 @@ def tokenize_audio_rows(codes, add_eos: bool = True):
     return rows, mask
 
 
-def tokenize_start(text_ids, codes):
-    """tokenizeStart: the text rows, then the voice prompt's audio rows without EOS."""
+def tokenize_audio(codec, pcm, n_codebooks: int, add_eos: bool = True):
+    """tokenizeAudio (MarvisTTS.swift:318-348) including the codec call: pcm float32 at the codec's rate -> (rows, mask) of the first
+    n_codebooks rows of MimiCodec.encode (they do not depend on the later stages, so only they are computed)."""
+    return tokenize_audio_rows(codec.encode(pcm, n_q=n_codebooks), add_eos=add_eos)
+
+
+def tokenize_segment(text_ids, codec, pcm, n_codebooks: int, add_eos: bool = True):
+    """tokenizeSegment (MarvisTTS.swift:350-354): the text rows, then the audio rows of the clip."""
+    tr, tm = tokenize_text_rows(text_ids, n_codebooks)
+    ar, am = tokenize_audio(codec, pcm, n_codebooks, add_eos=add_eos)
+    return np.concatenate([tr, ar], 0), np.concatenate([tm, am], 0)
+
+
+def tokenize_start(text_ids, codes, pcm=None, n_codebooks: int | None = None):
+    """tokenizeStart: the text rows, then the voice prompt's audio rows without EOS.  The prompt is either its codes [K, T], or a
+    MimiCodec with an encoder and the clip: tokenize_start(text_ids, codec, pcm, n_codebooks)."""
+    if pcm is not None:
+        codec = codes
+        return tokenize_segment(text_ids, codec, pcm, codec.cfg.quantizer_nq if n_codebooks is None else n_codebooks, add_eos=False)
     codes = np.asarray(codes, np.int32)
     tr, tm = tokenize_text_rows(text_ids, codes.shape[0])
     ar, am = tokenize_audio_rows(codes, add_eos=False)
@@ -247,6 +265,14 @@ class MarvisTTS:
     def _uniforms(self, uniforms, cb):
         return np.ascontiguousarray(uniforms, np.float32).reshape(-1, cb)
 
+    def reference_prompt(self, text_ids, samples, rate: int):
+        """makeContext + tokenizeStart (MarvisTTS.swift:356-398) for a caller's reference clip: resample to the codec's rate
+        (AudioResampler, on the device), encode, and build the prompt -> (rows, mask) for generate / generate_streaming.
+        text_ids = the caller's tokenizer output for "[0]" + the clip's transcript."""
+        from . import audio_io
+        wav = audio_io.resample(self.model.ctx, np.ascontiguousarray(samples, np.float32).reshape(-1), int(rate), int(self.mimi.cfg.sample_rate))
+        return tokenize_start(text_ids, self.mimi, wav, self.model.cfg.n_codebooks)
+
     def generate(self, prompt_rows, mask, quality: str, uniforms, temperature: float = 0.9, top_p: float = 0.8) -> np.ndarray:
         """Whole sentence -> float32 PCM through MimiCodec.decode ([codebooks][n] codes)."""
         cb = self.model.codebooks(QUALITY_CODEBOOKS[quality])
@@ -279,4 +305,4 @@ class MarvisTTS:
 
 
 __all__ = ["MarvisConfig", "MarvisStackConfig", "MarvisModel", "MarvisTTS", "FLAVORS", "QUALITY_CODEBOOKS", "tokenize_text_rows", "tokenize_audio_rows",
-           "tokenize_start", "sample_top_p_ascending"]
+           "tokenize_audio", "tokenize_segment", "tokenize_start", "sample_top_p_ascending"]

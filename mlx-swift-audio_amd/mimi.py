@@ -1,6 +1,7 @@
-"""Host-side mirror of the reference's Mimi decoder interface (TTS/Marvis/Mimi/Mimi.swift), backed by the gfx950 HIP layer:
-Mimi.decode (:184-192) and MimiStreamingDecoder (:213-239), the two calls of MarvisTTS.swift:534-536.  No arithmetic happens in
-Python.  Whole-clip and streamed decodes are different functions of the same codes, as in the reference ("Mimi")."""
+"""Host-side mirror of the reference's Mimi interface (TTS/Marvis/Mimi/Mimi.swift), backed by the gfx950 HIP layer:
+Mimi.decode (:184-192) and MimiStreamingDecoder (:213-239), the two calls of MarvisTTS.swift:534-536, and Mimi.encode (:174-182), the
+codec call of tokenizeAudio (MarvisTTS.swift:323).  No arithmetic happens in Python.  Whole-clip and streamed decodes are different
+functions of the same codes, as in the reference ("Mimi").  The encode side is there when the weights carry it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -112,6 +113,47 @@ class MimiCodec:
 
     def output_len(self, n_frames: int) -> int:
         return int(self.ctx.lib.mia_mimi_output_len(self.h, n_frames))
+
+    # ---- encode side (present when the weights carried the encoder tensors)
+    @property
+    def has_encoder(self) -> bool:
+        return self.encode_frames(1) > 0
+
+    def encode_frames(self, n_samples: int) -> int:
+        """Code frames of n_samples samples: every strided stage rounds up (0 without an encoder or for n_samples < 1)."""
+        return int(self.ctx.lib.mia_mimi_encode_frames(self.h, int(n_samples)))
+
+    def _n_q(self, n_q) -> int:
+        return self.cfg.quantizer_nq if n_q is None else int(n_q)
+
+    def encode(self, pcm, n_q: int | None = None) -> np.ndarray:
+        """Mimi.encode: float32 [n_samples] at the codec's rate -> int32 [n_q, T], the first n_q stages of the split quantiser."""
+        x = np.ascontiguousarray(pcm, np.float32).reshape(-1)
+        k = self._n_q(n_q)
+        T = self.encode_frames(x.size)
+        codes = np.zeros((max(k, 1), max(T, 1)), np.int32)
+        nf = C.c_int64(0)
+        self.ctx.check(self.ctx.lib.mia_mimi_encode(self.h, x.ctypes.data if x.size else None, x.size, k, codes.ctypes.data, max(T, 1), C.byref(nf), _lib.MEM_HOST))
+        return np.ascontiguousarray(codes.reshape(-1)[:k * nf.value].reshape(k, nf.value))
+
+    def encode_latent(self, pcm) -> np.ndarray:
+        """The rows the quantiser sees: float32 [T, d_model] (SEANet encoder, encoder transformer, edge-padded downsample)."""
+        x = np.ascontiguousarray(pcm, np.float32).reshape(-1)
+        T = max(self.encode_frames(x.size), 1)
+        lat = np.empty((T, self.cfg.transformer.d_model), np.float32)
+        nf = C.c_int64(0)
+        self.ctx.check(self.ctx.lib.mia_mimi_encode_latent(self.h, x.ctypes.data if x.size else None, x.size, lat.ctypes.data, T, C.byref(nf), _lib.MEM_HOST))
+        return lat[:nf.value]
+
+    def quantize(self, latent, n_q: int | None = None) -> np.ndarray:
+        """SplitResidualVectorQuantizer.encode alone: float32 [T, d_model] -> int32 [n_q, T]."""
+        z = np.ascontiguousarray(latent, np.float32)
+        if z.ndim != 2 or z.shape[1] != self.cfg.transformer.d_model:
+            raise ValueError(f"latent must be [T, {self.cfg.transformer.d_model}]")
+        k = self._n_q(n_q)
+        codes = np.zeros((max(k, 1), max(z.shape[0], 1)), np.int32)
+        self.ctx.check(self.ctx.lib.mia_mimi_quantize(self.h, z.ctypes.data if z.size else None, z.shape[0], k, codes.ctypes.data, _lib.MEM_HOST))
+        return codes[:k, :z.shape[0]]
 
     def decode(self, codes) -> np.ndarray:
         """Mimi.decode: codes int [n_q, T] -> float32 [T * samples_per_frame] (full bidirectional attention over the clip)."""

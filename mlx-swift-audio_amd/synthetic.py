@@ -749,13 +749,18 @@ def _mimi_202407():
     return mimi_202407(32)
 
 
+MIMI_INPUT_PROJ_GAIN = 1.0          # latent rows of unit scale project to unit components, the scale of the first codebooks
+
+
 MIMI_CONFIGS = {"mimi_micro": _mimi_micro(6), "mimi_micro_ctx250": _mimi_micro(250), "mimi_202407": _mimi_202407()}
 
 
-def mimi_weights(cfg, seed: int = 0) -> dict[str, np.ndarray]:
+def mimi_weights(cfg, seed: int = 0, encoder: bool = False) -> dict[str, np.ndarray]:
     """Random-init Mimi decoder-side tensors under the names Mimi.sanitize produces (Mimi.swift:305-377), float32.  LayerScale is not
     the identity, LayerNorm weight / bias are not 1 / 0, cluster_usage has entries below the 1e-5 floor, and the convolution gains
-    (LeCun x sqrt(2) after each ELU, so the activations neither die nor blow up through the stages) leave the waveform's peak at O(0.1 - 1)."""
+    (LeCun x sqrt(2) after each ELU, so the activations neither die nor blow up through the stages) leave the waveform's peak at O(0.1 - 1).
+    encoder=True adds the encoder-side tensors (_mimi_encoder_weights) from a second generator: the decoder-side ones are the same bits
+    either way."""
     w: dict[str, np.ndarray] = {}
     rng = np.random.Generator(np.random.PCG64(seed + 4242))
     s, t = cfg.seanet, cfg.transformer
@@ -801,6 +806,52 @@ def mimi_weights(cfg, seed: int = 0) -> dict[str, np.ndarray]:
         conv(p + "residuals.0.block.0.conv.conv", c // s.compress, s.residual_ksize, c, 1.4)
         conv(p + "residuals.0.block.1.conv.conv", c, 1, c // s.compress, 1.4)
     conv("decoder.final_conv1d.conv.conv", 1, s.last_ksize, c, 0.15)
+    if encoder:
+        w.update(_mimi_encoder_weights(cfg, seed))
+    return w
+
+
+def _mimi_encoder_weights(cfg, seed: int) -> dict[str, np.ndarray]:
+    """The encoder side of mimi_weights: SEANet encoder, encoder transformer, latent downsample and the quantiser's two input
+    projections.  LeCun x sqrt(2) gains behind each ELU keep the activations O(1) for a clip of O(0.3) samples; the input projections
+    are scaled so that the projected vector has the codebooks' own scale (unit components: the first stages then spread over many
+    entries instead of all falling on the few shortest ones)."""
+    w: dict[str, np.ndarray] = {}
+    rng = np.random.Generator(np.random.PCG64(seed + 4242 + 1000003))
+    s, t = cfg.seanet, cfg.transformer
+    D, dq = t.d_model, cfg.quantizer_dim
+
+    def normal(shape, scale):
+        return (scale * rng.standard_normal(shape)).astype(np.float32)
+
+    def conv(p, cout, k, cin, gain):
+        w[p + ".weight"] = normal((cout, k, cin), gain / math.sqrt(k * cin))
+        w[p + ".bias"] = normal(cout, 0.02)
+
+    conv("encoder.init_conv1d.conv.conv", s.nfilters, s.ksize, 1, 3.0)            # no ELU in front; samples of O(0.3)
+    c = s.nfilters
+    for i in range(len(s.ratios)):
+        r = s.ratios[len(s.ratios) - 1 - i]
+        p = f"encoder.layers.{i}."
+        conv(p + "residuals.0.block.0.conv.conv", c // s.compress, s.residual_ksize, c, 1.4)
+        conv(p + "residuals.0.block.1.conv.conv", c, 1, c // s.compress, 1.0)
+        conv(p + "downsample.conv.conv", 2 * c, 2 * r, c, 1.0)                  # input = x + block(x): already twice the variance
+        c *= 2
+    conv("encoder.final_conv1d.conv.conv", s.dimension, s.last_ksize, c, 1.4)
+    for l in range(t.num_layers):
+        p = f"encoder_transformer.transformer.layers.{l}."
+        for nm in ("norm1", "norm2"):
+            w[p + nm + ".weight"] = (1.0 + 0.2 * rng.standard_normal(D)).astype(np.float32)
+            w[p + nm + ".bias"] = normal(D, 0.1)
+        w[p + "self_attn.in_proj.weight"] = normal((3 * D, D), 1.5 / math.sqrt(D))
+        w[p + "self_attn.out_proj.weight"] = normal((D, D), 1.0 / math.sqrt(D))
+        w[p + "gating.linear1.weight"] = normal((t.dim_feedforward, D), 1.0 / math.sqrt(D))
+        w[p + "gating.linear2.weight"] = normal((D, t.dim_feedforward), 1.0 / math.sqrt(t.dim_feedforward))
+        w[p + "layer_scale_1.scale"] = rng.uniform(0.2, 0.8, D).astype(np.float32)
+        w[p + "layer_scale_2.scale"] = rng.uniform(0.2, 0.8, D).astype(np.float32)
+    w["downsample.conv.conv.weight"] = normal((D, 2 * cfg.upsample_stride, D), 1.0 / math.sqrt(2 * cfg.upsample_stride * D))
+    w["quantizer.rvq_first.input_proj.weight"] = normal((dq, 1, D), MIMI_INPUT_PROJ_GAIN / math.sqrt(D))
+    w["quantizer.rvq_rest.input_proj.weight"] = normal((dq, 1, D), MIMI_INPUT_PROJ_GAIN / math.sqrt(D))
     return w
 
 
