@@ -20,14 +20,6 @@
 // ------------------------------------------------------------------------------------------------
 constexpr int ROW_NV = 2;   // float4 per thread: D <= 256 * 4 * ROW_NV
 
-__device__ __forceinline__ float block256_sum(float v, float* sh) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
 // h is written in activation FRAGMENT order (skinny.h): the row is the A operand of the step's next skinny GEMM
 template <typename T>
 __device__ __forceinline__ void row_layernorm_store(const f32x4 (&v)[ROW_NV], int nv, int D, const float* __restrict__ gamma,

@@ -1,5 +1,6 @@
 // lm.h -- host-side interface between the LM decode sources: lm.hip (step kernels, prompt pass, step graph, entry points),
-// lm_sample.hip (the top-p, RAS and greedy samplers), lm_load.hip (checkpoint loader, state buffers, packed-weight attach) and lm_kvq.hip
+// the samplers (lm_sample_top_p.hip: Orpheus top-p; lm_sample_ras.hip: CosyVoice2 RAS; lm_sample_topk.hip: Fun-ASR greedy and top-k / top-p;
+// their shared device code is lm_sample_device.h), lm_load.hip (checkpoint loader, state buffers, packed-weight attach) and lm_kvq.hip
 // (the quantised KV cache: its prompt-pass quantiser and its attention); lm_prefill_attn.hip (the prompt pass's tiled causal attention) reads it too.
 #pragma once
 #include <vector>
@@ -89,7 +90,7 @@ enum { LM_STEP_FORWARD = 0, LM_STEP_TOP_P = 1, LM_STEP_RAS = 2, LM_STEP_GREEDY =
 // launch a kernel template's F16 or BF16 instance; expects `const bool f16` and `hipStream_t s` in scope
 #define LAUNCH_T(kern, grid, block, lds, ...) do { if (f16) hipLaunchKernelGGL((kern<F16>), grid, block, lds, s, __VA_ARGS__); else hipLaunchKernelGGL((kern<BF16>), grid, block, lds, s, __VA_ARGS__); } while (0)
 
-// ---- lm_sample.hip: row b of every array belongs to sequence b (logits [B][V]; tokens / uniforms / out_tokens [B][max_ctx]; hist [B][64]) ----
+// ---- lm_sample_*.hip: row b of every array belongs to sequence b (logits [B][V]; tokens / uniforms / out_tokens [B][max_ctx]; hist [B][64]) ----
 // top-p sampler, six launches.  ws: lm_sample_ws_bytes() per sequence.  n_prompt < 0: every sequence's state holds its own prompt length
 void lm_sample_launch(hipStream_t s, float* logits, int V, int32_t* tokens, int32_t* hist, const float* uniforms, LmState* st, void* ws, const mia_lm_sampler& sp,
                       int n_prompt, int max_ctx, int B);

@@ -3,7 +3,7 @@
 // Replaces, per token, OrpheusModel / OrpheusLMHeadModel (TTS/Orpheus/BuildingBlocks/TransformerBlock.swift:70-105,129-139,
 // 165-180,223-233), Llama3RoPE (TTS/Shared/Llama3RoPE.swift:27-66,104-114), SwiGLUMLP (TTS/Shared/SwiGLUMLP.swift:27-29),
 // Qwen2Attention / Qwen2 blocks (TTS/CosyVoice2/LLM/Qwen2LM.swift:48-151), Qwen3Attention with its per-head q / k RMSNorm
-// (STT/FunASR/Layers/Qwen3Model.swift:72-109); the samplers that end a step are lm_sample.hip.
+// (STT/FunASR/Layers/Qwen3Model.swift:72-109); the samplers that end a step are lm_sample_*.hip.
 //
 // Decode at batch 1 is HBM-bound on the weights (Orpheus-3B: 6.6 GB bf16 per token).  Every projection is the skinny
 // MFMA GEMM of skinny_rowmajor.hip (weights HBM -> VGPR once, split-K partials summed in a fixed order by the consumer
@@ -26,14 +26,6 @@ namespace {
 
 constexpr int LM_NV = 4;   // float4 per thread of the 256-thread row kernels: hidden <= 4096
 
-__device__ __forceinline__ float blk256_sum(float v, float* sh) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
 template <typename T>
 __device__ __forceinline__ void rms_store(const f32x4 (&v)[LM_NV], int nv, int D, float eps, const float* __restrict__ w, uint16_t* __restrict__ h, float* sh) {
   const int tid = threadIdx.x;
@@ -44,7 +36,7 @@ __device__ __forceinline__ void rms_store(const f32x4 (&v)[LM_NV], int nv, int D
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < LM_NV; ++i) if (tid + 256 * i < nv) q += (v[i][0] * v[i][0] + v[i][1] * v[i][1]) + (v[i][2] * v[i][2] + v[i][3] * v[i][3]);
-  const float rstd = rsqrtf(blk256_sum(q, sh) / (float)D + eps);
+  const float rstd = rsqrtf(block256_sum(q, sh) / (float)D + eps);
 #pragma unroll
   for (int i = 0; i < LM_NV; ++i) {
     const int c = tid + 256 * i;

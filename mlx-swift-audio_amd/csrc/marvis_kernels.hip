@@ -2,8 +2,8 @@
 // (MarvisModel._embedTokens + the mask + sum of generateFrame, MarvisModel.swift:474-476,553-577), the ascending top-p sampler of
 // every head (the rule is stated at mia_sample_top_p_ascending in mia.h) and the frame's bookkeeping (MarvisTTS.decodePrompt,
 // MarvisTTS.swift:483-503).  Workgroup b of the sampler and of the bookkeeping is sequence b.
+#include "lm_sample_device.h"
 #include "marvis.h"
-#include "mia_device.h"
 
 namespace {
 
@@ -38,25 +38,8 @@ __global__ __launch_bounds__(256) void mv_embed_rows(const int32_t* __restrict__
 }
 
 // ---- the sampler ---------------------------------------------------------------------------------------------------------------
+// (the workgroup scan and reductions are lm_sample_device.h's: their order is a function of the thread index alone)
 constexpr int SMP_NT = 1024, SMP_NW = SMP_NT / 64, SMP_NPT = MV_MAX_VOCAB / SMP_NT;
-
-// exclusive prefix of v over the workgroup's threads in thread order, and the total: an up-shuffle scan inside each wave, then the wave
-// totals added serially -- the order is a function of the thread index alone
-__device__ __forceinline__ float blk_scan_excl(float v, float* wred, float* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const float t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-  float exc = __shfl_up(inc, 1, 64);
-  if (lane == 0) exc = 0.f;
-  __syncthreads();                       // wred may still be read from the previous use
-  if (lane == 63) wred[wave] = inc;
-  __syncthreads();
-  float pre = 0.f, tot = 0.f;
-  for (int w = 0; w < SMP_NW; ++w) { if (w == wave) pre = tot; tot += wred[w]; }
-  *total = tot;
-  return pre + exc;
-}
 
 __device__ __forceinline__ float key_p(unsigned long long k) { const uint32_t hi = (uint32_t)(k >> 32); return hi ? __uint_as_float(hi - 1u) : 0.f; }
 
@@ -71,7 +54,7 @@ __global__ __launch_bounds__(SMP_NT) void mv_sample(MvSampleArgs a, int NP) {
   a.logits += b * a.ld_logits; a.uniforms += b * a.ld_uniforms; a.out += (int64_t)b * a.ld_ids;
   if (a.forced) a.forced += (int64_t)b * a.ld_ids;
   if (a.emb_out) a.emb_out += (int64_t)b * a.D;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, V = a.V;
+  const int tid = threadIdx.x, V = a.V;
   int ucur = a.st ? a.st->u_cursor : 0;
   ucur = ucur < 0 ? 0 : (ucur < a.n_uniforms ? ucur : a.n_uniforms - 1);      // never past the buffer
   const float u = a.uniforms[ucur];
@@ -84,11 +67,7 @@ __global__ __launch_bounds__(SMP_NT) void mv_sample(MvSampleArgs a, int NP) {
     z[i] = j < V ? a.logits[j] / a.temperature : NAN;
     m = fmaxf(m, z[i]);                  // fmaxf drops a NaN operand
   }
-  m = wave_max(m);
-  if (lane == 0) wred[wave] = m;
-  __syncthreads();
-  m = wred[0];
-  for (int w = 1; w < SMP_NW; ++w) m = fmaxf(m, wred[w]);
+  m = block_max<SMP_NW>(m, wred);
   float e[SMP_NPT], s = 0.f;
 #pragma unroll
   for (int i = 0; i < SMP_NPT; ++i) {
@@ -96,12 +75,7 @@ __global__ __launch_bounds__(SMP_NT) void mv_sample(MvSampleArgs a, int NP) {
     v = v == v ? v : 0.f;
     e[i] = v; s += v;
   }
-  s = wave_sum(s);
-  __syncthreads();
-  if (lane == 0) wred[wave] = s;
-  __syncthreads();
-  float S = 0.f;
-  for (int w = 0; w < SMP_NW; ++w) S += wred[w];
+  const float S = block_sum<SMP_NW>(s, wred);
   if (tid == 0) { sh_j0 = V - 1; sh_pick = V - 1; sh_id = 0; }
   int n_kept = 0;
   if (S > 0.f && S < INFINITY) {
@@ -134,7 +108,7 @@ __global__ __launch_bounds__(SMP_NT) void mv_sample(MvSampleArgs a, int NP) {
     float run = 0.f;
     for (int pos = base; pos < end; ++pos) run += key_p(keys[pos]);
     float total;
-    float pre = blk_scan_excl(run, wred, &total);
+    float pre = block_excl_scan<float, SMP_NW>(run, wred, &total);
     // 4. kept: from the first entry whose cumulative sum exceeds 1 - top_p (none: the largest alone)
     const float thr = 1.0f - a.top_p;
     {
@@ -149,7 +123,7 @@ __global__ __launch_bounds__(SMP_NT) void mv_sample(MvSampleArgs a, int NP) {
     const int kbeg = base > j0 ? base : j0;
     run = 0.f;
     for (int pos = kbeg; pos < end; ++pos) run += key_p(keys[pos]);
-    pre = blk_scan_excl(run, wred, &total);
+    pre = block_excl_scan<float, SMP_NW>(run, wred, &total);
     const float target = u * total;
     {
       float c = pre; int first = V;

@@ -104,6 +104,16 @@ __device__ __forceinline__ float wave_max(float v) {
   return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
 }
 
+// all-reduce over a 256-thread workgroup (the row kernels of the decode steps); sh: 4 words of LDS.  The four wave sums are added
+// pairwise, (0 + 1) + (2 + 3) -- not the serial order of the samplers' block_sum<4> (lm_sample_device.h), and not to become it
+__device__ __forceinline__ float block256_sum(float v, float* sh) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
 // exact (erf) GELU, MLXNN GELU() default.  erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, far
 // below the 16-bit rounding of every consumer): one v_exp, one v_rcp and a 5-term Horner chain instead of libm's branchy
 // erff, which cost ~45 % of the MLP1 GEMM when run 245 M times per layer in its epilogue.

@@ -239,7 +239,7 @@ class OuteTTSPromptProcessor:
 
 class OuteTTS:
     """generateChunk (OuteTTS.swift:380-511): prompt ids -> sampled ids -> (c1, c2) codes -> DAC waveform.  The sampler is the top-p kernel
-    of lm_sample.hip with OuteTTS's parameters (penalty 1.1 over the last 64 generated ids, top-p keeping the first token that crosses p).
+    of lm_sample_top_p.hip with OuteTTS's parameters (penalty 1.1 over the last 64 generated ids, top-p keeping the first token that crosses p).
     The reference divides by the temperature before the penalty, the kernel after: the same function in real arithmetic, one fp32 rounding
     apart.  The prompt repeats the whole speaker profile for every sentence (:327-340, about 1 900 ids for the bundled profile), so the
     constructor puts the handle's prompt pass on the tiled attention kernel; prompt_attention=None leaves the handle's mode alone."""

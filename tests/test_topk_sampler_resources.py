@@ -1,4 +1,4 @@
-"""Resource guards of the top-k / top-p sampler kernels of lm_sample.hip (no GPU needed: hipcc cross-compiles gfx950): no kernel spills
+"""Resource guards of the top-k / top-p sampler kernels of lm_sample_topk.hip (no GPU needed: hipcc cross-compiles gfx950): no kernel spills
 registers or uses private memory, and the finishing kernel's static LDS is within what its comment states (16.2 KB)."""
 import os
 import re
@@ -19,7 +19,7 @@ def _resources():
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "k.s")
         subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only",
-                        "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "mlx-swift-audio_amd", "csrc", "lm_sample.hip"), "-o", out],
+                        "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "mlx-swift-audio_amd", "csrc", "lm_sample_topk.hip"), "-o", out],
                        check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
         text = open(out).read()
     res = {}
