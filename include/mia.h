@@ -192,7 +192,8 @@ int mia_op_conv1d_f32(mia_ctx* ctx, const float* x, int64_t ldx, int T_in, const
 /* MLX affine de-quantisation of a checkpoint tensor at load time (the reference's default checkpoints are 4-bit, group 64:
  * STT/Whisper/WhisperModel.swift:189-196, TTS/Orpheus/TTSEngine/OrpheusWeightLoader.swift:28-60):
  *   out[r][c] = scales[r][c / group] * code[r][c] + biases[r][c / group],  code c of row r = bits [(c % (32/bits)) * bits, ...) of
- *   wq[r][c / (32/bits)] (uint32, little end first).  bits 4 | 8; scales / biases in scale_dtype; out in out_dtype (MIA_F32 | F16 | BF16). */
+ *   wq[r][c / (32/bits)] (uint32, little end first); at 6 bits a row is one little-endian bit stream, code c in bits [6 c, 6 c + 6) of
+ *   the row's bytes (4 codes in 3 bytes, cols % 64 == 0).  bits 4 | 6 | 8; scales / biases in scale_dtype; out in out_dtype (MIA_F32 | F16 | BF16). */
 int mia_dequant_affine(mia_ctx* ctx, const uint32_t* wq, const void* scales, const void* biases, int64_t rows, int64_t cols,
                        int group_size, int bits, int scale_dtype, void* out, int out_dtype, int mem);
 
@@ -282,7 +283,7 @@ int mia_op_lm_prompt_attention(mia_ctx* ctx, const void* q, const void* k, const
                                int dtype);
 
 /* Test hook: the LM decode step's skinny GEMMs (csrc/skinny.h: skinny_gemm_launch on 16-bit weights, skinny_gemm_q_launch on packed 4- /
- * 8-bit weights) with every launch argument exposed, so each kernel form the two launchers choose from the shape can be compared with a
+ * 6- / 8-bit weights) with every launch argument exposed, so each kernel form the two launchers choose from the shape can be compared with a
  * reference on its own.  DEVICE pointers, enqueued on the context's stream.  A [M][lda] and the 16-bit outputs are in `dtype`
  * (MIA_BF16 | MIA_F16); acc[m][n] = sum_k A[m][k] W[n][k] in fp32, summed in a fixed order that depends on the shape only.
  *   mode 1 (OUTF32):  out fp32 [M][ldo] = acc (* rstd[m]) + bias[n]
@@ -293,7 +294,7 @@ int mia_op_lm_prompt_attention(mia_ctx* ctx, const void* q, const void* k, const
  *   ss_in != NULL (fp32 [ss_tiles][M], 1 <= ss_tiles <= 512): rstd[m] = rsqrt(sum_t ss_in[t][m] / ss_dim + eps) * rs_scale; else rstd = 1.
  * Weights: wfrag == NULL: W [N][K] row-major in `dtype`, K % (32 S) == 0; w_frag != 0 makes the op repack W into weight fragment order
  *   (dec_launch_repack_wfrag, into the context workspace) and run the fragment-order loads -- results are identical.  wfrag != NULL:
- *   the packed form, wfrag / stfrag as mia_quant_repack builds them for `bits` (4 | 8) and compute type `dtype`, K % (128 S) == 0.
+ *   the packed form, wfrag / stfrag as mia_quant_repack builds them for `bits` (4 | 6 | 8) and compute type `dtype`, K % (128 S) == 0.
  * M_cap (0 = M): the rows the caller's buffers are sized for.  The packed launcher picks its kernel form from max(M, M_cap), so that a
  *   row's result does not depend on how many rows the call carries (the LM step passes the handle's batch capacity).
  * lda % 8 == 0, lda >= K, ldo >= N (N / 2 for mode 4); S > 1 only in mode 2; A, W, wfrag, stfrag, out, xres and nw 16-byte aligned, bias
@@ -389,7 +390,8 @@ int mia_whisper_attach_quantized(mia_whisper* w, const mia_tensor_view* tensors,
 int mia_whisper_use_packed(mia_whisper* w, int on);
 /* Test hook: the host repack of one packed Linear [N][K] (K % 128 == 0) into the fragment-ordered arrays the packed step kernels read:
  * wfrag [ceil(N/16)][K/128][bits/4][64][4] uint32, stfrag [ceil(N/16)][K/128][16][4] float = (scale, bias - MAG * scale) per group, MAG =
- * 1024 (MIA_F16 compute) or 128 (MIA_BF16), x 17 for 8 bit.  Host memory in and out; needs no device. */
+ * 1024 (MIA_F16 compute) or 128 (MIA_BF16), x 17 for 6 and 8 bit.  bits 6: wfrag [ceil(N/16)][K/128][384], the low-nibble plane [64][4]
+ * followed by the plane of 2-bit high parts [64][2] (csrc/skinny_quant.hip).  bits 4 | 6 | 8.  Host memory in and out; needs no device. */
 int mia_quant_repack(const uint32_t* codes, const void* scales, const void* biases, int N, int K, int bits, int scale_dtype,
                      int compute_dtype, uint32_t* wfrag, float* stfrag);
 /* Test hook: force the encoder GEMM tile variant (0 / 1: 128^2 register / LDS-DMA staged, 2: 256^2 two-buffer, 3: automatic
@@ -736,10 +738,10 @@ typedef struct {
 } mia_lm_sampler;
 
 mia_lm* mia_lm_load(mia_ctx* ctx, const mia_lm_config* cfg, const mia_tensor_view* tensors, int n_tensors, int dtype);
-/* MLX-affine quantised (group 64; 4- or 8-bit codes) weights for the decode step: the reference's default Orpheus / CosyVoice2
+/* MLX-affine quantised (group 64; 4-, 6- or 8-bit codes) weights for the decode step: the reference's default Orpheus / CosyVoice2
  * checkpoints are quantised (TTS/Orpheus/TTSEngine/OrpheusWeightLoader.swift:28-60; the bit width is a loader option,
  * Models/TranscriptionResult.swift:162-198) and MLX multiplies them packed (quantizedMatmul).  mia_lm_attach_quantized takes every step
- * Linear as stored -- `<name>.weight` (MIA_U32 codes [N][K * bits / 32], little end first), `<name>.scales`, `<name>.biases` ([N][K/64],
+ * Linear as stored -- `<name>.weight` (MIA_U32 codes [N][K * bits / 32], one little-endian bit stream per row), `<name>.scales`, `<name>.biases` ([N][K/64],
  * both f16 or both bf16) -- onto a handle loaded from the de-quantised checkpoint; the per-token step then streams the packed codes and
  * multiplies them as MLX's own kernels do (per group: scale * sum(code * x) + bias * sum(x), the codes exact in the MFMA's 16-bit
  * operands, fp32 group sums), the batched prompt pass keeps the 16-bit copy.  One attach per handle.  mia_lm_attach_q4 = bits 4.
@@ -923,7 +925,18 @@ int mia_sample_top_p(mia_ctx* ctx, const float* logits, int V, const int32_t* hi
  * since its reset.  A MIA_ERR_DEVICE after the first launch of a call (a failed launch or copy) resets the handle: its message says so.
  * Host pointers.
  * mia_marvis_set_debug: bit 0 launches every frame's kernels directly (no hipGraph), bit 1 walks prompts row by row through the step (no
- * batched prompt pass).  Ids are the same with bit 0; with bit 1 the logits agree up to fp32 summation order. */
+ * batched prompt pass).  Ids are the same with bit 0; with bit 1 the logits agree up to fp32 summation order.
+ * Packed weights (the published checkpoints are MLX-affine 6-bit, group 64, and the reference keeps every module that has a `.scales`
+ * packed: MarvisTTS.installWeights, MarvisTTS.swift:220-226): mia_marvis_attach_quantized takes, onto a handle loaded from the
+ * de-quantised checkpoint, `<p>.weight` (MIA_U32 codes [N][K * bits / 32]), `<p>.scales`, `<p>.biases` ([N][K/64], both f16 or both bf16)
+ * for p = {backbone,decoder}.layers.L.self_attn.{q,k,v,o}_proj, .mlp.{gate,up,down}_proj and projection, and codebook0_head when the
+ * checkpoint stores its `.scales`; bits 4 | 6 | 8, group_size 64.  q_proj / k_proj get the loader's row permutation on all three tensors
+ * (packing runs along the input axis, so permuting rows is exact).  audio_head is never quantised and the embedding tables stay 16-bit
+ * tables.  Hidden sizes, heads * head_dim and intermediate sizes of both stacks must be multiples of 128.  The frame's single-row steps
+ * then stream the packed codes through the LM step's packed GEMMs (mia_lm_attach_quantized); prompts keep the 16-bit prompt pass.  One
+ * attach per handle; the frame graph is dropped.  Errors as mia_lm_attach_quantized; after any of them the handle is exactly as before --
+ * neither stack is packed unless both and the projection are.  mia_marvis_use_packed(m, 0 | 1) switches the frame between the 16-bit and
+ * the packed weights (1 after a successful attach; 1 without an attach is MIA_ERR_INVALID_ARGUMENT) and drops the frame graph. */
 typedef struct mia_marvis_config mia_marvis_config;    /* defined in include/mia_marvis.h */
 typedef struct mia_marvis mia_marvis;
 mia_marvis* mia_marvis_load(mia_ctx* ctx, const mia_marvis_config* cfg, const mia_tensor_view* tensors, int n_tensors, int dtype, int32_t* status);
@@ -931,6 +944,8 @@ void mia_marvis_free(mia_marvis* m);
 int mia_marvis_reset(mia_marvis* m);
 int mia_marvis_set_debug(mia_marvis* m, int flags);
 int mia_marvis_set_batch(mia_marvis* m, int max_batch);
+int mia_marvis_attach_quantized(mia_marvis* m, const mia_tensor_view* tensors, int n_tensors, int group_size, int bits);
+int mia_marvis_use_packed(mia_marvis* m, int on);
 int mia_marvis_frame(mia_marvis* m, const int32_t* tokens, const int32_t* mask, int T, int max_codebooks, float temperature, float top_p,
                      const float* uniforms, const int32_t* forced, int32_t* ids_out, float* logits_out);
 int mia_marvis_generate(mia_marvis* m, const int32_t* tokens, const int32_t* mask, int T, int max_codebooks, float temperature, float top_p,

@@ -355,6 +355,8 @@ PROTOTYPES = {
     "mia_marvis_reset": (i32, [vp]),
     "mia_marvis_set_debug": (i32, [vp, i32]),
     "mia_marvis_set_batch": (i32, [vp, i32]),
+    "mia_marvis_attach_quantized": (i32, [vp, TV, i32, i32, i32]),
+    "mia_marvis_use_packed": (i32, [vp, i32]),
     "mia_marvis_frame": (i32, [vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp]),
     "mia_marvis_generate": (i32, [vp, vp, vp, i32, i32, f32, f32, i32, vp, vp, vp]),
     "mia_marvis_generate_batch": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, i32, vp, vp, vp]),

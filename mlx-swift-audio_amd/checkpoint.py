@@ -79,7 +79,7 @@ def dequantize_affine(ctx: _lib.Context, wq: np.ndarray, scales: np.ndarray, bia
     lib = ctx.lib
     w = np.ascontiguousarray(wq).view(np.uint32) if wq.dtype != np.uint32 else np.ascontiguousarray(wq)
     rows = int(np.prod(w.shape[:-1]))
-    cols = w.shape[-1] * (32 // bits)
+    cols = w.shape[-1] * 32 // bits
     sdt = _mia_dtype(scales)
     s, b = np.ascontiguousarray(scales), np.ascontiguousarray(biases)
     if s.size != rows * (cols // group_size) or b.size != s.size or _mia_dtype(biases) != sdt:
@@ -127,7 +127,7 @@ def quantize_affine(w: np.ndarray, group_size: int = 64, bits: int = 4, scale_dt
     """A SIMPLIFIED min / max affine quantiser in MLX's storage layout -- the direction the reference's loaders take for checkpoints
     that are not already quantised (`quantize(model:) { (64, bits, .affine) }`, STT/Whisper/WhisperModel.swift:189-196): per group of
     `group_size` consecutive inputs, scale = (max - min) / (2^bits - 1), bias = min, code = round((w - bias) / scale); codes packed
-    little end first into uint32 words.  mx.quantize additionally nudges scale / bias (edge and sign handling), which this does not
+    little end first into uint32 words (bits 4, 6 or 8: pack_codes).  mx.quantize additionally nudges scale / bias (edge and sign handling), which this does not
     reproduce: parity of the CODES with mx.quantize is unpinned; the contract of the hot path is de-quantisation (scale * code + bias),
     which is layout-exact.  Returns (codes uint32 [N, K*bits/32], scales, biases [N, K/group_size] in `scale_dtype`) -- the three
     tensors a quantised checkpoint stores for the layer (feed them to CausalLM.attach_q4 / expand them with dequantize_affine)."""
@@ -140,12 +140,27 @@ def quantize_affine(w: np.ndarray, group_size: int = 64, bits: int = 4, scale_dt
     bias = lo.astype(scale_dtype)
     s32 = scale.astype(np.float32)[..., None]
     q = np.clip(np.rint((g - bias.astype(np.float32)[..., None]) / s32), 0, top).astype(np.uint32)
+    return pack_codes(q.reshape(n, k), bits), scale, bias
+
+
+def pack_codes(q: np.ndarray, bits: int) -> np.ndarray:
+    """Codes [N, K] -> uint32 [N, K*bits/32] in MLX's storage: a row is one little-endian bit stream, code k in bits [k*bits, (k+1)*bits)
+    (4 and 8 bit: whole codes per word; 6 bit: 4 codes in 3 bytes, codes straddle words)."""
+    q = np.asarray(q, np.uint32)
+    n, k = q.shape
+    if bits not in (4, 6, 8) or (k * bits) % 32:
+        raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, f"pack_codes: {bits}-bit rows of {k} codes do not fill whole words")
+    if bits == 6:
+        q4 = q.reshape(n, k // 4, 4)
+        v = q4[:, :, 0] | (q4[:, :, 1] << np.uint32(6)) | (q4[:, :, 2] << np.uint32(12)) | (q4[:, :, 3] << np.uint32(18))
+        b = np.stack([v & 255, (v >> np.uint32(8)) & 255, v >> np.uint32(16)], -1).astype(np.uint8)
+        return np.ascontiguousarray(b.reshape(n, -1)).view("<u4")
     per = 32 // bits
     q = q.reshape(n, k // per, per)
     packed = np.zeros(q.shape[:2], np.uint32)
     for j in range(per):
         packed |= q[:, :, j] << np.uint32(j * bits)
-    return packed, scale, bias
+    return packed
 
 
 def sanitize_mimi_name(raw: str) -> str:

@@ -13,7 +13,7 @@ struct LmState { int pos; int n_hist; int finished; int n_gen; int n_embeds; int
 
 struct RasParams { float top_p; int top_k; int win; float tau; int eos; int min_len; int max_len; int n_uniforms; };
 
-// MLX-affine 4- / 8-bit copy of one fused matrix in MFMA fragment order (skinny_quant.hip: skinny_gemm_qi); null = use the 16-bit weights
+// MLX-affine 4- / 6- / 8-bit copy of one fused matrix in MFMA fragment order (skinny_quant.hip: skinny_gemm_qi); null = use the 16-bit weights
 struct Q4W { uint32_t* wfrag = nullptr; float* stfrag = nullptr; };
 
 struct LmLayer {
@@ -40,7 +40,7 @@ struct mia_lm {
   void* lm_head = nullptr;      // 16-bit [V][hidden] (== embed when tied)
   void* lm_head_f = nullptr;    // lm_head in MFMA-fragment order (decode step)
   Q4W q_head;                   // 4-bit copy of lm_head (mia_lm_attach_q4)
-  int q_bits = 0;               // 4 | 8 once packed weights are attached (mia_lm_attach_quantized), 0 = none
+  int q_bits = 0;               // 4 | 6 | 8 once packed weights are attached (mia_lm_attach_quantized), 0 = none
   bool q4 = false;              // the step GEMVs stream the packed weights
   float* head_bias = nullptr;   // optional (CosyVoice2 llm_decoder)
   int head_vocab = 0;           // rows of lm_head (CosyVoice2: speech vocabulary + 3)
@@ -169,5 +169,13 @@ const char* lm_prefill_attn_check(const LmPromptAttn& a);
 int lm_prefill_attn_launch(const LmPromptAttn& a, hipStream_t s);
 
 // ---- lm_load.hip ----
+// The packed-weight attach in two halves, so that a caller with several handles (marvis.hip: two stacks) packs all of them or none.
+// lm_attach_prepare checks the arguments and the tensors, repacks and uploads every step Linear into `out` and changes nothing of the
+// handle; on failure its buffers are freed again, the context holds the message ("<who>: ...") and the MIA_ERR_* code is returned.
+// lm_attach_commit hands the buffers to the handle, re-picks the splits and switches the step to the packed weights (cannot fail).
+struct LmPacked { std::vector<void*> fresh; std::vector<Q4W> layers; Q4W head; int bits = 0; };      // layers: q_qkv, q_o, q_gu, q_down per layer
+int lm_attach_prepare(mia_lm* m, const mia_tensor_view* tensors, int n_tensors, int group_size, int bits, const char* who, LmPacked& out);
+void lm_attach_commit(mia_lm* m, LmPacked& p);
+void lm_attach_discard(LmPacked& p);
 // every per-sequence buffer, for B sequences side by side (rows of the skinny GEMMs; caches [L][B][Hkv][max_ctx][dh]); drops the step graph
 int lm_alloc_state(mia_lm* m, int B);

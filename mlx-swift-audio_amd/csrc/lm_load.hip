@@ -175,23 +175,30 @@ extern "C" mia_lm* mia_lm_load(mia_ctx* ctx, const mia_lm_config* cfg, const mia
   return m;
 }
 
-// ---- MLX-affine 4-bit weights for the decode step (OrpheusWeightLoader.swift:28-60: the reference's default checkpoints are q4, group 64) ----
+// ---- MLX-affine 4- / 6- / 8-bit weights for the decode step (OrpheusWeightLoader.swift:28-60: the reference's default checkpoints are q4, group 64) ----
 // tensors: for every Linear of the step, `<name>.weight` (MIA_U32 packed codes [N][K * bits / 32]), `<name>.scales`, `<name>.biases`
 // ([N][K/64], both MIA_F16 or both MIA_BF16), names as in the checkpoint (model.layers.L.self_attn.{q,k,v,o}_proj, mlp.{gate,up,down}_proj,
 // model.embed_tokens / lm_head).  The handle must already hold the de-quantised 16-bit weights (mia_lm_load on the expanded
 // checkpoint): the batched prompt pass keeps using them, the per-token step switches to the packed form.  Nothing of the handle changes
 // unless every matrix was repacked and uploaded.  A bad argument or tensor list is MIA_ERR_INVALID_ARGUMENT; a refused hipMalloc
 // MIA_ERR_OUT_OF_MEMORY, a failed upload MIA_ERR_DEVICE.
-extern "C" int mia_lm_attach_quantized(mia_lm* m, const mia_tensor_view* tensors, int n_tensors, int group_size, int bits) {
-  if (!m) return MIA_ERR_MODEL_NOT_LOADED;
+// (the two halves are declared in lm.h: marvis.hip packs its two stacks through them)
+void lm_attach_discard(LmPacked& p) {
+  for (void* q : p.fresh) (void)hipFree(q);
+  p = LmPacked{};
+}
+
+int lm_attach_prepare(mia_lm* m, const mia_tensor_view* tensors, int n_tensors, int group_size, int bits, const char* who, LmPacked& out) {
   mia_ctx* ctx = m->ctx;
-  MIA_CHECK_ARG(ctx, tensors && n_tensors > 0 && group_size == 64 && (bits == 4 || bits == 8), "lm_attach_quantized: tensors required, group size 64, 4 or 8 bits");
-  MIA_CHECK_ARG(ctx, m->q_bits == 0, "lm_attach_quantized: packed weights are already attached to this handle (load a fresh handle to replace them)");
+  MIA_CHECK_ARG(ctx, tensors && n_tensors > 0 && group_size == 64 && (bits == 4 || bits == 6 || bits == 8), "%s: tensors required, group size 64, 4, 6 or 8 bits", who);
+  MIA_CHECK_ARG(ctx, m->q_bits == 0, "%s: packed weights are already attached to this handle (load a fresh handle to replace them)", who);
   const mia_lm_config& c = m->cfg;
   const int D = c.hidden, dh = c.head_dim, Nq = c.n_heads * dh, Nk = c.n_kv_heads * dh;
-  MIA_CHECK_ARG(ctx, D % 128 == 0 && Nq % 128 == 0 && c.inter % 128 == 0, "lm_attach_quantized: hidden, n_heads*head_dim and inter must be multiples of 128");
+  MIA_CHECK_ARG(ctx, D % 128 == 0 && Nq % 128 == 0 && c.inter % 128 == 0, "%s: hidden, n_heads*head_dim and inter must be multiples of 128", who);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
-  std::vector<void*> fresh;                      // joins m->allocs only when everything is in place
+  out = LmPacked{};
+  out.layers.assign((size_t)4 * c.n_layers, Q4W{});
+  std::vector<void*>& fresh = out.fresh;         // joins m->allocs only when everything is in place (lm_attach_commit)
   TensorLoader L; L.allocs = &fresh;
   L.index(tensors, n_tensors);
   int sdt = -1;
@@ -212,28 +219,46 @@ extern "C" int mia_lm_attach_quantized(mia_lm* m, const mia_tensor_view* tensors
   bool ok = true;
   for (int l = 0; l < c.n_layers && ok; ++l) {
     const std::string p = "model.layers." + std::to_string(l);
-    LmLayer& ly = m->layers[l];
-    ok = pack(p + ".self_attn.", {{"q_proj", Nq}, {"k_proj", Nk}, {"v_proj", Nk}}, D, false, ly.q_qkv) && pack(p + ".self_attn.", {{"o_proj", D}}, Nq, false, ly.q_o) &&
-         pack(p + ".mlp.", {{"gate_proj", c.inter}, {"up_proj", c.inter}}, D, true, ly.q_gu) && pack(p + ".mlp.", {{"down_proj", D}}, c.inter, false, ly.q_down);
+    Q4W* ly = &out.layers[(size_t)4 * l];
+    ok = pack(p + ".self_attn.", {{"q_proj", Nq}, {"k_proj", Nk}, {"v_proj", Nk}}, D, false, ly[0]) && pack(p + ".self_attn.", {{"o_proj", D}}, Nq, false, ly[1]) &&
+         pack(p + ".mlp.", {{"gate_proj", c.inter}, {"up_proj", c.inter}}, D, true, ly[2]) && pack(p + ".mlp.", {{"down_proj", D}}, c.inter, false, ly[3]);
   }
   // the tied / plain LM head, when the checkpoint packs it (the CosyVoice2 speech head stays 16-bit: it is not quantised there)
   const char* hp = c.tie_embeddings ? "model.embed_tokens" : "lm_head";
-  if (ok && m->head_vocab == 0 && L.has(std::string(hp) + ".scales")) ok = pack("", {{hp, c.vocab}}, D, false, m->q_head);
+  if (ok && m->head_vocab == 0 && L.has(std::string(hp) + ".scales")) ok = pack("", {{hp, c.vocab}}, D, false, out.head);
   if (ok && hipDeviceSynchronize() != hipSuccess) ok = L.fail(MIA_ERR_DEVICE, "device error during upload");
-  if (!ok) {      // a partly packed handle must not run: drop every packed pointer and the attach's buffers; the handle is as before
-    for (LmLayer& ly : m->layers) { ly.q_qkv = Q4W{}; ly.q_o = Q4W{}; ly.q_gu = Q4W{}; ly.q_down = Q4W{}; }
-    m->q_head = Q4W{};
-    for (void* p : fresh) (void)hipFree(p);
-    return mia_fail(ctx, L.code, "lm_attach_quantized: %s", L.err.c_str());
+  if (!ok) {      // nothing of the handle was touched: drop the attach's buffers
+    lm_attach_discard(out);
+    return mia_fail(ctx, L.code, "%s: %s", who, L.err.c_str());
   }
-  m->allocs.insert(m->allocs.end(), fresh.begin(), fresh.end());
+  out.bits = bits;
+  return MIA_OK;
+}
+
+void lm_attach_commit(mia_lm* m, LmPacked& p) {
+  const mia_lm_config& c = m->cfg;
+  const int D = c.hidden, Nq = c.n_heads * c.head_dim;
+  for (int l = 0; l < c.n_layers; ++l) {
+    LmLayer& ly = m->layers[l];
+    ly.q_qkv = p.layers[(size_t)4 * l]; ly.q_o = p.layers[(size_t)4 * l + 1]; ly.q_gu = p.layers[(size_t)4 * l + 2]; ly.q_down = p.layers[(size_t)4 * l + 3];
+  }
+  m->q_head = p.head;
+  m->allocs.insert(m->allocs.end(), p.fresh.begin(), p.fresh.end());
   // the packed kernel splits K in 128-input blocks: re-pick the cross-workgroup splits on that granule (the 16-bit step uses the same
   // splits from here on)
   auto split128 = [](int K, int want) { for (int sp = want; sp > 1; --sp) if (K % (128 * sp) == 0) return sp; return 1; };
   m->S_qkv = split128(D, 4); m->S_o = split128(Nq, 4); m->S_down = split128(c.inter, 8);
-  m->q_bits = bits;
+  m->q_bits = p.bits;
   m->q4 = true;
   m->graph_mode = -1;          // the captured step holds the 16-bit launches: re-capture
+  p = LmPacked{};
+}
+
+extern "C" int mia_lm_attach_quantized(mia_lm* m, const mia_tensor_view* tensors, int n_tensors, int group_size, int bits) {
+  if (!m) return MIA_ERR_MODEL_NOT_LOADED;
+  LmPacked p;
+  if (const int rc = lm_attach_prepare(m, tensors, n_tensors, group_size, bits, "lm_attach_quantized", p)) return rc;
+  lm_attach_commit(m, p);
   return MIA_OK;
 }
 

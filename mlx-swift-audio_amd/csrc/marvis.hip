@@ -8,6 +8,8 @@
 // steps (row 0 contributes only its K/V).  Interleaved RoPE is turned into the step kernels' split-half form by permuting the rows of
 // every q_proj / k_proj head at load ("Marvis").  The kernels the frame adds are marvis_kernels.hip.  Input rows reach the
 // stacks as fp32 embedding rows (mia_lm::embeds), which lm_embed_norm turns into the first layer's normalised activation.
+// mia_marvis_attach_quantized puts the checkpoint's packed Linears (MLX-affine 4 / 6 / 8 bit) beside the 16-bit ones: both stacks through
+// the LM attach (lm.h: lm_attach_prepare / lm_attach_commit), the projection into a Q4W of this handle; the frame's GEMMs then stream them.
 // mia_marvis_set_batch sizes the handle and both stacks for B sentences side by side (row b of every step = sequence b); one graph launch
 // per frame for all of them.
 #include <algorithm>
@@ -19,6 +21,7 @@
 #include "../../include/mia_marvis.h"
 #include "gemm.h"
 #include "marvis.h"
+#include "quant_repack.h"
 #include "skinny.h"
 
 struct mia_marvis {
@@ -30,6 +33,8 @@ struct mia_marvis {
   void* text_emb = nullptr;      // 16-bit [text_vocab][D]
   void* audio_emb = nullptr;     // 16-bit [K * V][D]
   void* proj = nullptr; void* proj_f = nullptr;          // 16-bit [d_dec][D], row-major and in fragment order
+  Q4W q_proj;                    // packed copy of the projection (mia_marvis_attach_quantized); the stacks' own packed copies are in bb / dec
+  int q_bits = 0;                // 4 | 6 | 8 once packed weights are attached; bb->q4 / dec->q4 say whether the frame streams them
   std::vector<void*> head, head_f;                       // K - 1 heads, transposed to [V][d_dec]; the fragment copies pad the rows to 16 with zeros
   // device state, B_cap sequences side by side (mia_marvis_set_batch): row / record b belongs to sequence b
   int B_cap = 1;
@@ -89,8 +94,8 @@ struct StackViews {
     views.push_back(v);
   }
   void permuted(const mia_tensor_view& src, const std::string& name, int heads, int dh) {
-    const size_t es = mia_dtype_size(src.dtype);
-    if (src.ndim != 2 || src.shape[0] != (int64_t)heads * dh || (src.dtype != MIA_F32 && src.dtype != MIA_F16 && src.dtype != MIA_BF16)) { alias(src, name); return; }   // the loader names what is wrong
+    const size_t es = src.dtype == MIA_U32 ? 4 : mia_dtype_size(src.dtype);      // (packed codes: mia_dtype_size knows the float types only)
+    if (src.ndim != 2 || src.shape[0] != (int64_t)heads * dh || (src.dtype != MIA_F32 && src.dtype != MIA_F16 && src.dtype != MIA_BF16 && src.dtype != MIA_U32)) { alias(src, name); return; }   // the loader names what is wrong
     const size_t row = (size_t)src.shape[1] * es;
     bufs.emplace_back((size_t)heads * dh * row);
     char* dst = bufs.back().data();
@@ -181,17 +186,18 @@ int mv_enqueue_frame(mia_marvis* mv, int nb, int cb, float temperature, float to
     mv_launch_sample(s, a, nb);
   };
   if (lm_enqueue_layers(bb, nb)) return -1;
-  if (lm_enqueue_linear_of_last(bb, nb, bb->lm_head, bb->lm_head_f, nullptr, nullptr, mv->logits, ld_lg, V)) return -1;      // codebook0_head(lastH)
+  if (lm_enqueue_linear_of_last(bb, nb, bb->lm_head, bb->lm_head_f, nullptr, &bb->q_head, mv->logits, ld_lg, V)) return -1;      // codebook0_head(lastH)
   sample(0);
   if (cb > 1) {
     // decoder row 0 = projection(lastH), from the backbone's last carried activation exactly as the head reads it
-    if (lm_enqueue_linear_of_last(bb, nb, mv->proj, mv->proj_f, nullptr, nullptr, dec->embeds, ld_de, Dd)) return -1;
+    if (lm_enqueue_linear_of_last(bb, nb, mv->proj, mv->proj_f, nullptr, &mv->q_proj, dec->embeds, ld_de, Dd)) return -1;
     if (lm_enqueue_layers(dec, nb)) return -1;
     lm_enqueue_advance(dec, nb);
     for (int i = 1; i < cb; ++i) {       // row i = projection(audio_emb(i - 1, c_{i-1})) -> audio_head[i - 1] -> c_i
       SkinnyArgs a{mv->a16, D, (const uint16_t*)mv->proj_f, nullptr, dec->embeds + (size_t)i * Dd, ld_de, nullptr, nullptr, nullptr, nb, Dd, D, 1, MIA_ACT_NONE, 0, 0, 0};
       a.w_frag = 1;
-      if (skinny_gemm_launch(a, SK_OUTF32, mv->dtype, s)) return -1;
+      if (bb->q4 && mv->q_proj.wfrag) { if (skinny_gemm_q_launch(a, mv->q_proj.wfrag, mv->q_proj.stfrag, mv->q_bits, SK_OUTF32, mv->dtype, s, mv->B_cap)) return -1; }
+      else if (skinny_gemm_launch(a, SK_OUTF32, mv->dtype, s)) return -1;
       if (lm_enqueue_layers(dec, nb)) return -1;
       if (lm_enqueue_linear_of_last(dec, nb, mv->head[i - 1], mv->head_f[i - 1], nullptr, nullptr, mv->logits + (size_t)i * V, ld_lg, V)) return -1;
       lm_enqueue_advance(dec, nb);
@@ -399,6 +405,97 @@ extern "C" mia_marvis* mia_marvis_load(mia_ctx* ctx, const mia_marvis_config* cf
   if (mv_reset(mv) != MIA_OK || hipDeviceSynchronize() != hipSuccess) return fail(MIA_ERR_DEVICE, "device error during upload");
   if (status) *status = MIA_OK;
   return mv;
+}
+
+namespace {
+
+// one stack's packed tensors under the LM attach's names; q_proj / k_proj: the loader's row permutation on codes, scales and biases alike
+void mv_packed_views(const Stack& sk, const TensorLoader& L, StackViews& sv) {
+  const std::string p = sk.prefix;
+  const char* lin[] = {".self_attn.v_proj", ".self_attn.o_proj", ".mlp.gate_proj", ".mlp.up_proj", ".mlp.down_proj"};
+  const char* part[] = {".weight", ".scales", ".biases"};
+  for (int l = 0; l < sk.layers; ++l) {
+    const std::string src = p + ".layers." + std::to_string(l), dst = "model.layers." + std::to_string(l);
+    for (const char* t : part) {
+      if (const mia_tensor_view* v = L.find(src + ".self_attn.q_proj" + t)) sv.permuted(*v, dst + ".self_attn.q_proj" + t, sk.heads, sk.head_dim);
+      if (const mia_tensor_view* v = L.find(src + ".self_attn.k_proj" + t)) sv.permuted(*v, dst + ".self_attn.k_proj" + t, sk.kv_heads, sk.head_dim);
+      for (const char* n : lin) if (const mia_tensor_view* v = L.find(src + n + t)) sv.alias(*v, dst + n + t);
+    }
+  }
+}
+
+// the LM attach names a tensor under its own key: put the stack's prefix back (as mv_load_stack does)
+void mv_rename_error(mia_ctx* ctx, const char* prefix) {
+  size_t at;
+  while ((at = ctx->err.find("'model.embed_tokens")) != std::string::npos) ctx->err.replace(at, 19, "'codebook0_head");
+  while ((at = ctx->err.find("'model.")) != std::string::npos) ctx->err.replace(at, 7, std::string("'") + prefix + ".");
+}
+
+}  // namespace
+
+extern "C" int mia_marvis_attach_quantized(mia_marvis* mv, const mia_tensor_view* tensors, int n_tensors, int group_size, int bits) {
+  if (!mv) return MIA_ERR_MODEL_NOT_LOADED;
+  mia_ctx* ctx = mv->ctx;
+  const mia_marvis_config& c = mv->cfg;
+  MIA_CHECK_ARG(ctx, tensors && n_tensors > 0 && group_size == 64 && (bits == 4 || bits == 6 || bits == 8), "marvis_attach_quantized: tensors required, group size 64, 4, 6 or 8 bits");
+  MIA_CHECK_ARG(ctx, mv->q_bits == 0, "marvis_attach_quantized: packed weights are already attached to this handle (load a fresh handle to replace them)");
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  TensorLoader L;
+  L.index(tensors, n_tensors);
+  const Stack sb{"backbone", c.bb_hidden, c.bb_inter, c.bb_layers, c.bb_heads, c.bb_kv_heads, c.bb_head_dim, 0, 0.f, 0.f};
+  const Stack sd{"decoder", c.dec_hidden, c.dec_inter, c.dec_layers, c.dec_heads, c.dec_kv_heads, c.dec_head_dim, 0, 0.f, 0.f};
+  StackViews vb, vd;
+  mv_packed_views(sb, L, vb);
+  mv_packed_views(sd, L, vd);
+  // codebook0_head is the backbone handle's tied head: the LM attach packs it when its `.scales` is there
+  for (const char* t : {".weight", ".scales", ".biases"})
+    if (const mia_tensor_view* v = L.find(std::string("codebook0_head") + t)) vb.alias(*v, std::string("model.embed_tokens") + t);
+  LmPacked pb, pd;
+  if (vb.views.empty() || vd.views.empty()) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "marvis_attach_quantized: no packed tensor of the %s stack in the list", vb.views.empty() ? "backbone" : "decoder");
+  if (const int rc = lm_attach_prepare(mv->bb, vb.views.data(), (int)vb.views.size(), group_size, bits, "marvis_attach_quantized", pb)) { mv_rename_error(ctx, "backbone"); return rc; }
+  if (const int rc = lm_attach_prepare(mv->dec, vd.views.data(), (int)vd.views.size(), group_size, bits, "marvis_attach_quantized", pd)) {
+    lm_attach_discard(pb);
+    mv_rename_error(ctx, "decoder");
+    return rc;
+  }
+  // the projection [d_dec][D]: K = the backbone's hidden size, which the backbone's attach has checked against the 128-input block
+  std::vector<void*> fresh;
+  TensorLoader P; P.allocs = &fresh;
+  P.index(tensors, n_tensors);
+  Q4Src src{};
+  int sdt = -1;
+  Q4W qp;
+  std::vector<std::pair<int, int>> rows;
+  for (int n = 0; n < c.dec_hidden; ++n) rows.push_back({0, n});
+  const bool ok = q_find_linear(P, "projection", c.dec_hidden, c.bb_hidden, bits, false, &sdt, src) &&
+                  q_upload(P, {src}, rows, c.bb_hidden, bits, sdt, mv->dtype == MIA_F16 ? 1024.0f : 128.0f, &qp.wfrag, &qp.stfrag) &&
+                  (hipDeviceSynchronize() == hipSuccess || P.fail(MIA_ERR_DEVICE, "device error during upload"));
+  if (!ok) {      // neither stack has been touched yet
+    for (void* p : fresh) (void)hipFree(p);
+    lm_attach_discard(pb); lm_attach_discard(pd);
+    return mia_fail(ctx, P.code, "marvis_attach_quantized: %s", P.err.c_str());
+  }
+  // everything is in place: nothing below can fail
+  lm_attach_commit(mv->bb, pb);
+  lm_attach_commit(mv->dec, pd);
+  mv->allocs.insert(mv->allocs.end(), fresh.begin(), fresh.end());
+  mv->q_proj = qp;
+  mv->q_bits = bits;
+  mv_drop_graph(mv);            // the captured frame holds the 16-bit launches
+  return MIA_OK;
+}
+
+// the frame on the packed (1) or the 16-bit (0) weights of a handle that has both
+extern "C" int mia_marvis_use_packed(mia_marvis* mv, int on) {
+  if (!mv) return MIA_ERR_MODEL_NOT_LOADED;
+  MIA_CHECK_ARG(mv->ctx, !on || mv->q_bits != 0, "marvis_use_packed: no packed weights attached (mia_marvis_attach_quantized)");
+  MIA_HIP(mv->ctx, hipSetDevice(mv->ctx->device));
+  MIA_HIP(mv->ctx, hipStreamSynchronize(mv->ctx->stream));
+  mv->bb->q4 = mv->dec->q4 = on != 0;
+  mv->bb->graph_mode = mv->dec->graph_mode = -1;
+  mv_drop_graph(mv);
+  return MIA_OK;
 }
 
 // test hook: bit 0 launches every frame's kernels directly (no hipGraph), bit 1 walks prompts through the step (no batched prompt pass)

@@ -19,8 +19,10 @@ float q_to_f32(const void* p, size_t i, int sdt) {
 
 void q_repack_host(const std::vector<Q4Src>& src, const std::vector<std::pair<int, int>>& rows, int K, int bits, int sdt, float mag,
                    std::vector<uint32_t>& wf, std::vector<float>& st) {
-  const int N = (int)rows.size(), tiles = (N + 15) / 16, nblk = K / 128, np = bits / 4, cpw = 32 / bits, wpr = K / cpw, gpr = K / 64;
-  wf.assign((size_t)tiles * nblk * np * 64 * 4, 0u);
+  // bits 6: a full low-nibble plane and a 2-bit high plane of half its size (skinny_quant.hip): 384 words per (tile, block)
+  const int N = (int)rows.size(), tiles = (N + 15) / 16, nblk = K / 128, np = bits == 4 ? 1 : 2, wpr = K * bits / 32, gpr = K / 64;
+  const size_t blk_words = bits == 6 ? 384 : (size_t)np * 256;
+  wf.assign((size_t)tiles * nblk * blk_words, 0u);
   st.assign((size_t)tiles * nblk * 16 * 4, 0.f);
   const float tmul = mag * (np == 2 ? 17.0f : 1.0f);
   for (int t = 0; t < tiles; ++t)
@@ -29,18 +31,33 @@ void q_repack_host(const std::vector<Q4Src>& src, const std::vector<std::pair<in
       const Q4Src& q = src[rows[n].first];
       const uint32_t* wrow = q.w + (size_t)rows[n].second * wpr;
       const size_t g0 = (size_t)rows[n].second * gpr;
-      auto code = [&](int k) -> uint32_t { return (wrow[k / cpw] >> ((k % cpw) * bits)) & ((1u << bits) - 1u); };   // MLX packing: little end first
+      // MLX packing: the row is one little-endian bit stream, code k at bits [k bits, (k + 1) bits) -- a 6-bit code may straddle two words
+      auto code = [&](int k) -> uint32_t {
+        const int bit = k * bits, w = bit >> 5, sh = bit & 31;
+        uint32_t v = wrow[w] >> sh;
+        if (sh + bits > 32) v |= wrow[w + 1] << (32 - sh);
+        return v & ((1u << bits) - 1u);
+      };
       for (int b = 0; b < nblk; ++b) {
+        uint32_t* blk = &wf[((size_t)t * nblk + b) * blk_words];
         for (int c = 0; c < 4; ++c)
           for (int stp = 0; stp < 4; ++stp) {
             const int k0 = b * 128 + 32 * stp + 8 * c;
-            for (int p = 0; p < np; ++p) {
+            for (int p = 0; p < (bits == 6 ? 1 : np); ++p) {
               uint32_t word = 0;
               for (int i = 0; i < 4; ++i) {
                 const uint32_t q0 = (code(k0 + 2 * i) >> (4 * p)) & 15u, q1 = (code(k0 + 2 * i + 1) >> (4 * p)) & 15u;
                 word |= (q0 << (4 * i)) | (q1 << (16 + 4 * i));
               }
-              wf[((((size_t)t * nblk + b) * np + p) * 64 + 16 * c + r) * 4 + stp] = word;
+              blk[((size_t)p * 64 + 16 * c + r) * 4 + stp] = word;
+            }
+            if (bits == 6) {               // high plane: word stp / 2 of the lane, the K-step's four pairs at pair slots 4 (stp & 1) ..
+              uint32_t half = 0;
+              for (int i = 0; i < 4; ++i) {
+                const uint32_t q0 = code(k0 + 2 * i) >> 4, q1 = code(k0 + 2 * i + 1) >> 4;
+                half |= (q0 << (2 * i)) | (q1 << (16 + 2 * i));
+              }
+              blk[256 + (size_t)(16 * c + r) * 2 + (stp >> 1)] |= half << (8 * (stp & 1));
             }
           }
         for (int g = 0; g < 2; ++g) {
@@ -86,7 +103,7 @@ bool q_upload(TensorLoader& L, const std::vector<Q4Src>& src, const std::vector<
 // Test hook (include/mia.h): the repack alone, host memory in and out -- needs no device.
 extern "C" int mia_quant_repack(const uint32_t* codes, const void* scales, const void* biases, int N, int K, int bits, int scale_dtype,
                                 int compute_dtype, uint32_t* wfrag, float* stfrag) {
-  if (!codes || !scales || !biases || !wfrag || !stfrag || N <= 0 || K <= 0 || K % 128 != 0 || (bits != 4 && bits != 8)) return MIA_ERR_INVALID_ARGUMENT;
+  if (!codes || !scales || !biases || !wfrag || !stfrag || N <= 0 || K <= 0 || K % 128 != 0 || (bits != 4 && bits != 6 && bits != 8)) return MIA_ERR_INVALID_ARGUMENT;
   if (scale_dtype != MIA_F16 && scale_dtype != MIA_BF16 && scale_dtype != MIA_F32) return MIA_ERR_INVALID_ARGUMENT;
   if (compute_dtype != MIA_F16 && compute_dtype != MIA_BF16) return MIA_ERR_INVALID_ARGUMENT;
   std::vector<Q4Src> src{Q4Src{codes, scales, biases}};

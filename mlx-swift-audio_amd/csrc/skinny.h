@@ -91,7 +91,7 @@ bool dec_wfrag_copy(const void* src, int N, int K, std::vector<void*>& allocs, h
 // head is exactly 4 GiB).
 // The kernel form is chosen from the shape alone; tests/_skinny_cases.py restates the rule (dispatch16) -- change the two together.
 int skinny_gemm_launch(const SkinnyArgs& a, int mode, int dtype, hipStream_t s);
-// MLX-affine 4- / 8-bit weights in fragment order (skinny_quant.hip: skinny_gemm_qi); modes SK_OUTF32 / SK_PARTIAL / SK_SWIGLU / SK_RESID
+// MLX-affine 4- / 6- / 8-bit weights in fragment order (skinny_quant.hip: skinny_gemm_qi); modes SK_OUTF32 / SK_PARTIAL / SK_SWIGLU / SK_RESID
 // M_cap: the rows the caller's handle can hold (0 = M).  The launcher chooses between kernel forms that split K differently -- four
 // tiles per wave above 16 rows, the one-wave vocabulary head up to 16 -- and so sum in a different order.  It chooses from
 // max(M, M_cap): with M_cap = the handle's batch capacity a row's result does not depend on how many rows this call carries

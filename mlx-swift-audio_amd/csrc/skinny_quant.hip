@@ -1,10 +1,10 @@
-// skinny_quant.hip -- the LM step's skinny GEMM on packed 4- / 8-bit weights (skinny.h: skinny_gemm_q_launch).
+// skinny_quant.hip -- the LM step's skinny GEMM on packed 4- / 6- / 8-bit weights (skinny.h: skinny_gemm_q_launch).
 #include "skinny_device.h"
 #include "skinny_quant_device.h"
 
 // ------------------------------------------------------------------------------------------------
-// The same skinny GEMM on MLX-affine quantised weights (group 64: w = scale * code + bias; 4- or 8-bit codes), multiplied PACKED: the
-// step streams ~5 (or ~9) bits per weight from HBM instead of 16.  Replaces MLX's quantizedMatmul on the reference's default
+// The same skinny GEMM on MLX-affine quantised weights (group 64: w = scale * code + bias; 4-, 6- or 8-bit codes), multiplied PACKED: the
+// step streams ~5 (or ~7, ~9) bits per weight from HBM instead of 16.  Replaces MLX's quantizedMatmul on the reference's default
 // checkpoints (TTS/Orpheus/TTSEngine/OrpheusWeightLoader.swift:28-60, STT/Whisper/WhisperModel.swift:189-200; 4- and 8-bit:
 // Models/TranscriptionResult.swift:162-198).
 //
@@ -18,11 +18,18 @@
 // issue latency -- 14 us for the 27 MB gate|up matrix of Orpheus-3B, 1.9 TB/s).  The magic offset is removed in the group fix-up:
 // sum (MAG + q) a = MAG A + sum q a, so y += s P + t A with t = b - MAG s (fp32, built at attach time) and A = sum_k a[m][k] -- itself
 // an MFMA with an all-ones operand, shared by the tiles of a wave.  An 8-bit code is two 4-bit planes, q = 16 hi + lo: the hi plane goes
-// through the same unpack + MFMA into its own accumulator, P = P_lo + 16 P_hi and t = b - 17 MAG s.
+// through the same unpack + MFMA into its own accumulator, P = P_lo + 16 P_hi and t = b - 17 MAG s.  A 6-bit code (Marvis' published
+// checkpoints, TTS/Marvis/MarvisTTS.swift:220-226) is the same with a hi plane of 2 bits, hi = q >> 4 in 0..3: stored sixteen to a word so
+// that (word >> 2 i) & 0x00030003 isolates the hi parts of two adjacent K-values, a lane's 8 operand values again cost 7 VALU
+// instructions; everything behind the unpack is the 8-bit arithmetic (two accumulators, fma(16, P_hi, P_lo), t = b - 17 MAG s), and the
+// codes streamed are 6 bits per weight exactly.
 //
 // HBM layout (built once at attach, lm_load.hip:q_repack):
 //   wfrag  [tile = n/16][blk = k/128][plane][lane = 16 c + r][4 words]: word st of lane (r, c) = the plane's nibbles of
 //          W[16 tile + r][128 blk + 32 st + 8 c .. +7], nibble of K-value 2 i at bits [4 i, 4 i + 4), of 2 i + 1 at bits [16 + 4 i, ..)
+//   6 bit: [tile][blk] is 1536 B -- the lo plane as above (1024 B), then the hi plane [lane = 16 c + r][2 words] (512 B): word g of lane
+//          (r, c) = the 2-bit hi parts of the lane's 16 K-values of group g (K-steps st = 2 g and 2 g + 1), pair slot j = 4 (st & 1) + i:
+//          W[16 tile + r][128 blk + 32 st + 8 c + 2 i] at bits [2 j, 2 j + 2), its neighbour 2 i + 1 at bits [16 + 2 j, ..)
 //   stfrag [tile][blk][row r][4] fp32: (s, t) of the block's two groups -- the weights are the MFMA's COLUMN operand, so a lane's four
 //          accumulator values share one output column and one 16-byte load per block brings its scale and offset
 // Results agree with the 16-bit step on the de-quantised checkpoint to the rounding of the de-quantised weights to 16 bit (this form
@@ -76,8 +83,9 @@ __device__ __forceinline__ void skinny_store_tr(const SkinnyArgs& a, const f32x4
 }
 
 // M16: at most 16 rows (single-sequence decode, small batches): the second 16-row MFMA half and its activation loads are skipped
-// NP: nibble planes per code (1 = 4-bit, 2 = 8-bit)
-template <typename T, int MODE, int NT, int NW, bool M16, int NP>
+// NP: planes per code (1 = 4-bit, 2 = 6- and 8-bit); HB: bits per code of the hi plane (4 = a nibble plane like the lo one, 16 B per lane
+// and block; 2 = the 6-bit form's, 8 B per lane and block)
+template <typename T, int MODE, int NT, int NW, bool M16, int NP, int HB>
 __global__ __launch_bounds__(64 * NW) void skinny_gemm_qi(SkinnyArgs a, QFrag q) {
   __shared__ float rs[32];
   const int lane = threadIdx.x & 63;
@@ -100,11 +108,11 @@ __global__ __launch_bounds__(64 * NW) void skinny_gemm_qi(SkinnyArgs a, QFrag q)
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const int tl = tile0 + t < n_tiles ? tile0 + t : n_tiles - 1;      // tiles past the end re-read the last one and are never stored
-    wp[t] = reinterpret_cast<const u32x4*>(q.wfrag) + ((int64_t)tl * nblk) * (NP * 64) + lane;
+    wp[t] = reinterpret_cast<const u32x4*>(q.wfrag) + ((int64_t)tl * nblk) * (HB == 2 ? 96 : NP * 64) + lane;
     sp[t] = reinterpret_cast<const f32x4*>(q.stfrag) + ((int64_t)tl * nblk) * 16 + r;      // (s, t) of the block's two groups for column r
   }
   // codes and (scale, offset) pairs as buffer loads at 32-bit byte offsets, non-temporal (aux 2): see dec_skinny_fflat
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(q.wfrag), (short)0, (int)((unsigned)n_tiles * (unsigned)nblk * (NP * 64 * 16u)), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(q.wfrag), (short)0, (int)((unsigned)n_tiles * (unsigned)nblk * (HB == 2 ? 1536u : NP * 64 * 16u)), 0x00020000);
   const __amdgpu_buffer_rsrc_t rst = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(q.stfrag), (short)0, (int)((unsigned)n_tiles * (unsigned)nblk * 256u), 0x00020000);
   uint32_t wo[NT], so[NT];
 #pragma unroll
@@ -116,12 +124,17 @@ __global__ __launch_bounds__(64 * NW) void skinny_gemm_qi(SkinnyArgs a, QFrag q)
 #pragma unroll
   for (int t = 0; t < NT; ++t) { acc[t][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[t][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
   const s16x8 zfrag = (s16x8){0, 0, 0, 0, 0, 0, 0, 0};
-  struct Blk { u32x4 w[NT][NP]; f32x4 st[NT]; s16x8 a0[4], a1[4]; };
+  struct Blk { u32x4 w[NT][HB == 2 ? 1 : NP]; u32x2 h2[HB == 2 ? NT : 1]; f32x4 st[NT]; s16x8 a0[4], a1[4]; };      // h2: the 2-bit hi plane (HB == 2 only)
   auto load_blk = [&](Blk& b, int blk) {
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
+      if (HB == 2) {    // lo plane at the block's start, the lane's 8 B of the hi plane 1024 B in (wo holds 16 lane; the hi plane's rows are 8 lane)
+        b.w[t][0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, (int)(wo[t] + (uint32_t)blk * 1536u), 0, 2));
+        b.h2[HB == 2 ? t : 0] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rw, (int)(wo[t] - 8u * (uint32_t)lane + (uint32_t)blk * 1536u + 1024u), 0, 2));
+      } else {
 #pragma unroll
-      for (int p = 0; p < NP; ++p) b.w[t][p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, (int)(wo[t] + (uint32_t)(blk * NP + p) * 1024u), 0, 2));
+        for (int p = 0; p < NP; ++p) b.w[t][HB == 2 ? 0 : p] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, (int)(wo[t] + (uint32_t)(blk * NP + p) * 1024u), 0, 2));
+      }
       b.st[t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rst, (int)(so[t] + (uint32_t)blk * 256u), 0, 2));
     }
 #pragma unroll
@@ -137,6 +150,10 @@ __global__ __launch_bounds__(64 * NW) void skinny_gemm_qi(SkinnyArgs a, QFrag q)
     return __builtin_bit_cast(s16x8, (u32x4){(word & 0x000f000fu) | QMagic<T>::pair, ((word >> 4) & 0x000f000fu) | QMagic<T>::pair,
                                              ((word >> 8) & 0x000f000fu) | QMagic<T>::pair, ((word >> 12) & 0x000f000fu) | QMagic<T>::pair});
   };
+  auto unpack2 = [](uint32_t word) -> s16x8 {    // 8 hi parts of 2 bits (the word already shifted to the K-step's four pair slots) -> 8 x (MAG + hi)
+    return __builtin_bit_cast(s16x8, (u32x4){(word & 0x00030003u) | QMagic<T>::pair, ((word >> 2) & 0x00030003u) | QMagic<T>::pair,
+                                             ((word >> 4) & 0x00030003u) | QMagic<T>::pair, ((word >> 6) & 0x00030003u) | QMagic<T>::pair});
+  };
   auto mma_blk = [&](const Blk& b) {
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
@@ -149,7 +166,9 @@ __global__ __launch_bounds__(64 * NW) void skinny_gemm_qi(SkinnyArgs a, QFrag q)
         f32x4 P0[NP], P1[NP];
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-          const s16x8 f0 = unpack(b.w[t][p][2 * g]), f1 = unpack(b.w[t][p][2 * g + 1]);
+          s16x8 f0, f1;
+          if (HB == 2 && p == 1) { const uint32_t hw = b.h2[HB == 2 ? t : 0][g]; f0 = unpack2(hw); f1 = unpack2(hw >> 8); }
+          else { f0 = unpack(b.w[t][HB == 2 ? 0 : p][2 * g]); f1 = unpack(b.w[t][HB == 2 ? 0 : p][2 * g + 1]); }
           P0[p] = T::mfma16(b.a0[2 * g], f0, zero4);
           P0[p] = T::mfma16(b.a0[2 * g + 1], f1, P0[p]);
           if (!M16) { P1[p] = T::mfma16(b.a1[2 * g], f0, zero4); P1[p] = T::mfma16(b.a1[2 * g + 1], f1, P1[p]); }
@@ -186,7 +205,7 @@ __global__ __launch_bounds__(64 * NW) void skinny_gemm_qi(SkinnyArgs a, QFrag q)
   skinny_store_tr<T, MODE, NT>(a, acc, n0, m0, split, lane, rs);
 }
 
-template <typename T, bool M16, int NP>
+template <typename T, bool M16, int NP, int HB>
 static void skinny_qi_launch_m(const SkinnyArgs& a, const QFrag& q, int mode, hipStream_t s, int M_cap) {
   const int tiles = (a.N + 15) / 16, nblk = a.K / 128;
   const int zb = (a.M + 31) / 32;
@@ -205,7 +224,7 @@ static void skinny_qi_launch_m(const SkinnyArgs& a, const QFrag& q, int mode, hi
   // of the workgroups) -- Orpheus-3B, V 156 940: 75.4 us as 9 809 four-wave workgroups, 72.6 as one-wave ones, 67.8 in this form
   // (4 tiles x 4 waves: 107.6)
   const bool head41 = mode == SK_OUTF32 && tiles >= 4096 && Mf <= 16;
-#define QI_GO(MODE_, NT_, NW_) hipLaunchKernelGGL((skinny_gemm_qi<T, MODE_, NT_, NW_, M16, NP>), dim3((tiles + NT_ - 1) / NT_, a.S, zb), dim3(64 * NW_), 0, s, a, q)
+#define QI_GO(MODE_, NT_, NW_) hipLaunchKernelGGL((skinny_gemm_qi<T, MODE_, NT_, NW_, M16, NP, HB>), dim3((tiles + NT_ - 1) / NT_, a.S, zb), dim3(64 * NW_), 0, s, a, q)
 #define QI_LAUNCH(MODE_)                                                                                   \
   do {                                                                                                     \
     if (head41) QI_GO(MODE_, 4, 1);                                                                        \
@@ -229,18 +248,19 @@ static void skinny_qi_launch_m(const SkinnyArgs& a, const QFrag& q, int mode, hi
 
 template <typename T>
 static void skinny_qi_launch_t(const SkinnyArgs& a, const QFrag& q, int bits, int mode, hipStream_t s, int M_cap) {
-  if (bits == 8) { if (a.M <= 16) skinny_qi_launch_m<T, true, 2>(a, q, mode, s, M_cap); else skinny_qi_launch_m<T, false, 2>(a, q, mode, s, M_cap); }
-  else { if (a.M <= 16) skinny_qi_launch_m<T, true, 1>(a, q, mode, s, M_cap); else skinny_qi_launch_m<T, false, 1>(a, q, mode, s, M_cap); }
+  if (bits == 8) { if (a.M <= 16) skinny_qi_launch_m<T, true, 2, 4>(a, q, mode, s, M_cap); else skinny_qi_launch_m<T, false, 2, 4>(a, q, mode, s, M_cap); }
+  else if (bits == 6) { if (a.M <= 16) skinny_qi_launch_m<T, true, 2, 2>(a, q, mode, s, M_cap); else skinny_qi_launch_m<T, false, 2, 2>(a, q, mode, s, M_cap); }      // the 8-bit form rule
+  else { if (a.M <= 16) skinny_qi_launch_m<T, true, 1, 4>(a, q, mode, s, M_cap); else skinny_qi_launch_m<T, false, 1, 4>(a, q, mode, s, M_cap); }
 }
 
 // quantised form of skinny_gemm_launch: a.W is ignored, the weights come from the fragment-ordered arrays (see skinny_gemm_qi)
 // (the form rule -- skinny_qi_launch_m / _t -- is restated in tests/_skinny_cases.py: dispatch_q; change the two together)
 int skinny_gemm_q_launch(const SkinnyArgs& a, const uint32_t* wfrag, const float* stfrag, int bits, int mode, int dtype, hipStream_t s, int M_cap) {
   if (a.M <= 0 || a.N <= 0 || a.K <= 0 || a.S <= 0 || a.K % (128 * a.S) != 0 || a.lda % 8 != 0 || !wfrag || !stfrag) return -1;
-  if (bits != 4 && bits != 8) return -1;
-  // the kernel's buffer resources and byte offsets are 32 bit: codes [tiles][K / 128][bits / 4] KB (the (scale, offset) array is smaller;
-  // A is loaded through 64-bit pointers here and needs no such limit)
-  if ((uint64_t)((a.N + 15) / 16) * (uint64_t)(a.K / 128) * 1024 * (uint64_t)(bits / 4) > 0xffffffffull) return -1;
+  if (bits != 4 && bits != 6 && bits != 8) return -1;
+  // the kernel's buffer resources and byte offsets are 32 bit: codes [tiles][K / 128][bits / 4] KB, 1536 B per block at 6 bits (the
+  // (scale, offset) array is smaller; A is loaded through 64-bit pointers here and needs no such limit)
+  if ((uint64_t)((a.N + 15) / 16) * (uint64_t)(a.K / 128) * (bits == 6 ? 1536u : 1024u * (uint64_t)(bits / 4)) > 0xffffffffull) return -1;
   if (mode != SK_OUTF32 && mode != SK_PARTIAL && mode != SK_SWIGLU && mode != SK_RESID) return -1;
   if (mode == SK_SWIGLU && (a.N & 3)) return -1;
   if (mode == SK_RESID && (a.S != 1 || (a.N & 15) || !a.xres || !a.nw || !a.ss_out)) return -1;

@@ -33,7 +33,7 @@ class CausalLM:
         return CausalLM(ctx, h, cfg)
 
     def attach_q4(self, packed: dict[str, np.ndarray], group_size: int = 64, bits: int = 4) -> None:
-        """mia_lm_attach_quantized (bits 4 | 8): `packed` holds every step Linear as the checkpoint stores it -- `<name>.weight` uint32 codes,
+        """mia_lm_attach_quantized (bits 4 | 6 | 8): `packed` holds every step Linear as the checkpoint stores it -- `<name>.weight` uint32 codes,
         `<name>.scales` / `<name>.biases` float16 (or uint16 arrays tagged .st_dtype == "BF16", as checkpoint.read_safetensors returns
         bf16 payloads).  The handle must have been loaded from the de-quantised tensors of the same checkpoint."""
         lib = self.ctx.lib

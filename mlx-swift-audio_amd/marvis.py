@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._abi import BF16, F16, F32, MarvisConfig as _CConfig, tensor_views
+from ._abi import BF16, F16, F32, U32, MarvisConfig as _CConfig, tensor_views
 
 QUALITY_CODEBOOKS = {"low": 8, "medium": 16, "high": 24, "maximum": 32}      # MarvisEngine.QualityLevel.codebookCount (MarvisEngine.swift:55-68)
 MAX_AUDIO_FRAMES = int(60000 / 80.0)                                         # decodePrompt (MarvisTTS.swift:471)
@@ -166,6 +166,41 @@ class MarvisModel:
         if not h:
             raise _lib.MiaError(status.value or _lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
         return MarvisModel(ctx, h, cfg, dtype)
+
+    @staticmethod
+    def load_quantized(ctx: _lib.Context, cfg: MarvisConfig, raw_tensors: dict, dtype: int = BF16) -> "MarvisModel":
+        """The whole path for a published (MLX-affine quantised) checkpoint, as MarvisTTS.installWeights takes it (MarvisTTS.swift:220-226):
+        raw_tensors = the safetensors contents under the file's own keys.  sanitize_marvis, expand_checkpoint for the dense 16-bit copy
+        (embedding tables included), load, then attach the packed Linears; the frame runs on the packed weights."""
+        from . import checkpoint
+        tensors = checkpoint.sanitize_marvis(raw_tensors)
+        model = MarvisModel.load(ctx, cfg, checkpoint.expand_checkpoint(ctx, tensors), dtype)
+        model.attach_quantized(tensors)
+        return model
+
+    def attach_quantized(self, tensors: dict, bits: int | None = None, group_size: int = 64) -> None:
+        """mia_marvis_attach_quantized: `tensors` holds the Linears of both stacks, `projection` and (when stored quantised)
+        `codebook0_head` as the checkpoint stores them, under the keys of checkpoint.sanitize_marvis -- `<p>.weight` uint32 codes,
+        `<p>.scales` / `<p>.biases` float16 or bf16 (uint16 arrays tagged .st_dtype == "BF16"); anything without a `.scales` is left out,
+        and quantised embedding tables are ignored (they stay 16-bit tables).  bits (4 | 6 | 8): inferred from the packed width when not
+        given, as checkpoint.expand_checkpoint does.  The handle must have been loaded from the de-quantised tensors of the same
+        checkpoint.  One attach per handle; the frame then runs on the packed weights (use_packed(False) switches back)."""
+        packed = {}
+        for name, arr in tensors.items():
+            base = name.rsplit(".", 1)[0]
+            if name.endswith((".weight", ".scales", ".biases")) and base + ".scales" in tensors and not base.endswith("_embeddings"):
+                packed[name] = arr
+        if bits is None:
+            for name, arr in packed.items():
+                if name.endswith(".weight"):
+                    bits = (32 * arr.shape[-1]) // (packed[name[:-7] + ".scales"].shape[-1] * group_size)
+                    break
+        views, n, keep = tensor_views(packed, (U32, F16, BF16), "attach_quantized: '{name}' must be uint32 codes or 16-bit scales / biases (got {dtype})")
+        self.ctx.check(self.ctx.lib.mia_marvis_attach_quantized(self.h, views, n, int(group_size), int(bits or 0)))
+
+    def use_packed(self, on: bool) -> None:
+        """mia_marvis_use_packed: the frame reads the attached packed weights (True) or the 16-bit copy (False)."""
+        self.ctx.check(self.ctx.lib.mia_marvis_use_packed(self.h, 1 if on else 0))
 
     def codebooks(self, max_codebooks: int) -> int:
         return min(self.cfg.n_codebooks, max_codebooks)

@@ -303,9 +303,10 @@ def quant_repack(codes: np.ndarray, scales: np.ndarray, biases: np.ndarray, bits
     """mia_quant_repack (host): one packed Linear (quantize_affine's three arrays; bf16 scales as uint16 bit patterns) -> (wfrag, stfrag)."""
     lib = _lib.load()
     codes, scales, biases = np.ascontiguousarray(codes, np.uint32), np.ascontiguousarray(scales), np.ascontiguousarray(biases)
-    N, K = codes.shape[0], codes.shape[1] * (32 // bits)
+    N, K = codes.shape[0], codes.shape[1] * 32 // bits
     tiles = (N + 15) // 16
-    wf = np.zeros((tiles, K // 128, bits // 4, 64, 4), np.uint32)
+    # 6 bit: [64][4] low-nibble words then [64][2] words of 2-bit high parts per (tile, block) (csrc/skinny_quant.hip)
+    wf = np.zeros((tiles, K // 128, 384) if bits == 6 else (tiles, K // 128, bits // 4, 64, 4), np.uint32)
     st = np.zeros((tiles, K // 128, 16, 4), np.float32)
     rc = lib.mia_quant_repack(codes.ctypes.data, scales.ctypes.data, biases.ctypes.data, N, K, int(bits), int(scale_dtype), int(compute_dtype),
                               wf.ctypes.data, st.ctypes.data)
