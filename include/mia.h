@@ -315,6 +315,16 @@ typedef struct {
 } mia_skinny_desc;
 int mia_op_skinny_gemm(mia_ctx* ctx, const mia_skinny_desc* d);
 
+/* The many-row GEMM on packed weights (csrc/gemm_quant.hip), the kernel behind mia_lm_set_prompt_weights(lm, 1), without a model around
+ * it: C fp32 [M][ldc] = A [M][lda] (`dtype`: MIA_BF16 | MIA_F16) . Wq^T (+ R fp32 [M][ldr]; R may be NULL, and may be C itself).  wfrag /
+ * stfrag are the arrays mia_quant_repack builds for `bits` (4 | 6 | 8) and compute type `dtype` -- the ones mia_op_skinny_gemm reads.
+ * Per 64-input group the result is scale * sum(code * a) + bias * sum(a) with fp32 sums, groups added in ascending order; no weight is
+ * formed or rounded, and a row's result does not depend on M.  DEVICE pointers, enqueued on the context's stream.  Any M, N >= 1,
+ * K % 128 == 0, lda % 8 == 0, lda >= K, ldc / ldr >= N; A, wfrag and stfrag 16-byte aligned.  Anything else is MIA_ERR_INVALID_ARGUMENT
+ * and launches nothing.  The descriptor (include/mia_gemm_quant.h, included by the callers that fill one) follows mia_skinny_desc. */
+typedef struct mia_gemm_quant_desc mia_gemm_quant_desc;    /* defined in include/mia_gemm_quant.h */
+int mia_op_gemm_quant(mia_ctx* ctx, const mia_gemm_quant_desc* d);
+
 /* ---- Whisper ---------------------------------------------------------------------------------- */
 /* Model dimensions == ModelDimensions (STT/Whisper/Config/WhisperConfig.swift:9-86), read by the caller
  * from config.json. */
@@ -744,11 +754,25 @@ mia_lm* mia_lm_load(mia_ctx* ctx, const mia_lm_config* cfg, const mia_tensor_vie
  * Linear as stored -- `<name>.weight` (MIA_U32 codes [N][K * bits / 32], one little-endian bit stream per row), `<name>.scales`, `<name>.biases` ([N][K/64],
  * both f16 or both bf16) -- onto a handle loaded from the de-quantised checkpoint; the per-token step then streams the packed codes and
  * multiplies them as MLX's own kernels do (per group: scale * sum(code * x) + bias * sum(x), the codes exact in the MFMA's 16-bit
- * operands, fp32 group sums), the batched prompt pass keeps the 16-bit copy.  One attach per handle.  mia_lm_attach_q4 = bits 4.
+ * operands, fp32 group sums); the batched prompt pass multiplies the 16-bit copy until mia_lm_set_prompt_weights(lm, 1) moves it to the
+ * packed weights too.  One attach per handle.  mia_lm_attach_q4 = bits 4.
  * mia_lm_use_q4 toggles the step between the packed and the 16-bit weights (0 = 16-bit). */
 int mia_lm_attach_quantized(mia_lm* lm, const mia_tensor_view* tensors, int n_tensors, int group_size, int bits);
 int mia_lm_attach_q4(mia_lm* lm, const mia_tensor_view* tensors, int n_tensors, int group_size);
 int mia_lm_use_q4(mia_lm* lm, int on);
+/* Which weights the batched prompt pass multiplies.  0 (default): the 16-bit copy, exactly as without this call.  1: the attached packed
+ * weights, through a many-row packed GEMM (csrc/gemm_quant.hip) with the step's arithmetic -- per 64-input group scale * sum(code * x) +
+ * bias * sum(x), fp32 sums, no weight formed or rounded -- so that the K/V rows of a prompt and those of generated tokens come from the
+ * same function of the weights (the reference runs quantizedMatmul for both).  Everything else of the prompt pass is unchanged, and the
+ * mode does not depend on mia_lm_use_q4.  Mode 1 without attached weights, or another mode: MIA_ERR_INVALID_ARGUMENT.
+ * mia_lm_release_dense (packed weights attached, else MIA_ERR_INVALID_ARGUMENT) sets mia_lm_use_q4(1) and prompt mode 1 and frees the
+ * layers' 16-bit Linears -- q|k|v, o, gate|up, down, row-major and fragment order; the embedding table, norms, biases and the head stay.
+ * Afterwards mia_lm_use_q4(lm, 0) and mia_lm_set_prompt_weights(lm, 0) are MIA_ERR_UNSUPPORTED; everything else works as before.
+ * mia_lm_weight_bytes reports the device bytes of weight matrices the handle holds now: *dense the 16-bit ones (tables, head, Linears in
+ * both orders), *packed the attached codes and (scale, offset) pairs. */
+int mia_lm_set_prompt_weights(mia_lm* lm, int mode);
+int mia_lm_release_dense(mia_lm* lm);
+int mia_lm_weight_bytes(mia_lm* lm, int64_t* dense, int64_t* packed);
 /* Test hook: bit 0 = launch every step's kernels directly (no hipGraph), bit 1 = feed prompts token by token (no batched prompt
  * pass).  Results agree up to fp32 summation order. */
 int mia_lm_set_debug(mia_lm* lm, int flags);
@@ -933,7 +957,11 @@ int mia_sample_top_p(mia_ctx* ctx, const float* logits, int V, const int32_t* hi
  * checkpoint stores its `.scales`; bits 4 | 6 | 8, group_size 64.  q_proj / k_proj get the loader's row permutation on all three tensors
  * (packing runs along the input axis, so permuting rows is exact).  audio_head is never quantised and the embedding tables stay 16-bit
  * tables.  Hidden sizes, heads * head_dim and intermediate sizes of both stacks must be multiples of 128.  The frame's single-row steps
- * then stream the packed codes through the LM step's packed GEMMs (mia_lm_attach_quantized); prompts keep the 16-bit prompt pass.  One
+ * then stream the packed codes through the LM step's packed GEMMs (mia_lm_attach_quantized); prompts go through the 16-bit prompt pass
+ * until mia_marvis_use_packed_prompt(m, 1) puts the backbone's prompt pass on the packed weights (mia_lm_set_prompt_weights; the decoder
+ * has no prompt pass, and the frame graph does not hold the prompt pass, so nothing is dropped).  mia_marvis_release_dense frees the 16-bit
+ * layer Linears of both stacks (mia_lm_release_dense) with both switches at 1; mia_marvis_use_packed(m, 0) and
+ * mia_marvis_use_packed_prompt(m, 0) are MIA_ERR_UNSUPPORTED afterwards.  The projection's copies, audio_head and the tables stay.  One
  * attach per handle; the frame graph is dropped.  Errors as mia_lm_attach_quantized; after any of them the handle is exactly as before --
  * neither stack is packed unless both and the projection are.  mia_marvis_use_packed(m, 0 | 1) switches the frame between the 16-bit and
  * the packed weights (1 after a successful attach; 1 without an attach is MIA_ERR_INVALID_ARGUMENT) and drops the frame graph. */
@@ -946,6 +974,8 @@ int mia_marvis_set_debug(mia_marvis* m, int flags);
 int mia_marvis_set_batch(mia_marvis* m, int max_batch);
 int mia_marvis_attach_quantized(mia_marvis* m, const mia_tensor_view* tensors, int n_tensors, int group_size, int bits);
 int mia_marvis_use_packed(mia_marvis* m, int on);
+int mia_marvis_use_packed_prompt(mia_marvis* m, int on);
+int mia_marvis_release_dense(mia_marvis* m);
 int mia_marvis_frame(mia_marvis* m, const int32_t* tokens, const int32_t* mask, int T, int max_codebooks, float temperature, float top_p,
                      const float* uniforms, const int32_t* forced, int32_t* ids_out, float* logits_out);
 int mia_marvis_generate(mia_marvis* m, const int32_t* tokens, const int32_t* mask, int T, int max_codebooks, float temperature, float top_p,

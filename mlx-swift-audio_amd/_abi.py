@@ -50,6 +50,14 @@ class SkinnyDesc(C.Structure):
                 ("M_cap", i32)]
 
 
+class GemmQuantDesc(C.Structure):
+    """struct mia_gemm_quant_desc of include/mia_gemm_quant.h (mia.h only declares the type, so it is not in STRUCTS)."""
+    _fields_ = [("A", vp), ("lda", i64),
+                ("wfrag", vp), ("stfrag", vp), ("bits", i32),
+                ("C", vp), ("ldc", i64), ("R", vp), ("ldr", i64),
+                ("M", i32), ("N", i32), ("K", i32), ("dtype", i32)]
+
+
 class WhisperDims(C.Structure):
     _fields_ = [("n_mels", i32), ("n_audio_ctx", i32), ("n_audio_state", i32), ("n_audio_head", i32), ("n_audio_layer", i32),
                 ("n_vocab", i32), ("n_text_ctx", i32), ("n_text_state", i32), ("n_text_head", i32), ("n_text_layer", i32)]
@@ -254,6 +262,7 @@ PROTOTYPES = {
     "mia_op_kvq_attention": (i32, [vp, vp, vp, vp, vp] + [i32] * 6),
     "mia_op_lm_prompt_attention": (i32, [vp, vp, vp, vp, vp] + [i32] * 6),
     "mia_op_skinny_gemm": (i32, [vp, P(SkinnyDesc)]),
+    "mia_op_gemm_quant": (i32, [vp, vp]),
     # Whisper
     "mia_whisper_load": (vp, [vp, P(WhisperDims), TV, i32, i32]),
     "mia_whisper_free": (None, [vp]),
@@ -331,6 +340,9 @@ PROTOTYPES = {
     "mia_lm_attach_quantized": (i32, [vp, TV, i32, i32, i32]),
     "mia_lm_attach_q4": (i32, [vp, TV, i32, i32]),
     "mia_lm_use_q4": (i32, [vp, i32]),
+    "mia_lm_set_prompt_weights": (i32, [vp, i32]),
+    "mia_lm_release_dense": (i32, [vp]),
+    "mia_lm_weight_bytes": (i32, [vp, vp, vp]),
     "mia_lm_set_debug": (i32, [vp, i32]),
     "mia_lm_set_prompt_attention": (i32, [vp, i32]),
     "mia_lm_free": (None, [vp]),
@@ -357,6 +369,8 @@ PROTOTYPES = {
     "mia_marvis_set_batch": (i32, [vp, i32]),
     "mia_marvis_attach_quantized": (i32, [vp, TV, i32, i32, i32]),
     "mia_marvis_use_packed": (i32, [vp, i32]),
+    "mia_marvis_use_packed_prompt": (i32, [vp, i32]),
+    "mia_marvis_release_dense": (i32, [vp]),
     "mia_marvis_frame": (i32, [vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp]),
     "mia_marvis_generate": (i32, [vp, vp, vp, i32, i32, f32, f32, i32, vp, vp, vp]),
     "mia_marvis_generate_batch": (i32, [vp, vp, vp, vp, i32, i32, f32, f32, i32, vp, vp, vp]),

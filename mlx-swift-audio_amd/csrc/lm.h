@@ -27,7 +27,7 @@ struct LmLayer {
   void* wdown = nullptr;                         // [hidden][inter]
   // the same four in MFMA-fragment order (skinny.h) for the decode step's skinny GEMMs: one contiguous 1 KB per wave load instead of
   // 16 rows x 64 B (tools/micro/skinny_probe.hip, Orpheus-3B shapes, one sequence: 48.3 -> 43.7 us per layer); the batched prompt
-  // pass (gemm.hip) keeps reading the row-major copies
+  // pass (gemm.hip) keeps reading the row-major copies.  All eight are allocations of their own: mia_lm_release_dense frees them
   void* wqkv_f = nullptr; void* wo_f = nullptr; void* wgu_f = nullptr; void* wdown_f = nullptr;
 };
 
@@ -71,6 +71,8 @@ struct mia_lm {
   int graph_mode = -1;                  // LM_STEP_* below
   int debug_flags = 0;                  // test hook (mia_lm_set_debug): bit 0 = no hipGraph, bit 1 = no batched prompt pass
   int prompt_attn = 0;                  // mia_lm_set_prompt_attention: 0 = the row kernel (lm_attention), 1 = lm_prefill_attn.hip on the 16-bit cache
+  int prompt_packed = 0;                // mia_lm_set_prompt_weights: 0 = the prompt pass multiplies the 16-bit copy (gemm.hip), 1 = the packed weights (gemm_quant.hip)
+  bool dense_released = false;          // mia_lm_release_dense: the layers' 16-bit Linears and their fragment copies are gone; q4 and prompt_packed stay 1
   mia_lm_sampler graph_sampler{};
   RasParams graph_ras{};
   int graph_top_k = 0;                  // LM_STEP_TOPK: the effective k (temperature and top_p travel in graph_sampler)

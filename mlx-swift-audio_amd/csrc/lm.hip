@@ -500,7 +500,8 @@ int lm_enqueue_step(mia_lm* m, int mode, const mia_lm_sampler& sp, const RasPara
 // through the ordinary step (which owns the head and the sampler), so P = n_prompt - 1.  Per-row arithmetic mirrors the step:
 // fp32 residual stream, 16-bit RMSNorm output, fp32 q|k|v -> RoPE -> 16-bit, same attention kernel (row r sees keys [0, pos0+r]),
 // fp32 gate/up -> silu(g)*u -> 16-bit.  (The reference does the same thing: model(promptIds, cache) is one batched call,
-// OrpheusTTS.swift:262-279 / Qwen2LM.swift:353-361.)
+// OrpheusTTS.swift:262-279 / Qwen2LM.swift:353-361.)  With mia_lm_set_prompt_weights(1) the four GEMMs multiply the attached packed
+// weights instead (gemm_quant.hip), as the reference's quantizedMatmul does for prompt and step alike; nothing else changes.
 static constexpr int PF_ROWS = 512;
 static constexpr int PF_MIN_ROWS = LM_PREFILL_MIN_ROWS;
 
@@ -539,9 +540,19 @@ int lm_prefill_rows(mia_lm* m, const std::vector<int2>& rows, const std::vector<
   const bool tiled = m->prompt_attn == 1 && !m->kv_bits;
   const int qtile = lm_prefill_attn_qtile(c.n_heads, c.n_kv_heads);
   std::vector<std::vector<int4>> chunk_tiles(tiled ? (rows.size() + PF_ROWS - 1) / PF_ROWS : 0);    // alive until the call returns, like `rows`
-  auto gemm = [&](const void* A, int K, const void* W, const float* bias, float* C, int N, int M, const float* R) {
+  // mia_lm_set_prompt_weights(1): the four GEMMs read the packed weights the step streams (gemm_quant.hip) -- the prompt's K/V rows then
+  // come from the same function of the weights as the generated tokens' -- and W is not touched (it may be gone: mia_lm_release_dense)
+  const bool packed = m->prompt_packed != 0;
+  auto gemm = [&](const void* A, int K, const void* W, const Q4W& qw, float* C, int N, int M, const float* R) {
+    if (packed) {
+      GemmQuantArgs g;
+      g.A = (const uint16_t*)A; g.lda = K; g.wfrag = qw.wfrag; g.stfrag = qw.stfrag; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K;
+      if (R) { g.R = R; g.ldr = N; }
+      if (const char* e = gemm_quant_check(g, m->q_bits, m->dtype)) { ctx->err = e; return -1; }
+      return gemm_quant_launch(g, m->q_bits, m->dtype, s);
+    }
     GemmArgs g;
-    g.A = A; g.lda = K; g.W = W; g.bias = bias; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K; g.out_f32 = 1;
+    g.A = A; g.lda = K; g.W = W; g.C = C; g.ldc = N; g.M = M; g.N = N; g.K = K; g.out_f32 = 1;
     if (R) { g.R = R; g.ldr = N; }
     if (const char* e = mia_gemm_check(g)) { ctx->err = e; return -1; }
     return mia_gemm_launch(g, m->dtype, s);
@@ -563,7 +574,7 @@ int lm_prefill_rows(mia_lm* m, const std::vector<int2>& rows, const std::vector<
     }
     for (int l = 0; l < c.n_layers; ++l) {
       const LmLayer& L = m->layers[l];
-      if (gemm(h, D, L.wqkv, nullptr, qkv, Nqkv, M, nullptr)) return MIA_ERR_DEVICE;
+      if (gemm(h, D, L.wqkv, L.q_qkv, qkv, Nqkv, M, nullptr)) return MIA_ERR_DEVICE;
       lm_launch_rope_cache(m, l, qkv, L.bqkv, q, rowmap, M);
       if (l + 1 == c.n_layers) break;            // past its K/V rows the last layer feeds only the head, which the prompt pass skips
       if (tiled) {
@@ -571,12 +582,12 @@ int lm_prefill_rows(mia_lm* m, const std::vector<int2>& rows, const std::vector<
         if (const char* e = lm_prefill_attn_check(pa)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
         if (lm_prefill_attn_launch(pa, s)) return mia_fail(ctx, MIA_ERR_DEVICE, "lm: prompt attention launch failed");
       } else lm_launch_attention(m, false, M, q, l, att, rowmap, nullptr, 0, nullptr);
-      if (gemm(att, Nq, L.wo, nullptr, x, D, M, x)) return MIA_ERR_DEVICE;                // x += att . Wo^T
+      if (gemm(att, Nq, L.wo, L.q_o, x, D, M, x)) return MIA_ERR_DEVICE;                   // x += att . Wo^T
       LAUNCH_T(lm_reduce_norm, dim3(M), dim3(256), 0, (const float*)nullptr, 0, L.post_norm, x, h, D, c.rms_eps, 1);
-      if (gemm(h, D, L.wgu, nullptr, gu, 2 * I, M, nullptr)) return MIA_ERR_DEVICE;
+      if (gemm(h, D, L.wgu, L.q_gu, gu, 2 * I, M, nullptr)) return MIA_ERR_DEVICE;
       const int64_t n2 = (int64_t)M * I / 2;
       LAUNCH_T(lm_swiglu_rows, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, gu, act, n2);
-      if (gemm(act, I, L.wdown, nullptr, x, D, M, x)) return MIA_ERR_DEVICE;              // x += act . Wdown^T
+      if (gemm(act, I, L.wdown, L.q_down, x, D, M, x)) return MIA_ERR_DEVICE;             // x += act . Wdown^T
       LAUNCH_T(lm_reduce_norm, dim3(M), dim3(256), 0, (const float*)nullptr, 0, m->layers[l + 1].in_norm, x, h, D, c.rms_eps, 1);
     }
   }

@@ -179,7 +179,7 @@ extern "C" mia_lm* mia_lm_load(mia_ctx* ctx, const mia_lm_config* cfg, const mia
 // tensors: for every Linear of the step, `<name>.weight` (MIA_U32 packed codes [N][K * bits / 32]), `<name>.scales`, `<name>.biases`
 // ([N][K/64], both MIA_F16 or both MIA_BF16), names as in the checkpoint (model.layers.L.self_attn.{q,k,v,o}_proj, mlp.{gate,up,down}_proj,
 // model.embed_tokens / lm_head).  The handle must already hold the de-quantised 16-bit weights (mia_lm_load on the expanded
-// checkpoint): the batched prompt pass keeps using them, the per-token step switches to the packed form.  Nothing of the handle changes
+// checkpoint): the batched prompt pass keeps using them until mia_lm_set_prompt_weights(1), the per-token step switches to the packed form.  Nothing of the handle changes
 // unless every matrix was repacked and uploaded.  A bad argument or tensor list is MIA_ERR_INVALID_ARGUMENT; a refused hipMalloc
 // MIA_ERR_OUT_OF_MEMORY, a failed upload MIA_ERR_DEVICE.
 // (the two halves are declared in lm.h: marvis.hip packs its two stacks through them)
@@ -270,7 +270,85 @@ extern "C" int mia_lm_attach_q4(mia_lm* m, const mia_tensor_view* tensors, int n
 extern "C" int mia_lm_use_q4(mia_lm* m, int on) {
   if (!m) return MIA_ERR_MODEL_NOT_LOADED;
   MIA_CHECK_ARG(m->ctx, !on || m->q_bits != 0, "lm_use_q4: no packed weights attached");
+  if (!on && m->dense_released) return mia_fail(m->ctx, MIA_ERR_UNSUPPORTED, "lm_use_q4: the 16-bit Linears of this handle were released (mia_lm_release_dense)");
   m->q4 = on != 0;
   m->graph_mode = -1;
+  return MIA_OK;
+}
+
+// which weights the batched prompt pass multiplies: 0 = the 16-bit copy (gemm.hip; the default), 1 = the packed ones (gemm_quant.hip)
+extern "C" int mia_lm_set_prompt_weights(mia_lm* m, int mode) {
+  if (!m) return MIA_ERR_MODEL_NOT_LOADED;
+  MIA_CHECK_ARG(m->ctx, mode == 0 || mode == 1, "lm_set_prompt_weights: mode must be 0 or 1 (got %d)", mode);
+  MIA_CHECK_ARG(m->ctx, !mode || m->q_bits != 0, "lm_set_prompt_weights: no packed weights attached (mia_lm_attach_quantized)");
+  if (!mode && m->dense_released) return mia_fail(m->ctx, MIA_ERR_UNSUPPORTED, "lm_set_prompt_weights: the 16-bit Linears of this handle were released (mia_lm_release_dense)");
+  m->prompt_packed = mode;      // the prompt pass is launched directly, never captured: nothing to drop
+  return MIA_OK;
+}
+
+namespace {
+
+// the four Linears of a layer as (N, K): q|k|v, o, gate|up, down
+void lm_linear_dims(const mia_lm_config& c, int64_t (&nk)[4][2]) {
+  const int64_t D = c.hidden, Nq = (int64_t)c.n_heads * c.head_dim, Nk = (int64_t)c.n_kv_heads * c.head_dim;
+  nk[0][0] = Nq + 2 * Nk; nk[0][1] = D; nk[1][0] = D; nk[1][1] = Nq; nk[2][0] = 2 * (int64_t)c.inter; nk[2][1] = D; nk[3][0] = D; nk[3][1] = c.inter;
+}
+int64_t pad16(int64_t n) { return (n + 15) / 16 * 16; }
+// codes + (scale, offset) pairs of one packed matrix (quant_repack.hip: [tiles][K / 128] blocks)
+int64_t packed_bytes(int64_t N, int64_t K, int bits) { return pad16(N) / 16 * (K / 128) * ((bits == 6 ? 1536 : 256 * bits) + 256); }
+
+}  // namespace
+
+// Frees the layers' 16-bit Linears (row-major and fragment order) of a handle whose step and prompt pass can both run packed; both are
+// switched to the packed weights first, and the two switches back are MIA_ERR_UNSUPPORTED from here on.  The embedding table, the norms,
+// the biases and the head (16-bit and packed) stay.
+extern "C" int mia_lm_release_dense(mia_lm* m) {
+  if (!m) return MIA_ERR_MODEL_NOT_LOADED;
+  mia_ctx* ctx = m->ctx;
+  MIA_CHECK_ARG(ctx, m->q_bits != 0, "lm_release_dense: no packed weights attached (mia_lm_attach_quantized)");
+  if (m->dense_released) return MIA_OK;
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));      // nothing in flight reads what is about to go
+  m->q4 = true; m->prompt_packed = 1; m->graph_mode = -1;
+  auto drop = [&](void*& p) {
+    if (!p) return;
+    auto it = std::find(m->allocs.begin(), m->allocs.end(), p);
+    if (it != m->allocs.end()) { (void)hipFree(p); m->allocs.erase(it); }
+    p = nullptr;
+  };
+  for (LmLayer& ly : m->layers) {
+    drop(ly.wqkv); drop(ly.wo); drop(ly.wgu); drop(ly.wdown);
+    drop(ly.wqkv_f); drop(ly.wo_f); drop(ly.wgu_f); drop(ly.wdown_f);
+  }
+  m->dense_released = true;
+  return MIA_OK;
+}
+
+// device bytes of weight matrices the handle holds now: *dense = the 16-bit ones (embedding tables, the head and its fragment copy, the
+// layers' Linears in both orders), *packed = the attached codes and (scale, offset) pairs.  Norm gains, biases and state are not counted.
+extern "C" int mia_lm_weight_bytes(mia_lm* m, int64_t* dense, int64_t* packed) {
+  if (!m) return MIA_ERR_MODEL_NOT_LOADED;
+  MIA_CHECK_ARG(m->ctx, dense && packed, "lm_weight_bytes: null pointer");
+  const mia_lm_config& c = m->cfg;
+  const int64_t D = c.hidden, HV = m->head_vocab > 0 ? m->head_vocab : c.vocab;
+  int64_t nk[4][2];
+  lm_linear_dims(c, nk);
+  int64_t d = 0, q = 0;
+  if (m->embed) d += (int64_t)c.vocab * D * 2;
+  if (m->lm_head && m->lm_head != m->embed) d += HV * D * 2;
+  if (m->lm_head_f) d += pad16(HV) * D * 2;
+  if (m->gen_embed) d += (int64_t)m->gen_rows * D * 2;
+  for (const LmLayer& ly : m->layers) {
+    const void* rm[4] = {ly.wqkv, ly.wo, ly.wgu, ly.wdown};
+    const void* fr[4] = {ly.wqkv_f, ly.wo_f, ly.wgu_f, ly.wdown_f};
+    const Q4W* qw[4] = {&ly.q_qkv, &ly.q_o, &ly.q_gu, &ly.q_down};
+    for (int i = 0; i < 4; ++i) {
+      if (rm[i]) d += nk[i][0] * nk[i][1] * 2;
+      if (fr[i]) d += pad16(nk[i][0]) * nk[i][1] * 2;
+      if (qw[i]->wfrag) q += packed_bytes(nk[i][0], nk[i][1], m->q_bits);
+    }
+  }
+  if (m->q_head.wfrag) q += packed_bytes(HV, D, m->q_bits);
+  *dense = d; *packed = q;
   return MIA_OK;
 }

@@ -490,11 +490,32 @@ extern "C" int mia_marvis_attach_quantized(mia_marvis* mv, const mia_tensor_view
 extern "C" int mia_marvis_use_packed(mia_marvis* mv, int on) {
   if (!mv) return MIA_ERR_MODEL_NOT_LOADED;
   MIA_CHECK_ARG(mv->ctx, !on || mv->q_bits != 0, "marvis_use_packed: no packed weights attached (mia_marvis_attach_quantized)");
+  if (!on && mv->bb->dense_released) return mia_fail(mv->ctx, MIA_ERR_UNSUPPORTED, "marvis_use_packed: the 16-bit Linears of this handle were released (mia_marvis_release_dense)");
   MIA_HIP(mv->ctx, hipSetDevice(mv->ctx->device));
   MIA_HIP(mv->ctx, hipStreamSynchronize(mv->ctx->stream));
   mv->bb->q4 = mv->dec->q4 = on != 0;
   mv->bb->graph_mode = mv->dec->graph_mode = -1;
   mv_drop_graph(mv);
+  return MIA_OK;
+}
+
+// the backbone's prompt pass on the packed (1) or the 16-bit (0) weights; the decoder has no prompt pass and the frame graph does not hold
+// the prompt pass, so nothing is dropped
+extern "C" int mia_marvis_use_packed_prompt(mia_marvis* mv, int on) {
+  if (!mv) return MIA_ERR_MODEL_NOT_LOADED;
+  MIA_CHECK_ARG(mv->ctx, !on || mv->q_bits != 0, "marvis_use_packed_prompt: no packed weights attached (mia_marvis_attach_quantized)");
+  return mia_lm_set_prompt_weights(mv->bb, on ? 1 : 0);
+}
+
+// both stacks give up their 16-bit layer Linears (mia_lm_release_dense); the frame and the prompt pass run packed from here on
+extern "C" int mia_marvis_release_dense(mia_marvis* mv) {
+  if (!mv) return MIA_ERR_MODEL_NOT_LOADED;
+  MIA_CHECK_ARG(mv->ctx, mv->q_bits != 0, "marvis_release_dense: no packed weights attached (mia_marvis_attach_quantized)");
+  MIA_HIP(mv->ctx, hipSetDevice(mv->ctx->device));
+  MIA_HIP(mv->ctx, hipStreamSynchronize(mv->ctx->stream));
+  if (const int rc = mia_lm_release_dense(mv->bb)) return rc;
+  if (const int rc = mia_lm_release_dense(mv->dec)) return rc;
+  mv_drop_graph(mv);            // a frame captured on the 16-bit weights must not be replayed
   return MIA_OK;
 }
 

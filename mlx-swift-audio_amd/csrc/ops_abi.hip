@@ -203,6 +203,20 @@ extern "C" int mia_op_skinny_gemm(mia_ctx* ctx, const mia_skinny_desc* d) {
   return MIA_OK;
 }
 
+// The packed prompt pass's GEMM (gemm_quant.hip) on caller-provided device arrays; gemm_quant_check is the gatekeeper.
+#include "../../include/mia_gemm_quant.h"
+extern "C" int mia_op_gemm_quant(mia_ctx* ctx, const mia_gemm_quant_desc* d) {
+  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, d, "op_gemm_quant: null descriptor");
+  GemmQuantArgs a;
+  a.A = (const uint16_t*)d->A; a.lda = d->lda; a.wfrag = d->wfrag; a.stfrag = d->stfrag; a.C = d->C; a.ldc = d->ldc; a.R = d->R; a.ldr = d->ldr;
+  a.M = d->M; a.N = d->N; a.K = d->K;
+  if (const char* e = gemm_quant_check(a, d->bits, d->dtype)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "op_%s", e);
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  if (gemm_quant_launch(a, d->bits, d->dtype, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_gemm_quant: launch failed");
+  return MIA_OK;
+}
+
 // fp32 attention, head dim 64, with every mode of attn_f32.hip (test hook): positional keys p with bias_u / bias_v, seq_len, chunk; device
 // pointers, q/k/v [B*T][ld] with head h in columns h*64.., out [B*T][ldo]
 extern "C" int mia_op_attention_f32_ex(mia_ctx* ctx, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv,

@@ -104,3 +104,17 @@ int skinny_gemm_launch(const SkinnyArgs& a, int mode, int dtype, hipStream_t s);
 // tests/test_skinny_gpu.py asserts the derived bound only across the boundary for those, and bit-equality of rows everywhere else.
 // (form rule restated in tests/_skinny_cases.py: dispatch_q)
 int skinny_gemm_q_launch(const SkinnyArgs& a, const uint32_t* wfrag, const float* stfrag, int bits, int mode, int dtype, hipStream_t s, int M_cap = 0);
+
+// ---- the many-row form on the same packed arrays (gemm_quant.hip): the LM's batched prompt pass on packed weights -----------------
+// C[M][N] fp32 = A[M][K] (16 bit, row stride lda) . Wq^T (+ R[M][N] fp32; R may alias C), wfrag / stfrag exactly as skinny_gemm_q_launch
+// reads them.  Any M, N >= 1, K % 128 == 0, lda % 8 == 0; no bias, no K split: a row's result depends on its own A row alone, whatever M.
+struct GemmQuantArgs {
+  const uint16_t* A = nullptr; int64_t lda = 0;
+  const uint32_t* wfrag = nullptr; const float* stfrag = nullptr;
+  float* C = nullptr; int64_t ldc = 0;
+  const float* R = nullptr; int64_t ldr = 0;
+  int M = 0, N = 0, K = 0;
+};
+// nullptr when the arguments satisfy the kernel's shape / alignment assumptions, else a message
+const char* gemm_quant_check(const GemmQuantArgs& a, int bits, int dtype);
+int gemm_quant_launch(const GemmQuantArgs& a, int bits, int dtype, hipStream_t s);

@@ -54,6 +54,22 @@ class CausalLM:
         lib = self.ctx.lib
         self.ctx.check(lib.mia_lm_use_q4(self.h, 1 if on else 0))
 
+    def set_prompt_weights(self, packed: bool) -> None:
+        """mia_lm_set_prompt_weights: the batched prompt pass on the attached packed weights (True) or on the 16-bit copy (False, the
+        default).  True needs attach_q4 first."""
+        self.ctx.check(self.ctx.lib.mia_lm_set_prompt_weights(self.h, 1 if packed else 0))
+
+    def release_dense(self) -> None:
+        """mia_lm_release_dense: step and prompt pass on the packed weights, then free the layers' 16-bit Linears.  Not reversible:
+        use_q4(False) and set_prompt_weights(False) raise ERR_UNSUPPORTED afterwards."""
+        self.ctx.check(self.ctx.lib.mia_lm_release_dense(self.h))
+
+    def weight_bytes(self) -> tuple[int, int]:
+        """mia_lm_weight_bytes: (dense, packed) device bytes of weight matrices the handle holds now."""
+        d, q = C.c_int64(0), C.c_int64(0)
+        self.ctx.check(self.ctx.lib.mia_lm_weight_bytes(self.h, C.byref(d), C.byref(q)))
+        return int(d.value), int(q.value)
+
     def close(self):
         if self.h and getattr(self.ctx, 'h', None):
             self.ctx.lib.mia_lm_free(self.h)
@@ -355,8 +371,10 @@ class OrpheusTTS:
     """generateChunk (TTS/Orpheus/TTSEngine/OrpheusTTS.swift:224-373) from token ids onward: LM sampling loop ->
     parseOutput -> SNAC decode.  Text tokenisation / voice prefix / sentence splitting stay with the caller (CPU text code)."""
 
-    def __init__(self, lm: CausalLM, snac, kv_bits: int | None = None):
+    def __init__(self, lm: CausalLM, snac, kv_bits: int | None = None, packed_prompt: bool | None = None):
         self.lm, self.snac = lm, snac
+        if packed_prompt is not None:                # the prompt pass on the attached packed weights (CausalLM.set_prompt_weights); None leaves the handle's mode alone
+            lm.set_prompt_weights(packed_prompt)
         if kv_bits is not None:                      # newCache(quantized: kv_bits != 0, bits: kv_bits); None leaves the handle's mode alone
             lm.new_cache(quantized=kv_bits != 0, bits=kv_bits or 4)
 

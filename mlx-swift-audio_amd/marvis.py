@@ -202,6 +202,15 @@ class MarvisModel:
         """mia_marvis_use_packed: the frame reads the attached packed weights (True) or the 16-bit copy (False)."""
         self.ctx.check(self.ctx.lib.mia_marvis_use_packed(self.h, 1 if on else 0))
 
+    def use_packed_prompt(self, on: bool) -> None:
+        """mia_marvis_use_packed_prompt: the backbone's prompt pass on the attached packed weights (True) or the 16-bit copy (False)."""
+        self.ctx.check(self.ctx.lib.mia_marvis_use_packed_prompt(self.h, 1 if on else 0))
+
+    def release_dense(self) -> None:
+        """mia_marvis_release_dense: frame and prompt pass on the packed weights, then free both stacks' 16-bit layer Linears.  Not
+        reversible: use_packed(False) and use_packed_prompt(False) raise ERR_UNSUPPORTED afterwards."""
+        self.ctx.check(self.ctx.lib.mia_marvis_release_dense(self.h))
+
     def codebooks(self, max_codebooks: int) -> int:
         return min(self.cfg.n_codebooks, max_codebooks)
 

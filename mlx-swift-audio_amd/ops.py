@@ -334,3 +334,15 @@ def skinny_gemm(ctx: _lib.Context, **d) -> None:
         else:
             setattr(desc, name, {"S": 1, "rs_scale": 1.0}.get(name, 0) if v is None else v)
     _run(ctx, lambda: lib.mia_op_skinny_gemm(ctx.h, C.byref(desc)))
+
+
+def gemm_quant(ctx: _lib.Context, A, wfrag, stfrag, bits: int, C_out, M: int, N: int, K: int, dtype: int, R=None, lda=None, ldc=None, ldr=None) -> None:
+    """mia_op_gemm_quant: C_out fp32 [M][ldc] = A [M][lda] . Wq^T (+ R), the packed prompt pass's GEMM (csrc/gemm_quant.hip) on torch
+    device tensors; wfrag / stfrag as quant_repack builds them.  Strides default to the row strides of two-dimensional tensors; R may be
+    C_out itself.  Written in place."""
+    from ._abi import GemmQuantDesc
+    for t in (A, wfrag, stfrag, C_out, R):
+        assert t is None or t.is_cuda, "device tensors only"
+    desc = GemmQuantDesc(_ptr(A), _ld(A, lda), _ptr(wfrag), _ptr(stfrag), int(bits), _ptr(C_out), _ld(C_out, ldc), _ptr(R),
+                         _ld(R, ldr) if R is not None else 0, int(M), int(N), int(K), int(dtype))
+    _run(ctx, lambda: ctx.lib.mia_op_gemm_quant(ctx.h, C.byref(desc)))

@@ -242,13 +242,17 @@ class OuteTTS:
     of lm_sample_top_p.hip with OuteTTS's parameters (penalty 1.1 over the last 64 generated ids, top-p keeping the first token that crosses p).
     The reference divides by the temperature before the penalty, the kernel after: the same function in real arithmetic, one fp32 rounding
     apart.  The prompt repeats the whole speaker profile for every sentence (:327-340, about 1 900 ids for the bundled profile), so the
-    constructor puts the handle's prompt pass on the tiled attention kernel; prompt_attention=None leaves the handle's mode alone."""
+    constructor puts the handle's prompt pass on the tiled attention kernel; prompt_attention=None leaves the handle's mode alone.
+    packed_prompt (True / False) forwards to CausalLM.set_prompt_weights -- the prompt pass on the attached packed weights -- and None,
+    the default, leaves the handle's mode alone."""
 
     def __init__(self, lm, dac, processor: OuteTTSPromptProcessor, eos_id: int, default_speaker: SpeakerProfile | None = None,
-                 prompt_attention: int | None = 1):
+                 prompt_attention: int | None = 1, packed_prompt: bool | None = None):
         self.lm, self.dac, self.processor, self.eos_id, self.default_speaker = lm, dac, processor, int(eos_id), default_speaker
         if prompt_attention is not None:
             lm.set_prompt_attention(prompt_attention)
+        if packed_prompt is not None:
+            lm.set_prompt_weights(packed_prompt)
 
     def get_speaker(self, reference_audio, reference_text: str, reference_words, processor: "OuteTTSAudioProcessor | None" = None) -> SpeakerProfile:
         """getSpeaker (OuteTTS.swift): a profile from a 24 kHz clip, its text and its [(word, start, end)] list."""

@@ -18,6 +18,13 @@ WORDS equal words, on the dac_speech shape with random-init weights.  Per stage 
 clip, features of the clip and all words in one call -- the median of 5 host-inclusive runs after 2 warm-ups, the feature stage's kernel
 launch count, and the float64 numpy restatement of the feature stage (tests/_outetts_speaker_ref.py) timed once on this host for scale.
 
+--packed-prompt BITS measures the packed prompt pass instead (and nothing else): the layer Linears quantised (group 64, BITS = 4 | 6 | 8;
+the vocabulary head stays 16-bit) and attached to a handle loaded from the de-quantised tensors, then CausalLM.forward of 512, 2 087 and
+4 096 random ids (--lengths changes them) with set_prompt_weights(False) -- the 16-bit prompt pass, what every earlier build ran -- and
+(True) alternated in one process, tiled prompt attention in both: one warm-up of each, then --repeats (>= 7) timed runs each, min /
+median / max in ms; max |delta| / sigma of the last-position logits between the two; weight_bytes() before and after release_dense(),
+and the packed prompt pass once more after the release.
+
 --vocab: the reference reads the vocabulary size from the checkpoint's config.json; the default (128 256, Llama-3.2's) is an assumption."""
 import argparse
 import json
@@ -94,6 +101,56 @@ def speaker(seconds: float, n_words: int, seed: int):
     ctx.close()
 
 
+def packed_prompt(args):
+    from mlx_swift_audio_amd import checkpoint as CK
+    bits, reps = args.packed_prompt, max(7, args.repeats)
+    lengths = [int(x) for x in args.lengths] if args.lengths != [512, 4096] else [512, 2087, 4096]
+    cfg = dataclasses.replace(S.LM_CONFIGS["llama-3.2-1b"], vocab=args.vocab)
+    ctx = m.Context(0)
+    t0 = time.time()
+    dense = S.lm_weights(cfg, seed=args.seed, dtype=np.float16)
+    packed = {}
+    for k in [k for k in dense if k.endswith("_proj.weight")]:
+        q, s, b = CK.quantize_affine(np.asarray(dense[k], np.float32), 64, bits, np.float16)
+        packed[k], packed[k[:-7] + ".scales"], packed[k[:-7] + ".biases"] = q, s, b
+        dense[k] = CK.dequantize_affine(ctx, q, s, b, 64, bits).astype(np.float16)
+    model = HL.CausalLM.load(ctx, cfg, dense, m.BF16)
+    model.attach_q4(packed, bits=bits)
+    model.set_prompt_attention(1)
+    print(f"[outetts] weights generated, quantised, loaded and attached in {time.time() - t0:.1f}s", file=sys.stderr, flush=True)
+    rng = np.random.default_rng(args.seed)
+    res = {"model": "llama-3.2-1b", "vocab": cfg.vocab, "bits": bits, "repeats": reps, "prompt_attention": 1}
+
+    def forward_ms(ids, on):
+        model.set_prompt_weights(on)
+        model.reset()
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        lg = model.forward(ids)                      # synchronises before it returns
+        return (time.perf_counter() - t) * 1e3, lg
+
+    ids_of = {n: rng.integers(0, cfg.vocab, n).tolist() for n in lengths}
+    passes = {}
+    for n in lengths:
+        lg = {on: forward_ms(ids_of[n], on)[1] for on in (False, True)}
+        t = {False: [], True: []}
+        for _ in range(reps):
+            for on in (False, True):
+                t[on].append(forward_ms(ids_of[n], on)[0])
+        passes[str(n)] = {"rows": n, "dense16_ms": spread(t[False]), "packed_ms": spread(t[True]),
+                          "packed_over_dense16_median": round(spread(t[True])["median"] / spread(t[False])["median"], 2),
+                          "logits_max_delta_over_sigma": round(float(np.abs(lg[True] - lg[False]).max() / lg[False].std()), 5)}
+        print(f"[outetts] packed prompt pass {n}: {passes[str(n)]}", file=sys.stderr, flush=True)
+    res["prompt_pass"] = passes
+    res["weight_bytes_before_release"] = dict(zip(("dense", "packed"), model.weight_bytes()))
+    model.release_dense()
+    res["weight_bytes_after_release"] = dict(zip(("dense", "packed"), model.weight_bytes()))
+    res["packed_ms_after_release"] = {str(n): spread([forward_ms(ids_of[n], True)[0] for _ in range(reps)]) for n in lengths}
+    model.close()
+    ctx.close()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--vocab", type=int, default=128256, help="vocabulary size (an assumption: the checkpoint's config.json is not at hand)")
@@ -105,9 +162,12 @@ def main():
     ap.add_argument("--frames", type=int, default=300, help="DAC code frames to decode (75 per second)")
     ap.add_argument("--lengths", type=int, nargs="*", default=[512, 4096])
     ap.add_argument("--speaker", nargs=2, metavar=("SECONDS", "WORDS"), help="measure speaker-profile creation only")
+    ap.add_argument("--packed-prompt", type=int, metavar="BITS", help="measure the prompt pass on packed weights only")
     args = ap.parse_args()
     if args.speaker:
         return speaker(float(args.speaker[0]), int(args.speaker[1]), args.seed)
+    if args.packed_prompt:
+        return packed_prompt(args)
     reps = max(3, args.repeats)
     cfg = dataclasses.replace(S.LM_CONFIGS["llama-3.2-1b"], vocab=args.vocab)
     ctx = m.Context(0)
