@@ -1152,6 +1152,43 @@ int mia_campplus_forward(mia_campplus* m, const float* feats, int n_frames, floa
 /* CAMPPlus.inference (:788-818) for one clip: pcm float32 mono 16 kHz [n_samples] -> emb float32 [192]. */
 int mia_campplus_embed(mia_campplus* m, const float* pcm, int64_t n_samples, float* emb, int mem);
 
+/* ---- Kokoro: iSTFTNet decoder and F0 / N predictor blocks (prosody features + style -> 24 kHz waveform), fp32 -------------------
+ * Replaces KokoroDecoder + Generator (TTS/Kokoro/Decoder/KokoroDecoder.swift:83-112, Generator.swift:133-192) with the harmonic
+ * source (KokoroSineGen.swift, KokoroSourceModuleHnNSF.swift), the STFT pair (MLXSTFT.swift) and, when the tensors are there, the
+ * part of Predictor.F0NTrain behind `shared` (TTSEngine/KokoroModel.swift:66-89).  mia_kokoro_config (include/mia_kokoro.h, included
+ * by the callers that fill one) carries the constructor arguments; pred_dim = 0 means a handle without the F0 / N blocks.
+ * Tensors: float32 under the reference's keys as KokoroWeightLoader.sanitizeWeights leaves them (checkpoint.sanitize_kokoro):
+ * decoder.{encode,decode.N}.{conv1,conv2,conv1x1,pool}.{weight_g,weight_v,bias}, .{norm1,norm2}.fc.{weight,bias},
+ * decoder.{F0_conv,N_conv,asr_res.0}.*, decoder.generator.{ups.N,conv_post}.*, .noise_convs.N.{weight,bias},
+ * .{noise_res,resblocks}.N.{convs1,convs2}.K.*, .{adain1,adain2}.K.fc.*, .{alpha1,alpha2}.K [1][C][1], .m_source.l_linear.*, and
+ * (optional, all or none) predictor.{F0,N}.N.* with predictor.{F0_proj,N_proj}.{weight,bias}.  Weight norm is folded at load
+ * (w = g v / (||v|| + 1e-7) over every axis but 0 of the tensor as stored) and oriented by ConvWeighted's rule
+ * (ConvWeighted.swift:118-122).  A missing tensor is an INVALID_ARGUMENT error that names it.
+ * Channel-major arguments are [C][T], as the reference holds them; `data_mem` describes every buffer of a call (host or device, the HiFT entry points' convention).  Row counts: T in [1, 10000].
+ *   mia_kokoro_output_len: samples of a T-row decode (600 T for the production shape).
+ *   mia_kokoro_f0n: x [pred_dim][T] (the output of Predictor.shared), s_pred [style_dim] -> f0 [2 T], n [2 T].
+ *   mia_kokoro_source: f0 [L] -> source [300 L] (f0 up-sampling, SineGen, l_linear + tanh) and har [60 L + 1][22] (STFT 20 / 5:
+ *     11 magnitudes, then 11 phases; bins 0 and 10 have phase 0 or +pi).  noise float32 [300 L][9] stands in for
+ *     MLXRandom.normal(sineWaves.shape), NULL = none; the random initial phase has no effect on the output and is not an input.
+ *     Either output may be NULL.
+ *   mia_kokoro_generate: Generator.callAsFunction from a given har: x [up_initial][L], s [style_dim], har [60 L + 1][22] -> pcm [300 L].
+ *   mia_kokoro_decode: KokoroDecoder.callAsFunction: asr [dim_in][T], f0 [2 T], n [2 T], s [style_dim], noise as above for
+ *     L = 2 T (nullable) -> pcm [600 T].
+ * Out of scope: ALBERT, TextEncoder, DurationEncoder, the BiLSTMs and the alignment; voice packs; stacked utterances; 16-bit weights. */
+typedef struct mia_kokoro_config mia_kokoro_config;    /* defined in include/mia_kokoro.h */
+typedef struct mia_kokoro mia_kokoro;
+mia_kokoro* mia_kokoro_load(mia_ctx* ctx, const mia_kokoro_config* cfg, const mia_tensor_view* tensors, int n_tensors);
+void mia_kokoro_free(mia_kokoro* h);
+int64_t mia_kokoro_output_len(const mia_kokoro* h, int64_t T);
+int mia_kokoro_f0n(mia_kokoro* h, const float* x, int T, const float* s_pred, float* f0, float* n, int data_mem);
+int mia_kokoro_source(mia_kokoro* h, const float* f0, int L, const float* noise, float* source, float* har, int data_mem);
+int mia_kokoro_generate(mia_kokoro* h, const float* x, int L, const float* s, const float* har, float* pcm, int data_mem);
+int mia_kokoro_decode(mia_kokoro* h, const float* asr, int T, const float* f0, const float* n, const float* s, const float* noise,
+                      float* pcm, int data_mem);
+/* Operator-level hook: per-channel mean and 1 / sqrt(var + 1e-5) over the T rows of a row-major x [T][ld] (population variance, as
+ * MLX.variance gives; T = 1: variance 0).  Deterministic.  Device pointers; mean and rstd are [C]. */
+int mia_op_instance_norm(mia_ctx* ctx, const float* x, int64_t ld, int64_t T, int C, float* mean, float* rstd);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,8 +5,9 @@ host-side mirror of the reference interface.  Import as `mlx_swift_audio_amd` (s
 """
 from . import _lib
 from ._lib import BF16, F16, F32, Context, MiaError
+from .kokoro import KokoroConfig, KokoroDecoder
 from .marvis import MarvisConfig, MarvisModel, MarvisTTS
 from .mimi import MimiCodec, MimiConfig, MimiStream
 
-__all__ = ["_lib", "Context", "MiaError", "F32", "F16", "BF16", "MimiCodec", "MimiConfig", "MimiStream",
+__all__ = ["_lib", "Context", "MiaError", "F32", "F16", "BF16", "KokoroConfig", "KokoroDecoder", "MimiCodec", "MimiConfig", "MimiStream",
            "MarvisConfig", "MarvisModel", "MarvisTTS"]

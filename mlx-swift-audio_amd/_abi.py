@@ -58,6 +58,14 @@ class GemmQuantDesc(C.Structure):
                 ("M", i32), ("N", i32), ("K", i32), ("dtype", i32)]
 
 
+class KokoroConfig(C.Structure):
+    """struct mia_kokoro_config of include/mia_kokoro.h (mia.h only declares the type, so it is not in STRUCTS)."""
+    _fields_ = [("dim_in", i32), ("style_dim", i32), ("hidden", i32), ("asr_res_dim", i32), ("pred_dim", i32),
+                ("up_initial", i32), ("n_ups", i32), ("up_rates", i32 * 4), ("up_kernels", i32 * 4),
+                ("n_res_kernels", i32), ("res_kernels", i32 * 4), ("n_dilations", i32), ("dilations", i32 * 4),
+                ("n_fft", i32), ("hop", i32), ("n_harmonics", i32), ("voiced_threshold", i32), ("sample_rate", i32)]
+
+
 class WhisperDims(C.Structure):
     _fields_ = [("n_mels", i32), ("n_audio_ctx", i32), ("n_audio_state", i32), ("n_audio_head", i32), ("n_audio_layer", i32),
                 ("n_vocab", i32), ("n_text_ctx", i32), ("n_text_state", i32), ("n_text_head", i32), ("n_text_layer", i32)]
@@ -315,6 +323,15 @@ PROTOTYPES = {
     "mia_mimi_encode": (i32, [vp, vp, i64, i32, vp, i64, vp, i32]),
     "mia_mimi_encode_latent": (i32, [vp, vp, i64, vp, i64, vp, i32]),
     "mia_mimi_quantize": (i32, [vp, vp, i64, i32, vp, i32]),
+    # Kokoro decoder and F0 / N predictor blocks
+    "mia_kokoro_load": (vp, [vp, vp, TV, i32]),
+    "mia_kokoro_free": (None, [vp]),
+    "mia_kokoro_output_len": (i64, [vp, i64]),
+    "mia_kokoro_f0n": (i32, [vp, vp, i32, vp, vp, vp, i32]),
+    "mia_kokoro_source": (i32, [vp, vp, i32, vp, vp, vp, i32]),
+    "mia_kokoro_generate": (i32, [vp, vp, i32, vp, vp, vp, i32]),
+    "mia_kokoro_decode": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, i32]),
+    "mia_op_instance_norm": (i32, [vp, vp, i64, i64, i32, vp, vp]),
     # OuteTTS speaker-profile audio
     "mia_speaker_audio_create": (vp, [vp, vp, i64, i32, f32, f32]),
     "mia_speaker_audio_free": (None, [vp]),

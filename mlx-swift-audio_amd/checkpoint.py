@@ -236,3 +236,21 @@ def sanitize_marvis(tensors):
     if not isinstance(tensors, dict):
         return [sanitize_marvis_name(n) for n in tensors]
     return {sanitize_marvis_name(n): v for n, v in tensors.items()}
+
+
+_KOKORO_SCOPE = ("decoder.", "predictor.F0.", "predictor.N.", "predictor.F0_proj.", "predictor.N_proj.")
+
+
+def sanitize_kokoro(tensors):
+    """The decoder / F0 / N branch of KokoroWeightLoader.sanitizeWeights (TTSEngine/KokoroWeightLoader.swift:43-66,85-111) as a rule on
+    shapes: noise_convs / F0_proj / N_proj `.weight` and every three-axis weight_v swap their last two axes ([Cout][Cin][K] of the
+    checkpoint -> [Cout][K][Cin]; `ups`, stored [Cin][Cout][K], becomes [Cin][K][Cout] and `pool` [C][1][3] becomes [C][3][1]);
+    everything else passes.  Keys outside the decoder and the F0 / N predictor blocks are dropped (they belong to the text half)."""
+    out = {}
+    for key, v in tensors.items():
+        if not key.startswith(_KOKORO_SCOPE):
+            continue
+        a = np.asarray(v)
+        swap = a.ndim == 3 and ("weight_v" in key or (key.endswith(".weight") and any(s in key for s in ("noise_convs", "F0_proj", "N_proj"))))
+        out[key] = np.ascontiguousarray(a.transpose(0, 2, 1)) if swap else a
+    return out

@@ -906,3 +906,71 @@ def marvis_weights(cfg, seed: int = 0, round_to: str | None = None, head_scale: 
     rnd("codebook0_head.weight", (V, D), 3.0 * head_scale / math.sqrt(D))
     rnd("audio_head", (K - 1, Dd, V), 3.0 * head_scale / math.sqrt(Dd))
     return w
+
+
+# ---- Kokoro decoder and F0 / N predictor blocks (kokoro.KOKORO_CONFIGS) -------------------------------------------------------------------
+def kokoro_weights(cfg, seed: int = 0, predictor: bool = True) -> dict[str, np.ndarray]:
+    """Random-init tensors of KokoroDecoder (and, with `predictor`, of Predictor.F0 / N / F0_proj / N_proj) under the reference's keys and
+    in the layouts KokoroWeightLoader.sanitizeWeights leaves (TTSEngine/KokoroWeightLoader.swift:43-66,85-111): weight_v [Cout][K][Cin]
+    except `ups` ([Cin][K][Cout]) and `pool` ([C][3][1]).  weight_v is N(0, 1) and weight_g (about the gain, never 1) gives the folded
+    weights the usual fan-in scale; alpha lies in [0.5, 2]; the fc weights keep 1 + gamma positive and away from 1."""
+    w: dict[str, np.ndarray] = {}
+    sd = cfg.style_dim
+
+    def rng(name):
+        return np.random.Generator(np.random.PCG64(_key_seed(name, seed)))
+
+    def t(name, shape, std):
+        w[name] = (rng(name).standard_normal(shape, dtype=np.float32) * np.float32(std)).astype(np.float32)
+
+    def wn(p, shape, gain, bias_n=None):
+        """stored weight_v `shape`; the folded row norm is weight_g = gain (1 +- 10 %)"""
+        t(p + ".weight_v", shape, 1.0)
+        w[p + ".weight_g"] = (gain * (1.0 + 0.1 * rng(p + ".weight_g").standard_normal((shape[0], 1, 1)))).astype(np.float32)
+        if bias_n:
+            t(p + ".bias", (bias_n,), 0.05)
+
+    def fc(p, c):
+        t(p + ".fc.weight", (2 * c, sd), 0.25 / math.sqrt(sd)); t(p + ".fc.bias", (2 * c,), 0.1)
+
+    def blk(p, ci, co, up):
+        wn(p + ".conv1", (co, 3, ci), 1.0, co); wn(p + ".conv2", (co, 3, co), 1.0, co)
+        fc(p + ".norm1", ci); fc(p + ".norm2", co)
+        if ci != co:
+            wn(p + ".conv1x1", (co, 1, ci), 1.0)
+        if up:
+            wn(p + ".pool", (ci, 3, 1), 1.0, ci)
+
+    def resblock(p, c, k):
+        for i in range(3):
+            wn(f"{p}.convs1.{i}", (c, k, c), 1.0, c); wn(f"{p}.convs2.{i}", (c, k, c), 0.4, c)
+            fc(f"{p}.adain1.{i}", c); fc(f"{p}.adain2.{i}", c)
+            for a in ("alpha1", "alpha2"):
+                w[f"{p}.{a}.{i}"] = rng(f"{p}.{a}.{i}").uniform(0.5, 2.0, (1, c, 1)).astype(np.float32)
+
+    D, G = "decoder.", "decoder.generator."
+    cat = cfg.hidden + cfg.asr_res_dim + 2
+    blk(D + "encode", cfg.dim_in + 2, cfg.hidden, False)
+    for i in range(4):
+        blk(f"{D}decode.{i}", cat, cfg.up_initial if i == 3 else cfg.hidden, i == 3)
+    wn(D + "F0_conv", (1, 3, 1), 0.02, 1); wn(D + "N_conv", (1, 3, 1), 1.0, 1)
+    wn(D + "asr_res.0", (cfg.asr_res_dim, 1, cfg.dim_in), 1.0, cfg.asr_res_dim)
+    t(G + "m_source.l_linear.weight", (1, cfg.n_harmonics + 1), 1.0); t(G + "m_source.l_linear.bias", (1,), 0.05)
+    n = len(cfg.up_rates)
+    for i in range(n):
+        ci, co = cfg.up_initial >> i, cfg.up_initial >> (i + 1)
+        k, u = cfg.up_kernels[i], cfg.up_rates[i]
+        wn(f"{G}ups.{i}", (ci, k, co), math.sqrt(co * u / ci)); t(f"{G}ups.{i}.bias", (co,), 0.05)
+        dr = int(np.prod(cfg.up_rates[i + 1:])) if i + 1 < n else 1
+        kk = 1 if i + 1 == n else 2 * dr
+        t(f"{G}noise_convs.{i}.weight", (co, kk, cfg.n_fft + 2), 0.5 / math.sqrt(kk * (cfg.n_fft + 2))); t(f"{G}noise_convs.{i}.bias", (co,), 0.05)
+        resblock(f"{G}noise_res.{i}", co, 11 if i + 1 == n else 7)
+        for j, rk in enumerate(cfg.res_kernels):
+            resblock(f"{G}resblocks.{i * len(cfg.res_kernels) + j}", co, rk)
+    wn(G + "conv_post", (cfg.n_fft + 2, 7, cfg.up_initial >> n), 0.25, cfg.n_fft + 2)
+    if predictor and cfg.pred_dim:
+        P = cfg.pred_dim
+        for name in ("F0", "N"):
+            blk(f"predictor.{name}.0", P, P, False); blk(f"predictor.{name}.1", P, P // 2, True); blk(f"predictor.{name}.2", P // 2, P // 2, False)
+            t(f"predictor.{name}_proj.weight", (1, 1, P // 2), (60.0 if name == "F0" else 1.0) / math.sqrt(P // 2)); t(f"predictor.{name}_proj.bias", (1,), 1.0)
+    return w
