@@ -1174,7 +1174,7 @@ int mia_campplus_embed(mia_campplus* m, const float* pcm, int64_t n_samples, flo
  *   mia_kokoro_generate: Generator.callAsFunction from a given har: x [up_initial][L], s [style_dim], har [60 L + 1][22] -> pcm [300 L].
  *   mia_kokoro_decode: KokoroDecoder.callAsFunction: asr [dim_in][T], f0 [2 T], n [2 T], s [style_dim], noise as above for
  *     L = 2 T (nullable) -> pcm [600 T].
- * Out of scope: ALBERT, TextEncoder, DurationEncoder, the BiLSTMs and the alignment; voice packs; stacked utterances; 16-bit weights. */
+ * Out of scope: voice packs; stacked utterances; 16-bit weights.  The text half behind ALBERT is mia_kokoro_text_* below. */
 typedef struct mia_kokoro_config mia_kokoro_config;    /* defined in include/mia_kokoro.h */
 typedef struct mia_kokoro mia_kokoro;
 mia_kokoro* mia_kokoro_load(mia_ctx* ctx, const mia_kokoro_config* cfg, const mia_tensor_view* tensors, int n_tensors);
@@ -1185,6 +1185,40 @@ int mia_kokoro_source(mia_kokoro* h, const float* f0, int L, const float* noise,
 int mia_kokoro_generate(mia_kokoro* h, const float* x, int L, const float* s, const float* har, float* pcm, int data_mem);
 int mia_kokoro_decode(mia_kokoro* h, const float* asr, int T, const float* f0, const float* n, const float* s, const float* noise,
                       float* pcm, int data_mem);
+/* ---- Kokoro, text half: DurationEncoder, duration head, TextEncoder, alignment and predictor.shared, fp32 -------------------------
+ * A second handle over the same weight dictionary (TTSEngine/{DurationEncoder,TextEncoder,KokoroModel}.swift, KokoroTTS.swift:303-407,
+ * BuildingBlocks/{LSTM,AdaLayerNorm,LayerNormInference}.swift), at B = 1 as the reference runs it, so the masks are no-ops and are not
+ * implemented.  ALBERT and bert_encoder stay with the caller: the chain starts at d_en, their output.  mia_kokoro_text_config
+ * (include/mia_kokoro.h): d_model and style_dim multiples of 32, d_model <= 512, d_model + style_dim <= 1024.
+ * Tensors (float32, sanitised keys): predictor.text_encoder.lstm{0,1,2}.*, .norm{0,1,2}.fc.{weight,bias}, predictor.{lstm,shared}.*,
+ * predictor.duration_proj.{weight [bins][d_model],bias}, text_encoder.embedding.weight [n_symbols][d_model],
+ * text_encoder.cnn.N.conv.{weight_g,weight_v,bias}, .norm.{gamma,beta}, text_encoder.lstm.*; an LSTM's eight tensors are
+ * {weight_ih,weight_hh,bias_ih,bias_hh}_l0 and the same with _reverse.  A missing tensor is an INVALID_ARGUMENT error that names it.
+ * Token-side arguments are time-major [N][C] (N in [1, 512]); what feeds the waveform half is channel-major, as that half takes it.
+ *   mia_kokoro_text_durations: d_en [N][d_model], s_pred [style_dim], speed > 0 -> d_out [N][d_model + style_dim] (DurationEncoder's
+ *     output), dur_out int32 [N] = max(1, rint(sum_bins sigmoid(duration_proj(lstm(d))) / speed)), dur_raw [N] = the value before rint.
+ *   mia_kokoro_text_encode: ids int32 [N] (padded as the reference pads them) -> t_en_out [N][d_model].
+ *   mia_kokoro_text_align: d [N][d_model + style_dim], t_en [N][d_model], dur int32 [N] (>= 0) -> en_out [T][d_model + style_dim]
+ *     (time-major: what _shared takes) and asr_out [d_model][T] (channel-major: what mia_kokoro_decode takes), T = sum(dur): row n is
+ *     copied dur[n] times, bit for bit.  *T holds the row capacity of both outputs on entry and T on return; a sum outside
+ *     [1, min(capacity, 10000)] is an INVALID_ARGUMENT error and nothing is written.  This is the one host read-back of the chain.
+ *   mia_kokoro_text_shared: en [T][d_model + style_dim] -> x_out [d_model][T], predictor.shared's output as mia_kokoro_f0n takes it. */
+typedef struct mia_kokoro_text_config mia_kokoro_text_config;    /* defined in include/mia_kokoro.h */
+typedef struct mia_kokoro_text mia_kokoro_text;
+mia_kokoro_text* mia_kokoro_text_load(mia_ctx* ctx, const mia_kokoro_text_config* cfg, const mia_tensor_view* tensors, int n_tensors);
+void mia_kokoro_text_free(mia_kokoro_text* h);
+int mia_kokoro_text_durations(mia_kokoro_text* h, const float* d_en, int N, const float* s_pred, float speed, float* d_out, int32_t* dur_out,
+                              float* dur_raw, int data_mem);
+int mia_kokoro_text_encode(mia_kokoro_text* h, const int32_t* ids, int N, float* t_en_out, int data_mem);
+int mia_kokoro_text_align(mia_kokoro_text* h, const float* d, const float* t_en, const int32_t* dur, int N, float* en_out, float* asr_out,
+                          int* T, int data_mem);
+int mia_kokoro_text_shared(mia_kokoro_text* h, const float* en, int T, float* x_out, int data_mem);
+/* Operator-level hook: one bidirectional LSTM (BuildingBlocks/LSTM.swift) from zero state on device pointers.  x [T][ldx] (columns
+ * [0, In)), the eight tensors as stored ([4 H][In], [4 H][H], [4 H], [4 H]; forward, then reverse) -> out [T][ldo], columns [0, H)
+ * forward and [H, 2 H) reverse.  H a multiple of 16 up to 256, In a multiple of 32 up to 1024, T in [1, 10000]; rows 16-byte aligned;
+ * x and out must not overlap.  One tap-GEMM launch and T step launches on the context's stream; deterministic. */
+int mia_op_bilstm(mia_ctx* ctx, const float* x, int64_t ldx, int64_t T, int In, int H, const float* w_ih, const float* w_hh, const float* b_ih,
+                  const float* b_hh, const float* w_ih_r, const float* w_hh_r, const float* b_ih_r, const float* b_hh_r, float* out, int64_t ldo);
 /* Operator-level hook: per-channel mean and 1 / sqrt(var + 1e-5) over the T rows of a row-major x [T][ld] (population variance, as
  * MLX.variance gives; T = 1: variance 0).  Deterministic.  Device pointers; mean and rstd are [C]. */
 int mia_op_instance_norm(mia_ctx* ctx, const float* x, int64_t ld, int64_t T, int C, float* mean, float* rstd);

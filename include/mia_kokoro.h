@@ -16,4 +16,10 @@ struct mia_kokoro_config {
   int32_t n_fft, hop, n_harmonics, voiced_threshold, sample_rate;
 };
 
+/* The configuration record of mia_kokoro_text_load: Predictor's dModel (= TextEncoder's channels), the style width, and TextEncoder's
+ * nSymbols, kernelSize and depth (TTSEngine/KokoroModel.swift:109-116).  The ctypes mirror is _abi.KokoroTextConfig. */
+struct mia_kokoro_text_config {
+  int32_t d_model, style_dim, n_symbols, kernel, depth;
+};
+
 #endif

@@ -66,6 +66,11 @@ class KokoroConfig(C.Structure):
                 ("n_fft", i32), ("hop", i32), ("n_harmonics", i32), ("voiced_threshold", i32), ("sample_rate", i32)]
 
 
+class KokoroTextConfig(C.Structure):
+    """struct mia_kokoro_text_config of include/mia_kokoro.h (mia.h only declares the type, so it is not in STRUCTS)."""
+    _fields_ = [("d_model", i32), ("style_dim", i32), ("n_symbols", i32), ("kernel", i32), ("depth", i32)]
+
+
 class WhisperDims(C.Structure):
     _fields_ = [("n_mels", i32), ("n_audio_ctx", i32), ("n_audio_state", i32), ("n_audio_head", i32), ("n_audio_layer", i32),
                 ("n_vocab", i32), ("n_text_ctx", i32), ("n_text_state", i32), ("n_text_head", i32), ("n_text_layer", i32)]
@@ -331,6 +336,14 @@ PROTOTYPES = {
     "mia_kokoro_source": (i32, [vp, vp, i32, vp, vp, vp, i32]),
     "mia_kokoro_generate": (i32, [vp, vp, i32, vp, vp, vp, i32]),
     "mia_kokoro_decode": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, i32]),
+    # Kokoro text half
+    "mia_kokoro_text_load": (vp, [vp, vp, TV, i32]),
+    "mia_kokoro_text_free": (None, [vp]),
+    "mia_kokoro_text_durations": (i32, [vp, vp, i32, vp, f32, vp, vp, vp, i32]),
+    "mia_kokoro_text_encode": (i32, [vp, vp, i32, vp, i32]),
+    "mia_kokoro_text_align": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i32]),
+    "mia_kokoro_text_shared": (i32, [vp, vp, i32, vp, i32]),
+    "mia_op_bilstm": (i32, [vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64]),
     "mia_op_instance_norm": (i32, [vp, vp, i64, i64, i32, vp, vp]),
     # OuteTTS speaker-profile audio
     "mia_speaker_audio_create": (vp, [vp, vp, i64, i32, f32, f32]),

@@ -241,16 +241,30 @@ def sanitize_marvis(tensors):
 _KOKORO_SCOPE = ("decoder.", "predictor.F0.", "predictor.N.", "predictor.F0_proj.", "predictor.N_proj.")
 
 
-def sanitize_kokoro(tensors):
+def sanitize_kokoro_text_name(key: str) -> str:
+    """The renames of KokoroWeightLoader for the text half (:43-53,68-75,113-171): duration_proj.linear_layer.* -> duration_proj.*,
+    predictor.text_encoder.lstms.{0,2,4} -> lstm{0,1,2} and .lstms.{1,3,5} -> norm{0,1,2}, text_encoder.cnn.i.{0,1} -> .conv / .norm."""
+    p = key.replace("duration_proj.linear_layer.", "duration_proj.").split(".")
+    if p[:3] == ["predictor", "text_encoder", "lstms"] and len(p) >= 5 and p[3].isdigit():
+        p[2:4] = [("lstm" if int(p[3]) % 2 == 0 else "norm") + str(int(p[3]) // 2)]
+    elif p[:2] == ["text_encoder", "cnn"] and len(p) >= 5 and p[3] in ("0", "1"):
+        p[3] = "conv" if p[3] == "0" else "norm"
+    return ".".join(p)
+
+
+def sanitize_kokoro(tensors, text: bool = False):
     """The decoder / F0 / N branch of KokoroWeightLoader.sanitizeWeights (TTSEngine/KokoroWeightLoader.swift:43-66,85-111) as a rule on
     shapes: noise_convs / F0_proj / N_proj `.weight` and every three-axis weight_v swap their last two axes ([Cout][Cin][K] of the
     checkpoint -> [Cout][K][Cin]; `ups`, stored [Cin][Cout][K], becomes [Cin][K][Cout] and `pool` [C][1][3] becomes [C][3][1]);
-    everything else passes.  Keys outside the decoder and the F0 / N predictor blocks are dropped (they belong to the text half)."""
+    everything else passes.  Keys outside the decoder and the F0 / N predictor blocks are dropped unless `text` is set: then the rest
+    of `predictor.` and `text_encoder.` (what KokoroText.load takes) is kept too, renamed by sanitize_kokoro_text_name; `bert` stays
+    with the caller."""
+    scope = _KOKORO_SCOPE + (("predictor.", "text_encoder.") if text else ())
     out = {}
     for key, v in tensors.items():
-        if not key.startswith(_KOKORO_SCOPE):
+        if not key.startswith(scope):
             continue
         a = np.asarray(v)
         swap = a.ndim == 3 and ("weight_v" in key or (key.endswith(".weight") and any(s in key for s in ("noise_convs", "F0_proj", "N_proj"))))
-        out[key] = np.ascontiguousarray(a.transpose(0, 2, 1)) if swap else a
+        out[sanitize_kokoro_text_name(key) if text else key] = np.ascontiguousarray(a.transpose(0, 2, 1)) if swap else a
     return out

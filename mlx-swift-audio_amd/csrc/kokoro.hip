@@ -23,18 +23,12 @@
 #include "../../include/mia_kokoro.h"
 #include "codec.h"
 #include "kokoro.h"
+#include "kokoro_load.h"
 #include "mia_internal.h"
 #include "tensor_loader.h"
 
 namespace {
 
-inline int pad32(int c) { return (c + 31) / 32 * 32; }
-
-struct KConv {
-  float* w = nullptr; float* b = nullptr;
-  int N = 0, Cin = 0, taps = 1, dil = 1, pad = 0, stride = 1;   // N, Cin: padded to 32 unless the loader was told to keep N
-  int K = 0;                                                    // transposed conv: kernel size (taps = ceil(K / stride))
-};
 struct KAda { int off = 0, C = 0; };                            // gamma at style[off .. off + C), beta behind it
 struct KBlk {                                                   // AdainResBlk1d
   KConv c1, c2, sc;
@@ -76,57 +70,8 @@ struct mia_kokoro {
 
 namespace {
 
-struct KLoader : TensorLoader {
+struct KLoader : KConvLoader {
   int sd = 0;
-  // weight-normed tensor `p`.weight_v / weight_g, folded, as stored
-  bool folded(const std::string& p, std::vector<float>& w, int64_t d0, int64_t d1, int64_t d2) {
-    std::vector<float> v, g;
-    if (!f32(p + ".weight_v", v, {d0, d1, d2}) || !f32(p + ".weight_g", g, {d0, 1, 1})) return false;
-    const int64_t inner = d1 * d2;
-    w.resize(v.size());
-    for (int64_t i = 0; i < d0; ++i) {
-      float ss = 0.f;
-      for (int64_t k = 0; k < inner; ++k) ss += v[i * inner + k] * v[i * inner + k];
-      const float nrm = std::sqrt(ss) + 1e-7f;
-      for (int64_t k = 0; k < inner; ++k) w[i * inner + k] = v[i * inner + k] / nrm * g[i];
-    }
-    return true;
-  }
-  // the folded weight as [Cout][K][Cin] by ConvWeighted's rule: as stored when the stored last axis is Cin, all axes reversed otherwise
-  bool oriented(const std::string& p, std::vector<float>& w, int Cout, int K, int Cin) {
-    const mia_tensor_view* t = find(p + ".weight_v");
-    if (!t) return fail(MIA_ERR_INVALID_ARGUMENT, "missing tensor '" + p + ".weight_v'");
-    if (t->ndim == 3 && t->shape[2] == Cin) return folded(p, w, Cout, K, Cin);
-    std::vector<float> s;
-    if (!folded(p, s, Cin, K, Cout)) return false;
-    w.resize(s.size());
-    for (int ci = 0; ci < Cin; ++ci) for (int k = 0; k < K; ++k) for (int co = 0; co < Cout; ++co)
-      w[((size_t)co * K + k) * Cin + ci] = s[((size_t)ci * K + k) * Cout + co];
-    return true;
-  }
-  bool bias_of(const std::string& p, bool has, int Cout, int Np, std::vector<float>& b) {
-    b.assign(Np, 0.f);
-    if (!has) return true;
-    std::vector<float> t;
-    if (!f32(p + ".bias", t, {Cout})) return false;
-    std::copy(t.begin(), t.end(), b.begin());
-    return true;
-  }
-  // [Cout][K][Cin] -> tap-GEMM weights [Np][K][Cp], zero rows / columns for the padding
-  void place(const std::vector<float>& w, const std::vector<float>& b, int Cout, int K, int Cin, bool keepN, int dil, int pad, int stride, KConv& o) {
-    const int Cp = pad32(Cin), Np = keepN ? Cout : pad32(Cout);
-    std::vector<float> wp((size_t)Np * K * Cp, 0.f);
-    for (int co = 0; co < Cout; ++co) for (int k = 0; k < K; ++k) for (int ci = 0; ci < Cin; ++ci)
-      wp[((size_t)co * K + k) * Cp + ci] = w[((size_t)co * K + k) * Cin + ci];
-    std::vector<float> bp(b); bp.resize(Np, 0.f);
-    o.w = up(wp); o.b = up(bp); o.N = Np; o.Cin = Cp; o.taps = K; o.dil = dil; o.pad = pad; o.stride = stride;
-  }
-  bool conv_wn(const std::string& p, int Cout, int K, int Cin, int dil, int pad, bool has_bias, bool keepN, KConv& o) {
-    std::vector<float> w, b;
-    if (!oriented(p, w, Cout, K, Cin) || !bias_of(p, has_bias, Cout, Cout, b)) return false;
-    place(w, b, Cout, K, Cin, keepN, dil, pad, 1, o);
-    return true;
-  }
   // Conv1dInference: plain weight [Cout][K][Cin] + bias
   bool conv_plain(const std::string& p, int Cout, int K, int Cin, int pad, int stride, bool keepN, KConv& o) {
     std::vector<float> w, b;
@@ -238,14 +183,8 @@ int carve(mia_kokoro* h, int64_t T, int64_t L, Scratch& sc) {
 }
 
 // ---- launches ------------------------------------------------------------------------------------------------------------------------------
-struct COpt { const float* R = nullptr; int64_t ldr = 0; const float* R2 = nullptr; float scale = 0.f; float lrelu = 0.f; int64_t ldy = 0; };
-
 int run_conv(mia_kokoro* h, const KConv& c, const float* X, int64_t T_in, float* Y, int64_t T_out, const COpt& o = COpt()) {
-  ConvGemmArgs g;
-  g.X = X; g.ldx = c.Cin; g.T_in = (int)T_in; g.W = c.w; g.bias = c.b; g.lrelu_slope = o.lrelu;
-  g.Y = Y; g.ldy = o.ldy ? o.ldy : c.N; g.T_out = (int)T_out; g.R = o.R; g.R2 = o.R2; g.ldr = o.ldr ? o.ldr : c.N; g.out_scale = o.scale;
-  g.M = (int)T_out; g.N = c.N; g.Cin = c.Cin; g.taps = c.taps; g.dil = c.dil; g.pad = c.pad; g.x_row_mul = c.stride;
-  return codec_conv_gemm_run(h->ctx, g, 1, "kokoro");
+  return kconv_run(h->ctx, c, X, T_in, Y, T_out, o);
 }
 
 // k = 1 convolution on T rows, every row written twice (rows 2 t and 2 t + 1): the nearest x 2 up-sampling of the shortcut commutes with it

@@ -1,7 +1,9 @@
-"""Host-side mirror of Kokoro's waveform half (TTS/Kokoro), backed by the gfx950 HIP layer: KokoroDecoder.callAsFunction
+"""Host-side mirror of Kokoro (TTS/Kokoro), backed by the gfx950 HIP layer.  Waveform half (KokoroDecoder): KokoroDecoder.callAsFunction
 (Decoder/KokoroDecoder.swift:83-112) with its Generator (Decoder/Generator.swift:133-192), and the F0 / N blocks of
-Predictor.F0NTrain behind `shared` (TTSEngine/KokoroModel.swift:66-89).  No arithmetic happens in Python.  Text to phoneme ids, ALBERT,
-the text encoder, the BiLSTMs and the alignment stay with the caller ("Kokoro")."""
+Predictor.F0NTrain behind `shared` (TTSEngine/KokoroModel.swift:66-89).  Text half (KokoroText): DurationEncoder, predictor.lstm and the
+duration head, TextEncoder, the alignment and predictor.shared (KokoroTTS.swift:303-407).  KokoroPipeline chains the two from d_en (the
+output of bert_encoder) to PCM.  No arithmetic happens in Python.  Text to phoneme ids, ALBERT and the voice packs stay with the caller
+("Kokoro")."""
 from __future__ import annotations
 
 import ctypes as C
@@ -10,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._abi import KokoroConfig as _CConfig, tensor_views
+from ._abi import KokoroConfig as _CConfig, KokoroTextConfig as _CTextConfig, tensor_views
 
 
 @dataclass(frozen=True)
@@ -31,6 +33,10 @@ class KokoroConfig:
     n_harmonics: int = 8
     voiced_threshold: int = 10
     sample_rate: int = 24000
+    d_model: int = 512                 # text half: Predictor's dModel = TextEncoder's channels (= dim_in = pred_dim)
+    n_symbols: int = 178
+    text_kernel: int = 5
+    text_depth: int = 3
 
     @property
     def upsample_scale(self) -> int:
@@ -39,7 +45,8 @@ class KokoroConfig:
 
 
 KOKORO_CONFIGS = {"kokoro_82m": KokoroConfig(),
-                  "kokoro_micro": KokoroConfig(dim_in=64, style_dim=32, hidden=96, asr_res_dim=32, pred_dim=64, up_initial=64)}
+                  "kokoro_micro": KokoroConfig(dim_in=64, style_dim=32, hidden=96, asr_res_dim=32, pred_dim=64, up_initial=64,
+                                               d_model=64, n_symbols=24)}
 
 
 def _pad4(v):
@@ -166,3 +173,161 @@ def instance_norm(ctx: _lib.Context, x: np.ndarray, ld: int | None = None):
     ctx.check(ctx.lib.mia_op_instance_norm(ctx.h, d.data_ptr(), ld, T, Cn, mean.data_ptr(), rstd.data_ptr()))
     ctx.synchronize()
     return mean.cpu().numpy(), rstd.cpu().numpy()
+
+
+LSTM_KEYS = tuple(f"{t}_l0{d}" for d in ("", "_reverse") for t in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+
+
+def bilstm(ctx: _lib.Context, x: np.ndarray, weights: dict[str, np.ndarray]):
+    """mia_op_bilstm on a host array x [T, In] (staged through device memory) with the eight tensors of one BiLSTM under LSTM_KEYS:
+    -> [T, 2 H], forward | reverse."""
+    import torch
+    x = np.ascontiguousarray(x, np.float32)
+    T, In = x.shape
+    H = int(np.asarray(weights["weight_hh_l0"]).shape[-1])
+    dev = torch.device("cuda", ctx.device)
+    w = [torch.from_numpy(np.ascontiguousarray(weights[k], np.float32)).to(dev) for k in LSTM_KEYS]
+    d = torch.from_numpy(x).to(dev)
+    out = torch.empty((T, 2 * H), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)
+    ctx.check(ctx.lib.mia_op_bilstm(ctx.h, d.data_ptr(), In, T, In, H, *[t.data_ptr() for t in w], out.data_ptr(), 2 * H))
+    ctx.synchronize()
+    return out.cpu().numpy()
+
+
+class KokoroText:
+    """The text half behind ALBERT.  Token-side arrays are time-major [N, C]; `asr` and the output of `shared` are channel-major, as
+    KokoroDecoder takes them."""
+
+    def __init__(self, ctx, h, cfg):
+        self.ctx, self.h, self.cfg = ctx, h, cfg
+        ctx.adopt(self)
+
+    @staticmethod
+    def load(ctx: _lib.Context, cfg: KokoroConfig, weights: dict[str, np.ndarray]) -> "KokoroText":
+        """weights: float32 under the reference's sanitised keys (checkpoint.sanitize_kokoro(raw, text=True))."""
+        c = _CTextConfig(cfg.d_model, cfg.style_dim, cfg.n_symbols, cfg.text_kernel, cfg.text_depth)
+        views, n, keep = tensor_views(weights)
+        h = ctx.lib.mia_kokoro_text_load(ctx.h, C.byref(c), views, n)
+        if not h:
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
+        return KokoroText(ctx, h, cfg)
+
+    def close(self):
+        if self.h and getattr(self.ctx, "h", None):
+            self.ctx.lib.mia_kokoro_text_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def width(self) -> int:
+        return self.cfg.d_model + self.cfg.style_dim
+
+    def durations(self, d_en, s_pred, speed: float = 1.0):
+        """d_en [N, d_model], s_pred [style_dim] -> (d [N, d_model + style_dim], durations int32 [N], their value before rounding [N])."""
+        x = np.ascontiguousarray(d_en, np.float32)
+        if x.ndim != 2 or x.shape[1] != self.cfg.d_model:
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, f"Kokoro: d_en must be [N, {self.cfg.d_model}]")
+        N = x.shape[0]
+        s = _f32(s_pred, (self.cfg.style_dim,), "s_pred")
+        d = np.empty((N, self.width), np.float32)
+        dur = np.empty(max(N, 1), np.int32)
+        raw = np.empty(max(N, 1), np.float32)
+        self.ctx.check(self.ctx.lib.mia_kokoro_text_durations(self.h, x.ctypes.data, N, s.ctypes.data, float(speed), d.ctypes.data,
+                                                              dur.ctypes.data, raw.ctypes.data, _lib.MEM_HOST))
+        return d, dur[:N], raw[:N]
+
+    def encode(self, ids):
+        """ids [N] (padded as the reference pads them) -> t_en [N, d_model]."""
+        i = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        out = np.empty((i.shape[0], self.cfg.d_model), np.float32)
+        self.ctx.check(self.ctx.lib.mia_kokoro_text_encode(self.h, i.ctypes.data, i.shape[0], out.ctypes.data, _lib.MEM_HOST))
+        return out
+
+    def align(self, d, t_en, dur):
+        """d [N, d_model + style_dim], t_en [N, d_model], durations [N] -> (en [T, d_model + style_dim], asr [d_model, T]), T = sum."""
+        dur = np.ascontiguousarray(dur, np.int32).reshape(-1)
+        N = dur.shape[0]
+        d = _f32(d, (N, self.width), "d")
+        t = _f32(t_en, (N, self.cfg.d_model), "t_en")
+        cap = int(min(max(int(dur.astype(np.int64).sum()), 1), 10001))
+        en = np.empty((cap, self.width), np.float32)
+        asr = np.empty(cap * self.cfg.d_model, np.float32)
+        T = C.c_int(cap)
+        self.ctx.check(self.ctx.lib.mia_kokoro_text_align(self.h, d.ctypes.data, t.ctypes.data, dur.ctypes.data, N, en.ctypes.data,
+                                                          asr.ctypes.data, C.byref(T), _lib.MEM_HOST))
+        return en[:T.value], asr[:T.value * self.cfg.d_model].reshape(self.cfg.d_model, T.value)
+
+    def shared(self, en):
+        """en [T, d_model + style_dim] -> predictor.shared's output [d_model, T], what KokoroDecoder.f0n takes."""
+        e = np.ascontiguousarray(en, np.float32)
+        if e.ndim != 2 or e.shape[1] != self.width:
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, f"Kokoro: en must be [T, {self.width}]")
+        T = e.shape[0]
+        x = np.empty((self.cfg.d_model, max(T, 1)), np.float32)
+        self.ctx.check(self.ctx.lib.mia_kokoro_text_shared(self.h, e.ctypes.data, T, x.ctypes.data, _lib.MEM_HOST))
+        return x
+
+
+class KokoroPipeline:
+    """generateAudioForTokens from line 303 on (KokoroTTS.swift:303-415): d_en, the padded ids and a voice-pack row to PCM.  Activations
+    stay on the device between the stages; only the durations (and their sum) come back to the host.  The device buffers are torch
+    tensors, so `torch` must be imported before the context is created (as for every hook here that takes device tensors)."""
+
+    def __init__(self, text: KokoroText, decoder: KokoroDecoder):
+        cfg = text.cfg
+        if text.ctx is not decoder.ctx or (cfg.d_model, cfg.d_model, cfg.style_dim) != (decoder.cfg.dim_in, decoder.cfg.pred_dim, decoder.cfg.style_dim):
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, "Kokoro: the two halves must share a context, d_model = dim_in = pred_dim and style_dim")
+        self.text, self.decoder, self.ctx, self.cfg = text, decoder, text.ctx, cfg
+        self.last_durations = None
+
+    def synthesize(self, d_en, ids, voice_row, speed: float = 1.0, noise=None, durations=None):
+        """d_en [N, d_model], ids [N], voice_row [2 style_dim] (decoder style | predictor style) -> waveform [600 T].  `durations`
+        [N] forces the alignment; `noise` [600 T, n_harmonics + 1] stands in for the source's random draw."""
+        import torch
+        cfg, ctx, lib, DEV = self.cfg, self.ctx, self.ctx.lib, _lib.MEM_DEVICE
+        D, S = cfg.d_model, cfg.style_dim
+        x = np.ascontiguousarray(d_en, np.float32)
+        i = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        N = i.shape[0]
+        if x.shape != (N, D) or i.min(initial=0) < 0 or i.max(initial=0) >= cfg.n_symbols:
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, f"Kokoro: d_en must be [N, {D}] and ids [N] inside the symbol table")
+        v = _f32(voice_row, (2 * S,), "voice_row")
+        dev = torch.device("cuda", ctx.device)
+
+        def up(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+        def new(*shape, dtype=torch.float32):
+            return torch.empty(shape, dtype=dtype, device=dev)
+
+        dx, di, s_dec, s_pred = up(x), up(i), up(v[:S]), up(v[S:])
+        d, predicted, raw, t_en = new(N, D + S), new(N, dtype=torch.int32), new(N), new(N, D)
+        dur = predicted if durations is None else up(np.ascontiguousarray(durations, np.int32).reshape(N))     # forced: d is still needed
+        torch.cuda.synchronize(dev)
+        ctx.check(lib.mia_kokoro_text_durations(self.text.h, dx.data_ptr(), N, s_pred.data_ptr(), float(speed), d.data_ptr(),
+                                                predicted.data_ptr(), raw.data_ptr(), DEV))
+        ctx.check(lib.mia_kokoro_text_encode(self.text.h, di.data_ptr(), N, t_en.data_ptr(), DEV))
+        ctx.synchronize()
+        self.last_durations = dur.cpu().numpy()
+        T = int(self.last_durations.astype(np.int64).sum())
+        if T < 1 or T > 10000:
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, f"Kokoro: the durations sum to {T} rows, outside [1, 10000]")
+        nz = up(self.decoder._noise(noise, 2 * T)) if noise is not None else None
+        en, asr, xs, f0, n = new(T, D + S), new(D, T), new(D, T), new(2 * T), new(2 * T)
+        pcm = new(self.decoder.output_len(T))
+        torch.cuda.synchronize(dev)
+        Tc = C.c_int(T)
+        ctx.check(lib.mia_kokoro_text_align(self.text.h, d.data_ptr(), t_en.data_ptr(), dur.data_ptr(), N, en.data_ptr(), asr.data_ptr(),
+                                            C.byref(Tc), DEV))
+        ctx.check(lib.mia_kokoro_text_shared(self.text.h, en.data_ptr(), T, xs.data_ptr(), DEV))
+        ctx.check(lib.mia_kokoro_f0n(self.decoder.h, xs.data_ptr(), T, s_pred.data_ptr(), f0.data_ptr(), n.data_ptr(), DEV))
+        ctx.check(lib.mia_kokoro_decode(self.decoder.h, asr.data_ptr(), T, f0.data_ptr(), n.data_ptr(), s_dec.data_ptr(),
+                                        nz.data_ptr() if nz is not None else None, pcm.data_ptr(), DEV))
+        ctx.synchronize()
+        return pcm.cpu().numpy()

@@ -909,11 +909,13 @@ def marvis_weights(cfg, seed: int = 0, round_to: str | None = None, head_scale: 
 
 
 # ---- Kokoro decoder and F0 / N predictor blocks (kokoro.KOKORO_CONFIGS) -------------------------------------------------------------------
-def kokoro_weights(cfg, seed: int = 0, predictor: bool = True) -> dict[str, np.ndarray]:
+def kokoro_weights(cfg, seed: int = 0, predictor: bool = True, text: bool = False) -> dict[str, np.ndarray]:
     """Random-init tensors of KokoroDecoder (and, with `predictor`, of Predictor.F0 / N / F0_proj / N_proj) under the reference's keys and
     in the layouts KokoroWeightLoader.sanitizeWeights leaves (TTSEngine/KokoroWeightLoader.swift:43-66,85-111): weight_v [Cout][K][Cin]
     except `ups` ([Cin][K][Cout]) and `pool` ([C][3][1]).  weight_v is N(0, 1) and weight_g (about the gain, never 1) gives the folded
-    weights the usual fan-in scale; alpha lies in [0.5, 2]; the fc weights keep 1 + gamma positive and away from 1."""
+    weights the usual fan-in scale; alpha lies in [0.5, 2]; the fc weights keep 1 + gamma positive and away from 1.  `text` adds the text
+    half (DurationEncoder, predictor.lstm / shared / duration_proj, TextEncoder) under the sanitised keys; LSTM weights scale as
+    1 / sqrt(H), so the gates do not saturate, and duration_proj has 50 bins as the checkpoint does."""
     w: dict[str, np.ndarray] = {}
     sd = cfg.style_dim
 
@@ -973,4 +975,24 @@ def kokoro_weights(cfg, seed: int = 0, predictor: bool = True) -> dict[str, np.n
         for name in ("F0", "N"):
             blk(f"predictor.{name}.0", P, P, False); blk(f"predictor.{name}.1", P, P // 2, True); blk(f"predictor.{name}.2", P // 2, P // 2, False)
             t(f"predictor.{name}_proj.weight", (1, 1, P // 2), (60.0 if name == "F0" else 1.0) / math.sqrt(P // 2)); t(f"predictor.{name}_proj.bias", (1,), 1.0)
+    if text:
+        Dm, Hh = cfg.d_model, cfg.d_model // 2
+
+        def lstm(p, n_in):
+            for d in ("", "_reverse"):
+                t(f"{p}.weight_ih_l0{d}", (4 * Hh, n_in), 1.0 / math.sqrt(n_in)); t(f"{p}.weight_hh_l0{d}", (4 * Hh, Hh), 1.0 / math.sqrt(Hh))
+                t(f"{p}.bias_ih_l0{d}", (4 * Hh,), 0.1); t(f"{p}.bias_hh_l0{d}", (4 * Hh,), 0.1)
+
+        for i in range(3):
+            lstm(f"predictor.text_encoder.lstm{i}", Dm + sd)
+            t(f"predictor.text_encoder.norm{i}.fc.weight", (2 * Dm, sd), 0.25 / math.sqrt(sd)); t(f"predictor.text_encoder.norm{i}.fc.bias", (2 * Dm,), 0.1)
+        lstm("predictor.lstm", Dm + sd); lstm("predictor.shared", Dm + sd)
+        t("predictor.duration_proj.weight", (50, Dm), 6.0 / math.sqrt(Dm))          # durations of a few frames that differ between tokens
+        w["predictor.duration_proj.bias"] = (rng("predictor.duration_proj.bias").standard_normal(50) - 2.0).astype(np.float32)
+        t("text_encoder.embedding.weight", (cfg.n_symbols, Dm), 1.0)
+        for i in range(cfg.text_depth):
+            wn(f"text_encoder.cnn.{i}.conv", (Dm, cfg.text_kernel, Dm), 1.0, Dm)
+            w[f"text_encoder.cnn.{i}.norm.gamma"] = (1.0 + 0.1 * rng(f"text_encoder.cnn.{i}.norm.gamma").standard_normal(Dm)).astype(np.float32)
+            t(f"text_encoder.cnn.{i}.norm.beta", (Dm,), 0.1)
+        lstm("text_encoder.lstm", Dm)
     return w

@@ -5,6 +5,10 @@ decode - source - generate.  The generator's stages carry no timers of their own
 materialised form only, so there is no fused / materialised comparison to report.
 
     python tools/bench_kokoro.py [--T 400] [--config kokoro_82m] [--repeat 7]
+
+--text times the text half instead (N tokens, default 100, durations forced to sum to T): ms for durations, encode, align, shared and
+the whole KokoroPipeline.synthesize beside decode alone, and the per-step cost of the recurrent kernel as `shared` ms / T (its input
+projection included) against the 1.5 us floor of a dependent launch.
 """
 import argparse
 import json
@@ -33,7 +37,11 @@ def main():
     ap.add_argument("--T", type=int, default=400)
     ap.add_argument("--config", default="kokoro_82m")
     ap.add_argument("--repeat", type=int, default=7)
+    ap.add_argument("--text", action="store_true")
+    ap.add_argument("--N", type=int, default=100)
     a = ap.parse_args()
+    if a.text:
+        return text_main(a)
     import mlx_swift_audio_amd as m
     from mlx_swift_audio_amd import synthetic
     from mlx_swift_audio_amd.kokoro import KOKORO_CONFIGS, KokoroDecoder
@@ -59,6 +67,43 @@ def main():
     print(json.dumps({"config": a.config, "T": T, "audio_s": audio_s, "ms": {k: round(v, 3) for k, v in ms.items()},
                       "x_real_time": round(audio_s / (ms["decode"] * 1e-3), 1), "adain": "materialised"}))
     model.close()
+    ctx.close()
+
+
+def text_main(a):
+    import torch  # noqa: F401  (before the HIP library loads: the pipeline holds its device buffers as torch tensors)
+
+    import mlx_swift_audio_amd as m
+    from mlx_swift_audio_amd import synthetic
+    from mlx_swift_audio_amd.kokoro import KOKORO_CONFIGS, KokoroDecoder, KokoroPipeline, KokoroText
+    cfg = KOKORO_CONFIGS[a.config]
+    ctx = m.Context(0)
+    w = synthetic.kokoro_weights(cfg, 2, text=True)
+    text, dec = KokoroText.load(ctx, cfg, w), KokoroDecoder.load(ctx, cfg, w)
+    rng = np.random.default_rng(0)
+    N, T = a.N, a.T
+    d_en = rng.standard_normal((N, cfg.d_model)).astype(np.float32)
+    ids = rng.integers(0, cfg.n_symbols, N).astype(np.int32)
+    voice = rng.standard_normal(2 * cfg.style_dim).astype(np.float32)
+    s_dec, s_pred = voice[:cfg.style_dim], voice[cfg.style_dim:]
+    dur = np.full(N, T // N, np.int32)
+    dur[:T - int(dur.sum())] += 1
+    noise = rng.standard_normal((2 * T * cfg.upsample_scale, cfg.n_harmonics + 1)).astype(np.float32)
+    d, _, _ = text.durations(d_en, s_pred)
+    t_en = text.encode(ids)
+    en, asr = text.align(d, t_en, dur)
+    f0, n = dec.f0n(text.shared(en), s_pred)
+    pipe = KokoroPipeline(text, dec)
+    ms = {"durations": _median_ms(lambda: text.durations(d_en, s_pred), a.repeat),
+          "encode": _median_ms(lambda: text.encode(ids), a.repeat),
+          "align": _median_ms(lambda: text.align(d, t_en, dur), a.repeat),
+          "shared": _median_ms(lambda: text.shared(en), a.repeat),
+          "synthesize": _median_ms(lambda: pipe.synthesize(d_en, ids, voice, noise=noise, durations=dur), a.repeat),
+          "decode": _median_ms(lambda: dec.decode(asr, f0, n, s_dec, noise), a.repeat)}
+    print(json.dumps({"config": a.config, "N": N, "T": T, "ms": {k: round(v, 3) for k, v in ms.items()},
+                      "lstm_step_us": round(ms["shared"] * 1e3 / T, 2), "launch_floor_us": 1.5, "persistent_lstm": "not built"}))
+    for h in (text, dec):
+        h.close()
     ctx.close()
 
 
