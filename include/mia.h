@@ -1174,7 +1174,8 @@ int mia_campplus_embed(mia_campplus* m, const float* pcm, int64_t n_samples, flo
  *   mia_kokoro_generate: Generator.callAsFunction from a given har: x [up_initial][L], s [style_dim], har [60 L + 1][22] -> pcm [300 L].
  *   mia_kokoro_decode: KokoroDecoder.callAsFunction: asr [dim_in][T], f0 [2 T], n [2 T], s [style_dim], noise as above for
  *     L = 2 T (nullable) -> pcm [600 T].
- * Out of scope: voice packs; stacked utterances; 16-bit weights.  The text half behind ALBERT is mia_kokoro_text_* below. */
+ * Out of scope: voice-pack files; stacked utterances; 16-bit weights.  The text half behind ALBERT is mia_kokoro_text_* below, ALBERT
+ * and bert_encoder are mia_kokoro_bert_* behind that. */
 typedef struct mia_kokoro_config mia_kokoro_config;    /* defined in include/mia_kokoro.h */
 typedef struct mia_kokoro mia_kokoro;
 mia_kokoro* mia_kokoro_load(mia_ctx* ctx, const mia_kokoro_config* cfg, const mia_tensor_view* tensors, int n_tensors);
@@ -1188,7 +1189,7 @@ int mia_kokoro_decode(mia_kokoro* h, const float* asr, int T, const float* f0, c
 /* ---- Kokoro, text half: DurationEncoder, duration head, TextEncoder, alignment and predictor.shared, fp32 -------------------------
  * A second handle over the same weight dictionary (TTSEngine/{DurationEncoder,TextEncoder,KokoroModel}.swift, KokoroTTS.swift:303-407,
  * BuildingBlocks/{LSTM,AdaLayerNorm,LayerNormInference}.swift), at B = 1 as the reference runs it, so the masks are no-ops and are not
- * implemented.  ALBERT and bert_encoder stay with the caller: the chain starts at d_en, their output.  mia_kokoro_text_config
+ * implemented.  The chain starts at d_en, the output of ALBERT and bert_encoder (mia_kokoro_bert_encode below).  mia_kokoro_text_config
  * (include/mia_kokoro.h): d_model and style_dim multiples of 32, d_model <= 512, d_model + style_dim <= 1024.
  * Tensors (float32, sanitised keys): predictor.text_encoder.lstm{0,1,2}.*, .norm{0,1,2}.fc.{weight,bias}, predictor.{lstm,shared}.*,
  * predictor.duration_proj.{weight [bins][d_model],bias}, text_encoder.embedding.weight [n_symbols][d_model],
@@ -1213,6 +1214,27 @@ int mia_kokoro_text_encode(mia_kokoro_text* h, const int32_t* ids, int N, float*
 int mia_kokoro_text_align(mia_kokoro_text* h, const float* d, const float* t_en, const int32_t* dur, int N, float* en_out, float* asr_out,
                           int* T, int data_mem);
 int mia_kokoro_text_shared(mia_kokoro_text* h, const float* en, int T, float* x_out, int data_mem);
+/* ---- Kokoro, ALBERT and bert_encoder: padded phoneme ids -> d_en, fp32 -------------------------------------------------------------
+ * A third handle over the same weight dictionary (the Swift files of TTS/Kokoro/Albert, KokoroTTS.swift:262-287), at B = 1: the attention mask of
+ * the one padded sequence is all ones and adds zero, so no mask is implemented; the pooler has no caller and is not built.  One layer
+ * group with one inner layer, applied n_layers times with the same weights; every LayerNorm has eps 1e-12; the GELU is the exact-erf one.
+ * mia_kokoro_bert_config (include/mia_kokoro.h): hidden a multiple of 64 up to 1024 with heads x 64 == hidden, embed a multiple of 32 up
+ * to 256, intermediate and out_dim multiples of 32.  Tensors (float32, as the checkpoint stores them, nothing transposed):
+ * bert.embeddings.{word,position,token_type}_embeddings.weight, bert.embeddings.LayerNorm.{weight,bias},
+ * bert.encoder.embedding_hidden_mapping_in.{weight,bias}, under bert.encoder.albert_layer_groups.0.albert_layers.0.:
+ * attention.{query,key,value,dense}.{weight,bias}, attention.LayerNorm.*, full_layer_layer_norm.*, ffn.*, ffn_output.*; and
+ * bert_encoder.{weight,bias}.  bert.pooler.* and *position_ids are accepted and ignored.  A missing tensor is an INVALID_ARGUMENT error
+ * that names it.
+ *   mia_kokoro_bert_encode: ids int32 [N], a HOST array in either mode (padded with 0 at both ends as the reference pads them; every id
+ *     in [0, vocab), checked before anything is launched), N in [1, min(max_positions, 512)] -> hidden_out [N][hidden] (ALBERT's sequence
+ *     output) and d_en_out [N][out_dim] (bert_encoder of it, time-major: what mia_kokoro_text_durations takes).  Either output may be
+ *     NULL, not both; data_mem describes the outputs.  n_layers <= 0: the configuration's count; a smaller positive count stops after
+ *     that many layer applications.  Deterministic: two calls give the same bytes. */
+typedef struct mia_kokoro_bert_config mia_kokoro_bert_config;    /* defined in include/mia_kokoro.h */
+typedef struct mia_kokoro_bert mia_kokoro_bert;
+mia_kokoro_bert* mia_kokoro_bert_load(mia_ctx* ctx, const mia_kokoro_bert_config* cfg, const mia_tensor_view* tensors, int n_tensors);
+void mia_kokoro_bert_free(mia_kokoro_bert* h);
+int mia_kokoro_bert_encode(mia_kokoro_bert* h, const int32_t* ids, int N, int n_layers, float* hidden_out, float* d_en_out, int data_mem);
 /* Operator-level hook: one bidirectional LSTM (BuildingBlocks/LSTM.swift) from zero state on device pointers.  x [T][ldx] (columns
  * [0, In)), the eight tensors as stored ([4 H][In], [4 H][H], [4 H], [4 H]; forward, then reverse) -> out [T][ldo], columns [0, H)
  * forward and [H, 2 H) reverse.  H a multiple of 16 up to 256, In a multiple of 32 up to 1024, T in [1, 10000]; rows 16-byte aligned;

@@ -22,4 +22,11 @@ struct mia_kokoro_text_config {
   int32_t d_model, style_dim, n_symbols, kernel, depth;
 };
 
+/* The configuration record of mia_kokoro_bert_load: AlbertConfig (TTS/Kokoro/Albert/AlbertConfig.swift) without the dropout rates and the
+ * layer-norm eps (1e-12, fixed), and out_dim = bert_encoder's output width (Predictor's dModel).  One layer group with one inner layer.
+ * The ctypes mirror is _abi.KokoroBertConfig (tests/test_kokoro_bert_abi.py compares the two field for field). */
+struct mia_kokoro_bert_config {
+  int32_t vocab, embed, hidden, heads, intermediate, n_layers, max_positions, type_vocab, out_dim;
+};
+
 #endif

@@ -71,6 +71,12 @@ class KokoroTextConfig(C.Structure):
     _fields_ = [("d_model", i32), ("style_dim", i32), ("n_symbols", i32), ("kernel", i32), ("depth", i32)]
 
 
+class KokoroBertConfig(C.Structure):
+    """struct mia_kokoro_bert_config of include/mia_kokoro.h (mia.h only declares the type, so it is not in STRUCTS)."""
+    _fields_ = [("vocab", i32), ("embed", i32), ("hidden", i32), ("heads", i32), ("intermediate", i32), ("n_layers", i32),
+                ("max_positions", i32), ("type_vocab", i32), ("out_dim", i32)]
+
+
 class WhisperDims(C.Structure):
     _fields_ = [("n_mels", i32), ("n_audio_ctx", i32), ("n_audio_state", i32), ("n_audio_head", i32), ("n_audio_layer", i32),
                 ("n_vocab", i32), ("n_text_ctx", i32), ("n_text_state", i32), ("n_text_head", i32), ("n_text_layer", i32)]
@@ -343,6 +349,10 @@ PROTOTYPES = {
     "mia_kokoro_text_encode": (i32, [vp, vp, i32, vp, i32]),
     "mia_kokoro_text_align": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i32]),
     "mia_kokoro_text_shared": (i32, [vp, vp, i32, vp, i32]),
+    # Kokoro ALBERT + bert_encoder
+    "mia_kokoro_bert_load": (vp, [vp, vp, TV, i32]),
+    "mia_kokoro_bert_free": (None, [vp]),
+    "mia_kokoro_bert_encode": (i32, [vp, vp, i32, i32, vp, vp, i32]),
     "mia_op_bilstm": (i32, [vp, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64]),
     "mia_op_instance_norm": (i32, [vp, vp, i64, i64, i32, vp, vp]),
     # OuteTTS speaker-profile audio

@@ -17,6 +17,8 @@ LIB = os.path.join(LIBDIR, "libmia.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-ffp-contract=off"]
+# per-source additions.  kokoro_bert.hip: fp32 operations stay scalar per lane (no pairing into v_pk_*_f32 forms)
+EXTRA_FLAGS = {"kokoro_bert.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _sources():
@@ -37,7 +39,7 @@ def _compile(src: str, force: bool) -> str:
     sp = os.path.join(CSRC, src)
     if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(sp), _headers_mtime()):
         return obj
-    cmd = [HIPCC, *FLAGS, "-c", sp, "-o", obj]
+    cmd = [HIPCC, *FLAGS, *EXTRA_FLAGS.get(src, []), "-c", sp, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")

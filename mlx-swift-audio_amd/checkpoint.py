@@ -252,16 +252,21 @@ def sanitize_kokoro_text_name(key: str) -> str:
     return ".".join(p)
 
 
-def sanitize_kokoro(tensors, text: bool = False):
+def sanitize_kokoro(tensors, text: bool = False, bert: bool = False):
     """The decoder / F0 / N branch of KokoroWeightLoader.sanitizeWeights (TTSEngine/KokoroWeightLoader.swift:43-66,85-111) as a rule on
     shapes: noise_convs / F0_proj / N_proj `.weight` and every three-axis weight_v swap their last two axes ([Cout][Cin][K] of the
     checkpoint -> [Cout][K][Cin]; `ups`, stored [Cin][Cout][K], becomes [Cin][K][Cout] and `pool` [C][1][3] becomes [C][3][1]);
     everything else passes.  Keys outside the decoder and the F0 / N predictor blocks are dropped unless `text` is set: then the rest
-    of `predictor.` and `text_encoder.` (what KokoroText.load takes) is kept too, renamed by sanitize_kokoro_text_name; `bert` stays
-    with the caller."""
+    of `predictor.` and `text_encoder.` (what KokoroText.load takes) is kept too, renamed by sanitize_kokoro_text_name.  With
+    `bert`, `bert.*` (minus the `position_ids` tables, which the reference's loader drops) and `bert_encoder.*` are kept under their
+    stored names (what KokoroBert.load takes)."""
     scope = _KOKORO_SCOPE + (("predictor.", "text_encoder.") if text else ())
     out = {}
     for key, v in tensors.items():
+        if bert and key.startswith(("bert.", "bert_encoder.")):
+            if "position_ids" not in key:
+                out[key] = np.asarray(v)
+            continue
         if not key.startswith(scope):
             continue
         a = np.asarray(v)

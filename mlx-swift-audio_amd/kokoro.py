@@ -1,9 +1,9 @@
 """Host-side mirror of Kokoro (TTS/Kokoro), backed by the gfx950 HIP layer.  Waveform half (KokoroDecoder): KokoroDecoder.callAsFunction
 (Decoder/KokoroDecoder.swift:83-112) with its Generator (Decoder/Generator.swift:133-192), and the F0 / N blocks of
 Predictor.F0NTrain behind `shared` (TTSEngine/KokoroModel.swift:66-89).  Text half (KokoroText): DurationEncoder, predictor.lstm and the
-duration head, TextEncoder, the alignment and predictor.shared (KokoroTTS.swift:303-407).  KokoroPipeline chains the two from d_en (the
-output of bert_encoder) to PCM.  No arithmetic happens in Python.  Text to phoneme ids, ALBERT and the voice packs stay with the caller
-("Kokoro")."""
+duration head, TextEncoder, the alignment and predictor.shared (KokoroTTS.swift:303-407).  KokoroBert: ALBERT and bert_encoder
+(TTS/Kokoro/Albert, KokoroTTS.swift:262-287).  KokoroPipeline chains them from padded phoneme ids (or from a d_en the caller brings) to
+PCM.  No arithmetic happens in Python.  Text to phoneme ids and reading voice-pack files stay with the caller ("Kokoro")."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._abi import KokoroConfig as _CConfig, KokoroTextConfig as _CTextConfig, tensor_views
+from ._abi import KokoroBertConfig as _CBertConfig, KokoroConfig as _CConfig, KokoroTextConfig as _CTextConfig, tensor_views
 
 
 @dataclass(frozen=True)
@@ -37,6 +37,13 @@ class KokoroConfig:
     n_symbols: int = 178
     text_kernel: int = 5
     text_depth: int = 3
+    bert_embed: int = 128              # ALBERT (AlbertConfig.swift); its vocabulary is n_symbols, bert_encoder's output width d_model
+    bert_hidden: int = 768
+    bert_heads: int = 12
+    bert_intermediate: int = 2048
+    bert_layers: int = 12
+    bert_positions: int = 512
+    bert_types: int = 2
 
     @property
     def upsample_scale(self) -> int:
@@ -46,7 +53,8 @@ class KokoroConfig:
 
 KOKORO_CONFIGS = {"kokoro_82m": KokoroConfig(),
                   "kokoro_micro": KokoroConfig(dim_in=64, style_dim=32, hidden=96, asr_res_dim=32, pred_dim=64, up_initial=64,
-                                               d_model=64, n_symbols=24)}
+                                               d_model=64, n_symbols=24, bert_embed=32, bert_hidden=128, bert_heads=2,
+                                               bert_intermediate=192, bert_layers=3, bert_positions=160)}
 
 
 def _pad4(v):
@@ -274,28 +282,95 @@ class KokoroText:
         return x
 
 
-class KokoroPipeline:
-    """generateAudioForTokens from line 303 on (KokoroTTS.swift:303-415): d_en, the padded ids and a voice-pack row to PCM.  Activations
-    stay on the device between the stages; only the durations (and their sum) come back to the host.  The device buffers are torch
-    tensors, so `torch` must be imported before the context is created (as for every hook here that takes device tensors)."""
+class KokoroBert:
+    """ALBERT and bert_encoder (TTS/Kokoro/Albert, KokoroTTS.swift:262-287): padded phoneme ids -> d_en, what KokoroText.durations
+    takes.  One shared layer applied cfg.bert_layers times; B = 1, so the all-ones attention mask adds zero and is not implemented."""
 
-    def __init__(self, text: KokoroText, decoder: KokoroDecoder):
+    def __init__(self, ctx, h, cfg):
+        self.ctx, self.h, self.cfg = ctx, h, cfg
+        ctx.adopt(self)
+
+    @staticmethod
+    def load(ctx: _lib.Context, cfg: KokoroConfig, weights: dict[str, np.ndarray]) -> "KokoroBert":
+        """weights: float32 under the checkpoint's own names (checkpoint.sanitize_kokoro(raw, bert=True)); bert.pooler.* is ignored."""
+        c = _CBertConfig(cfg.n_symbols, cfg.bert_embed, cfg.bert_hidden, cfg.bert_heads, cfg.bert_intermediate, cfg.bert_layers,
+                         cfg.bert_positions, cfg.bert_types, cfg.d_model)
+        views, n, keep = tensor_views(weights)
+        h = ctx.lib.mia_kokoro_bert_load(ctx.h, C.byref(c), views, n)
+        if not h:
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, ctx.lib.mia_last_error(ctx.h).decode())
+        return KokoroBert(ctx, h, cfg)
+
+    def close(self):
+        if self.h and getattr(self.ctx, "h", None):
+            self.ctx.lib.mia_kokoro_bert_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def encode(self, ids, n_layers=None, return_hidden: bool = False):
+        """ids [N] (padded with 0 at both ends, as the reference pads them) -> d_en [N, d_model], or (ALBERT's sequence output
+        [N, bert_hidden], d_en) with `return_hidden`.  n_layers: stop after that many applications of the layer (default: all)."""
+        i = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        N = i.shape[0]
+        hidden = np.empty((N, self.cfg.bert_hidden), np.float32) if return_hidden else None
+        d_en = np.empty((N, self.cfg.d_model), np.float32)
+        self.ctx.check(self.ctx.lib.mia_kokoro_bert_encode(self.h, i.ctypes.data if N else None, N, int(n_layers or 0),
+                                                           hidden.ctypes.data if return_hidden else None, d_en.ctypes.data, _lib.MEM_HOST))
+        return (hidden, d_en) if return_hidden else d_en
+
+
+def voice_row(pack, n: int):
+    """The voice-pack row of an utterance of n >= 1 phoneme ids (KokoroTTS.swift:294-300): pack [P, 1, 2 style] or [P, 2 style] ->
+    row min(n - 1, P - 1), [2 style]."""
+    p = np.asarray(pack)
+    if p.ndim == 3 and p.shape[1] == 1:
+        p = p[:, 0]
+    if p.ndim != 2 or p.shape[0] < 1 or n < 1:
+        raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, "Kokoro: the voice pack must be [P, 1, 2 style_dim] or [P, 2 style_dim] and n >= 1")
+    return p[min(n - 1, p.shape[0] - 1)]
+
+
+class KokoroPipeline:
+    """generateAudioForTokens (KokoroTTS.swift:262-415).  synthesize_ids: phoneme ids and a voice pack to PCM; synthesize: from line 303
+    on, d_en, the padded ids and a voice-pack row to PCM.  Activations stay on the device between the stages; only the durations (and
+    their sum) come back to the host.  The device buffers are torch tensors, so `torch` must be imported before the context is created
+    (as for every hook here that takes device tensors)."""
+
+    def __init__(self, text: KokoroText, decoder: KokoroDecoder, bert: KokoroBert | None = None):
         cfg = text.cfg
         if text.ctx is not decoder.ctx or (cfg.d_model, cfg.d_model, cfg.style_dim) != (decoder.cfg.dim_in, decoder.cfg.pred_dim, decoder.cfg.style_dim):
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, "Kokoro: the two halves must share a context, d_model = dim_in = pred_dim and style_dim")
-        self.text, self.decoder, self.ctx, self.cfg = text, decoder, text.ctx, cfg
+        if bert is not None and (bert.ctx is not text.ctx or (bert.cfg.d_model, bert.cfg.n_symbols) != (cfg.d_model, cfg.n_symbols)):
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, "Kokoro: bert must share the context, d_model and n_symbols of the text half")
+        self.text, self.decoder, self.bert, self.ctx, self.cfg = text, decoder, bert, text.ctx, cfg
         self.last_durations = None
+
+    def synthesize_ids(self, phoneme_ids, voice_pack, speed: float = 1.0, noise=None, durations=None):
+        """phoneme ids [n] (unpadded, n + 2 <= 512) and a voice pack -> waveform [600 T]: pads [0] + ids + [0], takes
+        voice_row(voice_pack, n) and runs bert -> durations -> encode -> align -> shared -> f0n -> decode on the device."""
+        if self.bert is None:
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, "Kokoro: synthesize_ids needs a pipeline built with bert")
+        i = np.ascontiguousarray(phoneme_ids, np.int32).reshape(-1)
+        return self.synthesize(None, np.concatenate([[0], i, [0]]).astype(np.int32), voice_row(voice_pack, i.shape[0]), speed, noise, durations)
 
     def synthesize(self, d_en, ids, voice_row, speed: float = 1.0, noise=None, durations=None):
         """d_en [N, d_model], ids [N], voice_row [2 style_dim] (decoder style | predictor style) -> waveform [600 T].  `durations`
-        [N] forces the alignment; `noise` [600 T, n_harmonics + 1] stands in for the source's random draw."""
+        [N] forces the alignment; `noise` [600 T, n_harmonics + 1] stands in for the source's random draw.  d_en = None (a pipeline
+        with bert): it is computed from the ids on the device."""
         import torch
         cfg, ctx, lib, DEV = self.cfg, self.ctx, self.ctx.lib, _lib.MEM_DEVICE
         D, S = cfg.d_model, cfg.style_dim
-        x = np.ascontiguousarray(d_en, np.float32)
         i = np.ascontiguousarray(ids, np.int32).reshape(-1)
         N = i.shape[0]
-        if x.shape != (N, D) or i.min(initial=0) < 0 or i.max(initial=0) >= cfg.n_symbols:
+        if d_en is None and self.bert is None:
+            raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, "Kokoro: synthesize needs d_en, or a pipeline built with bert")
+        x = None if d_en is None else np.ascontiguousarray(d_en, np.float32)
+        if (x is not None and x.shape != (N, D)) or i.min(initial=0) < 0 or i.max(initial=0) >= cfg.n_symbols:
             raise _lib.MiaError(_lib.ERR_INVALID_ARGUMENT, f"Kokoro: d_en must be [N, {D}] and ids [N] inside the symbol table")
         v = _f32(voice_row, (2 * S,), "voice_row")
         dev = torch.device("cuda", ctx.device)
@@ -306,10 +381,12 @@ class KokoroPipeline:
         def new(*shape, dtype=torch.float32):
             return torch.empty(shape, dtype=dtype, device=dev)
 
-        dx, di, s_dec, s_pred = up(x), up(i), up(v[:S]), up(v[S:])
+        dx, di, s_dec, s_pred = new(N, D) if x is None else up(x), up(i), up(v[:S]), up(v[S:])
         d, predicted, raw, t_en = new(N, D + S), new(N, dtype=torch.int32), new(N), new(N, D)
         dur = predicted if durations is None else up(np.ascontiguousarray(durations, np.int32).reshape(N))     # forced: d is still needed
         torch.cuda.synchronize(dev)
+        if x is None:
+            ctx.check(lib.mia_kokoro_bert_encode(self.bert.h, i.ctypes.data if N else None, N, 0, None, dx.data_ptr(), DEV))
         ctx.check(lib.mia_kokoro_text_durations(self.text.h, dx.data_ptr(), N, s_pred.data_ptr(), float(speed), d.data_ptr(),
                                                 predicted.data_ptr(), raw.data_ptr(), DEV))
         ctx.check(lib.mia_kokoro_text_encode(self.text.h, di.data_ptr(), N, t_en.data_ptr(), DEV))

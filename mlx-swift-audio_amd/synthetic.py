@@ -909,13 +909,16 @@ def marvis_weights(cfg, seed: int = 0, round_to: str | None = None, head_scale: 
 
 
 # ---- Kokoro decoder and F0 / N predictor blocks (kokoro.KOKORO_CONFIGS) -------------------------------------------------------------------
-def kokoro_weights(cfg, seed: int = 0, predictor: bool = True, text: bool = False) -> dict[str, np.ndarray]:
+def kokoro_weights(cfg, seed: int = 0, predictor: bool = True, text: bool = False, bert: bool = False) -> dict[str, np.ndarray]:
     """Random-init tensors of KokoroDecoder (and, with `predictor`, of Predictor.F0 / N / F0_proj / N_proj) under the reference's keys and
     in the layouts KokoroWeightLoader.sanitizeWeights leaves (TTSEngine/KokoroWeightLoader.swift:43-66,85-111): weight_v [Cout][K][Cin]
     except `ups` ([Cin][K][Cout]) and `pool` ([C][3][1]).  weight_v is N(0, 1) and weight_g (about the gain, never 1) gives the folded
     weights the usual fan-in scale; alpha lies in [0.5, 2]; the fc weights keep 1 + gamma positive and away from 1.  `text` adds the text
     half (DurationEncoder, predictor.lstm / shared / duration_proj, TextEncoder) under the sanitised keys; LSTM weights scale as
-    1 / sqrt(H), so the gates do not saturate, and duration_proj has 50 bins as the checkpoint does."""
+    1 / sqrt(H), so the gates do not saturate, and duration_proj has 50 bins as the checkpoint does.  `bert` adds ALBERT and bert_encoder
+    under the checkpoint's names (Linear weights scale as 1 / sqrt(fan-in) behind post-LayerNorm layers, so activations stay O(1)
+    through every application of the shared layer).  Every tensor has a generator of its own, seeded by its name: a flag adds keys and
+    changes none."""
     w: dict[str, np.ndarray] = {}
     sd = cfg.style_dim
 
@@ -995,4 +998,25 @@ def kokoro_weights(cfg, seed: int = 0, predictor: bool = True, text: bool = Fals
             w[f"text_encoder.cnn.{i}.norm.gamma"] = (1.0 + 0.1 * rng(f"text_encoder.cnn.{i}.norm.gamma").standard_normal(Dm)).astype(np.float32)
             t(f"text_encoder.cnn.{i}.norm.beta", (Dm,), 0.1)
         lstm("text_encoder.lstm", Dm)
+    if bert:
+        E, Hd, I = cfg.bert_embed, cfg.bert_hidden, cfg.bert_intermediate
+
+        def norm(p, n):
+            w[p + ".weight"] = (1.0 + 0.1 * rng(p + ".weight").standard_normal(n)).astype(np.float32)
+            t(p + ".bias", (n,), 0.1)
+
+        def linear(p, n_out, n_in):
+            t(p + ".weight", (n_out, n_in), 1.0 / math.sqrt(n_in)); t(p + ".bias", (n_out,), 0.1)
+
+        for name, rows in (("word", cfg.n_symbols), ("position", cfg.bert_positions), ("token_type", cfg.bert_types)):
+            t(f"bert.embeddings.{name}_embeddings.weight", (rows, E), 0.6)
+        norm("bert.embeddings.LayerNorm", E)
+        linear("bert.encoder.embedding_hidden_mapping_in", Hd, E)
+        Y = "bert.encoder.albert_layer_groups.0.albert_layers.0."
+        for name in ("query", "key", "value", "dense"):
+            linear(Y + "attention." + name, Hd, Hd)
+        norm(Y + "attention.LayerNorm", Hd); norm(Y + "full_layer_layer_norm", Hd)
+        linear(Y + "ffn", I, Hd); linear(Y + "ffn_output", Hd, I)
+        linear("bert.pooler", Hd, Hd)                                               # in the checkpoint, never read
+        linear("bert_encoder", cfg.d_model, Hd)
     return w

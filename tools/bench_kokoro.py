@@ -9,6 +9,9 @@ materialised form only, so there is no fused / materialised comparison to report
 --text times the text half instead (N tokens, default 100, durations forced to sum to T): ms for durations, encode, align, shared and
 the whole KokoroPipeline.synthesize beside decode alone, and the per-step cost of the recurrent kernel as `shared` ms / T (its input
 projection included) against the 1.5 us floor of a dependent launch.
+
+--bert times ALBERT + bert_encoder (N padded ids, default 100, and 512): ms for KokoroBert.encode alone, host memory in and out, and for
+synthesize_ids beside synthesize from a host d_en in the same process (durations forced to sum to T).
 """
 import argparse
 import json
@@ -39,9 +42,12 @@ def main():
     ap.add_argument("--repeat", type=int, default=7)
     ap.add_argument("--text", action="store_true")
     ap.add_argument("--N", type=int, default=100)
+    ap.add_argument("--bert", action="store_true")
     a = ap.parse_args()
     if a.text:
         return text_main(a)
+    if a.bert:
+        return bert_main(a)
     import mlx_swift_audio_amd as m
     from mlx_swift_audio_amd import synthetic
     from mlx_swift_audio_amd.kokoro import KOKORO_CONFIGS, KokoroDecoder
@@ -103,6 +109,38 @@ def text_main(a):
     print(json.dumps({"config": a.config, "N": N, "T": T, "ms": {k: round(v, 3) for k, v in ms.items()},
                       "lstm_step_us": round(ms["shared"] * 1e3 / T, 2), "launch_floor_us": 1.5, "persistent_lstm": "not built"}))
     for h in (text, dec):
+        h.close()
+    ctx.close()
+
+
+def bert_main(a):
+    import torch  # noqa: F401  (before the HIP library loads: the pipeline holds its device buffers as torch tensors)
+
+    import mlx_swift_audio_amd as m
+    from mlx_swift_audio_amd import synthetic
+    from mlx_swift_audio_amd.kokoro import KOKORO_CONFIGS, KokoroBert, KokoroDecoder, KokoroPipeline, KokoroText, voice_row
+    cfg = KOKORO_CONFIGS[a.config]
+    ctx = m.Context(0)
+    w = synthetic.kokoro_weights(cfg, 2, text=True, bert=True)
+    bert, text, dec = KokoroBert.load(ctx, cfg, w), KokoroText.load(ctx, cfg, w), KokoroDecoder.load(ctx, cfg, w)
+    pipe = KokoroPipeline(text, dec, bert)
+    rng = np.random.default_rng(0)
+    pack = rng.standard_normal((510, 1, 2 * cfg.style_dim)).astype(np.float32)
+    out = {"config": a.config, "T": a.T, "launches": 3 + 7 * cfg.bert_layers, "estimate_ms_at_N100": "< 1", "ms": {}}
+    for N in (a.N, 512):
+        ids = rng.integers(1, cfg.n_symbols, N - 2).astype(np.int32)
+        padded = np.concatenate([[0], ids, [0]]).astype(np.int32)
+        dur = np.full(N, a.T // N, np.int32)
+        dur[:a.T - int(dur.sum())] += 1
+        noise = rng.standard_normal((2 * a.T * cfg.upsample_scale, cfg.n_harmonics + 1)).astype(np.float32)
+        d_en = bert.encode(padded)
+        row = voice_row(pack, N - 2)
+        out["ms"][f"N={N}"] = {
+            "bert_encode": round(_median_ms(lambda: bert.encode(padded), a.repeat), 3),
+            "synthesize_ids": round(_median_ms(lambda: pipe.synthesize_ids(ids, pack, noise=noise, durations=dur), a.repeat), 3),
+            "synthesize_from_host_d_en": round(_median_ms(lambda: pipe.synthesize(d_en, padded, row, noise=noise, durations=dur), a.repeat), 3)}
+    print(json.dumps(out))
+    for h in (bert, text, dec):
         h.close()
     ctx.close()
 
