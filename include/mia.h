@@ -236,6 +236,16 @@ typedef struct {
 } mia_conv_gemm_desc;
 int mia_op_conv_gemm_f32(mia_ctx* ctx, const mia_conv_gemm_desc* d, int phases);
 
+/* Test hook and operator: the tap GEMM of mia_op_conv_gemm_f32 on bf16 weights.  d->W must be NULL; w [phases][N][ldw] bf16, ldw and
+ * w_phase_stride of d in elements, both multiples of 8, w 16-byte aligned.  X, Y, R, R2 and bias stay fp32 and nothing is rounded: X is
+ * split into three bf16 terms whose products with w are exact, so the result differs from the fp32 kernel's on the same weight values
+ * by accumulation rounding only.  Served: the leaky-ReLU prologue, bias, R, out_scale, R2, x_row_mul / dil / pad, the y row mapping
+ * and phases.  Fields outside the served subset (alpha / ralpha, noise, tanh_out, act, phase_len / x_phase_step, n_seq > 1, seq_len):
+ * MIA_ERR_UNSUPPORTED with the field named.  DEVICE pointers; w is `const void*` like every 16-bit payload of this header.
+ * _tile forces the block tile: 0 = the launch rule of the fp32 kernel, 1 = 64 x 64, 2 = 128 x 64, 3 = 128 x 128 (same bits on each). */
+int mia_op_conv_gemm_w16(mia_ctx* ctx, const mia_conv_gemm_desc* d, const void* w, int phases);
+int mia_op_conv_gemm_w16_tile(mia_ctx* ctx, const mia_conv_gemm_desc* d, const void* w, int phases, int tile);
+
 /* Test hook: mia_op_attention_f32 with the remaining modes of the fp32 attention kernel.  p [T][ldp] (nullable) = positional keys shared
  * by the batch, with bias_u / bias_v [H][64]: score(i, j) = ((q_i + u) . k_j + (q_i + v) . p_j) * scale (RelPositionMultiHeadedAttention,
  * Codec/S3Gen/Transformer/Attention.swift:143-195).  seq_len int32 [B] (nullable): keys at or beyond seq_len[b] are masked, and sequence
@@ -1174,8 +1184,8 @@ int mia_campplus_embed(mia_campplus* m, const float* pcm, int64_t n_samples, flo
  *   mia_kokoro_generate: Generator.callAsFunction from a given har: x [up_initial][L], s [style_dim], har [60 L + 1][22] -> pcm [300 L].
  *   mia_kokoro_decode: KokoroDecoder.callAsFunction: asr [dim_in][T], f0 [2 T], n [2 T], s [style_dim], noise as above for
  *     L = 2 T (nullable) -> pcm [600 T].
- * Out of scope: voice-pack files; stacked utterances; 16-bit weights.  The text half behind ALBERT is mia_kokoro_text_* below, ALBERT
- * and bert_encoder are mia_kokoro_bert_* behind that. */
+ * Out of scope: voice-pack files; stacked utterances.  The text half behind ALBERT is mia_kokoro_text_* below, ALBERT and
+ * bert_encoder are mia_kokoro_bert_* behind that. */
 typedef struct mia_kokoro_config mia_kokoro_config;    /* defined in include/mia_kokoro.h */
 typedef struct mia_kokoro mia_kokoro;
 mia_kokoro* mia_kokoro_load(mia_ctx* ctx, const mia_kokoro_config* cfg, const mia_tensor_view* tensors, int n_tensors);
@@ -1186,6 +1196,11 @@ int mia_kokoro_source(mia_kokoro* h, const float* f0, int L, const float* noise,
 int mia_kokoro_generate(mia_kokoro* h, const float* x, int L, const float* s, const float* har, float* pcm, int data_mem);
 int mia_kokoro_decode(mia_kokoro* h, const float* asr, int T, const float* f0, const float* n, const float* s, const float* noise,
                       float* pcm, int data_mem);
+/* Kokoro decoder handle: run every tap-GEMM convolution of f0n / generate / decode on bf16 copies of the folded weights
+ * (mia_op_conv_gemm_w16: exact in the activations).  The first on == 1 forms the copies (round to nearest even of the folded fp32
+ * weight, padding rows / columns stay zero) and keeps the fp32 ones; on == 0 returns to the fp32 launches, which are then exactly what
+ * they were.  Off by default.  The rounding is of the FOLDED weight g v / ||v||, which is not a bf16 value even when v and g are. */
+int mia_kokoro_use_w16(mia_kokoro* h, int on);
 /* ---- Kokoro, text half: DurationEncoder, duration head, TextEncoder, alignment and predictor.shared, fp32 -------------------------
  * A second handle over the same weight dictionary (TTSEngine/{DurationEncoder,TextEncoder,KokoroModel}.swift, KokoroTTS.swift:303-407,
  * BuildingBlocks/{LSTM,AdaLayerNorm,LayerNormInference}.swift), at B = 1 as the reference runs it, so the masks are no-ops and are not

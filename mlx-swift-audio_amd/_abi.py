@@ -274,6 +274,8 @@ PROTOTYPES = {
     "mia_dequant_affine": (i32, [vp, vp, vp, vp, i64, i64, i32, i32, i32, vp, i32, i32]),
     "mia_op_attention_f32": (i32, [vp, vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, f32]),
     "mia_op_conv_gemm_f32": (i32, [vp, P(ConvGemmDesc), i32]),
+    "mia_op_conv_gemm_w16": (i32, [vp, P(ConvGemmDesc), vp, i32]),
+    "mia_op_conv_gemm_w16_tile": (i32, [vp, P(ConvGemmDesc), vp, i32, i32]),
     "mia_op_attention_f32_ex": (i32, [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, i32, f32, vp, i32]),
     "mia_op_attention_h128": (i32, [vp, vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, f32, vp, i32, i32]),
     "mia_op_fsmn_add": (i32, [vp, vp, i64, vp, i64, vp, i32, i32, i32, i32, i32, vp, i32, i32]),
@@ -342,6 +344,7 @@ PROTOTYPES = {
     "mia_kokoro_source": (i32, [vp, vp, i32, vp, vp, vp, i32]),
     "mia_kokoro_generate": (i32, [vp, vp, i32, vp, vp, vp, i32]),
     "mia_kokoro_decode": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, i32]),
+    "mia_kokoro_use_w16": (i32, [vp, i32]),
     # Kokoro text half
     "mia_kokoro_text_load": (vp, [vp, vp, TV, i32]),
     "mia_kokoro_text_free": (None, [vp]),

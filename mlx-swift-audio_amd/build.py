@@ -17,8 +17,9 @@ LIB = os.path.join(LIBDIR, "libmia.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-ffp-contract=off"]
-# per-source additions.  kokoro_bert.hip: fp32 operations stay scalar per lane (no pairing into v_pk_*_f32 forms)
-EXTRA_FLAGS = {"kokoro_bert.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# per-source additions.  kokoro_bert.hip, conv_gemm_w16.hip: fp32 operations stay scalar per lane (no pairing into v_pk_*_f32 forms)
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"kokoro_bert.hip": _NO_PK_F32, "conv_gemm_w16.hip": _NO_PK_F32}
 
 
 def _sources():

@@ -84,6 +84,19 @@ static inline int codec_conv_gemm_run(mia_ctx* ctx, const ConvGemmArgs& g, int p
   if (codec_conv_gemm_launch(g, phases, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "%s: conv_gemm launch failed", who);
   return MIA_OK;
 }
+// The same GEMM on bf16 weights w [phases][N][ldw] and fp32 activations, exact (conv_gemm_w16.hip: three-way bf16 split of X on the
+// bf16 MFMA).  g.W stays null; served: the leaky-ReLU prologue, bias, R / out_scale / R2, the row mappings and phases.  The check names
+// the field of anything else (*unsupported = true then) and adds ldw % 8 == 0, w_phase_stride % 8 == 0 to codec_conv_gemm_check's rules.
+// tile: 0 = codec_conv_gemm_launch's fill rule, 1 = 64 x 64, 2 = 128 x 64, 3 = 128 x 128 (the operator tests force each).
+const char* conv_gemm_w16_check(const ConvGemmArgs& g, const uint16_t* w, bool* unsupported = nullptr);
+int conv_gemm_w16_launch(const ConvGemmArgs& g, const uint16_t* w, int phases, hipStream_t s, int tile = 0);
+int conv_w16_round_launch(const float* src, uint16_t* dst, int64_t n, hipStream_t s);      // dst = bf16_rn(src)
+static inline int conv_gemm_w16_run(mia_ctx* ctx, const ConvGemmArgs& g, const uint16_t* w, int phases, const char* who, int tile = 0) {
+  bool unsup = false;
+  if (const char* e = conv_gemm_w16_check(g, w, &unsup)) return mia_fail(ctx, unsup ? MIA_ERR_UNSUPPORTED : MIA_ERR_INVALID_ARGUMENT, "%s: %s", who, e);
+  if (conv_gemm_w16_launch(g, w, phases, ctx->stream, tile)) return mia_fail(ctx, MIA_ERR_DEVICE, "%s: conv_gemm_w16 launch failed", who);
+  return MIA_OK;
+}
 int codec_dwconv_launch(const float* x, float* y, const float* w, const float* bias, const float* a_pre, const float* a_post, int T, int C,
                         int K, int dil, hipStream_t s, const SeqArgs& q = SeqArgs());
 int codec_conv_out1_launch(const float* x, float* out, const float* w, const float* bias, const float* alpha, int T, int C, int K, hipStream_t s,

@@ -66,6 +66,7 @@ struct mia_kokoro {
   KBlk pF0[3], pN[3];
   KConv projF0, projN;
   float* arena = nullptr; size_t arena_floats = 0;
+  bool w16 = false;                      // mia_kokoro_use_w16: the tap GEMMs read the bf16 copies (KConv::w16)
 };
 
 namespace {
@@ -184,25 +185,25 @@ int carve(mia_kokoro* h, int64_t T, int64_t L, Scratch& sc) {
 
 // ---- launches ------------------------------------------------------------------------------------------------------------------------------
 int run_conv(mia_kokoro* h, const KConv& c, const float* X, int64_t T_in, float* Y, int64_t T_out, const COpt& o = COpt()) {
-  return kconv_run(h->ctx, c, X, T_in, Y, T_out, o);
+  return kconv_run(h->ctx, c, X, T_in, Y, T_out, o, h->w16);
 }
 
 // k = 1 convolution on T rows, every row written twice (rows 2 t and 2 t + 1): the nearest x 2 up-sampling of the shortcut commutes with it
 int run_conv_dup(mia_kokoro* h, const KConv& c, const float* X, int64_t T, float* Y) {
   ConvGemmArgs g;
-  g.X = X; g.ldx = c.Cin; g.T_in = (int)T; g.W = c.w; g.bias = c.b;
+  g.X = X; g.ldx = c.Cin; g.T_in = (int)T; g.bias = c.b;
   g.Y = Y; g.ldy = c.N; g.T_out = (int)(2 * T); g.y_row_mul = 2; g.y_phase_step = 1;
   g.M = (int)T; g.N = c.N; g.Cin = c.Cin; g.taps = 1; g.dil = 1; g.pad = 0;
-  return codec_conv_gemm_run(h->ctx, g, 2, "kokoro");
+  return kconv_launch(h->ctx, g, c, 2, h->w16);
 }
 
 // transposed conv: Y rows [row_shift, row_shift + T_out)
 int run_convt(mia_kokoro* h, const KConv& c, const float* X, int64_t T_in, float* Y, int64_t T_out, int row_shift, float lrelu) {
   ConvGemmArgs g;
-  g.X = X; g.ldx = c.Cin; g.T_in = (int)T_in; g.W = c.w; g.w_phase_stride = (int64_t)c.N * c.taps * c.Cin; g.bias = c.b; g.lrelu_slope = lrelu;
+  g.X = X; g.ldx = c.Cin; g.T_in = (int)T_in; g.w_phase_stride = (int64_t)c.N * c.taps * c.Cin; g.bias = c.b; g.lrelu_slope = lrelu;
   g.M = (int)T_in + c.taps - 1; g.N = c.N; g.Cin = c.Cin; g.taps = c.taps; g.dil = 1; g.pad = c.taps - 1;
   g.Y = Y + (int64_t)row_shift * c.N; g.ldy = c.N; g.T_out = (int)T_out; g.y_row_mul = c.stride; g.y_row_off = -c.pad; g.y_phase_step = 1;
-  return codec_conv_gemm_run(h->ctx, g, c.stride, "kokoro");
+  return kconv_launch(h->ctx, g, c, c.stride, h->w16);
 }
 
 #define KOK_LAUNCH(h, expr) do { if (expr) return mia_fail((h)->ctx, MIA_ERR_DEVICE, "kokoro: kernel launch failed (%s)", #expr); } while (0)
@@ -487,6 +488,34 @@ int mia_kokoro_decode(mia_kokoro* h, const float* asr, int T, const float* f0, c
   if (int rc = run_block(h, sc, h->decode[3], cat, T, sc.big[6], 0, t)) return rc;
   if (int rc = dev_generate(h, sc, L)) return rc;
   return io.finish();
+}
+
+int mia_kokoro_use_w16(mia_kokoro* h, int on) {
+  if (!h) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(h->ctx, on == 0 || on == 1, "kokoro_use_w16: on must be 0 or 1");
+  if (!on) { h->w16 = false; return MIA_OK; }
+  MIA_HIP(h->ctx, hipSetDevice(h->ctx->device));
+  std::vector<KConv*> cs;                 // every convolution the three launch sites can be handed
+  auto blk = [&](KBlk& b) { cs.push_back(&b.c1); cs.push_back(&b.c2); cs.push_back(&b.sc); };
+  auto res = [&](KRes& r) { for (int i = 0; i < 3; ++i) { cs.push_back(&r.c1[i]); cs.push_back(&r.c2[i]); } };
+  blk(h->encode);
+  for (KBlk& b : h->decode) blk(b);
+  cs.push_back(&h->asr_res); cs.push_back(&h->post); cs.push_back(&h->projF0); cs.push_back(&h->projN);
+  for (int i = 0; i < 4; ++i) {
+    cs.push_back(&h->ups[i]); cs.push_back(&h->nzc[i]); res(h->nres[i]);
+    for (KRes& r : h->rb[i]) res(r);
+  }
+  for (int i = 0; i < 3; ++i) { blk(h->pF0[i]); blk(h->pN[i]); }
+  for (KConv* c : cs) {
+    if (!c->w || c->w16) continue;        // absent from this configuration, or copied by an earlier call
+    uint16_t* q = nullptr;
+    if (hipMalloc((void**)&q, c->w_elems() * 2) != hipSuccess) return mia_fail(h->ctx, MIA_ERR_OUT_OF_MEMORY, "kokoro_use_w16: hipMalloc failed");
+    h->allocs.push_back(q);
+    if (conv_w16_round_launch(c->w, q, (int64_t)c->w_elems(), h->ctx->stream)) return mia_fail(h->ctx, MIA_ERR_DEVICE, "kokoro_use_w16: launch failed");
+    c->w16 = q;
+  }
+  h->w16 = true;
+  return MIA_OK;
 }
 
 int mia_op_instance_norm(mia_ctx* ctx, const float* x, int64_t ld, int64_t T, int C, float* mean, float* rstd) {

@@ -15,6 +15,8 @@ struct KConv {
   float* w = nullptr; float* b = nullptr;
   int N = 0, Cin = 0, taps = 1, dil = 1, pad = 0, stride = 1;   // N, Cin: padded to 32 unless the loader was told to keep N
   int K = 0;                                                    // transposed conv: kernel size (taps = ceil(K / stride))
+  uint16_t* w16 = nullptr;                                      // bf16 copy of w (mia_kokoro_use_w16), null in the text and ALBERT handles
+  size_t w_elems() const { return (size_t)(K ? stride : 1) * N * taps * Cin; }     // a transposed conv holds `stride` phases
 };
 
 struct KConvLoader : TensorLoader {
@@ -71,10 +73,17 @@ struct KConvLoader : TensorLoader {
 
 struct COpt { const float* R = nullptr; int64_t ldr = 0; const float* R2 = nullptr; float scale = 0.f; float lrelu = 0.f; int64_t ldy = 0; };
 
-inline int kconv_run(mia_ctx* ctx, const KConv& c, const float* X, int64_t T_in, float* Y, int64_t T_out, const COpt& o = COpt()) {
+// the checked tap-GEMM launch on the fp32 weights, or (w16: the decoder handle's switch) on their bf16 copies
+inline int kconv_launch(mia_ctx* ctx, ConvGemmArgs& g, const KConv& c, int phases, bool w16) {
+  if (!w16) { g.W = c.w; return codec_conv_gemm_run(ctx, g, phases, "kokoro"); }
+  if (!c.w16) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "kokoro: a convolution has no bf16 copy of its weights");
+  return conv_gemm_w16_run(ctx, g, c.w16, phases, "kokoro");
+}
+
+inline int kconv_run(mia_ctx* ctx, const KConv& c, const float* X, int64_t T_in, float* Y, int64_t T_out, const COpt& o = COpt(), bool w16 = false) {
   ConvGemmArgs g;
-  g.X = X; g.ldx = c.Cin; g.T_in = (int)T_in; g.W = c.w; g.bias = c.b; g.lrelu_slope = o.lrelu;
+  g.X = X; g.ldx = c.Cin; g.T_in = (int)T_in; g.bias = c.b; g.lrelu_slope = o.lrelu;
   g.Y = Y; g.ldy = o.ldy ? o.ldy : c.N; g.T_out = (int)T_out; g.R = o.R; g.R2 = o.R2; g.ldr = o.ldr ? o.ldr : c.N; g.out_scale = o.scale;
   g.M = (int)T_out; g.N = c.N; g.Cin = c.Cin; g.taps = c.taps; g.dil = c.dil; g.pad = c.pad; g.x_row_mul = c.stride;
-  return codec_conv_gemm_run(ctx, g, 1, "kokoro");
+  return kconv_launch(ctx, g, c, 1, w16);
 }

@@ -137,10 +137,7 @@ extern "C" int mia_op_conv1d_f32(mia_ctx* ctx, const float* x, int64_t ldx, int 
 }
 
 // the tap GEMM with every launch argument exposed (test hook; the formula is at the top of codec.h and in include/mia.h)
-extern "C" int mia_op_conv_gemm_f32(mia_ctx* ctx, const mia_conv_gemm_desc* d, int phases) {
-  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
-  MIA_CHECK_ARG(ctx, d, "op_conv_gemm_f32: null descriptor");
-  MIA_HIP(ctx, hipSetDevice(ctx->device));
+static ConvGemmArgs conv_gemm_args_of(const mia_conv_gemm_desc* d) {
   ConvGemmArgs g;
   g.X = d->X; g.ldx = d->ldx; g.T_in = d->T_in; g.W = d->W; g.ldw = d->ldw; g.w_phase_stride = d->w_phase_stride; g.bias = d->bias;
   g.alpha = d->alpha; g.ralpha = d->ralpha; g.lrelu_slope = d->lrelu_slope; g.Y = d->Y; g.ldy = d->ldy; g.T_out = d->T_out;
@@ -148,8 +145,31 @@ extern "C" int mia_op_conv_gemm_f32(mia_ctx* ctx, const mia_conv_gemm_desc* d, i
   g.noise = d->noise; g.out_scale = d->out_scale; g.M = d->M; g.N = d->N; g.Cin = d->Cin; g.taps = d->taps; g.dil = d->dil; g.pad = d->pad;
   g.x_row_mul = d->x_row_mul; g.gelu = d->act; g.tanh_out = d->tanh_out; g.phase_len = d->phase_len; g.x_phase_step = d->x_phase_step;
   g.n_seq = d->n_seq; g.x_seq_step = d->x_seq_step; g.y_seq_step = d->y_seq_step; g.seq_len = d->seq_len; g.noise_seq_off = d->noise_seq_off;
+  return g;
+}
+extern "C" int mia_op_conv_gemm_f32(mia_ctx* ctx, const mia_conv_gemm_desc* d, int phases) {
+  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, d, "op_conv_gemm_f32: null descriptor");
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  const ConvGemmArgs g = conv_gemm_args_of(d);
   if (const char* e = conv_gemm_abi_check(g, phases)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "op_conv_gemm_f32: %s", e);
   return codec_conv_gemm_run(ctx, g, phases, "op_conv_gemm_f32");
+}
+
+// the same on bf16 weights (conv_gemm_w16.hip); tile forces an instantiation (0: the launch rule)
+extern "C" int mia_op_conv_gemm_w16_tile(mia_ctx* ctx, const mia_conv_gemm_desc* d, const void* w_bf16, int phases, int tile) {
+  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  const uint16_t* w = static_cast<const uint16_t*>(w_bf16);
+  MIA_CHECK_ARG(ctx, d && w, "op_conv_gemm_w16: null argument");
+  MIA_CHECK_ARG(ctx, tile >= 0 && tile <= 3, "op_conv_gemm_w16: tile must be 0 (rule), 1 (64 x 64), 2 (128 x 64) or 3 (128 x 128)");
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  const ConvGemmArgs g = conv_gemm_args_of(d);
+  ConvGemmArgs c = g; c.W = reinterpret_cast<const float*>(w);          // the pointer rule of the fp32 hook, on the weights actually read
+  if (const char* e = conv_gemm_abi_check(c, phases)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "op_conv_gemm_w16: %s", e);
+  return conv_gemm_w16_run(ctx, g, w, phases, "op_conv_gemm_w16", tile);
+}
+extern "C" int mia_op_conv_gemm_w16(mia_ctx* ctx, const mia_conv_gemm_desc* d, const void* w, int phases) {
+  return mia_op_conv_gemm_w16_tile(ctx, d, w, phases, 0);
 }
 
 // The LM step's skinny GEMMs with every launch argument exposed (test hook; formulas in skinny.h and include/mia.h).  The launchers'

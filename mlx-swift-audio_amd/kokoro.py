@@ -104,6 +104,11 @@ class KokoroDecoder:
     def output_len(self, T: int) -> int:
         return int(self.ctx.lib.mia_kokoro_output_len(self.h, int(T)))
 
+    def use_w16(self, on: bool = True) -> None:
+        """Run the tap-GEMM convolutions of f0n / generate / decode on bf16 copies of the folded weights (formed by the first on=True;
+        the activations stay fp32 and are not rounded).  on=False returns to the fp32 weights.  Off by default."""
+        self.ctx.check(self.ctx.lib.mia_kokoro_use_w16(self.h, 1 if on else 0))
+
     def _noise(self, noise, L):
         if noise is None:
             return None

@@ -251,10 +251,8 @@ def conv1d_f32(ctx: _lib.Context, x, w, y, *, Cin: int, taps: int = 1, stride: i
     return dy.cpu().numpy()
 
 
-def conv_gemm_f32(ctx: _lib.Context, phases: int = 1, **d) -> np.ndarray:
-    """mia_op_conv_gemm_f32: keyword arguments are the fields of mia_conv_gemm_desc, arrays for its pointers (X, Y, R, R2 two-dimensional:
-    ldx / ldy / ldr default to their row strides; Y's contents are what unwritten elements keep, a device tensor is written in place).
-    Returns Y's whole buffer."""
+def _conv_gemm_desc(d):
+    """(descriptor, device tensors by field) of the keyword arguments of conv_gemm_f32 / conv_gemm_w16."""
     unknown = set(d) - {n for n, _ in ConvGemmDesc._fields_}
     assert not unknown, f"not a mia_conv_gemm_desc field: {sorted(unknown)}"
     t = {k: _dev(d.get(k)) for k in _DESC_F32}
@@ -267,7 +265,26 @@ def conv_gemm_f32(ctx: _lib.Context, phases: int = 1, **d) -> np.ndarray:
             setattr(desc, name, _ld(t[{"ldx": "X", "ldy": "Y", "ldr": "R"}[name]] if name != "ldr" or t["R"] is not None else t["R2"], d.get(name)))
         else:
             setattr(desc, name, d.get(name, _DESC_DEFAULTS.get(name, 0)))
+    return desc, t
+
+
+def conv_gemm_f32(ctx: _lib.Context, phases: int = 1, **d) -> np.ndarray:
+    """mia_op_conv_gemm_f32: keyword arguments are the fields of mia_conv_gemm_desc, arrays for its pointers (X, Y, R, R2 two-dimensional:
+    ldx / ldy / ldr default to their row strides; Y's contents are what unwritten elements keep, a device tensor is written in place).
+    Returns Y's whole buffer."""
+    desc, t = _conv_gemm_desc(d)
     _run(ctx, lambda: ctx.lib.mia_op_conv_gemm_f32(ctx.h, C.byref(desc), int(phases)))
+    return None if t["Y"] is None else t["Y"].cpu().numpy()
+
+
+def conv_gemm_w16(ctx: _lib.Context, w_bf16, phases: int = 1, tile: int = 0, **d) -> np.ndarray:
+    """mia_op_conv_gemm_w16(_tile): the descriptor of conv_gemm_f32 without W, and the weights as bf16 payloads: a uint16 array or a
+    torch.bfloat16 / int16 device tensor, [phases][N][ldw].  tile forces the block tile (0: the launch rule).  Returns Y's whole buffer."""
+    import torch
+    w = w_bf16 if isinstance(w_bf16, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(w_bf16, np.uint16).view(np.int16)).cuda()
+    assert w.is_cuda and w.element_size() == 2, "bf16 payloads on the device"
+    desc, t = _conv_gemm_desc(d)
+    _run(ctx, lambda: ctx.lib.mia_op_conv_gemm_w16_tile(ctx.h, C.byref(desc), w.data_ptr(), int(phases), int(tile)))
     return None if t["Y"] is None else t["Y"].cpu().numpy()
 
 

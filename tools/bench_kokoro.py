@@ -12,6 +12,10 @@ projection included) against the 1.5 us floor of a dependent launch.
 
 --bert times ALBERT + bert_encoder (N padded ids, default 100, and 512): ms for KokoroBert.encode alone, host memory in and out, and for
 synthesize_ids beside synthesize from a host d_en in the same process (durations forced to sum to T).
+
+--w16 is the A/B of KokoroDecoder.use_w16 (the tap GEMMs on bf16 copies of the weights, conv_gemm_w16.hip): one process, one handle,
+f0n / generate / decode with the switch off, on, and off again (the third column shows what the first two differ by when nothing
+changed), same protocol, clocks as found.
 """
 import argparse
 import json
@@ -43,6 +47,7 @@ def main():
     ap.add_argument("--text", action="store_true")
     ap.add_argument("--N", type=int, default=100)
     ap.add_argument("--bert", action="store_true")
+    ap.add_argument("--w16", action="store_true")
     a = ap.parse_args()
     if a.text:
         return text_main(a)
@@ -64,6 +69,16 @@ def main():
     noise = rng.standard_normal((L * cfg.upsample_scale, cfg.n_harmonics + 1)).astype(np.float32)
     xg = rng.standard_normal((cfg.up_initial, L)).astype(np.float32)
     _, har = model.source(f0, noise)
+    if a.w16:
+        calls = {"f0n": lambda: model.f0n(xp, s), "generate": lambda: model.generate(xg, s, har), "decode": lambda: model.decode(asr, f0, n, s, noise)}
+        ms = {}
+        for col, on in (("fp32", False), ("w16", True), ("fp32_again", False)):
+            model.use_w16(on)
+            ms[col] = {k: round(_median_ms(fn, a.repeat), 3) for k, fn in calls.items()}
+        print(json.dumps({"config": a.config, "T": T, "audio_s": model.output_len(T) / cfg.sample_rate, "ms": ms}))
+        model.close()
+        ctx.close()
+        return
     ms = {"decode": _median_ms(lambda: model.decode(asr, f0, n, s, noise), a.repeat),
           "predictor_blocks": _median_ms(lambda: model.f0n(xp, s), a.repeat),
           "source_stft": _median_ms(lambda: model.source(f0, noise), a.repeat),
