@@ -292,6 +292,13 @@ int mia_op_kvq_attention(mia_ctx* ctx, const void* q, const void* k, const void*
 int mia_op_lm_prompt_attention(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int n, int dh,
                                int dtype);
 
+/* The same over the packed cache (lm_prefill_attn_kvq.hip, see mia_lm_set_kvq_prompt_attention): k / v go through the prompt pass's
+ * quantising cache writer (QuantizedKVCache(groupSize: 64, bits:), bits 4 | 8), and the tiled kernel attends over the codes.  Shapes,
+ * pointers and errors as above; bits outside {4, 8}: MIA_ERR_INVALID_ARGUMENT.  With MIA_F16 the range limit stated at
+ * mia_lm_set_kvq_prompt_attention applies to v. */
+int mia_op_lm_prompt_attention_kvq(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int n,
+                                   int dh, int bits, int dtype);
+
 /* Test hook: the LM decode step's skinny GEMMs (csrc/skinny.h: skinny_gemm_launch on 16-bit weights, skinny_gemm_q_launch on packed 4- /
  * 6- / 8-bit weights) with every launch argument exposed, so each kernel form the two launchers choose from the shape can be compared with a
  * reference on its own.  DEVICE pointers, enqueued on the context's stream.  A [M][lda] and the 16-bit outputs are in `dtype`
@@ -795,6 +802,16 @@ int mia_lm_set_debug(mia_lm* lm, int flags);
  * probabilities, not bit for bit; within mode 1 a row's result does not depend on the chunk or batch it sits in.  Any other mode:
  * MIA_ERR_INVALID_ARGUMENT. */
 int mia_lm_set_prompt_attention(mia_lm* lm, int mode);
+/* The same choice for the prompt pass on the PACKED cache (mia_lm_set_kv_quant(bits 4 | 8)), a switch of its own.  0 (default): the packed
+ * cache's row kernel, one workgroup per (query head, prompt row), each de-quantising its head's cache from key 0.  1: the tiled causal
+ * grouped-query kernel of lm_prefill_attn_kvq.hip -- the codes are the matrix-core operands, scale and bias are applied in fp32 around
+ * the MFMAs, no cached value is re-rounded to 16 bits -- for every layer of every run.  No effect while the cache is 16-bit;
+ * mia_lm_set_prompt_attention keeps its meaning; the cache writer and the decode step are the same in both modes.  The modes agree to
+ * fp32 summation order and the rounding of (probability x value scale) to a hi + lo pair of 16-bit numbers; within mode 1 a row's
+ * result does not depend on the chunk or batch it sits in.  RANGE LIMIT of mode 1 on MIA_F16 handles: a V row whose max - min over a
+ * group of 64 reaches about 239 (4 bit) / 254 (8 bit) can overflow f16 inside the kernel and give inf / NaN outputs, which mode 0 and
+ * the 16-bit cache's kernels do not; MIA_BF16 handles have no such limit.  Any other mode: MIA_ERR_INVALID_ARGUMENT. */
+int mia_lm_set_kvq_prompt_attention(mia_lm* lm, int mode);
 void mia_lm_free(mia_lm* lm);
 int mia_lm_reset(mia_lm* lm);
 /* model(ids, cache) then logits[0,-1] (OrpheusTTS.swift:245-251,289): appends n ids to the KV cache, returns the fp32

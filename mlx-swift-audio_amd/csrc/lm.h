@@ -1,7 +1,8 @@
 // lm.h -- host-side interface between the LM decode sources: lm.hip (step kernels, prompt pass, step graph, entry points),
 // the samplers (lm_sample_top_p.hip: Orpheus top-p; lm_sample_ras.hip: CosyVoice2 RAS; lm_sample_topk.hip: Fun-ASR greedy and top-k / top-p;
 // their shared device code is lm_sample_device.h), lm_load.hip (checkpoint loader, state buffers, packed-weight attach) and lm_kvq.hip
-// (the quantised KV cache: its prompt-pass quantiser and its attention); lm_prefill_attn.hip (the prompt pass's tiled causal attention) reads it too.
+// (the quantised KV cache: its prompt-pass quantiser and its attention); lm_prefill_attn.hip and lm_prefill_attn_kvq.hip (the prompt pass's
+// tiled causal attention on the 16-bit and on the packed cache) read it too.
 #pragma once
 #include <vector>
 
@@ -71,6 +72,7 @@ struct mia_lm {
   int graph_mode = -1;                  // LM_STEP_* below
   int debug_flags = 0;                  // test hook (mia_lm_set_debug): bit 0 = no hipGraph, bit 1 = no batched prompt pass
   int prompt_attn = 0;                  // mia_lm_set_prompt_attention: 0 = the row kernel (lm_attention), 1 = lm_prefill_attn.hip on the 16-bit cache
+  int kvq_prompt_attn = 0;              // mia_lm_set_kvq_prompt_attention: 0 = the row kernel (lm_kvq_attention), 1 = lm_prefill_attn_kvq.hip on the packed cache
   int prompt_packed = 0;                // mia_lm_set_prompt_weights: 0 = the prompt pass multiplies the 16-bit copy (gemm.hip), 1 = the packed weights (gemm_quant.hip)
   bool dense_released = false;          // mia_lm_release_dense: the layers' 16-bit Linears and their fragment copies are gone; q4 and prompt_packed stay 1
   mia_lm_sampler graph_sampler{};
@@ -169,6 +171,10 @@ int lm_prefill_attn_qtile(int Hq, int Hkv);
 void lm_prefill_attn_tiles(const int2* rows, int M, int qtile, std::vector<int4>& tiles);
 const char* lm_prefill_attn_check(const LmPromptAttn& a);
 int lm_prefill_attn_launch(const LmPromptAttn& a, hipStream_t s);
+// ---- lm_prefill_attn_kvq.hip: the same attention over one layer's PACKED cache (the codes are the MFMA operands); `a` is the layer's
+// view (all sequences, the chunk's rows already written by lm_kvq_launch_rope_cache), q / out [M][Hq * dh], tiles as above (device)
+const char* lm_prefill_attn_kvq_check(const LmKvq& a, const uint16_t* q, const uint16_t* out, const int4* tiles, int n_tiles);
+int lm_prefill_attn_kvq_launch(const LmKvq& a, const uint16_t* q, uint16_t* out, const int4* tiles, int n_tiles, hipStream_t s);
 
 // ---- lm_load.hip ----
 // The packed-weight attach in two halves, so that a caller with several handles (marvis.hip: two stacks) packs all of them or none.

@@ -11,7 +11,7 @@
 // The prompt is consumed one position per step through the same graph (identical maths to a causal prefill).
 // This file: the step's row kernels next to their launch sites, the batched prompt pass, the step graph and the entry points; the
 // loader and the packed-weight attach are lm_load.hip, the prompt pass's optional tiled attention is lm_prefill_attn.hip
-// (mia_lm_set_prompt_attention), and lm.h is what the sources share.
+// (mia_lm_set_prompt_attention) and lm_prefill_attn_kvq.hip (mia_lm_set_kvq_prompt_attention), and lm.h is what the sources share.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -535,9 +535,11 @@ int lm_prefill_rows(mia_lm* m, const std::vector<int2>& rows, const std::vector<
   float* gu = (float*)b; b += b_gu;
   uint16_t* act = (uint16_t*)b; b += b_act;
   int2* rowmap = (int2*)b; b += b_map;
-  int4* tiles = (int4*)b;                          // query tiles of the chunk (prompt_attn 1 only)
-  // mia_lm_set_prompt_attention(1): the chunk's attention is lm_prefill_attn.hip's tiled kernel; the packed cache keeps lm_kvq's row kernel
-  const bool tiled = m->prompt_attn == 1 && !m->kv_bits;
+  int4* tiles = (int4*)b;                          // query tiles of the chunk (the tiled kernels only)
+  // mia_lm_set_prompt_attention(1): the chunk's attention is lm_prefill_attn.hip's tiled kernel on the 16-bit cache;
+  // mia_lm_set_kvq_prompt_attention(1): lm_prefill_attn_kvq.hip's on the packed cache.  Each switch is read only in its own cache mode
+  const bool tiled_q = m->kvq_prompt_attn == 1 && m->kv_bits;
+  const bool tiled = (m->prompt_attn == 1 && !m->kv_bits) || tiled_q;
   const int qtile = lm_prefill_attn_qtile(c.n_heads, c.n_kv_heads);
   std::vector<std::vector<int4>> chunk_tiles(tiled ? (rows.size() + PF_ROWS - 1) / PF_ROWS : 0);    // alive until the call returns, like `rows`
   // mia_lm_set_prompt_weights(1): the four GEMMs read the packed weights the step streams (gemm_quant.hip) -- the prompt's K/V rows then
@@ -577,7 +579,11 @@ int lm_prefill_rows(mia_lm* m, const std::vector<int2>& rows, const std::vector<
       if (gemm(h, D, L.wqkv, L.q_qkv, qkv, Nqkv, M, nullptr)) return MIA_ERR_DEVICE;
       lm_launch_rope_cache(m, l, qkv, L.bqkv, q, rowmap, M);
       if (l + 1 == c.n_layers) break;            // past its K/V rows the last layer feeds only the head, which the prompt pass skips
-      if (tiled) {
+      if (tiled_q) {
+        const LmKvq kq = lm_kvq_layer(m, l);
+        if (const char* e = lm_prefill_attn_kvq_check(kq, q, att, tiles, pa.n_tiles)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
+        if (lm_prefill_attn_kvq_launch(kq, q, att, tiles, pa.n_tiles, s)) return mia_fail(ctx, MIA_ERR_DEVICE, "lm: prompt attention launch failed");
+      } else if (tiled) {
         pa.kc = (const uint16_t*)m->k_cache + (size_t)l * m->B_cap * pa.seq_stride; pa.vc = (const uint16_t*)m->v_cache + (size_t)l * m->B_cap * pa.seq_stride;
         if (const char* e = lm_prefill_attn_check(pa)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
         if (lm_prefill_attn_launch(pa, s)) return mia_fail(ctx, MIA_ERR_DEVICE, "lm: prompt attention launch failed");
@@ -644,6 +650,16 @@ extern "C" int mia_lm_set_prompt_attention(mia_lm* m, int mode) {
   if (!m) return MIA_ERR_MODEL_NOT_LOADED;
   MIA_CHECK_ARG(m->ctx, mode == 0 || mode == 1, "lm_set_prompt_attention: mode must be 0 or 1 (got %d)", mode);
   m->prompt_attn = mode;
+  return MIA_OK;
+}
+
+// which attention the batched prompt pass runs on the PACKED cache (mia_lm_set_kv_quant): 0 = lm_kvq_attention, one workgroup per (query
+// head, row) -- the default; 1 = lm_prefill_attn_kvq.hip's tiled matrix-core kernel on the codes.  Independent of
+// mia_lm_set_prompt_attention; no effect while the cache is 16-bit; the cache writer and the step graph are not affected.
+extern "C" int mia_lm_set_kvq_prompt_attention(mia_lm* m, int mode) {
+  if (!m) return MIA_ERR_MODEL_NOT_LOADED;
+  MIA_CHECK_ARG(m->ctx, mode == 0 || mode == 1, "lm_set_kvq_prompt_attention: mode must be 0 or 1 (got %d)", mode);
+  m->kvq_prompt_attn = mode;
   return MIA_OK;
 }
 

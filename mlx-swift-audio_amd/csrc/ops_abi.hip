@@ -429,3 +429,35 @@ extern "C" int mia_op_lm_prompt_attention(mia_ctx* ctx, const void* q, const voi
   if (lm_prefill_attn_launch(a, ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_lm_prompt_attention: launch failed");
   return f.read(io, out, n, dtype);
 }
+
+// lm_prefill_attn_kvq.hip without a model around it: the same rows through the prompt pass's quantising cache writer (lm_kvq_rope_cache
+// with all rotation angles zero), then the tiled kernel over the codes.
+extern "C" int mia_op_lm_prompt_attention_kvq(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int n, int dh, int bits,
+                                              int dtype) {
+  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, q && k && v && out, "op_lm_prompt_attention_kvq: null pointer");
+  MIA_CHECK_ARG(ctx, dtype == MIA_BF16 || dtype == MIA_F16, "op_lm_prompt_attention_kvq: dtype must be MIA_BF16 or MIA_F16");
+  MIA_CHECK_ARG(ctx, Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq <= 1024 && n >= 1 && n <= T && T <= 8192, "op_lm_prompt_attention_kvq: bad shape (Hq %% Hkv == 0, 1 <= n <= T <= 8192)");
+  MIA_CHECK_ARG(ctx, bits == 4 || bits == 8, "op_lm_prompt_attention_kvq: bits must be 4 or 8 (got %d)", bits);
+  int code = MIA_OK;
+  if (const char* e = lm_kvq_check(bits, 64, dh, &code)) return mia_fail(ctx, code, "op_lm_prompt_attention_kvq: %s (bits %d, head_dim %d)", e, bits, dh);
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  LmOpRows f;
+  f.build(q, k, v, Hq, Hkv, T, n, dh, dtype);
+  std::vector<int4> tiles;
+  lm_prefill_attn_tiles(f.rowmap.data() + (T - n), n, lm_prefill_attn_qtile(Hq, Hkv), tiles);     // rows 0 .. n - 1 of q / att below
+  HostIo io = HostIo::device(ctx);
+  const size_t rows = (size_t)Hkv * T;
+  const size_t b_tiles = align_up(tiles.size() * sizeof(int4), 256), b_codes = align_up(rows * dh * bits / 8, 256), b_pairs = align_up(rows * (dh / 64) * 4, 256);
+  if (int rc = f.stage(ctx, io, Hq, Hkv, T, n, dh, dtype, b_tiles + 2 * b_codes + 2 * b_pairs, 0)) return rc;
+  const int4* d_tiles = io.table(tiles.data(), f.extra, tiles.size() * sizeof(int4));
+  char* d_kc = f.extra + b_tiles; char* d_vc = d_kc + b_codes; char* d_kp = d_vc + b_codes; char* d_vp = d_kp + b_pairs;
+  mia_lm& sh = f.sh;
+  sh.kv_bits = bits; sh.kq_codes = (uint32_t*)d_kc; sh.vq_codes = (uint32_t*)d_vc; sh.kq_pairs = (uint32_t*)d_kp; sh.vq_pairs = (uint32_t*)d_vp;
+  lm_launch_rope_cache(&sh, 0, f.d_part, nullptr, f.d_q, f.d_map, T);
+  const LmKvq a{dtype, dh, bits, Hq, Hkv, T, sh.kq_codes, sh.vq_codes, sh.kq_pairs, sh.vq_pairs, nullptr, sh.inv_freq};
+  const uint16_t* d_qn = f.d_q + (size_t)(T - n) * f.Nq;
+  if (const char* e = lm_prefill_attn_kvq_check(a, d_qn, f.d_att, d_tiles, (int)tiles.size())) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s", e);
+  if (lm_prefill_attn_kvq_launch(a, d_qn, f.d_att, d_tiles, (int)tiles.size(), ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_lm_prompt_attention_kvq: launch failed");
+  return f.read(io, out, n, dtype);
+}

@@ -50,6 +50,12 @@ class CausalLM:
         lib = self.ctx.lib
         self.ctx.check(lib.mia_lm_set_prompt_attention(self.h, int(mode)))
 
+    def set_kvq_prompt_attention(self, mode: int) -> None:
+        """mia_lm_set_kvq_prompt_attention: the prompt pass on the quantised cache -- 0 = its row kernel (default), 1 = the tiled
+        matrix-core kernel on the codes.  No effect while the cache is 16-bit.  On F16 handles mode 1 can overflow (inf / NaN) once a V
+        row's max - min over a group of 64 reaches about 239 (4 bit) / 254 (8 bit); BF16 handles have no such limit."""
+        self.ctx.check(self.ctx.lib.mia_lm_set_kvq_prompt_attention(self.h, int(mode)))
+
     def use_q4(self, on: bool) -> None:
         lib = self.ctx.lib
         self.ctx.check(lib.mia_lm_use_q4(self.h, 1 if on else 0))

@@ -189,6 +189,18 @@ def lm_prompt_attention(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.n
     return out
 
 
+def lm_prompt_attention_kvq(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.ndarray, bits: int = 4, dtype: int = _lib.BF16) -> np.ndarray:
+    """mia_op_lm_prompt_attention_kvq: lm_prompt_attention over the quantised cache (bits 4 | 8, groups of 64) the op fills from k / v:
+    the tiled kernel of lm_prefill_attn_kvq.hip, which multiplies the codes.  Same shapes.  (F16: see set_kvq_prompt_attention's range limit.)"""
+    lib = ctx.lib
+    n, Hq, dh = q.shape
+    Hkv, T, _ = k.shape
+    q16, k16, v16 = to16(q, dtype), to16(k, dtype), to16(v, dtype)
+    out = np.empty((n, Hq, dh), np.float32)
+    ctx.check(lib.mia_op_lm_prompt_attention_kvq(ctx.h, q16.ctypes.data, k16.ctypes.data, v16.ctypes.data, out.ctypes.data, Hq, Hkv, T, n, dh, int(bits), dtype))
+    return out
+
+
 def rfft_block(ctx: _lib.Context) -> int:
     """mia_op_rfft_block: the largest power-of-two transform one workgroup runs in LDS; larger ones take the four-step split."""
     return int(ctx.lib.mia_op_rfft_block())

@@ -244,13 +244,17 @@ class OuteTTS:
     apart.  The prompt repeats the whole speaker profile for every sentence (:327-340, about 1 900 ids for the bundled profile), so the
     constructor puts the handle's prompt pass on the tiled attention kernel; prompt_attention=None leaves the handle's mode alone.
     packed_prompt (True / False) forwards to CausalLM.set_prompt_weights -- the prompt pass on the attached packed weights -- and None,
-    the default, leaves the handle's mode alone."""
+    the default, leaves the handle's mode alone.  kv_bits 4 | 8 puts the handle on the quantised KV cache (newCache(quantized: true, bits:))
+    and its prompt pass on the tiled kernel that reads the codes; None touches neither."""
 
     def __init__(self, lm, dac, processor: OuteTTSPromptProcessor, eos_id: int, default_speaker: SpeakerProfile | None = None,
-                 prompt_attention: int | None = 1, packed_prompt: bool | None = None):
+                 prompt_attention: int | None = 1, packed_prompt: bool | None = None, kv_bits: int | None = None):
         self.lm, self.dac, self.processor, self.eos_id, self.default_speaker = lm, dac, processor, int(eos_id), default_speaker
         if prompt_attention is not None:
             lm.set_prompt_attention(prompt_attention)
+        if kv_bits is not None:
+            lm.new_cache(quantized=True, bits=kv_bits)
+            lm.set_kvq_prompt_attention(1)
         if packed_prompt is not None:
             lm.set_prompt_weights(packed_prompt)
 

@@ -25,6 +25,12 @@ the vocabulary head stays 16-bit) and attached to a handle loaded from the de-qu
 median / max in ms; max |delta| / sigma of the last-position logits between the two; weight_bytes() before and after release_dense(),
 and the packed prompt pass once more after the release.
 
+--kv-bits BITS measures the prompt pass on the quantised KV cache instead (and nothing else; BITS = 4 | 8): CausalLM.forward of 512, 2 087
+and 4 096 random ids (--lengths changes them) on one handle, set_kvq_prompt_attention off, then on, then off again -- one warm-up, then
+--repeats (>= 7) timed runs per reading, min / median / max in ms, clocks as found -- beside the 16-bit cache's tiled kernel from the same
+run; max |delta| / sigma of the last-position logits between the two modes; and generate_batch of 8 profile prompts up to the first
+token, timed the same way.
+
 --vocab: the reference reads the vocabulary size from the checkpoint's config.json; the default (128 256, Llama-3.2's) is an assumption."""
 import argparse
 import json
@@ -104,7 +110,7 @@ def speaker(seconds: float, n_words: int, seed: int):
 def packed_prompt(args):
     from mlx_swift_audio_amd import checkpoint as CK
     bits, reps = args.packed_prompt, max(7, args.repeats)
-    lengths = [int(x) for x in args.lengths] if args.lengths != [512, 4096] else [512, 2087, 4096]
+    lengths = [512, 2087, 4096] if args.lengths is None else [int(x) for x in args.lengths]
     cfg = dataclasses.replace(S.LM_CONFIGS["llama-3.2-1b"], vocab=args.vocab)
     ctx = m.Context(0)
     t0 = time.time()
@@ -151,6 +157,70 @@ def packed_prompt(args):
     print(json.dumps(res))
 
 
+def kv_bits(args):
+    bits, reps = args.kv_bits, max(7, args.repeats)
+    lengths = [512, 2087, 4096] if args.lengths is None else [int(x) for x in args.lengths]
+    cfg = dataclasses.replace(S.LM_CONFIGS["llama-3.2-1b"], vocab=args.vocab)
+    ctx = m.Context(0)
+    t0 = time.time()
+    model = HL.CausalLM.load(ctx, cfg, S.lm_weights(cfg, seed=args.seed, dtype=np.float16), m.BF16)
+    model.set_prompt_attention(1)                    # the 16-bit cache's tiled kernel, for the figures beside the packed cache's
+    print(f"[outetts] weights generated and loaded in {time.time() - t0:.1f}s", file=sys.stderr, flush=True)
+    rng = np.random.default_rng(args.seed)
+    proc, spk = R.processor(), R.seeded_speaker(args.seed, args.words, args.pairs)
+    B = 8
+    prompts = [proc.get_completion_prompt_tokens(f"Sentence number {b} of the batch.", spk) for b in range(B)]
+    ub = rng.random((B, 1)).astype(np.float32)
+    kw = dict(temperature=0.4, top_p=0.9, rep_penalty=OT.REPETITION_PENALTY, rep_window=OT.REPETITION_CONTEXT_SIZE, stop_ids=(cfg.vocab - 1,), max_new_tokens=1)
+
+    def median_ms(f):
+        ts = []
+        for i in range(reps + 1):                    # one warm-up
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            f()                                      # forward / generate_batch synchronise before they return
+            ts.append((time.perf_counter() - t) * 1e3)
+        return spread(ts[1:])
+
+    def forward(ids):
+        model.reset()
+        return model.forward(ids)
+
+    def off_on_off(f):
+        out = {}
+        for name, mode in (("off", 0), ("on", 1), ("off_again", 0)):
+            model.set_kvq_prompt_attention(mode)
+            out[name] = median_ms(f)
+        spread_off = abs(out["off"]["median"] - out["off_again"]["median"])
+        out["off_minus_on_median"] = round(min(out["off"]["median"], out["off_again"]["median"]) - out["on"]["median"], 3)
+        out["off_spread_median"] = round(spread_off, 3)
+        return out
+
+    res = {"model": "llama-3.2-1b", "vocab": cfg.vocab, "kv_bits": bits, "repeats": reps, "prompt_pass": {}}
+    ids_of = {n: rng.integers(0, cfg.vocab, n).tolist() for n in lengths}
+    for n in lengths:
+        res["prompt_pass"][str(n)] = {"rows": n, "cache16_tiled_ms": median_ms(lambda: forward(ids_of[n]))}
+    model.new_cache(quantized=True, bits=bits)
+    for n in lengths:
+        r = res["prompt_pass"][str(n)]
+        r.update(off_on_off(lambda: forward(ids_of[n])))
+        lg = {}
+        for mode in (0, 1):
+            model.set_kvq_prompt_attention(mode)
+            lg[mode] = forward(ids_of[n])
+        r["logits_max_delta_over_sigma"] = round(float(np.abs(lg[1] - lg[0]).max() / lg[0].std()), 5)
+        print(f"[outetts] kv-bits {bits} prompt pass {n}: {r}", file=sys.stderr, flush=True)
+    model.set_batch(B)
+    x8 = {"sequences": B, "prompt_rows": sum(len(p) - 1 for p in prompts)}
+    x8.update(off_on_off(lambda: model.generate_batch(prompts, ub, **kw)))
+    model.new_cache(quantized=False)
+    x8["cache16_tiled_ms"] = median_ms(lambda: model.generate_batch(prompts, ub, **kw))
+    res["prompts_plus_first_token_x8"] = x8
+    model.close()
+    ctx.close()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--vocab", type=int, default=128256, help="vocabulary size (an assumption: the checkpoint's config.json is not at hand)")
@@ -160,10 +230,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--new-tokens", type=int, default=128)
     ap.add_argument("--frames", type=int, default=300, help="DAC code frames to decode (75 per second)")
-    ap.add_argument("--lengths", type=int, nargs="*", default=[512, 4096])
+    ap.add_argument("--lengths", type=int, nargs="*", default=None, help="prompt lengths (default 512 4096; with --packed-prompt / --kv-bits 512 2087 4096)")
     ap.add_argument("--speaker", nargs=2, metavar=("SECONDS", "WORDS"), help="measure speaker-profile creation only")
     ap.add_argument("--packed-prompt", type=int, metavar="BITS", help="measure the prompt pass on packed weights only")
+    ap.add_argument("--kv-bits", type=int, choices=(4, 8), metavar="BITS", help="measure the prompt pass on the quantised KV cache only")
     args = ap.parse_args()
+    if args.kv_bits:
+        return kv_bits(args)
     if args.speaker:
         return speaker(float(args.speaker[0]), int(args.speaker[1]), args.seed)
     if args.packed_prompt:
@@ -189,7 +262,7 @@ def main():
         return (time.perf_counter() - t) * 1e3, lg
 
     passes = {}
-    for n in [len(prompt)] + [int(x) for x in args.lengths]:
+    for n in [len(prompt)] + ([512, 4096] if args.lengths is None else [int(x) for x in args.lengths]):
         ids = prompt if n == len(prompt) else rng.integers(0, R.VOCAB, n).tolist()
         lg = {mode: forward_ms(ids, mode)[1] for mode in (0, 1)}                 # warm-up of both modes at this length
         t = {0: [], 1: []}
