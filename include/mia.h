@@ -299,6 +299,16 @@ int mia_op_lm_prompt_attention(mia_ctx* ctx, const void* q, const void* k, const
 int mia_op_lm_prompt_attention_kvq(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int n,
                                    int dh, int bits, int dtype);
 
+/* The decode step's attention on the 16-bit cache without a model around it: one query row at position T - 1.  Rows 0 .. T - 2 of k / v
+ * [Hkv][T][dh] (`dtype`, taken as already rotated) go through the prompt pass's 16-bit cache writer; row T - 1 of q|k|v arrives as the
+ * step's q|k|v GEMM partial (one split-K slice, no bias, rotation angles zero), so the step's fused preamble runs and writes cache row
+ * T - 1 itself, at the position it reads from a state record.  mode 0: lm_attention's fused form, what the step runs by default; mode 1:
+ * the split-key pair of lm_step_attn.hip (see mia_lm_set_step_attention).  q [Hq][dh]; out fp32 [Hq][dh]: the 16-bit attention row
+ * widened.  HOST pointers.  dh 64 | 128, Hq % Hkv == 0, 1 <= T <= 8192, mode 0 | 1: anything else is MIA_ERR_INVALID_ARGUMENT; another
+ * head_dim, or mode 1 with more than 16 query heads per KV head: MIA_ERR_UNSUPPORTED. */
+int mia_op_lm_step_attention(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int dh, int mode,
+                             int dtype);
+
 /* Test hook: the LM decode step's skinny GEMMs (csrc/skinny.h: skinny_gemm_launch on 16-bit weights, skinny_gemm_q_launch on packed 4- /
  * 6- / 8-bit weights) with every launch argument exposed, so each kernel form the two launchers choose from the shape can be compared with a
  * reference on its own.  DEVICE pointers, enqueued on the context's stream.  A [M][lda] and the 16-bit outputs are in `dtype`
@@ -812,6 +822,17 @@ int mia_lm_set_prompt_attention(mia_lm* lm, int mode);
  * group of 64 reaches about 239 (4 bit) / 254 (8 bit) can overflow f16 inside the kernel and give inf / NaN outputs, which mode 0 and
  * the 16-bit cache's kernels do not; MIA_BF16 handles have no such limit.  Any other mode: MIA_ERR_INVALID_ARGUMENT. */
 int mia_lm_set_kvq_prompt_attention(mia_lm* lm, int mode);
+/* Which attention the DECODE STEP runs on the 16-bit cache.  0 (default): lm_attention, one workgroup per (query head, sequence), each
+ * walking its head's whole cache on the vector pipe.  1: the split-key pair of lm_step_attn.hip -- one workgroup per (KV head, sequence,
+ * slice of 256 keys anchored at key 0) attends for every query head of the KV group at once, Q K^T and P V on the matrix cores, and
+ * writes one fp32 (max, sum, accumulator) partial per head and slice; a second launch merges a head's live partials in ascending slice
+ * order.  The workgroup count grows with the context and a group's K / V are read once per step.  The partition depends on the
+ * sequence's position alone, so a sequence's bits do not depend on its batch, on the capacity or on graph versus direct launch; the two
+ * modes agree to the 16-bit rounding of the attention probabilities, not bit for bit.  The first mode-1 call allocates a workspace of
+ * capacity x n_heads x ceil(max_ctx / 256) x (head_dim + 2) floats, freed with the handle.  The call drops the captured step graph.  No
+ * effect while the cache is quantised (mia_lm_set_kv_quant); the prompt pass is not affected.  More than 16 query heads per KV head:
+ * MIA_ERR_UNSUPPORTED; a mode other than 0 | 1: MIA_ERR_INVALID_ARGUMENT. */
+int mia_lm_set_step_attention(mia_lm* lm, int mode);
 void mia_lm_free(mia_lm* lm);
 int mia_lm_reset(mia_lm* lm);
 /* model(ids, cache) then logits[0,-1] (OrpheusTTS.swift:245-251,289): appends n ids to the KV cache, returns the fp32

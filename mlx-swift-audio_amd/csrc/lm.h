@@ -2,7 +2,7 @@
 // the samplers (lm_sample_top_p.hip: Orpheus top-p; lm_sample_ras.hip: CosyVoice2 RAS; lm_sample_topk.hip: Fun-ASR greedy and top-k / top-p;
 // their shared device code is lm_sample_device.h), lm_load.hip (checkpoint loader, state buffers, packed-weight attach) and lm_kvq.hip
 // (the quantised KV cache: its prompt-pass quantiser and its attention); lm_prefill_attn.hip and lm_prefill_attn_kvq.hip (the prompt pass's
-// tiled causal attention on the 16-bit and on the packed cache) read it too.
+// tiled causal attention on the 16-bit and on the packed cache) and lm_step_attn.hip (the step's split-key attention) read it too.
 #pragma once
 #include <vector>
 
@@ -73,6 +73,8 @@ struct mia_lm {
   int debug_flags = 0;                  // test hook (mia_lm_set_debug): bit 0 = no hipGraph, bit 1 = no batched prompt pass
   int prompt_attn = 0;                  // mia_lm_set_prompt_attention: 0 = the row kernel (lm_attention), 1 = lm_prefill_attn.hip on the 16-bit cache
   int kvq_prompt_attn = 0;              // mia_lm_set_kvq_prompt_attention: 0 = the row kernel (lm_kvq_attention), 1 = lm_prefill_attn_kvq.hip on the packed cache
+  int step_attn = 0;                    // mia_lm_set_step_attention: 0 = lm_attention's fused form, 1 = lm_step_attn.hip's split-key pair on the 16-bit cache
+  float* step_ws = nullptr;             // mode 1's partials [B_cap][n_heads][ceil(max_ctx / 256)][dh + 2] (one of state_allocs: lm_alloc_state re-sizes it)
   int prompt_packed = 0;                // mia_lm_set_prompt_weights: 0 = the prompt pass multiplies the 16-bit copy (gemm.hip), 1 = the packed weights (gemm_quant.hip)
   bool dense_released = false;          // mia_lm_release_dense: the layers' 16-bit Linears and their fragment copies are gone; q4 and prompt_packed stay 1
   mia_lm_sampler graph_sampler{};
@@ -176,6 +178,24 @@ int lm_prefill_attn_launch(const LmPromptAttn& a, hipStream_t s);
 const char* lm_prefill_attn_kvq_check(const LmKvq& a, const uint16_t* q, const uint16_t* out, const int4* tiles, int n_tiles);
 int lm_prefill_attn_kvq_launch(const LmKvq& a, const uint16_t* q, uint16_t* out, const int4* tiles, int n_tiles, hipStream_t s);
 
+// ---- lm_step_attn.hip: the decode step's split-key attention over one layer's 16-bit cache, fused preamble included ----
+constexpr int LM_STEP_SLICE = 256;        // keys per workgroup, anchored at key 0
+constexpr int LM_STEP_MAX_GROUP = 16;     // query heads per KV head: the columns of one 16x16x32 MFMA
+struct LmStepAttn {
+  uint16_t* kc = nullptr; uint16_t* vc = nullptr;   // the layer's caches [nb][Hkv][max_ctx][dh]; row st[b].pos of sequence b is written here
+  uint16_t* out = nullptr;                // [nb][Hq * dh]
+  float* ws = nullptr;                    // [nb][Hq][ceil(max_ctx / 256)][dh + 2]: (m, l, acc[dh]) per (sequence, head, slice)
+  const LmState* st = nullptr;            // [nb]
+  const float* part = nullptr; int S = 1; // q|k|v GEMM slices [S][nb][(Hq + 2 Hkv) dh], S <= 4
+  const float* bias = nullptr; const float* inv_freq = nullptr;
+  const float* qkn = nullptr; float qk_eps = 0.f;   // per-head q / k RMSNorm gains [2][dh] or null
+  int nb = 0, Hq = 0, Hkv = 0, dh = 0, max_ctx = 0, dtype = MIA_BF16;
+};
+inline int lm_step_attn_slices(int max_ctx) { return (max_ctx + LM_STEP_SLICE - 1) / LM_STEP_SLICE; }
+inline size_t lm_step_attn_ws_floats(int nb, int Hq, int max_ctx, int dh) { return (size_t)nb * Hq * lm_step_attn_slices(max_ctx) * (dh + 2); }
+// null when the shape is served, else the message (head_dim 64 | 128, at most LM_STEP_MAX_GROUP query heads per KV head)
+const char* lm_step_attn_check(int Hq, int Hkv, int dh);
+int lm_step_attn_launch(const LmStepAttn& a, hipStream_t s);
 // ---- lm_load.hip ----
 // The packed-weight attach in two halves, so that a caller with several handles (marvis.hip: two stacks) packs all of them or none.
 // lm_attach_prepare checks the arguments and the tensors, repacks and uploads every step Linear into `out` and changes nothing of the

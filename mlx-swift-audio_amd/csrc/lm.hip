@@ -387,6 +387,13 @@ int lm_launch_attention(mia_lm* m, bool fused, int rows, const void* q, int laye
   uint16_t* kc = (uint16_t*)m->k_cache + (size_t)layer * m->B_cap * seq_stride;
   uint16_t* vc = (uint16_t*)m->v_cache + (size_t)layer * m->B_cap * seq_stride;
   const int dh = c.head_dim;
+  if (fused && m->step_attn == 1) {       // mia_lm_set_step_attention(1): lm_step_attn.hip's split-key pair, the same preamble inside
+    LmStepAttn a;
+    a.kc = kc; a.vc = vc; a.out = (uint16_t*)att; a.ws = m->step_ws; a.st = m->state; a.part = part; a.S = S; a.bias = bias; a.inv_freq = m->inv_freq;
+    a.qkn = m->qk_norm ? m->qk_norm + (size_t)layer * 2 * dh : nullptr; a.qk_eps = c.rms_eps;
+    a.nb = rows; a.Hq = c.n_heads; a.Hkv = c.n_kv_heads; a.dh = dh; a.max_ctx = c.max_ctx; a.dtype = m->dtype;
+    return lm_step_attn_launch(a, s);
+  }
   const size_t lds = (size_t)(c.max_ctx + ATT_NW * dh + 2 * ATT_NW + 3 * dh) * 4;
   const float scale = 1.0f / sqrtf((float)dh);
   const dim3 grid(c.n_heads, rows), block(64 * ATT_NW);
@@ -445,14 +452,14 @@ int lm_enqueue_layers(mia_lm* m, int nb) {
     if (fused_norm) {
       // layer 0 reads the embedding kernel's (normalised) h; later layers the previous down-proj's x * norm weight + its sums of squares
       if (skinny(m->h, D, L.wqkv, L.wqkv_f, nullptr, m->qkv_part, 0, Nqkv, D, m->S_qkv, SK_PARTIAL, &L.q_qkv, l > 0 ? ss_d : nullptr, nullptr, nullptr, L.in_rs)) return -1;
-      lm_launch_attention(m, true, nb, nullptr, l, m->att, nullptr, m->qkv_part, m->S_qkv, L.bqkv);      // RoPE + cache row + attention
+      if (lm_launch_attention(m, true, nb, nullptr, l, m->att, nullptr, m->qkv_part, m->S_qkv, L.bqkv)) return -1;      // RoPE + cache row + attention
       if (skinny(m->att, Nq, L.wo, L.wo_f, nullptr, m->h, D, D, Nq, 1, SK_RESID, &L.q_o, nullptr, L.post_norm_c, ss_o)) return -1;
       if (skinny(m->h, D, L.wgu, L.wgu_f, nullptr, m->act, c.inter, 2 * c.inter, D, 1, SK_SWIGLU, &L.q_gu, ss_o, nullptr, nullptr, L.post_rs)) return -1;
       if (skinny(m->act, c.inter, L.wdown, L.wdown_f, nullptr, m->h, D, D, c.inter, 1, SK_RESID, &L.q_down, nullptr, next_norm_c, ss_d)) return -1;
       continue;
     }
     if (skinny(m->h, D, L.wqkv, L.wqkv_f, nullptr, m->qkv_part, 0, Nqkv, D, m->S_qkv, SK_PARTIAL, &L.q_qkv)) return -1;
-    lm_launch_attention(m, true, nb, nullptr, l, m->att, nullptr, m->qkv_part, m->S_qkv, L.bqkv);      // RoPE + cache row + attention
+    if (lm_launch_attention(m, true, nb, nullptr, l, m->att, nullptr, m->qkv_part, m->S_qkv, L.bqkv)) return -1;      // RoPE + cache row + attention
     if (skinny(m->att, Nq, L.wo, L.wo_f, nullptr, m->partial, 0, D, Nq, m->S_o, SK_PARTIAL, &L.q_o)) return -1;
     LAUNCH_T(lm_reduce_norm, dim3(nb), dim3(256), 0, m->partial, m->S_o, L.post_norm, m->x, (uint16_t*)m->h, D, c.rms_eps, nb);
     if (skinny(m->h, D, L.wgu, L.wgu_f, nullptr, m->act, c.inter, 2 * c.inter, D, 1, SK_SWIGLU, &L.q_gu)) return -1;
@@ -660,6 +667,30 @@ extern "C" int mia_lm_set_kvq_prompt_attention(mia_lm* m, int mode) {
   if (!m) return MIA_ERR_MODEL_NOT_LOADED;
   MIA_CHECK_ARG(m->ctx, mode == 0 || mode == 1, "lm_set_kvq_prompt_attention: mode must be 0 or 1 (got %d)", mode);
   m->kvq_prompt_attn = mode;
+  return MIA_OK;
+}
+
+// which attention the DECODE STEP runs on the 16-bit cache: 0 = lm_attention's fused form, one workgroup per (query head, sequence) -- the
+// default; 1 = lm_step_attn.hip's pair, one workgroup per (KV head, sequence, 256-key slice) on the matrix cores plus a merge.  The graph
+// key does not hold the mode, so the captured step is dropped here; read only while the cache is 16-bit (lm_launch_attention)
+extern "C" int mia_lm_set_step_attention(mia_lm* m, int mode) {
+  if (!m) return MIA_ERR_MODEL_NOT_LOADED;
+  mia_ctx* ctx = m->ctx;
+  MIA_CHECK_ARG(ctx, mode == 0 || mode == 1, "lm_set_step_attention: mode must be 0 or 1 (got %d)", mode);
+  const mia_lm_config& c = m->cfg;
+  if (mode == 1)
+    if (const char* e = lm_step_attn_check(c.n_heads, c.n_kv_heads, c.head_dim))
+      return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "lm_set_step_attention: %s (n_heads %d, n_kv_heads %d, head_dim %d)", e, c.n_heads, c.n_kv_heads, c.head_dim);
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (mode == 1 && !m->step_ws) {
+    void* p = nullptr;
+    if (hipMalloc(&p, lm_step_attn_ws_floats(m->B_cap, c.n_heads, c.max_ctx, c.head_dim) * 4) != hipSuccess)
+      return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "lm_set_step_attention: workspace for %d sequences", m->B_cap);
+    m->state_allocs.push_back(p); m->step_ws = (float*)p;
+  }
+  if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; }
+  m->step_attn = mode;
   return MIA_OK;
 }
 

@@ -430,6 +430,38 @@ extern "C" int mia_op_lm_prompt_attention(mia_ctx* ctx, const void* q, const voi
   return f.read(io, out, n, dtype);
 }
 
+// The decode step's attention without a model around it: rows 0 .. T - 2 of K / V go through the prompt pass's 16-bit cache writer as
+// above; row T - 1 of q|k|v is handed over as the step's GEMM partial (one slice, no bias), so the fused preamble finishes the q row and
+// the new K / V row and writes cache row T - 1 at the position it reads from the state record.  mode 0: lm_attention<.., FUSED = true>,
+// mode 1: lm_step_attn.hip's split-key pair -- both through lm_launch_attention, as the step launches them.
+extern "C" int mia_op_lm_step_attention(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int dh, int mode, int dtype) {
+  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, q && k && v && out, "op_lm_step_attention: null pointer");
+  MIA_CHECK_ARG(ctx, dtype == MIA_BF16 || dtype == MIA_F16, "op_lm_step_attention: dtype must be MIA_BF16 or MIA_F16");
+  MIA_CHECK_ARG(ctx, Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq <= 1024 && T >= 1 && T <= 8192, "op_lm_step_attention: bad shape (Hq %% Hkv == 0, 1 <= T <= 8192)");
+  MIA_CHECK_ARG(ctx, mode == 0 || mode == 1, "op_lm_step_attention: mode must be 0 or 1 (got %d)", mode);
+  if (dh != 64 && dh != 128) return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "op_lm_step_attention: head_dim %d (64 or 128)", dh);
+  if (mode == 1)
+    if (const char* e = lm_step_attn_check(Hq, Hkv, dh)) return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "op_lm_step_attention: %s (Hq %d, Hkv %d)", e, Hq, Hkv);
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  LmOpRows f;
+  f.build(q, k, v, Hq, Hkv, T, 1, dh, dtype);
+  LmState st{};
+  st.pos = T - 1;
+  HostIo io = HostIo::device(ctx);
+  const size_t b_st = align_up(sizeof(LmState), 256), b_cache = align_up((size_t)Hkv * T * dh * 2, 256),
+               b_ws = mode == 1 ? align_up(lm_step_attn_ws_floats(1, Hq, T, dh) * 4, 256) : 0;
+  if (int rc = f.stage(ctx, io, Hq, Hkv, T, 1, dh, dtype, b_st + 2 * b_cache + b_ws, 0)) return rc;
+  mia_lm& sh = f.sh;
+  sh.state = const_cast<LmState*>(io.table(&st, f.extra, sizeof(LmState)));
+  sh.k_cache = f.extra + b_st; sh.v_cache = f.extra + b_st + b_cache;
+  sh.step_attn = mode; sh.step_ws = (float*)(f.extra + b_st + 2 * b_cache);
+  if (T > 1) lm_launch_rope_cache(&sh, 0, f.d_part, nullptr, f.d_q, f.d_map, T - 1);
+  if (lm_launch_attention(&sh, true, 1, nullptr, 0, f.d_att, nullptr, f.d_part + (size_t)(T - 1) * f.N, 1, nullptr) || hipGetLastError() != hipSuccess)
+    return mia_fail(ctx, MIA_ERR_DEVICE, "op_lm_step_attention: launch failed");
+  return f.read(io, out, 1, dtype);
+}
+
 // lm_prefill_attn_kvq.hip without a model around it: the same rows through the prompt pass's quantising cache writer (lm_kvq_rope_cache
 // with all rotation angles zero), then the tiled kernel over the codes.
 extern "C" int mia_op_lm_prompt_attention_kvq(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int n, int dh, int bits,

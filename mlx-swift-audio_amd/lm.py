@@ -56,6 +56,12 @@ class CausalLM:
         row's max - min over a group of 64 reaches about 239 (4 bit) / 254 (8 bit); BF16 handles have no such limit."""
         self.ctx.check(self.ctx.lib.mia_lm_set_kvq_prompt_attention(self.h, int(mode)))
 
+    def set_step_attention(self, on: bool) -> None:
+        """mia_lm_set_step_attention: the decode step's attention on the 16-bit cache -- False = one workgroup per (query head, sequence)
+        (default), True = the split-key matrix-core pair of lm_step_attn.hip (one workgroup per KV head, sequence and 256-key slice, then a
+        merge).  No effect while the cache is quantised.  More than 16 query heads per KV head: ERR_UNSUPPORTED."""
+        self.ctx.check(self.ctx.lib.mia_lm_set_step_attention(self.h, 1 if on else 0))
+
     def use_q4(self, on: bool) -> None:
         lib = self.ctx.lib
         self.ctx.check(lib.mia_lm_use_q4(self.h, 1 if on else 0))
@@ -377,8 +383,10 @@ class OrpheusTTS:
     """generateChunk (TTS/Orpheus/TTSEngine/OrpheusTTS.swift:224-373) from token ids onward: LM sampling loop ->
     parseOutput -> SNAC decode.  Text tokenisation / voice prefix / sentence splitting stay with the caller (CPU text code)."""
 
-    def __init__(self, lm: CausalLM, snac, kv_bits: int | None = None, packed_prompt: bool | None = None):
+    def __init__(self, lm: CausalLM, snac, kv_bits: int | None = None, packed_prompt: bool | None = None, split_step: bool = False):
         self.lm, self.snac = lm, snac
+        if split_step:                               # the decode step on the split-key attention (CausalLM.set_step_attention); False leaves the handle's mode alone
+            lm.set_step_attention(True)
         if packed_prompt is not None:                # the prompt pass on the attached packed weights (CausalLM.set_prompt_weights); None leaves the handle's mode alone
             lm.set_prompt_weights(packed_prompt)
         if kv_bits is not None:                      # newCache(quantized: kv_bits != 0, bits: kv_bits); None leaves the handle's mode alone

@@ -201,6 +201,18 @@ def lm_prompt_attention_kvq(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: 
     return out
 
 
+def lm_step_attention(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.ndarray, mode: int = 1, dtype: int = _lib.BF16) -> np.ndarray:
+    """mia_op_lm_step_attention: the decode step's attention for the last of T positions.  k / v [Hkv, T, dh] (fp32 here, rounded to
+    `dtype`): rows 0 .. T - 2 are cached, row T - 1 arrives with q [Hq, dh] as the step's q|k|v partial, so the fused preamble and the
+    cache-row write run.  mode 0 = lm_attention's fused form, 1 = the split-key pair of lm_step_attn.hip.  Returns fp32 [Hq, dh]."""
+    Hq, dh = q.shape
+    Hkv, T, _ = k.shape
+    q16, k16, v16 = to16(q, dtype), to16(k, dtype), to16(v, dtype)
+    out = np.empty((Hq, dh), np.float32)
+    ctx.check(ctx.lib.mia_op_lm_step_attention(ctx.h, q16.ctypes.data, k16.ctypes.data, v16.ctypes.data, out.ctypes.data, Hq, Hkv, T, dh, int(mode), dtype))
+    return out
+
+
 def rfft_block(ctx: _lib.Context) -> int:
     """mia_op_rfft_block: the largest power-of-two transform one workgroup runs in LDS; larger ones take the four-step split."""
     return int(ctx.lib.mia_op_rfft_block())

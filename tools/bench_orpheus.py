@@ -3,7 +3,9 @@
 64-token prompt (argv[3] changes it).  Prints one JSON line: prompt-pass time, ms per generated token, fraction of the HBM roofline
 (6.6 GB of weights per token), SNAC samples/s.  --kv-bits {0,4,8} (anywhere on the line) selects the KV cache: 0 = 16-bit (default),
 4 | 8 = quantised, group 64 (CausalLM.new_cache); the line then also carries the cache's byte model -- K/V bytes read per step at the
-mean context of the timed run, and that stream over the measured step time as a fraction of the 8 TB/s HBM peak."""
+mean context of the timed run, and that stream over the measured step time as a fraction of the 8 TB/s HBM peak.  --split-step measures
+the decode step instead (and nothing else): ms per generated token behind prompts of 300 and 1 200 random ids, and ms per step with 8
+and 32 sentences of 300 ids side by side, CausalLM.set_step_attention off, then on, then off again (tools/_split_step_bench.py)."""
 import json
 import os
 import sys
@@ -25,6 +27,9 @@ if "--kv-bits" in sys.argv:
     del sys.argv[i:i + 2]
     if kv_bits not in (0, 4, 8):
         sys.exit("--kv-bits must be 0, 4 or 8")
+split_step = "--split-step" in sys.argv
+if split_step:
+    sys.argv.remove("--split-step")
 name = sys.argv[1] if len(sys.argv) > 1 else "orpheus-3b"
 n_new = int(sys.argv[2]) if len(sys.argv) > 2 else 210
 cfg = S.LM_CONFIGS[name]
@@ -51,6 +56,13 @@ if q4:
     del packed
 if kv_bits:
     model.new_cache(quantized=True, bits=kv_bits)
+if split_step:                                   # the decode step with set_step_attention off / on / off again, and nothing else
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import _split_step_bench as SB
+    res = {"model": name, "dtype": "bf16", "weights": "mlx-affine q4 g64 (packed step)" if q4 else "bf16"}
+    res.update(SB.measure(model, cfg, (300, 1200), (8, 32), 300, 65, 7, 0, lambda s: print("[orpheus] " + s, file=sys.stderr, flush=True)))
+    print(json.dumps(res))
+    sys.exit(0)
 # K/V bytes per cached token per sequence: codes + one 16-bit (scale, bias) pair per 64 values, or 16-bit values
 kv_row = cfg.head_dim * kv_bits // 8 + cfg.head_dim // 64 * 4 if kv_bits else cfg.head_dim * 2
 kv_bytes_per_token = cfg.n_layers * 2 * cfg.n_kv_heads * kv_row

@@ -31,6 +31,10 @@ and 4 096 random ids (--lengths changes them) on one handle, set_kvq_prompt_atte
 run; max |delta| / sigma of the last-position logits between the two modes; and generate_batch of 8 profile prompts up to the first
 token, timed the same way.
 
+--split-step measures the decode step instead (and nothing else): ms per generated token behind prompts of 512, 2 087 and 4 096 random
+ids (--lengths changes them), and ms per step with 8 and 32 sentences of 2 087 ids side by side, CausalLM.set_step_attention off, then
+on, then off again on one handle -- tools/_split_step_bench.py states how a reading is taken.
+
 --vocab: the reference reads the vocabulary size from the checkpoint's config.json; the default (128 256, Llama-3.2's) is an assumption."""
 import argparse
 import json
@@ -221,6 +225,23 @@ def kv_bits(args):
     print(json.dumps(res))
 
 
+def split_step(args):
+    import _split_step_bench as SB
+    lengths = [512, 2087, 4096] if args.lengths is None else [int(x) for x in args.lengths]
+    cfg = dataclasses.replace(S.LM_CONFIGS["llama-3.2-1b"], vocab=args.vocab)
+    ctx = m.Context(0)
+    t0 = time.time()
+    model = HL.CausalLM.load(ctx, cfg, S.lm_weights(cfg, seed=args.seed, dtype=np.float16), m.BF16)
+    model.set_prompt_attention(1)
+    print(f"[outetts] weights generated and loaded in {time.time() - t0:.1f}s", file=sys.stderr, flush=True)
+    res = {"model": "llama-3.2-1b", "vocab": cfg.vocab, "dtype": "bf16"}
+    res.update(SB.measure(model, cfg, lengths, (8, 32), 2087, 65, max(7, args.repeats), args.seed,
+                          lambda s: print("[outetts] " + s, file=sys.stderr, flush=True)))
+    model.close()
+    ctx.close()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--vocab", type=int, default=128256, help="vocabulary size (an assumption: the checkpoint's config.json is not at hand)")
@@ -234,7 +255,10 @@ def main():
     ap.add_argument("--speaker", nargs=2, metavar=("SECONDS", "WORDS"), help="measure speaker-profile creation only")
     ap.add_argument("--packed-prompt", type=int, metavar="BITS", help="measure the prompt pass on packed weights only")
     ap.add_argument("--kv-bits", type=int, choices=(4, 8), metavar="BITS", help="measure the prompt pass on the quantised KV cache only")
+    ap.add_argument("--split-step", action="store_true", help="measure the decode step with set_step_attention off / on / off again only")
     args = ap.parse_args()
+    if args.split_step:
+        return split_step(args)
     if args.kv_bits:
         return kv_bits(args)
     if args.speaker:
