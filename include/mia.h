@@ -309,6 +309,14 @@ int mia_op_lm_prompt_attention_kvq(mia_ctx* ctx, const void* q, const void* k, c
 int mia_op_lm_step_attention(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int dh, int mode,
                              int dtype);
 
+/* The same over the packed cache (see mia_lm_set_kvq_step_attention): rows 0 .. T - 2 go through the prompt pass's quantising cache writer
+ * (bits 4 | 8, groups of 64); row T - 1 arrives as the step's partial, so the fused preamble and the quantising row write run and the new
+ * row is attended as the values read back.  mode 0: lm_kvq_attention's fused form; mode 1: the split over the codes of
+ * lm_step_attn_kvq.hip plus the merge of lm_step_attn.hip.  Shapes, pointers and errors as above; bits outside {4, 8}:
+ * MIA_ERR_INVALID_ARGUMENT. */
+int mia_op_lm_step_attention_kvq(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int dh,
+                                 int bits, int mode, int dtype);
+
 /* Test hook: the LM decode step's skinny GEMMs (csrc/skinny.h: skinny_gemm_launch on 16-bit weights, skinny_gemm_q_launch on packed 4- /
  * 6- / 8-bit weights) with every launch argument exposed, so each kernel form the two launchers choose from the shape can be compared with a
  * reference on its own.  DEVICE pointers, enqueued on the context's stream.  A [M][lda] and the 16-bit outputs are in `dtype`
@@ -830,9 +838,20 @@ int mia_lm_set_kvq_prompt_attention(mia_lm* lm, int mode);
  * sequence's position alone, so a sequence's bits do not depend on its batch, on the capacity or on graph versus direct launch; the two
  * modes agree to the 16-bit rounding of the attention probabilities, not bit for bit.  The first mode-1 call allocates a workspace of
  * capacity x n_heads x ceil(max_ctx / 256) x (head_dim + 2) floats, freed with the handle.  The call drops the captured step graph.  No
- * effect while the cache is quantised (mia_lm_set_kv_quant); the prompt pass is not affected.  More than 16 query heads per KV head:
- * MIA_ERR_UNSUPPORTED; a mode other than 0 | 1: MIA_ERR_INVALID_ARGUMENT. */
+ * effect while the cache is quantised (mia_lm_set_kv_quant): there mia_lm_set_kvq_step_attention chooses; the prompt pass is not
+ * affected.  More than 16 query heads per KV head: MIA_ERR_UNSUPPORTED; a mode other than 0 | 1: MIA_ERR_INVALID_ARGUMENT. */
 int mia_lm_set_step_attention(mia_lm* lm, int mode);
+/* The same choice for the decode step on the PACKED cache (mia_lm_set_kv_quant(bits 4 | 8)), a switch of its own.  0 (default):
+ * lm_kvq_attention's fused form, one workgroup per (query head, sequence), each de-quantising its head's whole cache on the vector
+ * pipe.  1: the split of lm_step_attn_kvq.hip -- the work split of mia_lm_set_step_attention's mode 1, with the codes as the
+ * matrix-core operands and scale and bias applied in fp32 around the MFMAs, so a cached row is unpacked once per KV group -- then the
+ * same merge launch.  The new row's codes and pairs are bit for bit mode 0's; the attention rows agree to fp32 summation order and the
+ * rounding of (probability x value scale) to a hi + lo pair of 16-bit numbers.  Batch equals single and graph equals direct launch bit
+ * for bit.  Shares mode 1's workspace with mia_lm_set_step_attention (same size, allocated by whichever asks first) and drops the
+ * captured step graph.  No effect while the cache is 16-bit.  RANGE LIMIT on MIA_F16 handles: a V row whose max - min over a group of
+ * 64 reaches 61 410 (4 bit) / 65 248 (8 bit) overflows f16 inside the kernel; MIA_BF16 handles have no such limit.  Errors as
+ * mia_lm_set_step_attention. */
+int mia_lm_set_kvq_step_attention(mia_lm* lm, int mode);
 void mia_lm_free(mia_lm* lm);
 int mia_lm_reset(mia_lm* lm);
 /* model(ids, cache) then logits[0,-1] (OrpheusTTS.swift:245-251,289): appends n ids to the KV cache, returns the fp32

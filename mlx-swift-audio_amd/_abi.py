@@ -284,6 +284,7 @@ PROTOTYPES = {
     "mia_op_lm_prompt_attention": (i32, [vp, vp, vp, vp, vp] + [i32] * 6),
     "mia_op_lm_prompt_attention_kvq": (i32, [vp, vp, vp, vp, vp] + [i32] * 7),
     "mia_op_lm_step_attention": (i32, [vp, vp, vp, vp, vp] + [i32] * 6),
+    "mia_op_lm_step_attention_kvq": (i32, [vp, vp, vp, vp, vp] + [i32] * 7),
     "mia_op_skinny_gemm": (i32, [vp, P(SkinnyDesc)]),
     "mia_op_gemm_quant": (i32, [vp, vp]),
     # Whisper
@@ -392,6 +393,7 @@ PROTOTYPES = {
     "mia_lm_set_prompt_attention": (i32, [vp, i32]),
     "mia_lm_set_kvq_prompt_attention": (i32, [vp, i32]),
     "mia_lm_set_step_attention": (i32, [vp, i32]),
+    "mia_lm_set_kvq_step_attention": (i32, [vp, i32]),
     "mia_lm_free": (None, [vp]),
     "mia_lm_reset": (i32, [vp]),
     "mia_lm_forward": (i32, [vp, vp, i32, vp]),

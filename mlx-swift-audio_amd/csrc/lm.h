@@ -2,7 +2,7 @@
 // the samplers (lm_sample_top_p.hip: Orpheus top-p; lm_sample_ras.hip: CosyVoice2 RAS; lm_sample_topk.hip: Fun-ASR greedy and top-k / top-p;
 // their shared device code is lm_sample_device.h), lm_load.hip (checkpoint loader, state buffers, packed-weight attach) and lm_kvq.hip
 // (the quantised KV cache: its prompt-pass quantiser and its attention); lm_prefill_attn.hip and lm_prefill_attn_kvq.hip (the prompt pass's
-// tiled causal attention on the 16-bit and on the packed cache) and lm_step_attn.hip (the step's split-key attention) read it too.
+// tiled causal attention on the 16-bit and on the packed cache) and lm_step_attn.hip / lm_step_attn_kvq.hip (the step's split-key attention on either cache) read it too.
 #pragma once
 #include <vector>
 
@@ -74,7 +74,8 @@ struct mia_lm {
   int prompt_attn = 0;                  // mia_lm_set_prompt_attention: 0 = the row kernel (lm_attention), 1 = lm_prefill_attn.hip on the 16-bit cache
   int kvq_prompt_attn = 0;              // mia_lm_set_kvq_prompt_attention: 0 = the row kernel (lm_kvq_attention), 1 = lm_prefill_attn_kvq.hip on the packed cache
   int step_attn = 0;                    // mia_lm_set_step_attention: 0 = lm_attention's fused form, 1 = lm_step_attn.hip's split-key pair on the 16-bit cache
-  float* step_ws = nullptr;             // mode 1's partials [B_cap][n_heads][ceil(max_ctx / 256)][dh + 2] (one of state_allocs: lm_alloc_state re-sizes it)
+  int kvq_step_attn = 0;                // mia_lm_set_kvq_step_attention: 0 = lm_kvq_attention's fused form, 1 = lm_step_attn_kvq.hip's split-key pair on the packed cache
+  float* step_ws = nullptr;             // either mode 1's partials [B_cap][n_heads][ceil(max_ctx / 256)][dh + 2] (one of state_allocs: lm_alloc_state re-sizes it)
   int prompt_packed = 0;                // mia_lm_set_prompt_weights: 0 = the prompt pass multiplies the 16-bit copy (gemm.hip), 1 = the packed weights (gemm_quant.hip)
   bool dense_released = false;          // mia_lm_release_dense: the layers' 16-bit Linears and their fragment copies are gone; q4 and prompt_packed stay 1
   mia_lm_sampler graph_sampler{};
@@ -196,6 +197,22 @@ inline size_t lm_step_attn_ws_floats(int nb, int Hq, int max_ctx, int dh) { retu
 // null when the shape is served, else the message (head_dim 64 | 128, at most LM_STEP_MAX_GROUP query heads per KV head)
 const char* lm_step_attn_check(int Hq, int Hkv, int dh);
 int lm_step_attn_launch(const LmStepAttn& a, hipStream_t s);
+// lm_step_attn_combine alone: merges the partials in a.ws into a.out (reads st, ws, out and the shape only)
+int lm_step_attn_combine_launch(const LmStepAttn& a, hipStream_t s);
+// ---- lm_step_attn_kvq.hip: the same split over one layer's PACKED cache (the codes are the MFMA operands), fused preamble and the
+// quantising row write included; the partials have LmStepAttn's layout and size and are merged by lm_step_attn_combine ----
+struct LmStepAttnKvq {
+  uint32_t* kq = nullptr; uint32_t* vq = nullptr; uint32_t* kp = nullptr; uint32_t* vp = nullptr;   // the layer's codes and pairs, all sequences; row st[b].pos is written here
+  uint16_t* out = nullptr;                // [nb][Hq * dh]
+  float* ws = nullptr;                    // [nb][Hq][ceil(max_ctx / 256)][dh + 2]
+  const LmState* st = nullptr;            // [nb]
+  const float* part = nullptr; int S = 1; // q|k|v GEMM slices [S][nb][(Hq + 2 Hkv) dh], S <= 4
+  const float* bias = nullptr; const float* inv_freq = nullptr;
+  int nb = 0, Hq = 0, Hkv = 0, dh = 0, bits = 0, max_ctx = 0, dtype = MIA_BF16;
+};
+// null when the shape is served (lm_step_attn_check's rules, bits 4 | 8)
+const char* lm_step_attn_kvq_check(int Hq, int Hkv, int dh, int bits);
+int lm_step_attn_kvq_launch(const LmStepAttnKvq& a, hipStream_t s);
 // ---- lm_load.hip ----
 // The packed-weight attach in two halves, so that a caller with several handles (marvis.hip: two stacks) packs all of them or none.
 // lm_attach_prepare checks the arguments and the tensors, repacks and uploads every step Linear into `out` and changes nothing of the

@@ -382,6 +382,13 @@ int lm_launch_attention(mia_lm* m, bool fused, int rows, const void* q, int laye
   // fused: rows = sequences (row b uses state b and the b-th cache of the layer); otherwise rows = (sequence, position) pairs
   const mia_lm_config& c = m->cfg;
   hipStream_t s = m->ctx->stream;
+  if (m->kv_bits && fused && m->kvq_step_attn == 1) {      // mia_lm_set_kvq_step_attention(1): lm_step_attn_kvq.hip's split-key pair on the codes
+    const LmKvq k = lm_kvq_layer(m, layer);
+    LmStepAttnKvq a;
+    a.kq = k.kq; a.vq = k.vq; a.kp = k.kp; a.vp = k.vp; a.out = (uint16_t*)att; a.ws = m->step_ws; a.st = m->state; a.part = part; a.S = S; a.bias = bias;
+    a.inv_freq = m->inv_freq; a.nb = rows; a.Hq = c.n_heads; a.Hkv = c.n_kv_heads; a.dh = c.head_dim; a.bits = m->kv_bits; a.max_ctx = c.max_ctx; a.dtype = m->dtype;
+    return lm_step_attn_kvq_launch(a, s);
+  }
   if (m->kv_bits) { lm_kvq_launch_attention(s, lm_kvq_layer(m, layer), fused, rows, (const uint16_t*)q, (uint16_t*)att, rowmap, part, S, bias); return 0; }
   const int64_t seq_stride = (int64_t)c.n_kv_heads * c.max_ctx * c.head_dim;
   uint16_t* kc = (uint16_t*)m->k_cache + (size_t)layer * m->B_cap * seq_stride;
@@ -673,26 +680,33 @@ extern "C" int mia_lm_set_kvq_prompt_attention(mia_lm* m, int mode) {
 // which attention the DECODE STEP runs on the 16-bit cache: 0 = lm_attention's fused form, one workgroup per (query head, sequence) -- the
 // default; 1 = lm_step_attn.hip's pair, one workgroup per (KV head, sequence, 256-key slice) on the matrix cores plus a merge.  The graph
 // key does not hold the mode, so the captured step is dropped here; read only while the cache is 16-bit (lm_launch_attention)
-extern "C" int mia_lm_set_step_attention(mia_lm* m, int mode) {
+// the two step-attention switches: same shape checks, one workspace (the partials of either pair have one size), the captured step dropped
+static int lm_set_step_mode(mia_lm* m, int mode, int mia_lm::*field, const char* who) {
   if (!m) return MIA_ERR_MODEL_NOT_LOADED;
   mia_ctx* ctx = m->ctx;
-  MIA_CHECK_ARG(ctx, mode == 0 || mode == 1, "lm_set_step_attention: mode must be 0 or 1 (got %d)", mode);
+  MIA_CHECK_ARG(ctx, mode == 0 || mode == 1, "%s: mode must be 0 or 1 (got %d)", who, mode);
   const mia_lm_config& c = m->cfg;
   if (mode == 1)
     if (const char* e = lm_step_attn_check(c.n_heads, c.n_kv_heads, c.head_dim))
-      return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "lm_set_step_attention: %s (n_heads %d, n_kv_heads %d, head_dim %d)", e, c.n_heads, c.n_kv_heads, c.head_dim);
+      return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "%s: %s (n_heads %d, n_kv_heads %d, head_dim %d)", who, e, c.n_heads, c.n_kv_heads, c.head_dim);
   MIA_HIP(ctx, hipSetDevice(ctx->device));
   MIA_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (mode == 1 && !m->step_ws) {
     void* p = nullptr;
     if (hipMalloc(&p, lm_step_attn_ws_floats(m->B_cap, c.n_heads, c.max_ctx, c.head_dim) * 4) != hipSuccess)
-      return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "lm_set_step_attention: workspace for %d sequences", m->B_cap);
+      return mia_fail(ctx, MIA_ERR_OUT_OF_MEMORY, "%s: workspace for %d sequences", who, m->B_cap);
     m->state_allocs.push_back(p); m->step_ws = (float*)p;
   }
   if (m->graph) { (void)hipGraphExecDestroy(m->graph); m->graph = nullptr; }
-  m->step_attn = mode;
+  m->*field = mode;
   return MIA_OK;
 }
+
+extern "C" int mia_lm_set_step_attention(mia_lm* m, int mode) { return lm_set_step_mode(m, mode, &mia_lm::step_attn, "lm_set_step_attention"); }
+
+// the same choice for the PACKED cache (mia_lm_set_kv_quant): 0 = lm_kvq_attention's fused form -- the default; 1 = lm_step_attn_kvq.hip's
+// split over the codes plus lm_step_attn.hip's merge.  Read only while the cache is packed; independent of mia_lm_set_step_attention
+extern "C" int mia_lm_set_kvq_step_attention(mia_lm* m, int mode) { return lm_set_step_mode(m, mode, &mia_lm::kvq_step_attn, "lm_set_kvq_step_attention"); }
 
 extern "C" int mia_lm_reset(mia_lm* m) {
   if (!m) return MIA_ERR_MODEL_NOT_LOADED;

@@ -28,47 +28,12 @@
 #include <type_traits>
 
 #include "lm.h"
+#include "lm_kvq_device.h"
 #include "mia_device.h"
 
 namespace {
 
 constexpr int KVQ_NW = 16;     // waves per attention workgroup (lm.hip: ATT_NW, same reasoning)
-
-// One group of 64 values, one per lane of a full wave: returns the value read back; `word` = the code dword this lane's 32 / BITS
-// neighbours share (identical in all of them), `pair` = scale | bias << 16.
-template <typename T, int BITS>
-__device__ __forceinline__ float kvq_group(float x, int lane, uint32_t& word, uint32_t& pair) {
-  constexpr float n = (float)((1 << BITS) - 1);
-  const float hi = wave_max(x), lo = -wave_max(-x);
-  const float sc = hi == lo ? 1.0f : (hi - lo) / n;
-  const uint16_t s16 = T::from_f32(sc), b16 = T::from_f32(lo);
-  const float s = T::to_f32(s16), b = T::to_f32(b16);
-  const float code = fminf(fmaxf(rintf((x - b) / s), 0.0f), n);
-  int w = (int)code << (BITS * (lane & (32 / BITS - 1)));
-  w |= dpp_i32<0xB1>(w);                        // lanes xor 1, xor 2: the quad's codes
-  w |= dpp_i32<0x4E>(w);
-  if (BITS == 4) w |= dpp_i32<0x141>(w);        // half-row mirror: the other quad of the 8 lanes
-  word = (uint32_t)w;
-  pair = (uint32_t)s16 | ((uint32_t)b16 << 16);
-  return s * code + b;
-}
-
-// a lane's 8 consecutive elements of one cached row
-template <typename T, int BITS>
-__device__ __forceinline__ void kvq_dq8(const uint32_t (&w)[BITS / 4], uint32_t pair, float (&x)[8]) {
-  const float s = T::to_f32((uint16_t)(pair & 0xffffu)), b = T::to_f32((uint16_t)(pair >> 16));
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const uint32_t code = BITS == 4 ? (w[0] >> (4 * j)) & 15u : (w[j >> 2] >> (8 * (j & 3))) & 255u;
-    x[j] = s * (float)code + b;
-  }
-}
-
-template <int BITS>
-__device__ __forceinline__ void kvq_load(const uint32_t* __restrict__ row, int c, uint32_t (&w)[BITS / 4]) {
-  if constexpr (BITS == 4) w[0] = row[c];
-  else { const u32x2 v = *reinterpret_cast<const u32x2*>(row + 2 * c); w[0] = v[0]; w[1] = v[1]; }
-}
 
 // q|k|v = sum_s partial[s] + bias; RoPE on q and k (lm_rope_cache's expressions); q -> qout; the K / V head's row -> 16 bit -> codes and
 // pairs at cache[kv head][pos].  One workgroup of DH threads per (head slot, row): slots [0, Hq) query heads, [Hq, Hq + Hkv) key

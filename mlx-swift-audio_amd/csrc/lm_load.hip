@@ -63,8 +63,9 @@ int lm_alloc_state(mia_lm* m, int B) {
   m->tokens = (int32_t*)dev((size_t)B * c.max_ctx * 4); m->hist = (int32_t*)dev((size_t)B * 64 * 4); m->uniforms = (float*)dev((size_t)B * c.max_ctx * 4);
   m->state = (LmState*)dev(sizeof(LmState) * B); m->smx = dev(lm_sample_ws_bytes() * B);
   m->embeds = (float*)dev((size_t)B * c.max_ctx * D * 4); m->out_tokens = (int32_t*)dev((size_t)B * c.max_ctx * 4);
-  // the split-key step attention's partials follow the capacity once mia_lm_set_step_attention(1) has asked for them
-  m->step_ws = m->step_attn ? (float*)dev(lm_step_attn_ws_floats(B, c.n_heads, c.max_ctx, dh) * 4) : nullptr;
+  // the split-key step attention's partials follow the capacity once mia_lm_set_step_attention(1) or mia_lm_set_kvq_step_attention(1)
+  // has asked for them (one buffer: the two switches act in different cache modes and their partials have one size)
+  m->step_ws = (m->step_attn || m->kvq_step_attn) ? (float*)dev(lm_step_attn_ws_floats(B, c.n_heads, c.max_ctx, dh) * 4) : nullptr;
   if (!ok) return -1;
   if (m->kv_bits) { (void)hipMemset(m->kq_codes, 0, kvq); (void)hipMemset(m->vq_codes, 0, kvq); (void)hipMemset(m->kq_pairs, 0, kvp); (void)hipMemset(m->vq_pairs, 0, kvp); }
   else { (void)hipMemset(m->k_cache, 0, kv); (void)hipMemset(m->v_cache, 0, kv); }

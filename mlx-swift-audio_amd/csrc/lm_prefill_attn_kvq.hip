@@ -41,38 +41,12 @@
 #include <type_traits>
 
 #include "lm.h"
+#include "lm_kvq_device.h"
 #include "mia_device.h"
 
 namespace {
 
 constexpr int KV_TILE = 64;
-
-// a thread's 8 consecutive codes of a row as fp32
-template <int BITS>
-__device__ __forceinline__ void codes8(const uint32_t (&w)[BITS / 4], float (&x)[8]) {
-  if constexpr (BITS == 4) {
-    const uint32_t lo = w[0] & 0x0f0f0f0fu, hi = (w[0] >> 4) & 0x0f0f0f0fu;      // even / odd elements, one per byte
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { x[2 * i] = (float)((lo >> (8 * i)) & 255u); x[2 * i + 1] = (float)((hi >> (8 * i)) & 255u); }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) x[j] = (float)((w[j >> 2] >> (8 * (j & 3))) & 255u);
-  }
-}
-
-// two integers 0 .. 255 -> two 16-bit numbers (exact: bf16 is the fp32's high half, f16 rounds nothing below 2048)
-template <typename T>
-__device__ __forceinline__ uint32_t pack_codes(float lo, float hi);
-template <>
-__device__ __forceinline__ uint32_t pack_codes<BF16>(float lo, float hi) { return (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xffff0000u); }
-template <>
-__device__ __forceinline__ uint32_t pack_codes<F16>(float lo, float hi) { return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(lo, hi)); }
-
-template <int BITS>
-__device__ __forceinline__ void load_codes(const uint32_t* __restrict__ p, uint32_t (&w)[BITS / 4]) {
-  if constexpr (BITS == 4) w[0] = *p;
-  else { const u32x2 v = *reinterpret_cast<const u32x2*>(p); w[0] = v[0]; w[1] = v[1]; }
-}
 
 struct KvqPromptAttn {
   const uint16_t* q; uint16_t* out;               // [M][Hq * dh]

@@ -292,6 +292,17 @@ const char* lm_step_attn_check(int Hq, int Hkv, int dh) {
   return nullptr;
 }
 
+// the second launch alone, for lm_step_attn_kvq.hip: its split kernel writes the same partials
+int lm_step_attn_combine_launch(const LmStepAttn& a, hipStream_t s) {
+  if (lm_step_attn_check(a.Hq, a.Hkv, a.dh) || !a.out || !a.ws || !a.st || a.nb <= 0 || a.max_ctx <= 0) return -1;
+  const dim3 cgrid(a.Hq, a.nb);
+#define SA_C(TT) do { if (a.dh == 128) hipLaunchKernelGGL((lm_step_attn_combine<TT, 128>), cgrid, dim3(128), 0, s, a); \
+                      else hipLaunchKernelGGL((lm_step_attn_combine<TT, 64>), cgrid, dim3(64), 0, s, a); } while (0)
+  if (a.dtype == MIA_F16) SA_C(F16); else SA_C(BF16);
+#undef SA_C
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int lm_step_attn_launch(const LmStepAttn& a, hipStream_t s) {
   if (lm_step_attn_check(a.Hq, a.Hkv, a.dh) || !a.kc || !a.vc || !a.out || !a.ws || !a.st || !a.part || !a.inv_freq || a.S < 1 || a.S > 4 || a.nb <= 0 || a.max_ctx <= 0)
     return -1;

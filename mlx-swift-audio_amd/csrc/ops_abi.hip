@@ -493,3 +493,40 @@ extern "C" int mia_op_lm_prompt_attention_kvq(mia_ctx* ctx, const void* q, const
   if (lm_prefill_attn_kvq_launch(a, d_qn, f.d_att, d_tiles, (int)tiles.size(), ctx->stream)) return mia_fail(ctx, MIA_ERR_DEVICE, "op_lm_prompt_attention_kvq: launch failed");
   return f.read(io, out, n, dtype);
 }
+
+// The decode step's attention on the PACKED cache without a model around it, built as mia_op_lm_step_attention is on mia_op_kvq_attention's
+// staging: rows 0 .. T - 2 of K / V go through the prompt pass's quantising cache writer; row T - 1 of q|k|v is the step's GEMM partial, so
+// the fused preamble and the quantising row write run at the position read from the state record.  mode 0: lm_kvq_attention<.., FUSED =
+// true>, mode 1: lm_step_attn_kvq.hip's split plus lm_step_attn.hip's merge -- both through lm_launch_attention, as the step launches them.
+extern "C" int mia_op_lm_step_attention_kvq(mia_ctx* ctx, const void* q, const void* k, const void* v, float* out, int Hq, int Hkv, int T, int dh, int bits, int mode,
+                                            int dtype) {
+  if (!ctx) return MIA_ERR_INVALID_ARGUMENT;
+  MIA_CHECK_ARG(ctx, q && k && v && out, "op_lm_step_attention_kvq: null pointer");
+  MIA_CHECK_ARG(ctx, dtype == MIA_BF16 || dtype == MIA_F16, "op_lm_step_attention_kvq: dtype must be MIA_BF16 or MIA_F16");
+  MIA_CHECK_ARG(ctx, Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && Hq <= 1024 && T >= 1 && T <= 8192, "op_lm_step_attention_kvq: bad shape (Hq %% Hkv == 0, 1 <= T <= 8192)");
+  MIA_CHECK_ARG(ctx, mode == 0 || mode == 1, "op_lm_step_attention_kvq: mode must be 0 or 1 (got %d)", mode);
+  MIA_CHECK_ARG(ctx, bits == 4 || bits == 8, "op_lm_step_attention_kvq: bits must be 4 or 8 (got %d)", bits);
+  int code = MIA_OK;
+  if (const char* e = lm_kvq_check(bits, 64, dh, &code)) return mia_fail(ctx, code, "op_lm_step_attention_kvq: %s (bits %d, head_dim %d)", e, bits, dh);
+  if (mode == 1)
+    if (const char* e = lm_step_attn_kvq_check(Hq, Hkv, dh, bits)) return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "op_lm_step_attention_kvq: %s (Hq %d, Hkv %d)", e, Hq, Hkv);
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  LmOpRows f;
+  f.build(q, k, v, Hq, Hkv, T, 1, dh, dtype);
+  LmState st{};
+  st.pos = T - 1;
+  HostIo io = HostIo::device(ctx);
+  const size_t rows = (size_t)Hkv * T;
+  const size_t b_st = align_up(sizeof(LmState), 256), b_codes = align_up(rows * dh * bits / 8, 256), b_pairs = align_up(rows * (dh / 64) * 4, 256),
+               b_ws = mode == 1 ? align_up(lm_step_attn_ws_floats(1, Hq, T, dh) * 4, 256) : 0;
+  if (int rc = f.stage(ctx, io, Hq, Hkv, T, 1, dh, dtype, b_st + 2 * b_codes + 2 * b_pairs + b_ws, 0)) return rc;
+  char* d_kc = f.extra + b_st; char* d_vc = d_kc + b_codes; char* d_kp = d_vc + b_codes; char* d_vp = d_kp + b_pairs;
+  mia_lm& sh = f.sh;
+  sh.state = const_cast<LmState*>(io.table(&st, f.extra, sizeof(LmState)));
+  sh.kv_bits = bits; sh.kq_codes = (uint32_t*)d_kc; sh.vq_codes = (uint32_t*)d_vc; sh.kq_pairs = (uint32_t*)d_kp; sh.vq_pairs = (uint32_t*)d_vp;
+  sh.kvq_step_attn = mode; sh.step_ws = (float*)(d_vp + b_pairs);
+  if (T > 1) lm_launch_rope_cache(&sh, 0, f.d_part, nullptr, f.d_q, f.d_map, T - 1);
+  if (lm_launch_attention(&sh, true, 1, nullptr, 0, f.d_att, nullptr, f.d_part + (size_t)(T - 1) * f.N, 1, nullptr) || hipGetLastError() != hipSuccess)
+    return mia_fail(ctx, MIA_ERR_DEVICE, "op_lm_step_attention_kvq: launch failed");
+  return f.read(io, out, 1, dtype);
+}

@@ -62,6 +62,14 @@ class CausalLM:
         merge).  No effect while the cache is quantised.  More than 16 query heads per KV head: ERR_UNSUPPORTED."""
         self.ctx.check(self.ctx.lib.mia_lm_set_step_attention(self.h, 1 if on else 0))
 
+    def set_kvq_step_attention(self, mode: int) -> None:
+        """mia_lm_set_kvq_step_attention: the decode step's attention on the quantised cache -- 0 = one workgroup per (query head,
+        sequence), each de-quantising its head's cache (default), 1 = the split over the codes of lm_step_attn_kvq.hip (the work split of
+        set_step_attention(True), a cached row unpacked once per KV group) plus the same merge.  No effect while the cache is 16-bit.
+        More than 16 query heads per KV head: ERR_UNSUPPORTED.  On F16 handles mode 1 overflows once a V row's max - min over a group of
+        64 reaches 61 410 (4 bit) / 65 248 (8 bit); BF16 handles have no such limit."""
+        self.ctx.check(self.ctx.lib.mia_lm_set_kvq_step_attention(self.h, int(mode)))
+
     def use_q4(self, on: bool) -> None:
         lib = self.ctx.lib
         self.ctx.check(lib.mia_lm_use_q4(self.h, 1 if on else 0))
@@ -385,8 +393,9 @@ class OrpheusTTS:
 
     def __init__(self, lm: CausalLM, snac, kv_bits: int | None = None, packed_prompt: bool | None = None, split_step: bool = False):
         self.lm, self.snac = lm, snac
-        if split_step:                               # the decode step on the split-key attention (CausalLM.set_step_attention); False leaves the handle's mode alone
+        if split_step:                               # the decode step on the split-key attention of either cache mode (each switch acts in its own); False leaves the handle's modes alone
             lm.set_step_attention(True)
+            lm.set_kvq_step_attention(1)
         if packed_prompt is not None:                # the prompt pass on the attached packed weights (CausalLM.set_prompt_weights); None leaves the handle's mode alone
             lm.set_prompt_weights(packed_prompt)
         if kv_bits is not None:                      # newCache(quantized: kv_bits != 0, bits: kv_bits); None leaves the handle's mode alone

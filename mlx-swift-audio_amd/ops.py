@@ -213,6 +213,18 @@ def lm_step_attention(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.nda
     return out
 
 
+def lm_step_attention_kvq(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np.ndarray, bits: int = 4, mode: int = 1, dtype: int = _lib.BF16) -> np.ndarray:
+    """mia_op_lm_step_attention_kvq: lm_step_attention over the quantised cache (bits 4 | 8, groups of 64): rows 0 .. T - 2 are cached as
+    codes, row T - 1 is quantised by the step itself and attended as the values read back.  mode 0 = lm_kvq_attention's fused form, 1 =
+    the split over the codes of lm_step_attn_kvq.hip.  Same shapes.  (F16: V groups with max - min below 61 410 at 4 bits, 65 248 at 8.)"""
+    Hq, dh = q.shape
+    Hkv, T, _ = k.shape
+    q16, k16, v16 = to16(q, dtype), to16(k, dtype), to16(v, dtype)
+    out = np.empty((Hq, dh), np.float32)
+    ctx.check(ctx.lib.mia_op_lm_step_attention_kvq(ctx.h, q16.ctypes.data, k16.ctypes.data, v16.ctypes.data, out.ctypes.data, Hq, Hkv, T, dh, int(bits), int(mode), dtype))
+    return out
+
+
 def rfft_block(ctx: _lib.Context) -> int:
     """mia_op_rfft_block: the largest power-of-two transform one workgroup runs in LDS; larger ones take the four-step split."""
     return int(ctx.lib.mia_op_rfft_block())

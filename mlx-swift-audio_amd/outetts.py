@@ -246,7 +246,8 @@ class OuteTTS:
     packed_prompt (True / False) forwards to CausalLM.set_prompt_weights -- the prompt pass on the attached packed weights -- and None,
     the default, leaves the handle's mode alone.  kv_bits 4 | 8 puts the handle on the quantised KV cache (newCache(quantized: true, bits:))
     and its prompt pass on the tiled kernel that reads the codes; None touches neither.  split_step=True puts the decode step on the
-    split-key attention (CausalLM.set_step_attention), which shares the long profile's K / V across a KV group; False leaves the handle alone."""
+    split-key attention of either cache mode (CausalLM.set_step_attention and set_kvq_step_attention; each acts only in its own), which
+    shares the long profile's K / V across a KV group; False leaves the handle alone."""
 
     def __init__(self, lm, dac, processor: OuteTTSPromptProcessor, eos_id: int, default_speaker: SpeakerProfile | None = None,
                  prompt_attention: int | None = 1, packed_prompt: bool | None = None, kv_bits: int | None = None,
@@ -254,6 +255,7 @@ class OuteTTS:
         self.lm, self.dac, self.processor, self.eos_id, self.default_speaker = lm, dac, processor, int(eos_id), default_speaker
         if split_step:
             lm.set_step_attention(True)
+            lm.set_kvq_step_attention(1)
         if prompt_attention is not None:
             lm.set_prompt_attention(prompt_attention)
         if kv_bits is not None:

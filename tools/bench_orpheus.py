@@ -5,7 +5,8 @@
 4 | 8 = quantised, group 64 (CausalLM.new_cache); the line then also carries the cache's byte model -- K/V bytes read per step at the
 mean context of the timed run, and that stream over the measured step time as a fraction of the 8 TB/s HBM peak.  --split-step measures
 the decode step instead (and nothing else): ms per generated token behind prompts of 300 and 1 200 random ids, and ms per step with 8
-and 32 sentences of 300 ids side by side, CausalLM.set_step_attention off, then on, then off again (tools/_split_step_bench.py)."""
+and 32 sentences of 300 ids side by side, CausalLM.set_step_attention off, then on, then off again (tools/_split_step_bench.py); with
+--kv-bits 4 | 8 the same on the quantised cache, toggling CausalLM.set_kvq_step_attention."""
 import json
 import os
 import sys
@@ -60,7 +61,9 @@ if split_step:                                   # the decode step with set_step
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import _split_step_bench as SB
     res = {"model": name, "dtype": "bf16", "weights": "mlx-affine q4 g64 (packed step)" if q4 else "bf16"}
-    res.update(SB.measure(model, cfg, (300, 1200), (8, 32), 300, 65, 7, 0, lambda s: print("[orpheus] " + s, file=sys.stderr, flush=True)))
+    res["kv_bits"] = kv_bits
+    res.update(SB.measure(model, cfg, (300, 1200), (8, 32), 300, 65, 7, 0, lambda s: print("[orpheus] " + s, file=sys.stderr, flush=True),
+                          toggle=model.set_kvq_step_attention if kv_bits else None))
     print(json.dumps(res))
     sys.exit(0)
 # K/V bytes per cached token per sequence: codes + one 16-bit (scale, bias) pair per 64 values, or 16-bit values

@@ -33,7 +33,8 @@ token, timed the same way.
 
 --split-step measures the decode step instead (and nothing else): ms per generated token behind prompts of 512, 2 087 and 4 096 random
 ids (--lengths changes them), and ms per step with 8 and 32 sentences of 2 087 ids side by side, CausalLM.set_step_attention off, then
-on, then off again on one handle -- tools/_split_step_bench.py states how a reading is taken.
+on, then off again on one handle -- tools/_split_step_bench.py states how a reading is taken.  --split-step --kv-bits 4 | 8: the same
+on the quantised cache, toggling CausalLM.set_kvq_step_attention.
 
 --vocab: the reference reads the vocabulary size from the checkpoint's config.json; the default (128 256, Llama-3.2's) is an assumption."""
 import argparse
@@ -233,10 +234,14 @@ def split_step(args):
     t0 = time.time()
     model = HL.CausalLM.load(ctx, cfg, S.lm_weights(cfg, seed=args.seed, dtype=np.float16), m.BF16)
     model.set_prompt_attention(1)
+    if args.kv_bits:                                 # the packed cache: its tiled prompt pass, and set_kvq_step_attention is what is toggled
+        model.new_cache(quantized=True, bits=args.kv_bits)
+        model.set_kvq_prompt_attention(1)
     print(f"[outetts] weights generated and loaded in {time.time() - t0:.1f}s", file=sys.stderr, flush=True)
-    res = {"model": "llama-3.2-1b", "vocab": cfg.vocab, "dtype": "bf16"}
+    res = {"model": "llama-3.2-1b", "vocab": cfg.vocab, "dtype": "bf16", "kv_bits": args.kv_bits or 0}
     res.update(SB.measure(model, cfg, lengths, (8, 32), 2087, 65, max(7, args.repeats), args.seed,
-                          lambda s: print("[outetts] " + s, file=sys.stderr, flush=True)))
+                          lambda s: print("[outetts] " + s, file=sys.stderr, flush=True),
+                          toggle=model.set_kvq_step_attention if args.kv_bits else None))
     model.close()
     ctx.close()
     print(json.dumps(res))
@@ -255,7 +260,7 @@ def main():
     ap.add_argument("--speaker", nargs=2, metavar=("SECONDS", "WORDS"), help="measure speaker-profile creation only")
     ap.add_argument("--packed-prompt", type=int, metavar="BITS", help="measure the prompt pass on packed weights only")
     ap.add_argument("--kv-bits", type=int, choices=(4, 8), metavar="BITS", help="measure the prompt pass on the quantised KV cache only")
-    ap.add_argument("--split-step", action="store_true", help="measure the decode step with set_step_attention off / on / off again only")
+    ap.add_argument("--split-step", action="store_true", help="measure the decode step with set_step_attention (with --kv-bits: set_kvq_step_attention, on the packed cache) off / on / off again only")
     args = ap.parse_args()
     if args.split_step:
         return split_step(args)
