@@ -360,6 +360,16 @@ int mia_op_skinny_gemm(mia_ctx* ctx, const mia_skinny_desc* d);
 typedef struct mia_gemm_quant_desc mia_gemm_quant_desc;    /* defined in include/mia_gemm_quant.h */
 int mia_op_gemm_quant(mia_ctx* ctx, const mia_gemm_quant_desc* d);
 
+/* Dynamic time warping with backtrace (the tail of mia_whisper_align; STT/Whisper/WhisperTiming.swift:46-130) of B cost matrices, without
+ * a model around it.  cost [B][rows][ld] fp32; clip b uses its first n_rows[b] rows and n_cols[b] columns.  acc is fp32, one add per
+ * cell; the move is 0 (diagonal) when c0 < c1 && c0 < c2, 1 (up) when c1 < c0 && c1 < c2, else 2 (left); acc[0][0] = 0, every other border
+ * +inf.  text_idx / time_idx [B][path_cap]: the path in forward order (row, column), path_len [B].  mode 0: the host loop; mode 1: the
+ * cost is uploaded and csrc/align_dtw.hip runs (one wave per clip) -- the same path, entry for entry.  All pointers are host memory.
+ * MIA_ERR_INVALID_ARGUMENT (before anything is launched) for n_rows[b] outside [1, rows], n_cols[b] outside [1, ld] or another mode, and
+ * for a path longer than path_cap (nothing is written past it); MIA_ERR_UNSUPPORTED in mode 1 for more than 448 rows or 1500 columns. */
+int mia_op_dtw(mia_ctx* ctx, const float* cost, int B, int rows, int64_t ld, const int32_t* n_rows, const int32_t* n_cols, int mode,
+               int32_t* text_idx, int32_t* time_idx, int32_t* path_len, int path_cap);
+
 /* ---- Whisper ---------------------------------------------------------------------------------- */
 /* Model dimensions == ModelDimensions (STT/Whisper/Config/WhisperConfig.swift:9-86), read by the caller
  * from config.json. */
@@ -543,14 +553,21 @@ int mia_whisper_encode_audio_windows(mia_whisper* w, mia_whisper_audio* a, const
  * STT/Whisper/WhisperModel.swift:95-99).  For every clip of the last encode: a teacher-forced decoder pass over
  * tokens[b][0..n_tokens[b]) = [sot sequence, no_timestamps, text tokens, eot] keeps the pre-softmax cross-attention scores of the
  * alignment heads (heads int32 [n_heads][2] = (layer, head), the model's alignment_heads); on the device: softmax over the first
- * num_frames[b] / 2 frames, standardisation over tokens, width-7 median filter (reflect), mean over heads; on the host like the
- * reference: DTW over rows [row_start, n_tokens[b] - 1) (row_start = index of no_timestamps) of the negated matrix.
+ * num_frames[b] / 2 frames, standardisation over tokens, width-7 median filter (reflect), mean over heads; then DTW over rows
+ * [row_start, n_tokens[b] - 1) (row_start = index of no_timestamps) of the negated matrix: on the host like the reference by default,
+ * or on the device behind the cost kernel after mia_whisper_set_align_dtw(w, 1) (csrc/align_dtw.hip: the same path, entry for entry;
+ * the whole cost buffer then stays on the device, and only the probabilities, the paths, the lengths and -- when `matrix` is given --
+ * each clip's own n_tokens[b] rows come back).
  *   token_probs [B][stride]: P(tokens[p + 1]) under softmax(logits[p][0:eot]);  text_idx / time_idx [B][path_cap] + path_len [B]: the
  *   DTW path (row index relative to row_start, frame index);  matrix (nullable) [B][stride][n_audio_ctx]: the filtered, head-averaged
  *   weights.  All host pointers.  Word splitting and the jump-time arithmetic (:735-820) stay with the caller (tokenizer text). */
 int mia_whisper_align(mia_whisper* w, const int32_t* tokens, int stride, const int32_t* n_tokens, const int32_t* heads, int n_heads,
                       const int32_t* num_frames, int row_start, int eot, float* token_probs, int32_t* text_idx, int32_t* time_idx,
                       int32_t* path_len, int path_cap, float* matrix);
+/* Where mia_whisper_align runs its DTW and backtrace: 0 = host (the default), 1 = device.  Mode 1 needs n_text_ctx <= 448 and
+ * n_audio_ctx <= 1500 (every published Whisper), else MIA_ERR_UNSUPPORTED; another mode is MIA_ERR_INVALID_ARGUMENT.  A clone inherits the
+ * mode of the handle it was cloned from. */
+int mia_whisper_set_align_dtw(mia_whisper* w, int mode);
 
 /* ---- neural codec decoders (fp32, like the reference) ------------------------------------------ */
 /* SNACConfig (TTS/Orpheus/SNAC/SNACConfig.swift:9-94); tensors use the checkpoint key schema the reference loads

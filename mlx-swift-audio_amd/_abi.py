@@ -287,6 +287,7 @@ PROTOTYPES = {
     "mia_op_lm_step_attention_kvq": (i32, [vp, vp, vp, vp, vp] + [i32] * 7),
     "mia_op_skinny_gemm": (i32, [vp, P(SkinnyDesc)]),
     "mia_op_gemm_quant": (i32, [vp, vp]),
+    "mia_op_dtw": (i32, [vp, vp, i32, i32, i64, vp, vp, i32, vp, vp, vp, i32]),
     # Whisper
     "mia_whisper_load": (vp, [vp, P(WhisperDims), TV, i32, i32]),
     "mia_whisper_free": (None, [vp]),
@@ -312,6 +313,7 @@ PROTOTYPES = {
     "mia_whisper_audio_read": (i32, [vp, i32, i64, i64, vp]),
     "mia_whisper_encode_audio_windows": (i32, [vp, vp, vp, vp, vp, i32]),
     "mia_whisper_align": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp]),
+    "mia_whisper_set_align_dtw": (i32, [vp, i32]),
     # neural codecs
     "mia_snac_load": (vp, [vp, P(SnacConfig), TV, i32]),
     "mia_dac_load": (vp, [vp, P(DacConfig), TV, i32]),

@@ -99,6 +99,7 @@ struct mia_whisper {
   float* emb_qst = nullptr;           // the embedding gather keeps the 16-bit table)
   int q_bits = 0;                     // 4 | 8 once packed decoder weights are attached, 0 = none
   int use_packed = 0;                 // mia_whisper_use_packed: the step's GEMMs read the packed weights
+  int align_dtw = 0;                  // mia_whisper_set_align_dtw: 1 = the alignment's DTW runs on the device (align_dtw.hip)
   float* dec_pos = nullptr;           // [n_text_ctx][D]
   std::vector<DecBlockW> dec;
   LNW dec_ln;

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "align_dtw.h"
 #include "decode.h"
 
 namespace {
@@ -400,32 +401,6 @@ __global__ __launch_bounds__(256) void align_median_mean(const float* __restrict
   cost[((int64_t)b * n_ctx + tok) * T + f] = -(acc / (float)n_slots);
 }
 
-// dtw + backtrace (WhisperTiming.swift:46-130), host code like the reference's; cost is [N][ld] with M valid columns
-void dtw_host(const float* cost, int N, int M, int64_t ld, std::vector<int32_t>& ti, std::vector<int32_t>& tj) {
-  const int R = N + 1, Cc = M + 1;
-  std::vector<float> acc((size_t)R * Cc, INFINITY);
-  std::vector<int8_t> tr((size_t)R * Cc, -1);
-  acc[0] = 0.f;
-  for (int j = 1; j <= M; ++j)
-    for (int i = 1; i <= N; ++i) {
-      const float c0 = acc[(size_t)(i - 1) * Cc + j - 1], c1 = acc[(size_t)(i - 1) * Cc + j], c2 = acc[(size_t)i * Cc + j - 1];
-      float c; int8_t t;
-      if (c0 < c1 && c0 < c2) { c = c0; t = 0; } else if (c1 < c0 && c1 < c2) { c = c1; t = 1; } else { c = c2; t = 2; }
-      acc[(size_t)i * Cc + j] = cost[(int64_t)(i - 1) * ld + (j - 1)] + c;
-      tr[(size_t)i * Cc + j] = t;
-    }
-  for (int j = 0; j < Cc; ++j) tr[j] = 2;
-  for (int i = 0; i < R; ++i) tr[(size_t)i * Cc] = 1;
-  int i = N, j = M;
-  ti.clear(); tj.clear();
-  while (i > 0 || j > 0) {
-    ti.push_back(i - 1); tj.push_back(j - 1);
-    const int8_t t = tr[(size_t)i * Cc + j];
-    if (t == 0) { --i; --j; } else if (t == 1) --i; else if (t == 2) --j; else { if (i > 0) --i; if (j > 0) --j; }
-  }
-  std::reverse(ti.begin(), ti.end()); std::reverse(tj.begin(), tj.end());
-}
-
 }  // namespace
 
 extern "C" int mia_whisper_align(mia_whisper* w, const int32_t* tokens, int stride, const int32_t* n_tokens, const int32_t* heads, int n_heads,
@@ -462,7 +437,12 @@ extern "C" int mia_whisper_align(mia_whisper* w, const int32_t* tokens, int stri
   // device scratch: qk [B][n_heads][C][T] | cost [B][C][T] | probs [B][C] | slot [L][H] | ntok [B] | nfr [B]
   const size_t n_qk = (size_t)B * n_heads * C * T, n_cost = (size_t)B * C * T;
   auto al = [](size_t n) { return (n + 63) / 64 * 64; };
-  const size_t floats = al(n_qk) + al(n_cost) + al((size_t)B * C) + al((size_t)L * H) + 2 * al(B);
+  // device DTW (mia_whisper_set_align_dtw): paths [2][B][dev_cap] | lengths [B] | trace, behind everything else
+  int max_rows = 0, max_cols = 0;
+  for (int b = 0; b < B; ++b) { max_rows = std::max(max_rows, ntok[b] - 1 - row_start); max_cols = std::max(max_cols, nfr[b]); }
+  const int dev_cap = std::min(path_cap, max_rows + max_cols);      // no path is longer
+  const size_t n_path = w->align_dtw ? al((size_t)(2 * dev_cap + 1) * B) : 0, n_trace = w->align_dtw ? dtw_trace_bytes(B, max_rows, max_cols) / 4 : 0;
+  const size_t floats = al(n_qk) + al(n_cost) + al((size_t)B * C) + al((size_t)L * H) + 2 * al(B) + n_path + n_trace;
   float* ws = (float*)mia_workspace(ctx, floats * 4);
   if (!ws) return MIA_ERR_OUT_OF_MEMORY;
   float* d_qk = ws; float* d_cost = d_qk + al(n_qk); float* d_probs = d_cost + al(n_cost);
@@ -486,6 +466,37 @@ extern "C" int mia_whisper_align(mia_whisper* w, const int32_t* tokens, int stri
   hipLaunchKernelGGL(align_standardize, dim3((T + 255) / 256, n_heads, B), dim3(256), 0, s, d_qk, d_ntok, d_nfr, n_heads, C, T);
   hipLaunchKernelGGL(align_median_mean, dim3((T + 255) / 256, max_tok, B), dim3(256), 0, s, d_qk, d_ntok, d_nfr, n_heads, C, T, d_cost);
   MIA_HIP(ctx, hipGetLastError());
+  if (w->align_dtw) {
+    // the DTW and its backtrace behind the cost kernel (align_dtw.hip); back come the probabilities, the paths and the lengths, and the
+    // clips' own rows of the matrix when the caller wants it
+    int32_t* d_path = (int32_t*)(d_nfr + al(B));
+    DtwArgs a;
+    a.cost = d_cost + (size_t)row_start * T; a.clip_stride = (int64_t)C * T; a.ld = T; a.n_rows = d_ntok; a.n_cols = d_nfr; a.row_sub = 1 + row_start;
+    a.B = B; a.max_rows = max_rows; a.max_cols = max_cols; a.trace = (uint32_t*)(d_path + n_path);
+    a.text_idx = d_path; a.time_idx = d_path + (size_t)B * dev_cap; a.path_len = d_path + (size_t)2 * B * dev_cap; a.path_cap = dev_cap;
+    if (const char* e = dtw_check(a)) return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "align: %s", e);
+    if (dtw_launch(a, s)) return mia_fail(ctx, MIA_ERR_DEVICE, "align: DTW launch failed");
+    std::vector<float> probs((size_t)B * C), rows(matrix ? (size_t)B * max_tok * T : 0);
+    std::vector<int32_t> got((size_t)(2 * dev_cap + 1) * B);
+    HostIo io = HostIo::host(ctx);
+    io.fetch(probs.data(), d_probs, probs.size() * 4);
+    io.fetch(got.data(), d_path, got.size() * 4);
+    if (matrix)
+      for (int b = 0; b < B; ++b) io.fetch(rows.data() + (size_t)b * max_tok * T, d_cost + (size_t)b * C * T, (size_t)ntok[b] * T * 4);
+    if (int rc = io.finish()) return rc;
+    const int32_t* len = got.data() + (size_t)2 * B * dev_cap;
+    for (int b = 0; b < B; ++b) {
+      for (int i = 0; i < stride; ++i) token_probs[(size_t)b * stride + i] = i < C ? probs[(size_t)b * C + i] : 0.f;
+      if (len[b] > path_cap) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "align: path_cap %d too small (need %zu)", path_cap, (size_t)len[b]);
+      path_len[b] = len[b];
+      std::copy(got.data() + (size_t)b * dev_cap, got.data() + (size_t)b * dev_cap + len[b], text_idx + (size_t)b * path_cap);
+      std::copy(got.data() + (size_t)(B + b) * dev_cap, got.data() + (size_t)(B + b) * dev_cap + len[b], time_idx + (size_t)b * path_cap);
+      if (matrix)
+        for (int t = 0; t < ntok[b]; ++t)
+          for (int f2 = 0; f2 < T; ++f2) matrix[((size_t)b * stride + t) * T + f2] = f2 < nfr[b] ? -rows[((size_t)b * max_tok + t) * T + f2] : 0.f;
+    }
+    return MIA_OK;
+  }
   std::vector<float> cost(n_cost);
   MIA_HIP(ctx, hipMemcpyAsync(cost.data(), d_cost, n_cost * 4, hipMemcpyDeviceToHost, s));
   std::vector<float> probs((size_t)B * C);
@@ -503,6 +514,17 @@ extern "C" int mia_whisper_align(mia_whisper* w, const int32_t* tokens, int stri
       for (int t = 0; t < ntok[b]; ++t)
         for (int f2 = 0; f2 < T; ++f2) matrix[((size_t)b * stride + t) * T + f2] = f2 < nfr[b] ? -cost[((size_t)b * C + t) * T + f2] : 0.f;
   }
+  return MIA_OK;
+}
+
+// Where mia_whisper_align runs its DTW: 0 (the default) on the host, 1 on the device (align_dtw.hip).  The paths are the same, entry for entry.
+extern "C" int mia_whisper_set_align_dtw(mia_whisper* w, int mode) {
+  if (!w) return MIA_ERR_MODEL_NOT_LOADED;
+  MIA_CHECK_ARG(w->ctx, mode == 0 || mode == 1, "set_align_dtw: mode must be 0 (host) or 1 (device), got %d", mode);
+  if (mode == 1 && (w->dims.n_text_ctx > DTW_MAX_ROWS || w->dims.n_audio_ctx > DTW_MAX_COLS))
+    return mia_fail(w->ctx, MIA_ERR_UNSUPPORTED, "set_align_dtw: the device DTW takes at most %d x %d (this model: %d x %d)", DTW_MAX_ROWS, DTW_MAX_COLS,
+                    w->dims.n_text_ctx, w->dims.n_audio_ctx);
+  w->align_dtw = mode;
   return MIA_OK;
 }
 

@@ -198,6 +198,7 @@ extern "C" mia_whisper* mia_whisper_clone(mia_whisper* src, mia_ctx* ctx) {
   w->conv1 = root->conv1; w->conv2 = root->conv2; w->enc_pos = root->enc_pos; w->enc = root->enc; w->ln_post = root->ln_post;
   w->tok_emb = root->tok_emb; w->tok_emb_f = root->tok_emb_f; w->emb_c1 = root->emb_c1; w->emb_c2 = root->emb_c2; w->dec_pos = root->dec_pos; w->dec = root->dec; w->dec_ln = root->dec_ln;
   w->emb_qw = root->emb_qw; w->emb_qst = root->emb_qst; w->q_bits = root->q_bits; w->use_packed = src->use_packed;      // (LinearW::qw / qst came with w->dec)
+  w->align_dtw = src->align_dtw;
   w->parent = root;
   root->n_clones += 1;
   return w;

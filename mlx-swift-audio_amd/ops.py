@@ -225,6 +225,26 @@ def lm_step_attention_kvq(ctx: _lib.Context, q: np.ndarray, k: np.ndarray, v: np
     return out
 
 
+def dtw(ctx: _lib.Context, cost, mode: int = 1, *, ld: int | None = None, path_cap: int | None = None):
+    """mia_op_dtw: the alignment's DTW with backtrace.  cost: one [N, M] array or a list of ragged ones (one batch, one call); mode 0 = the
+    host loop, 1 = the device kernel (align_dtw.hip).  Returns (text_idx, time_idx) lists for one array, a list of such pairs for a list.
+    ld: row stride of the packed batch (default: the widest clip); what lies outside a clip's own [N, M] is NaN, so a read of it shows."""
+    clips = [np.asarray(c, np.float32) for c in (cost if isinstance(cost, (list, tuple)) else [cost])]
+    B, rows = len(clips), max(c.shape[0] for c in clips)
+    ld = int(ld or max(c.shape[1] for c in clips))
+    buf = np.full((B, rows, ld), np.nan, np.float32)
+    for b, c in enumerate(clips):
+        buf[b, :c.shape[0], :c.shape[1]] = c
+    n = np.array([c.shape[0] for c in clips], np.int32)
+    m = np.array([c.shape[1] for c in clips], np.int32)
+    cap = int(path_cap or (n + m).max())
+    ti, tj, pl = np.zeros((B, cap), np.int32), np.zeros((B, cap), np.int32), np.zeros(B, np.int32)
+    ctx.check(ctx.lib.mia_op_dtw(ctx.h, buf.ctypes.data, B, rows, ld, n.ctypes.data, m.ctypes.data, int(mode), ti.ctypes.data, tj.ctypes.data,
+                                 pl.ctypes.data, cap))
+    paths = [(ti[b, :pl[b]].tolist(), tj[b, :pl[b]].tolist()) for b in range(B)]
+    return paths if isinstance(cost, (list, tuple)) else paths[0]
+
+
 def rfft_block(ctx: _lib.Context) -> int:
     """mia_op_rfft_block: the largest power-of-two transform one workgroup runs in LDS; larger ones take the four-step split."""
     return int(ctx.lib.mia_op_rfft_block())

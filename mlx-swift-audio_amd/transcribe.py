@@ -374,8 +374,10 @@ def transcribe_batch(full_mels: list[np.ndarray], n_samples: list[int], decode_f
 class WhisperSTT:
     """transcribe(audio:...) for a batch of clips on the HIP path (log-mel, encoder, decoder, alignment all on the GPU)."""
 
-    def __init__(self, ctx, model, tokenizer, suppress_ids, blank_ids, alignment_heads=None, split_to_word_tokens=None):
+    def __init__(self, ctx, model, tokenizer, suppress_ids, blank_ids, alignment_heads=None, split_to_word_tokens=None, device_dtw=False):
         self.ctx, self.model, self.tokenizer = ctx, model, tokenizer
+        if device_dtw:                                    # the word alignment's DTW on the device (align_dtw.hip): same paths as the host's;
+            model.set_align_dtw(1)                        # False leaves the model's mode as it is (host unless the caller set it)
         self.suppress_ids, self.blank_ids = list(suppress_ids), list(blank_ids)
         self.alignment_heads = alignment_heads            # [(layer, head)]: the checkpoint's alignment_heads (WhisperModel.swift:95-99)
         self.split_to_word_tokens = split_to_word_tokens  # tokens + [eot] -> (words, token groups) (WhisperTokenizer.swift:546-670)

@@ -155,6 +155,11 @@ class WhisperModel:
         lib = self.ctx.lib
         self.ctx.check(lib.mia_whisper_use_packed(self.h, 1 if on else 0))
 
+    def set_align_dtw(self, mode: int) -> None:
+        """mia_whisper_set_align_dtw: where align() runs its DTW and backtrace -- 0 the host (the default), 1 the device (same paths).  A
+        clone inherits the mode of the handle it is made from."""
+        self.ctx.check(self.ctx.lib.mia_whisper_set_align_dtw(self.h, int(mode)))
+
     def set_encode_stream(self, hip_stream: int | None) -> None:
         """mia_whisper_set_encode_stream: run the encoder half of every window on another HIP stream (raw pointer, e.g.
         torch.cuda.Stream(...).cuda_stream); None restores the single-stream form."""
