@@ -673,6 +673,18 @@ void mia_mimi_stream_free(mia_mimi_stream* s);
 int mia_mimi_stream_reset(mia_mimi_stream* s);
 int mia_mimi_stream_decode(mia_mimi_stream* s, const int32_t* codes, int n_q, int64_t n, float* pcm, int64_t pcm_capacity,
                            int64_t* n_samples, int pcm_mem);
+/* mia_mimi_stream_decode for n_streams independent streams in ONE pass (an MI355X-side addition: the reference steps one decoder at a
+ * time).  Every stream advances by the same n frames from its own position and history; the number of launches does not depend on
+ * n_streams.  streams: 1 to 32 distinct, unbroken streams of one handle (streams[0] names the handle and must not be null).
+ * codes: HOST int32 [n_streams][n_q][n].  Stream u's n * samples-per-frame samples start at pcm + u * pcm_capacity_per_stream, so a
+ * dense [n_streams][n * samples per frame] array passes its row length; *n_samples = the samples of ONE stream.
+ * Everything is checked before anything is launched or any stream is touched (MIA_ERR_INVALID_ARGUMENT: n_streams outside [1, 32], a
+ * null, repeated, broken or foreign stream, an n_q other than a stream's, an id outside [0, bins), a capacity below n * samples per
+ * frame); n = 0 succeeds with 0 samples.  After a device failure EVERY stream of the call needs mia_mimi_stream_reset.  A stream may be
+ * advanced by this entry and by mia_mimi_stream_decode in any order.  A stream's samples do not depend on the other streams of the
+ * call, on its slot, or on n_streams, bit for bit.  A context above 7934 is MIA_ERR_UNSUPPORTED here (the stacked attention's LDS). */
+int mia_mimi_stream_decode_batch(mia_mimi_stream* const* streams, int n_streams, const int32_t* codes, int n_q, int64_t n, float* pcm,
+                                 int64_t pcm_capacity_per_stream, int64_t* n_samples, int pcm_mem);
 /* Mimi encode (Mimi.encode, Mimi.swift:174-182; the codec call of MarvisTTS.tokenizeAudio, MarvisTTS.swift:318-348).  The encode side of
  * a handle is OPTIONAL: it is loaded when the tensors carry encoder.{init_conv1d,layers.N.residuals.0.block.M,layers.N.downsample,
  * final_conv1d}.conv.conv.*, encoder_transformer.transformer.layers.N.*, downsample.conv.conv.weight [D][2 stride][D] and

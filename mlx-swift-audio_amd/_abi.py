@@ -337,6 +337,7 @@ PROTOTYPES = {
     "mia_mimi_stream_free": (None, [vp]),
     "mia_mimi_stream_reset": (i32, [vp]),
     "mia_mimi_stream_decode": (i32, [vp, vp, i32, i64, vp, i64, vp, i32]),
+    "mia_mimi_stream_decode_batch": (i32, [vp, i32, vp, i32, i64, vp, i64, vp, i32]),
     "mia_mimi_encode_frames": (i64, [vp, i64]),
     "mia_mimi_encode": (i32, [vp, vp, i64, i32, vp, i64, vp, i32]),
     "mia_mimi_encode_latent": (i32, [vp, vp, i64, vp, i64, vp, i32]),

@@ -4,12 +4,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// Stacked streams (n_seq > 1) in the three launches that take them: stream u is grid.y = u, reads its own codes [n_q][n] behind the
+// previous stream's, and its rows / samples lie the given step (in floats) behind the previous stream's.  n_seq = 1: one stream.
 // z[t][:] = WfT^T e0[c0[t]] + WrT^T sum_{i >= 1} e_i[c_i[t]]     codes: device [n_q][n]; cb: [nq][bins][dq]; WfT / WrT: [dq][D]
 int mimi_embed_launch(const int32_t* codes, int n_q, int64_t n, const float* cb, int bins, int dq, const float* wfT, const float* wrT, float* z,
-                      int D, hipStream_t s);
+                      int D, hipStream_t s, int n_seq = 1, int64_t z_seq_step = 0);
 // depthwise causal transposed convolution, kernel 2 * stride: y[t * stride + r][c] = z[t][c] w[r][c] + z[t - 1][c] w[r + stride][c];
 // zp: [1 + n][D], row 0 = z[-1] (the carried row, zeros at the start of a clip)
-int mimi_upsample_launch(const float* zp, const float* w, float* y, int64_t n, int D, int stride, hipStream_t s);
+int mimi_upsample_launch(const float* zp, const float* w, float* y, int64_t n, int D, int stride, hipStream_t s, int n_seq = 1,
+                         int64_t zp_seq_step = 0, int64_t y_seq_step = 0);
 // split in_proj's [P][3 D] into q | k | v, interleaved-pair RoPE at position pos0 + row on q and k; k / v rows go to k_new / v_new (row stride D)
 int mimi_qkv_finish_launch(const float* qkv, float* q, float* k_new, float* v_new, int64_t P, int D, int64_t pos0, const double* inv_freq, hipStream_t s);
 // pair-windowed attention against a key history: queries are P rows at positions pos0 .. pos0 + P - 1 (pos0 and P even); the pair
@@ -17,7 +20,27 @@ int mimi_qkv_finish_launch(const float* qkv, float* q, float* k_new, float* v_ne
 int mimi_window_attn_launch(const float* q, const float* K, const float* V, float* out, int64_t P, int D, int H, int64_t pos0, int64_t row0_pos,
                             int ctx, float scale, hipStream_t s);
 // out[t] = bias + sum_{k, c} w[k * C + c] * elu(x[t + k][c])      x: [K - 1 + T][C], the first K - 1 rows are the left context
-int mimi_conv_out1_launch(const float* x, const float* w, const float* bias, float* out, int64_t T, int C, int K, hipStream_t s);
+int mimi_conv_out1_launch(const float* x, const float* w, const float* bias, float* out, int64_t T, int C, int K, hipStream_t s, int n_seq = 1,
+                          int64_t x_seq_step = 0, int64_t out_seq_step = 0);
+
+// ---- several streams in one pass (mia_mimi_stream_decode_batch).  The call's device table: one record per slot, uploaded once.
+struct MimiStreamRow {
+  float* conv_state;                   // the stream's carried convolution rows
+  float* hist;                         // its current key / value buffer [n_layers][2][cap][D]
+  int64_t cap, fill, pos;              // rows per run, rows present before this call, position of this call's first row
+};
+// For every stream u: the `ctx` rows at conv_state + st_off go in front of its run buf + u * seq_step = [ctx rows | T new rows] of C
+// floats, and the run's last ctx rows go back to the state.  src_new (optional): dense [n_streams * T][C] rows copied into the runs first.
+int mimi_carry_rows_launch(const MimiStreamRow* tab, int n_streams, int64_t st_off, float* buf, int64_t seq_step, int ctx, int C, int64_t T,
+                           const float* src_new, hipStream_t s);
+// mimi_qkv_finish on [n_streams * P][3 D]: row p of stream u at position pos[u] + p, k | v into row fill[u] + p of its history's layer
+int mimi_qkv_finish_streams_launch(const float* qkv, float* q, const MimiStreamRow* tab, int n_streams, int layer, int64_t P, int D, const double* inv_freq,
+                                   hipStream_t s);
+// mimi_window_attn's key rule for every (pair, head, stream) in one launch, each K / V row loaded once per pair; q / out: [n_streams * P][D].
+// The caller guarantees per stream what mimi_window_attn_launch checks: pos even, max(0, pos - ctx) >= pos - fill, fill + P <= cap.
+size_t mimi_pair_attn_lds(int ctx);    // dynamic LDS of the launch; it serves ctx while this is <= 64 KB
+int mimi_pair_attn_launch(const float* q, const MimiStreamRow* tab, int n_streams, int layer, float* out, int64_t P, int D, int H, int ctx, float scale,
+                          hipStream_t s);
 
 // ---- encode side (mimi_encode_kernels.hip)
 // edge padding of the latent downsample: y = [front copies of x[0] | the P rows of x | back copies of x[P - 1]], rows of D floats

@@ -46,6 +46,33 @@ const char* config_error(const mia_mimi_config& g) {
   return nullptr;
 }
 
+// The layers over `rows` rows of x, in place (one stream's P rows, or the stacked rows of several streams: LayerNorm and the four GEMMs are
+// per row).  attn(l) turns layer l's w.qkv into w.ob: the QKV finish and whichever attention the entry runs.
+template <class Attn>
+int transformer_layers(mia_mimi* m, const std::vector<MLayer>& layers, float* x, int64_t rows, const MimiTfWork& w, Attn attn) {
+  mia_ctx* ctx = m->ctx;
+  hipStream_t s = ctx->stream;
+  const int D = m->D;
+  auto dev_fail = [&](const char* what) { return mia_fail(ctx, MIA_ERR_DEVICE, "mimi: %s failed", what); };
+  auto gemm = [&](const float* X, int K, const float* W, int N, float* Y, const float* R, int act) {
+    ConvGemmArgs g;
+    g.X = X; g.ldx = K; g.T_in = (int)rows; g.W = W; g.M = (int)rows; g.N = N; g.Cin = K; g.taps = 1;
+    g.Y = Y; g.ldy = N; g.T_out = (int)rows; g.R = R; g.ldr = N; g.gelu = act;
+    return codec_conv_gemm_run(ctx, g, 1, "mimi");
+  };
+  for (int l = 0; l < (int)layers.size(); ++l) {
+    const MLayer& ly = layers[l];
+    if (mia_norm_launch(x, D, ly.ln1g, ly.ln1b, w.nb, D, (int)rows, D, 1e-5f, false, MIA_F32, s)) return dev_fail("norm launch");
+    if (int rc = gemm(w.nb, D, ly.win, 3 * D, w.qkv, nullptr, 0)) return rc;
+    if (int rc = attn(l)) return rc;
+    if (int rc = gemm(w.ob, D, ly.wout, D, x, x, 0)) return rc;
+    if (mia_norm_launch(x, D, ly.ln2g, ly.ln2b, w.nb, D, (int)rows, D, 1e-5f, false, MIA_F32, s)) return dev_fail("norm launch");
+    if (int rc = gemm(w.nb, D, ly.w1, m->FF, w.ff, nullptr, 7)) return rc;
+    if (int rc = gemm(w.ff, m->FF, ly.w2, D, x, x, 0)) return rc;
+  }
+  return MIA_OK;
+}
+
 struct Run {
   mia_mimi* m; mia_mimi_stream* st; hipStream_t s;
   // carried rows in front of a convolution's input: from the stream's state, or zeros
@@ -148,6 +175,30 @@ int check_call(mia_mimi* m, const char* who, const int32_t* codes, int n_q, int6
   return MIA_OK;
 }
 
+// room for P more rows in a stream's key / value history: when they do not fit behind the `fill` rows present, the last `context` rows
+// move to the front of the other buffer (grown if need be) and the two swap
+int hist_room(mia_mimi* m, mia_mimi_stream* st, int64_t P) {
+  mia_ctx* ctx = m->ctx;
+  const int D = m->D;
+  const size_t ctxr = (size_t)m->context;
+  if ((size_t)st->fill + (size_t)P <= st->cap[st->cur]) return MIA_OK;
+  const size_t keep = std::min((size_t)st->fill, ctxr);
+  const int o = st->cur ^ 1;
+  if (st->cap[o] < keep + (size_t)P) {
+    const size_t rows = ctxr + std::max((size_t)P, ctxr + 2);
+    size_t have = st->cap[o] * 2 * m->L * D;
+    st->cap[o] = 0;
+    if (int rc = mia_grow(ctx, st->hist[o], have, rows * 2 * m->L * D, "mimi: hipMalloc failed")) return rc;
+    st->cap[o] = rows;
+  }
+  if (keep)
+    MIA_HIP(ctx, hipMemcpy2DAsync(st->hist[o], st->cap[o] * D * 4, st->hist[st->cur] + ((size_t)st->fill - keep) * D, st->cap[st->cur] * D * 4,
+                                  keep * D * 4, (size_t)2 * m->L, hipMemcpyDeviceToDevice, ctx->stream));
+  st->cur = o;
+  st->fill = (int64_t)keep;
+  return MIA_OK;
+}
+
 int decode_call(mia_mimi* m, mia_mimi_stream* st, const int32_t* codes, int n_q, int64_t n, float* pcm, int64_t* n_samples, int mem) {
   mia_ctx* ctx = m->ctx;
   MIA_HIP(ctx, hipSetDevice(ctx->device));
@@ -165,25 +216,8 @@ int decode_call(mia_mimi* m, mia_mimi_stream* st, const int32_t* codes, int n_q,
   for (int i = 0; i < 3; ++i) o_sb[i] = cv.add(sbf * 4);
   char* ws = nullptr;
   if (!cv.workspace(ctx, ws)) return MIA_ERR_OUT_OF_MEMORY;
-  if (st) {              // room for this call's rows in the key / value history
-    const size_t ctxr = (size_t)m->context;
-    if ((size_t)st->fill + (size_t)P > st->cap[st->cur]) {
-      const size_t keep = std::min((size_t)st->fill, ctxr);
-      const int o = st->cur ^ 1;
-      if (st->cap[o] < keep + (size_t)P) {
-        const size_t rows = ctxr + std::max((size_t)P, ctxr + 2);
-        size_t have = st->cap[o] * 2 * m->L * D;
-        st->cap[o] = 0;
-        if (int rc = mia_grow(ctx, st->hist[o], have, rows * 2 * m->L * D, "mimi: hipMalloc failed")) return rc;
-        st->cap[o] = rows;
-      }
-      if (keep)
-        MIA_HIP(ctx, hipMemcpy2DAsync(st->hist[o], st->cap[o] * D * 4, st->hist[st->cur] + ((size_t)st->fill - keep) * D, st->cap[st->cur] * D * 4,
-                                      keep * D * 4, (size_t)2 * m->L, hipMemcpyDeviceToDevice, ctx->stream));
-      st->cur = o;
-      st->fill = (int64_t)keep;
-    }
-  }
+  if (st)
+    if (int rc = hist_room(m, st, P)) return rc;
   Work w;
   auto f = [&](size_t off) { return (float*)(ws + off); };
   w.zp = f(o_zp); w.xb = f(o_xb); w.tf = MimiTfWork{f(o_nb), f(o_qkv), f(o_qb), f(o_ob), f(o_ff), f(o_kt), f(o_vt)};
@@ -200,6 +234,122 @@ int decode_call(mia_mimi* m, mia_mimi_stream* st, const int32_t* codes, int n_q,
   return io.finish();
 }
 
+// ---- several streams in one pass.  The program of mimi_run with every buffer stacked per stream: stream u's [context | new rows] run of a
+// convolution lies `step` rows behind stream u - 1's, the tap GEMM runs with n_seq = S (taps never cross a stream), the transformer's
+// LayerNorms and GEMMs see the S * P rows as one matrix, and what differs between the streams -- state, history, position, fill -- is
+// read from the call's device table.  One launch per step whatever S is.
+struct WorkS { float *zp, *xt, *xb, *sb[3]; MimiTfWork tf; };
+
+int mimi_run_streams(mia_mimi* m, int S, const MimiStreamRow* d_tab, const int32_t* d_codes, int n_q, int64_t n, float* d_pcm, int64_t pcm_step, const WorkS& w) {
+  mia_ctx* ctx = m->ctx;
+  hipStream_t s = ctx->stream;
+  const int D = m->D, k0 = m->cfg.seanet_ksize;
+  const int64_t P = n * m->us;
+  auto dev_fail = [&](const char* what) { return mia_fail(ctx, MIA_ERR_DEVICE, "mimi: %s failed", what); };
+  // the carried rows of one convolution, all streams: state -> front of the runs, the runs' last rows -> state
+  auto carry = [&](size_t st_off, float* buf, int64_t step_rows, int ctx_rows, int C, int64_t T, const float* src_new) {
+    if (!ctx_rows) return 0;
+    return mimi_carry_rows_launch(d_tab, S, (int64_t)st_off, buf, step_rows * C, ctx_rows, C, T, src_new, s);
+  };
+
+  // ---- quantizer decode and upsample; the transformer's rows are dense [S * P][D]
+  if (mimi_embed_launch(d_codes, n_q, n, m->cb, m->bins, m->dq, m->wfT, m->wrT, w.zp + D, D, s, S, (1 + n) * D)) return dev_fail("embed launch");
+  if (carry(m->st_z, w.zp, 1 + n, 1, D, n, nullptr)) return dev_fail("state rows launch");
+  if (mimi_upsample_launch(w.zp, m->wup, w.xt, n, D, m->us, s, S, (1 + n) * D, P * D)) return dev_fail("upsample launch");
+
+  // ---- transformer
+  const int rc_tf = transformer_layers(m, m->layers, w.xt, (int64_t)S * P, w.tf, [&](int l) -> int {
+    if (mimi_qkv_finish_streams_launch(w.tf.qkv, w.tf.qb, d_tab, S, l, P, D, m->inv_freq, s)) return dev_fail("qkv finish launch");
+    if (mimi_pair_attn_launch(w.tf.qb, d_tab, S, l, w.tf.ob, P, D, m->H, m->context, 0.125f, s)) return dev_fail("pair attention launch");
+    return MIA_OK;
+  });
+  if (rc_tf) return rc_tf;
+
+  // ---- SEANet decoder: mimi_run's rotation of a / b / c, each a stack of S runs
+  auto conv = [&](const MConv& c, const float* X, int64_t x_step, int64_t T, float* Y, int64_t y_step, const float* R, int elu) {
+    ConvGemmArgs g;          // per stream X: [taps - 1 + T][Cin]
+    g.X = X; g.ldx = c.Cin; g.T_in = (int)(T + c.taps - 1); g.W = c.w; g.bias = c.b; g.M = (int)T; g.N = c.N; g.Cin = c.Cin; g.taps = c.taps;
+    g.Y = Y; g.ldy = c.N; g.T_out = (int)T; g.R = R; g.ldr = c.N; g.elu_pre = elu;
+    g.n_seq = S; g.x_seq_step = x_step; g.y_seq_step = y_step;
+    return codec_conv_gemm_run(ctx, g, 1, "mimi");
+  };
+  float *a = w.sb[0], *b = w.sb[1], *c = w.sb[2];
+  const int rk = m->cfg.seanet_residual_ksize, lk = m->cfg.seanet_last_ksize;
+  if (carry(m->st_x, w.xb, k0 - 1 + P, k0 - 1, D, P, w.xt)) return dev_fail("state rows launch");
+  if (k0 == 1 && hipMemcpyAsync(w.xb, w.xt, (size_t)S * P * D * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return dev_fail("row copy");
+  if (int rc = conv(m->init, w.xb, k0 - 1 + P, P, a + m->init.N, 1 + P, nullptr, 0)) return rc;
+  int64_t T = P, a_step = 1 + P;          // rows per stream of `a`: [1 carried row | T rows]
+  for (int i = 0; i < m->nr; ++i) {
+    const SLayer& l = m->sl[i];
+    const int Ci = l.up.Cin, Co = l.up.N, s_ = l.up.stride;
+    const int64_t To = T * s_;
+    const int next_ctx = i + 1 < m->nr ? 1 : lk - 1;
+    // b and the stage's output in `a` share one step: the residual rides the output's row mapping in the tap GEMM
+    const int64_t step = To + std::max(rk - 1, next_ctx);
+    if (carry(m->st_up[i], a, a_step, 1, Ci, T, nullptr)) return dev_fail("state rows launch");
+    {
+      ConvGemmArgs g;          // per stream X: [1 + T][Ci], row 0 = the carried input row; phase z writes rows t * stride + z
+      g.X = a; g.ldx = Ci; g.T_in = (int)(T + 1); g.W = l.up.w; g.w_phase_stride = (int64_t)Co * 2 * Ci; g.bias = l.up.b; g.elu_pre = 1;
+      g.M = (int)T; g.N = Co; g.Cin = Ci; g.taps = 2;
+      g.Y = b + (size_t)(rk - 1) * Co; g.ldy = Co; g.T_out = (int)To; g.y_row_mul = s_; g.y_phase_step = 1;
+      g.n_seq = S; g.x_seq_step = a_step; g.y_seq_step = step;
+      if (int rc = codec_conv_gemm_run(ctx, g, s_, "mimi")) return rc;
+    }
+    if (carry(m->st_c3[i], b, step, rk - 1, Co, To, nullptr)) return dev_fail("state rows launch");
+    if (int rc = conv(l.c3, b, step, To, c, To, nullptr, 1)) return rc;
+    if (int rc = conv(l.c1, c, To, To, a + (size_t)next_ctx * Co, step, b + (size_t)(rk - 1) * Co, 1)) return rc;
+    T = To; a_step = step;
+  }
+  const int nf = m->fin.Cin;
+  if (carry(m->st_fin, a, a_step, lk - 1, nf, T, nullptr)) return dev_fail("state rows launch");
+  if (mimi_conv_out1_launch(a, m->fin.w, m->fin.b, d_pcm, T, nf, lk, s, S, a_step * nf, pcm_step)) return dev_fail("output conv launch");
+  return MIA_OK;
+}
+
+int decode_batch_call(mia_mimi* m, mia_mimi_stream* const* sts, int S, const int32_t* codes, int n_q, int64_t n, float* pcm, int64_t cap, int64_t* n_samples,
+                      int mem) {
+  mia_ctx* ctx = m->ctx;
+  MIA_HIP(ctx, hipSetDevice(ctx->device));
+  const int D = m->D;
+  const int64_t P = n * m->us, Sps = n * m->spf, R = (int64_t)S * P;
+  HostIo io(ctx, mem);
+  Carve cv;
+  const size_t o_tab = cv.add((size_t)S * sizeof(MimiStreamRow)), o_codes = cv.add((size_t)S * n_q * n * 4), o_pcm = cv.add(io.staged((size_t)S * Sps * 4));
+  const size_t o_zp = cv.add((size_t)S * (1 + n) * D * 4), o_xt = cv.add((size_t)R * D * 4), o_xb = cv.add((size_t)S * (m->cfg.seanet_ksize - 1 + P) * D * 4);
+  const size_t o_nb = cv.add((size_t)R * D * 4), o_qkv = cv.add((size_t)R * 3 * D * 4), o_qb = cv.add((size_t)R * D * 4), o_ob = cv.add((size_t)R * D * 4);
+  const size_t o_ff = cv.add((size_t)R * m->FF * 4);
+  const size_t sbf = seanet_buf_floats(m, P) * S;          // a run's step never exceeds the single call's buffer
+  size_t o_sb[3];
+  for (int i = 0; i < 3; ++i) o_sb[i] = cv.add(sbf * 4);
+  char* ws = nullptr;
+  if (!cv.workspace(ctx, ws)) return MIA_ERR_OUT_OF_MEMORY;
+  std::vector<MimiStreamRow> tab(S);
+  for (int u = 0; u < S; ++u) {          // history compaction per stream, on the host, as the single call does it
+    mia_mimi_stream* st = sts[u];
+    if (int rc = hist_room(m, st, P)) return rc;
+    tab[u] = MimiStreamRow{st->conv_state, st->hist[st->cur], (int64_t)st->cap[st->cur], st->fill, st->pos};
+    // what mimi_window_attn_launch checks for one stream: every pair's lowest key is a row of the history
+    if ((st->pos & 1) || (st->pos > m->context ? st->pos - m->context : 0) < st->pos - st->fill || st->fill > st->pos)
+      return mia_fail(ctx, MIA_ERR_DEVICE, "mimi: stream %d's history does not hold its window", u);
+  }
+  WorkS w;
+  auto f = [&](size_t off) { return (float*)(ws + off); };
+  w.zp = f(o_zp); w.xt = f(o_xt); w.xb = f(o_xb); w.tf = MimiTfWork{f(o_nb), f(o_qkv), f(o_qb), f(o_ob), f(o_ff), nullptr, nullptr};
+  for (int i = 0; i < 3; ++i) w.sb[i] = f(o_sb[i]);
+  const MimiStreamRow* d_tab = io.table(tab.data(), ws + o_tab, (size_t)S * sizeof(MimiStreamRow));
+  const int32_t* d_codes = io.table(codes, ws + o_codes, (size_t)S * n_q * n * 4);
+  float* d_pcm = io.host() ? (float*)(ws + o_pcm) : pcm;          // staged dense; the caller's rows are `cap` samples apart
+  int rc = mimi_run_streams(m, S, d_tab, d_codes, n_q, n, d_pcm, io.host() ? Sps : cap, w);
+  if (rc != MIA_OK) {
+    for (int u = 0; u < S; ++u) sts[u]->broken = true;
+    return rc;
+  }
+  for (int u = 0; u < S; ++u) { sts[u]->fill += P; sts[u]->pos += P; }
+  if (n_samples) *n_samples = Sps;
+  if (io.host()) io.check(hipMemcpy2DAsync(pcm, (size_t)cap * 4, d_pcm, (size_t)Sps * 4, (size_t)Sps * 4, (size_t)S, io.to_caller(), ctx->stream));
+  return io.finish();
+}
+
 }  // namespace
 
 int mimi_transformer_run(mia_mimi* m, const std::vector<MLayer>& layers, mia_mimi_stream* st, float* x, int64_t P, const MimiTfWork& w) {
@@ -208,16 +358,7 @@ int mimi_transformer_run(mia_mimi* m, const std::vector<MLayer>& layers, mia_mim
   const int D = m->D;
   auto dev_fail = [&](const char* what) { return mia_fail(ctx, MIA_ERR_DEVICE, "mimi: %s failed", what); };
   const int64_t pos0 = st ? st->pos : 0;
-  auto gemm = [&](const float* X, int K, const float* W, int N, float* Y, const float* R, int act) {
-    ConvGemmArgs g;
-    g.X = X; g.ldx = K; g.T_in = (int)P; g.W = W; g.M = (int)P; g.N = N; g.Cin = K; g.taps = 1;
-    g.Y = Y; g.ldy = N; g.T_out = (int)P; g.R = R; g.ldr = N; g.gelu = act;
-    return codec_conv_gemm_run(ctx, g, 1, "mimi");
-  };
-  for (int l = 0; l < (int)layers.size(); ++l) {
-    const MLayer& ly = layers[l];
-    if (mia_norm_launch(x, D, ly.ln1g, ly.ln1b, w.nb, D, (int)P, D, 1e-5f, false, MIA_F32, s)) return dev_fail("norm launch");
-    if (int rc = gemm(w.nb, D, ly.win, 3 * D, w.qkv, nullptr, 0)) return rc;
+  return transformer_layers(m, layers, x, P, w, [&](int l) -> int {
     float *kn = w.kt, *vn = w.vt, *Kl = nullptr, *Vl = nullptr;
     if (st) {
       const size_t cap = st->cap[st->cur];
@@ -235,12 +376,8 @@ int mimi_transformer_run(mia_mimi* m, const std::vector<MLayer>& layers, mia_mim
       if (const char* e = mia_attn_f32_check(a)) return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "mimi: %s", e);
       if (mia_attn_f32_launch(a, s)) return dev_fail("attention launch");
     }
-    if (int rc = gemm(w.ob, D, ly.wout, D, x, x, 0)) return rc;
-    if (mia_norm_launch(x, D, ly.ln2g, ly.ln2b, w.nb, D, (int)P, D, 1e-5f, false, MIA_F32, s)) return dev_fail("norm launch");
-    if (int rc = gemm(w.nb, D, ly.w1, m->FF, w.ff, nullptr, 7)) return rc;
-    if (int rc = gemm(w.ff, m->FF, ly.w2, D, x, x, 0)) return rc;
-  }
-  return MIA_OK;
+    return MIA_OK;
+  });
 }
 
 extern "C" {
@@ -372,6 +509,36 @@ int mia_mimi_stream_decode(mia_mimi_stream* s, const int32_t* codes, int n_q, in
   if (n == 0) { if (n_samples) *n_samples = 0; return MIA_OK; }
   s->n_q = n_q;
   return decode_call(m, s, codes, n_q, n, pcm, n_samples, pcm_mem);
+}
+
+int mia_mimi_stream_decode_batch(mia_mimi_stream* const* streams, int n_streams, const int32_t* codes, int n_q, int64_t n, float* pcm,
+                                 int64_t pcm_capacity_per_stream, int64_t* n_samples, int pcm_mem) {
+  if (!streams || !streams[0]) return MIA_ERR_MODEL_NOT_LOADED;
+  mia_mimi* m = streams[0]->m;
+  mia_ctx* ctx = m->ctx;
+  const char* who = "mimi_stream_decode_batch";
+  MIA_CHECK_ARG(ctx, n_streams >= 1 && n_streams <= 32, "%s: n_streams must be in [1, 32] (got %d)", who, n_streams);
+  for (int u = 0; u < n_streams; ++u) {
+    const mia_mimi_stream* s = streams[u];
+    MIA_CHECK_ARG(ctx, s, "%s: stream %d is null", who, u);
+    MIA_CHECK_ARG(ctx, s->m == m, "%s: stream %d belongs to another codec handle", who, u);
+    for (int v = 0; v < u; ++v) MIA_CHECK_ARG(ctx, streams[v] != s, "%s: streams %d and %d are the same stream", who, v, u);
+    MIA_CHECK_ARG(ctx, !s->broken, "%s: an earlier call on stream %d failed on the device, reset the stream first", who, u);
+    MIA_CHECK_ARG(ctx, s->n_q < 0 || s->n_q == n_q, "%s: n_q changed from %d to %d within stream %d (reset it first)", who, s->n_q, n_q, u);
+  }
+  // the ids of all streams are one [n_streams * n_q][n] array to the range check; its frame limit then bounds the stacked buffers
+  if (int rc = check_call(m, who, codes, n_q, n, pcm, pcm_capacity_per_stream, pcm_mem)) return rc;
+  if (n == 0) { if (n_samples) *n_samples = 0; return MIA_OK; }
+  MIA_CHECK_ARG(ctx, (double)n_streams * n * m->spf * m->cfg.seanet_nfilters * 2.0 < 1073741824.0, "%s: %d streams of %lld frames exceed the call's buffers", who,
+                n_streams, (long long)n);
+  for (int64_t k = (int64_t)n_q * n; k < (int64_t)n_streams * n_q * n; ++k)
+    if (codes[k] < 0 || codes[k] >= m->bins)
+      return mia_fail(ctx, MIA_ERR_INVALID_ARGUMENT, "%s: id %d of stream %lld, codebook %lld, frame %lld is outside [0, %d)", who, codes[k],
+                      (long long)(k / ((int64_t)n_q * n)), (long long)(k / n % n_q), (long long)(k % n), m->bins);
+  if (mimi_pair_attn_lds(m->context) > 64 * 1024)
+    return mia_fail(ctx, MIA_ERR_UNSUPPORTED, "%s: context %d exceeds the stacked attention's LDS (use mia_mimi_stream_decode)", who, m->context);
+  for (int u = 0; u < n_streams; ++u) streams[u]->n_q = n_q;
+  return decode_batch_call(m, streams, n_streams, codes, n_q, n, pcm, pcm_capacity_per_stream, n_samples, pcm_mem);
 }
 
 }  // extern "C"

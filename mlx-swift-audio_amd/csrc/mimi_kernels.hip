@@ -14,6 +14,9 @@
 //                      query the scores are plain FMAs (lane = key), the softmax is one wave reduction, and the value sum has
 //                      lane = output column, so V rows are read coalesced.
 //  * mimi_conv_out1    ELU -> causal conv k (C -> 1), no tanh: the SEANet's last layer.
+//  * mimis_*           several streams in one pass (mia_mimi_stream_decode_batch): the carried rows of a convolution for all streams,
+//                      the QKV finish at each stream's own position and fill, and the stacked pair-windowed attention that loads
+//                      each K / V row once for the two queries of a pair.  embed / upsample / conv_out1 take the stream as grid.y.
 #include "mia_device.h"
 #include "mimi.h"
 
@@ -22,11 +25,14 @@ namespace {
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }
 
 __global__ __launch_bounds__(256) void mimi_embed(const int32_t* __restrict__ codes, int n_q, int64_t n, const float* __restrict__ cb, int bins,
-                                                  int dq, const float* __restrict__ wfT, const float* __restrict__ wrT, float* __restrict__ z, int D) {
+                                                  int dq, const float* __restrict__ wfT, const float* __restrict__ wrT, float* __restrict__ z, int D,
+                                                  int64_t z_seq_step) {
   extern __shared__ float sm[];          // e0[dq] | rest[dq]
   float* e0 = sm;
   float* er = sm + dq;
   const int64_t t = blockIdx.x;
+  codes += (int64_t)blockIdx.y * n_q * n;          // blockIdx.y = stacked stream: its own [n_q][n] codes, its rows z_seq_step floats on
+  z += (int64_t)blockIdx.y * z_seq_step;
   for (int j = threadIdx.x; j < dq; j += 256) {
     e0[j] = cb[(int64_t)codes[t] * dq + j];
     float acc = 0.f;
@@ -49,8 +55,10 @@ __global__ __launch_bounds__(256) void mimi_embed(const int32_t* __restrict__ co
 }
 
 __global__ __launch_bounds__(256) void mimi_upsample(const float* __restrict__ zp, const float* __restrict__ w, float* __restrict__ y, int64_t n, int D,
-                                                     int stride) {
+                                                     int stride, int64_t zp_seq_step, int64_t y_seq_step) {
   const int64_t total = n * stride * D;
+  zp += (int64_t)blockIdx.y * zp_seq_step;         // blockIdx.y = stacked stream
+  y += (int64_t)blockIdx.y * y_seq_step;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int64_t row = e / D;
     const int c = (int)(e - row * D);
@@ -134,8 +142,10 @@ __global__ __launch_bounds__(128) void mimi_window_attn(const float* __restrict_
 }
 
 __global__ __launch_bounds__(256) void mimi_conv_out1(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                      float* __restrict__ out, int64_t T, int C, int K) {
+                                                      float* __restrict__ out, int64_t T, int C, int K, int64_t x_seq_step, int64_t out_seq_step) {
   extern __shared__ float sw[];          // w[K * C]
+  x += (int64_t)blockIdx.y * x_seq_step;           // blockIdx.y = stacked stream
+  out += (int64_t)blockIdx.y * out_seq_step;
   for (int i = threadIdx.x; i < K * C; i += 256) sw[i] = w[i];
   __syncthreads();
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -152,21 +162,185 @@ __global__ __launch_bounds__(256) void mimi_conv_out1(const float* __restrict__ 
   out[t] = acc;
 }
 
+// ---- several streams in one pass.  Every kernel below reads what differs between the streams of a call from the call's table
+// (MimiStreamRow, one record per slot), so one launch serves them all and nothing in it depends on which slot a stream has.
+
+// The carried rows of one convolution, for every stream: state -> the `ctx` rows in front of the stream's [context | T new rows], and the
+// last `ctx` rows of that run back into the state.  One thread owns a float4 column of one stream and walks its rows in order, so the
+// in-place shift of the state (T < ctx: part of the new state is old state) reads every row before the same thread overwrites it.
+// src_new (optional): the T new rows are first copied in from a dense [n_streams * T][C] buffer (the transformer's output).
+__global__ __launch_bounds__(256) void mimis_carry_rows(const MimiStreamRow* __restrict__ tab, int64_t st_off, float* buf, int64_t seq_step, int ctx,
+                                                        int C, int64_t T, const float* __restrict__ src_new) {
+  const int c = (blockIdx.x * 256 + threadIdx.x) * 4;
+  if (c >= C) return;
+  const int u = blockIdx.y;
+  float* state = tab[u].conv_state + st_off + c;
+  float* b = buf + (int64_t)u * seq_step + c;
+  const float* nw = src_new ? src_new + (int64_t)u * T * C + c : b + (int64_t)ctx * C;
+  for (int r = 0; r < ctx; ++r) *reinterpret_cast<f32x4*>(b + (int64_t)r * C) = *reinterpret_cast<const f32x4*>(state + (int64_t)r * C);
+  if (src_new)
+    for (int64_t t = 0; t < T; ++t) *reinterpret_cast<f32x4*>(b + (ctx + t) * C) = *reinterpret_cast<const f32x4*>(nw + t * C);
+  for (int r = 0; r < ctx; ++r) {
+    const int64_t t = T + r - ctx;                             // the new state's row r: row T + r of [context | new rows]
+    *reinterpret_cast<f32x4*>(state + (int64_t)r * C) = *reinterpret_cast<const f32x4*>(t < 0 ? state + (T + r) * C : nw + t * C);
+  }
+}
+
+// mimi_qkv_finish over the stacked rows [n_streams * P][3 D]: row p of stream u is rotated at pos[u] + p, and its k | v go to row
+// fill[u] + p of layer l's runs in that stream's own history.
+__global__ __launch_bounds__(256) void mimis_qkv_finish(const float* __restrict__ qkv, float* __restrict__ q, const MimiStreamRow* __restrict__ tab, int layer,
+                                                        int64_t P, int D, const double* __restrict__ inv_freq) {
+  const int half = D >> 1;
+  const int64_t total = P * half;
+  const MimiStreamRow sr = tab[blockIdx.y];
+  float* kn = sr.hist + ((int64_t)layer * 2 * sr.cap + sr.fill) * D;
+  float* vn = kn + sr.cap * D;
+  qkv += (int64_t)blockIdx.y * P * 3 * D;
+  q += (int64_t)blockIdx.y * P * D;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const int64_t p = e / half;
+    const int col = (int)(e - p * half) * 2;
+    const int i = (col & 63) >> 1;
+    double sd, cd;
+    sincos((double)(sr.pos + p) * inv_freq[i], &sd, &cd);
+    const float sn = (float)sd, cs = (float)cd;
+    const float* src = qkv + p * 3 * D + col;
+    const float2 qa = *reinterpret_cast<const float2*>(src);
+    const float2 ka = *reinterpret_cast<const float2*>(src + D);
+    const float2 va = *reinterpret_cast<const float2*>(src + 2 * D);
+    *reinterpret_cast<float2*>(q + p * D + col) = make_float2(qa.x * cs - qa.y * sn, qa.x * sn + qa.y * cs);
+    *reinterpret_cast<float2*>(kn + p * D + col) = make_float2(ka.x * cs - ka.y * sn, ka.x * sn + ka.y * cs);
+    *reinterpret_cast<float2*>(vn + p * D + col) = va;
+  }
+}
+
+// The streamed attention of every (frame pair, head, stream) of a call: one workgroup of four waves each, no workgroup waits on another.
+// The two queries of a pair see the same keys [lo, p + 2), lo = max(0, p - ctx) (mimi_window_attn's rule), so the pair shares every row:
+//   scores  thread = key (key j of the window goes to thread j mod 256): it loads its K row ONCE, 16 x 128 bit, and forms the dot
+//           products with both queries, which sit in LDS (every lane reads the same address: a broadcast).  Each product is four
+//           interleaved partial sums over the 64 columns, combined (a0 + a1) + (a2 + a3).
+//   softmax per query the maximum and the sum over the window: a wave butterfly, then the four waves' values in wave order.
+//   values  wave w takes the keys j = w, w + 4, ...; lane = output column, so a V row is one coalesced 256-byte read, made ONCE, and
+//           feeds both queries' accumulators; the four waves' partial sums meet in LDS as ((w0 + w1) + (w2 + w3)) / sum.
+// Every sum's order is a function of the key's index in the window alone: it does not depend on the stream's slot, on the other
+// streams, on the number of streams or on the frames of the call.  LDS: [2][ctx + 2] scores | 512 floats that hold first the two
+// queries, then the reduction scratch, then the partial sums.
+__global__ __launch_bounds__(256) void mimis_pair_attn(const float* __restrict__ q, const MimiStreamRow* __restrict__ tab, int layer, float* __restrict__ out,
+                                                       int64_t P, int D, int ctx, float scale) {
+  extern __shared__ float sm[];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nkmax = ctx + 2;
+  float* sc = sm;                                            // [2][nkmax]
+  float* xq = sm + 2 * nkmax;                                // 512 floats
+  const int64_t pair = blockIdx.x;
+  const int h = blockIdx.y;
+  const MimiStreamRow sr = tab[blockIdx.z];
+  const int64_t p_abs = sr.pos + 2 * pair;
+  const int64_t lo = p_abs > ctx ? p_abs - ctx : 0;
+  const int nk = (int)(p_abs + 2 - lo);                      // <= ctx + 2
+  const int64_t row_lo = lo - (sr.pos - sr.fill);            // the history row that holds position lo
+  const float* Kb = sr.hist + ((int64_t)layer * 2 * sr.cap + row_lo) * D + h * 64;
+  const float* Vb = Kb + sr.cap * D;
+  const int64_t qrow = (int64_t)blockIdx.z * P + 2 * pair;
+  if (tid < 128) xq[tid] = q[(qrow + (tid >> 6)) * D + h * 64 + lane];
+  __syncthreads();
+  float m0 = -INFINITY, m1 = -INFINITY;
+  for (int j = tid; j < nk; j += 256) {
+    const float* kr = Kb + (int64_t)j * D;
+    float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const f32x4 kv = *reinterpret_cast<const f32x4*>(kr + 4 * i);
+      const f32x4 q0 = *reinterpret_cast<const f32x4*>(xq + 4 * i);
+      const f32x4 q1 = *reinterpret_cast<const f32x4*>(xq + 64 + 4 * i);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) { a[t] = fmaf(q0[t], kv[t], a[t]); b[t] = fmaf(q1[t], kv[t], b[t]); }
+    }
+    const float s0 = ((a[0] + a[1]) + (a[2] + a[3])) * scale, s1 = ((b[0] + b[1]) + (b[2] + b[3])) * scale;
+    sc[j] = s0; sc[nkmax + j] = s1;
+    m0 = fmaxf(m0, s0); m1 = fmaxf(m1, s1);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { m0 = fmaxf(m0, __shfl_xor(m0, o, 64)); m1 = fmaxf(m1, __shfl_xor(m1, o, 64)); }
+  __syncthreads();                                           // the queries have been read: their floats become the scratch
+  if (lane == 0) { xq[w] = m0; xq[4 + w] = m1; }
+  __syncthreads();
+  m0 = fmaxf(fmaxf(xq[0], xq[1]), fmaxf(xq[2], xq[3]));
+  m1 = fmaxf(fmaxf(xq[4], xq[5]), fmaxf(xq[6], xq[7]));
+  float l0 = 0.f, l1 = 0.f;
+  for (int j = tid; j < nk; j += 256) {
+    const float e0 = expf(sc[j] - m0), e1 = expf(sc[nkmax + j] - m1);
+    sc[j] = e0; sc[nkmax + j] = e1;
+    l0 += e0; l1 += e1;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { l0 += __shfl_xor(l0, o, 64); l1 += __shfl_xor(l1, o, 64); }
+  if (lane == 0) { xq[8 + w] = l0; xq[12 + w] = l1; }
+  __syncthreads();                                           // probabilities and the waves' sums are visible
+  l0 = (xq[8] + xq[9]) + (xq[10] + xq[11]);
+  l1 = (xq[12] + xq[13]) + (xq[14] + xq[15]);
+  float acc0 = 0.f, acc1 = 0.f;
+#pragma unroll 4
+  for (int j = w; j < nk; j += 4) {
+    const float v = Vb[(int64_t)j * D + lane];
+    acc0 = fmaf(sc[j], v, acc0);
+    acc1 = fmaf(sc[nkmax + j], v, acc1);
+  }
+  __syncthreads();                                           // the sums have been read: the scratch becomes the partial sums
+  xq[w * 128 + lane] = acc0;
+  xq[w * 128 + 64 + lane] = acc1;
+  __syncthreads();
+  if (tid < 128) {
+    const float l = tid < 64 ? l0 : l1;
+    out[(qrow + (tid >> 6)) * D + h * 64 + lane] = ((xq[tid] + xq[128 + tid]) + (xq[256 + tid] + xq[384 + tid])) / l;
+  }
+}
+
 inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
 }  // namespace
 
 int mimi_embed_launch(const int32_t* codes, int n_q, int64_t n, const float* cb, int bins, int dq, const float* wfT, const float* wrT, float* z,
-                      int D, hipStream_t s) {
-  if (n <= 0 || n > 0x7fffffff || n_q < 1 || dq <= 0 || dq > 4096 || D <= 0) return -1;
-  hipLaunchKernelGGL(mimi_embed, dim3((unsigned)n), dim3(256), (size_t)2 * dq * 4, s, codes, n_q, n, cb, bins, dq, wfT, wrT, z, D);
+                      int D, hipStream_t s, int n_seq, int64_t z_seq_step) {
+  if (n <= 0 || n > 0x7fffffff || n_q < 1 || dq <= 0 || dq > 4096 || D <= 0 || n_seq < 1 || n_seq > 65535) return -1;
+  hipLaunchKernelGGL(mimi_embed, dim3((unsigned)n, (unsigned)n_seq), dim3(256), (size_t)2 * dq * 4, s, codes, n_q, n, cb, bins, dq, wfT, wrT, z, D, z_seq_step);
   return ok();
 }
 
-int mimi_upsample_launch(const float* zp, const float* w, float* y, int64_t n, int D, int stride, hipStream_t s) {
-  if (n <= 0 || D <= 0 || stride <= 0) return -1;
+int mimi_upsample_launch(const float* zp, const float* w, float* y, int64_t n, int D, int stride, hipStream_t s, int n_seq, int64_t zp_seq_step,
+                         int64_t y_seq_step) {
+  if (n <= 0 || D <= 0 || stride <= 0 || n_seq < 1 || n_seq > 65535) return -1;
   const int64_t total = n * stride * D;
-  hipLaunchKernelGGL(mimi_upsample, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192)), dim3(256), 0, s, zp, w, y, n, D, stride);
+  hipLaunchKernelGGL(mimi_upsample, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192), (unsigned)n_seq), dim3(256), 0, s, zp, w, y, n, D, stride,
+                     zp_seq_step, y_seq_step);
+  return ok();
+}
+
+int mimi_carry_rows_launch(const MimiStreamRow* tab, int n_streams, int64_t st_off, float* buf, int64_t seq_step, int ctx, int C, int64_t T,
+                           const float* src_new, hipStream_t s) {
+  if (n_streams < 1 || n_streams > 65535 || ctx < 1 || C <= 0 || C % 4 || st_off % 4 || seq_step % 4 || T <= 0 || seq_step < (ctx + T) * C) return -1;
+  hipLaunchKernelGGL(mimis_carry_rows, dim3((unsigned)((C / 4 + 255) / 256), (unsigned)n_streams), dim3(256), 0, s, tab, st_off, buf, seq_step, ctx, C, T, src_new);
+  return ok();
+}
+
+int mimi_qkv_finish_streams_launch(const float* qkv, float* q, const MimiStreamRow* tab, int n_streams, int layer, int64_t P, int D, const double* inv_freq,
+                                   hipStream_t s) {
+  if (P <= 0 || D <= 0 || D % 64 || n_streams < 1 || n_streams > 65535 || layer < 0) return -1;
+  const int64_t total = P * (D / 2);
+  hipLaunchKernelGGL(mimis_qkv_finish, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 8192), (unsigned)n_streams), dim3(256), 0, s, qkv, q, tab, layer, P, D,
+                     inv_freq);
+  return ok();
+}
+
+size_t mimi_pair_attn_lds(int ctx) { return (size_t)(2 * (ctx + 2) + 512) * 4; }
+
+int mimi_pair_attn_launch(const float* q, const MimiStreamRow* tab, int n_streams, int layer, float* out, int64_t P, int D, int H, int ctx, float scale,
+                          hipStream_t s) {
+  if (P <= 0 || (P & 1) || D != H * 64 || ctx < 0 || mimi_pair_attn_lds(ctx) > 64 * 1024 || P / 2 > 0x7fffffff || H > 65535 || n_streams < 1 || n_streams > 65535 ||
+      layer < 0)
+    return -1;
+  hipLaunchKernelGGL(mimis_pair_attn, dim3((unsigned)(P / 2), (unsigned)H, (unsigned)n_streams), dim3(256), mimi_pair_attn_lds(ctx), s, q, tab, layer, out, P, D, ctx,
+                     scale);
   return ok();
 }
 
@@ -186,8 +360,10 @@ int mimi_window_attn_launch(const float* q, const float* K, const float* V, floa
   return ok();
 }
 
-int mimi_conv_out1_launch(const float* x, const float* w, const float* bias, float* out, int64_t T, int C, int K, hipStream_t s) {
-  if (T <= 0 || C <= 0 || C % 4 || K <= 0 || (size_t)K * C * 4 > 48 * 1024) return -1;
-  hipLaunchKernelGGL(mimi_conv_out1, dim3((unsigned)((T + 255) / 256)), dim3(256), (size_t)K * C * 4, s, x, w, bias, out, T, C, K);
+int mimi_conv_out1_launch(const float* x, const float* w, const float* bias, float* out, int64_t T, int C, int K, hipStream_t s, int n_seq,
+                          int64_t x_seq_step, int64_t out_seq_step) {
+  if (T <= 0 || C <= 0 || C % 4 || K <= 0 || (size_t)K * C * 4 > 48 * 1024 || n_seq < 1 || n_seq > 65535 || x_seq_step % 4) return -1;
+  hipLaunchKernelGGL(mimi_conv_out1, dim3((unsigned)((T + 255) / 256), (unsigned)n_seq), dim3(256), (size_t)K * C * 4, s, x, w, bias, out, T, C, K, x_seq_step,
+                     out_seq_step);
   return ok();
 }

@@ -173,6 +173,19 @@ class MimiCodec:
         self._streams.append(weakref.ref(s))
         return s
 
+    def decode_streams(self, streams, codes) -> np.ndarray:
+        """Advance several MimiStreams by the same n frames in one pass (mia_mimi_stream_decode_batch): codes int [S, n_q, n] ->
+        float32 [S, n * samples_per_frame].  Row u is what streams[u].decode_frames(codes[u]) would have returned."""
+        c = np.ascontiguousarray(codes, np.int32)
+        if c.ndim != 3 or c.shape[0] != len(streams):
+            raise ValueError("codes must be [len(streams), n_q, n]")
+        S, n_q, n = c.shape
+        pcm = np.empty((S, max(n * self.cfg.samples_per_frame, 1)), np.float32)
+        ns = C.c_int64(0)
+        handles = (C.c_void_p * max(S, 1))(*[s.h for s in streams])
+        self.ctx.check(self.ctx.lib.mia_mimi_stream_decode_batch(handles, S, c.ctypes.data, n_q, n, pcm.ctypes.data, pcm.shape[1], C.byref(ns), _lib.MEM_HOST))
+        return pcm[:, :ns.value]
+
     def close(self):
         if self.h and getattr(self.ctx, "h", None):
             for ref in self._streams:               # a stream points into its codec: release it first

@@ -42,9 +42,12 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--encode", action="store_true")
     ap.add_argument("--seconds", type=float, nargs="*", default=[10.0, 30.0])
+    ap.add_argument("--streams", type=int, nargs="*", default=[])
     a = ap.parse_args()
     if a.encode:
         return encode_main(a)
+    if a.streams:
+        return streams_main(a)
     cfg = synthetic.MIMI_CONFIGS["mimi_202407"]
     ctx = m.Context(0)
     codec = MimiCodec.load(ctx, cfg, synthetic.mimi_weights(cfg, a.seed))
@@ -78,6 +81,50 @@ def main():
                 stream.decode_frames(p)
         out["schedules"][f"stream_chunk_{c}"] = timed(run, len(parts))
     stream.close()
+    codec.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
+def streams_main(a):
+    """--streams S ...: S streams side by side, one frame per step over --frames steps: the loop of S single calls per step against one
+    decode_streams call per step, in this process, as loop / batch / loop again (the two loop readings show drift).  Per reading: one
+    untimed pass, then the median of 7 timed passes, in ms per frame step (host inclusive)."""
+    cfg = synthetic.MIMI_CONFIGS["mimi_202407"]
+    ctx = m.Context(0)
+    codec = MimiCodec.load(ctx, cfg, synthetic.mimi_weights(cfg, a.seed))
+    rng = np.random.Generator(np.random.PCG64(a.seed))
+    out = {"config": "mimi_202407", "mode": "streams", "steps": a.frames, "n_q": cfg.quantizer_nq, "unit": "ms per frame step, host inclusive", "streams": {}}
+    for S in a.streams:
+        codes = rng.integers(0, cfg.quantizer_bins, (S, cfg.quantizer_nq, a.frames)).astype(np.int32)
+        steps = [np.ascontiguousarray(codes[:, :, t:t + 1]) for t in range(a.frames)]
+        streams = [codec.new_stream() for _ in range(S)]
+
+        def loop():
+            for c in steps:
+                for u, s in enumerate(streams):
+                    s.decode_frames(c[u])
+
+        def batch():
+            for c in steps:
+                codec.decode_streams(streams, c)
+
+        def reading(fn):
+            ms = []
+            for i in range(8):
+                for s in streams:
+                    s.reset()
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                ms.append((time.perf_counter() - t0) * 1e3 / a.frames)
+            return round(sorted(ms[1:])[3], 4)
+
+        row = {"loop": reading(loop), "batch": reading(batch), "loop_again": reading(loop)}
+        row["batch_over_loop"] = round(row["batch"] / min(row["loop"], row["loop_again"]), 3)
+        out["streams"][str(S)] = row
+        for s in streams:
+            s.close()
     codec.close()
     ctx.close()
     print(json.dumps(out))
